@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- disparity maps/sec of the MI355X-native stereo-matching hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json): synthetic 1242x375 grayscale pairs, D=128, K=2 (config C2's shape);
 one "step" = one pass of the whole hot path (prologue -> cost volume + aggregation + WTA ->
@@ -45,6 +45,8 @@ PAIRS_PER_GPU = 64
 C3_PAIRS = 512
 HBM_PEAK_GBPS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 B_ALG_PER_PAIR = 12 * H * W      # 2 gray f32 inputs + 1 f32 output
+DUMP_BYTES = 64 * 10**6          # --dump-outputs: at most this much in all ranks' files together
+DUMP_SEED = 0                    # --dump-outputs: which pairs of a batch are written
 
 CONFIGS = [
     # name, H, W, K, dmin, dmax, entry, batch          (BASELINE.md section 2.2 + the reference's defaults)
@@ -442,6 +444,7 @@ def run_rank(args) -> None:
     pipelined = args.submit == "engine"
     runs, prof = region(pipelined, max(1, args.repeats))
     elapsed = sorted(runs)[len(runs) // 2]          # `value` is priced on the median region
+    dumped = dump_outputs(torch, args.dump_outputs, out, mine, rank, world) if args.dump_outputs else None
     # ---- the same steps once more on the caller's stream: one launch per kernel and step, nothing beside it -- the
     #      per-kernel durations the roofline is priced on (on the lanes every launch shares the chip with the other lane's)
     prof_lanes, elapsed_serial = None, elapsed
@@ -523,6 +526,8 @@ def run_rank(args) -> None:
                               "(no MFMA: integer abs-diff reductions), see roofline.valu and NOTES.md section 3.4")
     if c3 is not None and line is not None:
         line["c3"] = c3
+    if dumped is not None and line is not None:
+        line["dump_outputs"] = dumped
 
     # With several ranks the others wait in the closing barrier while rank 0 runs its extra legs: keep those to the
     # latency and copy-bandwidth measurements (< 1 s); the content / RGB / per-configuration legs belong to the N = 1 run.
@@ -609,6 +614,26 @@ def run_rank(args) -> None:
         print(json.dumps(line), file=getattr(args, "result_stream", sys.stdout), flush=True)
     group.barrier()
     group.close()
+
+
+def dump_outputs(torch, directory, out, mine, rank, world):
+    """--dump-outputs: what the timed path returned in its last step, the [n,H,W] float32 disparity maps of this rank's
+    pairs, as DIR/disparity.npy (DIR/disparity_rank<r>.npy with several ranks).  A whole batch is larger than
+    DUMP_BYTES, so the file holds a fixed sample of its pairs (seeded, in ascending order): with the same arguments
+    the same pairs, built from the same inputs, in every run.  Returns the record rank 0 puts into the result line."""
+    import numpy as np
+    n = out.shape[0]
+    per_pair = out[0].numel() * out.element_size()
+    take = min(n, max(1, (DUMP_BYTES // world - 4096) // per_pair))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=take, replace=False))
+    maps = out.index_select(0, torch.from_numpy(idx).to(out.device)).cpu().numpy().astype(np.float32, copy=False)
+    name = "disparity" if world == 1 else f"disparity_rank{rank}"
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), maps)
+    return {"dir": os.path.abspath(directory), "files": [name + ".npy"], "dtype": "float32", "shape": list(maps.shape),
+            "pair_index": [int(mine[i]) for i in idx],
+            "note": f"disparity maps of the last timed step, {take} of the {n} pairs of each rank (seed {DUMP_SEED}); "
+                    "pair_index: global pair indices (rank 0's), inputs seeded by pair index"}
 
 
 def real_scene_rates(torch, cuda_depth, out, device):
@@ -727,7 +752,13 @@ def main() -> None:
     ap.add_argument("--no-configs", dest="configs", action="store_false",
                     help="skip the per-configuration leg (every BASELINE configuration + the reference's default "
                          "configuration: single-call latency and batched throughput, line['configs']); ~3 s")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the disparity maps the timed path returned in its last step to "
+                         "DIR/disparity.npy (float32, a fixed seeded sample of the batch's pairs, at most 64 MB in all) "
+                         "so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     # stdout carries the ONE JSON line and nothing else: libraries that write to file descriptor 1

@@ -1,5 +1,5 @@
 import os, sys
-sys.path[:0] = ["/root/repo/stereo-depth_amd"]
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-depth_amd")]
 import numpy as np, torch, cuda_depth, stereo_synthetic as syn
 CASES = {"default": (1080, 1920, 2, 75, 262), "c4": (2160, 3840, 4, 0, 255), "c2": (375, 1242, 2, 0, 127)}
 name = sys.argv[1]

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path[:0]=[os.path.join("/root/repo","stereo-depth_amd")]
+sys.path[:0]=[os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),"stereo-depth_amd")]
 import numpy as np, torch, cuda_depth, stereo_synthetic as syn
 for (H,W,K,D,n) in ((2160,3840,4,256,16),(240,320,1,32,256),(375,1242,2,192,64)):
     cfg=cuda_depth.StereoMatchingConfiguration(height=H,width=W,downscale_factor=K,min_disparity=0,max_disparity=D-1)

@@ -19,6 +19,7 @@
  *   -- (grayscale entry, skips step 1; BASELINE configs)  smx_compute_gray / smx_compute_gray_u8
  *   -- (independent pairs, one launch set)                smx_compute_gray_batch / _rgb_batch
  *                                                         / _gray_u8_batch / _rgb_u8_batch
+ *   -- (left-right consistency check)                     smx_compute_lr_*_batch, smx_lr_check
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -185,7 +186,9 @@ int smx_compute_rgb_u8_batch(smx_engine *engine, int n, const uint8_t *left_nchw
                              const uint8_t *right_nchw, float *out_nhw, void *stream);
 
 /* Copies an intermediate of pair `pair_index` of the LAST call into dst (device pointer,
- * `bytes` must equal the stage size) on `stream`.  Test/debug facility. */
+ * `bytes` must equal the stage size) on `stream`.  Test/debug facility.  After an LR call of n pairs
+ * (smx_compute_lr_*, below) the last call is the one of 2n internal pairs: index i < n is (L_i, R_i), index n + i is
+ * the mirrored pair (flip R_i, flip L_i), so e.g. SMX_STAGE_WTA of n + i is the arg-max map of the right view, mirrored. */
 int    smx_get_intermediate(smx_engine *engine, int stage, int pair_index, void *dst,
                             size_t bytes, void *stream);
 size_t smx_stage_bytes(const smx_engine *engine, int stage);
@@ -313,6 +316,43 @@ int smx_disparity_to_points(int device_id, const float *disparity_hw, int H, int
  * prologue kernel.  Same results as smx_compute_rgb on the .float() of the same tensors. */
 int smx_compute_rgb_u8(smx_engine *engine, const uint8_t *left_chw, const uint8_t *right_chw,
                        float *out_hw, void *stream);
+
+/* Left-right consistency check: marks the pixels whose match does not point back to them -- occlusions, the band
+ * Y < min_disparity along the left edge, mismatches -- with invalid_disparity (the value PointCloudSaver drops,
+ * python/pipeline/depth_estimation_pipeline_hooks.py:87-88; smx_disparity_to_points above).  E(L, R) is what the plain
+ * entries compute; flip reverses the column axis (every plane of RGB input).
+ *   D_L = E(L, R)                                 (the same bits as the plain *_batch entry)
+ *   D_R = flip(E(flip R, flip L))                 the map referenced to the right image: the engine's own problem on the
+ *                                                 mirrored, swapped pair (same configuration, fp_convention and match_mode)
+ *   per pixel (X, Y), float32:
+ *     t  = floorf(D_L[X][Y] + 0.5f);  ok = isfinite(t) && t >= 0 && t <= Y
+ *     ok = ok && fabsf(D_L[X][Y] - D_R[X][Y - (int)t]) <= max_diff        (NaN D_R: not ok)
+ *     out[X][Y] = ok ? D_L[X][Y] : invalid_disparity
+ * One call = ONE engine call of 2n internal pairs on `stream` (the aggregation kernel sees twice the pairs) between an
+ * input pack / mirror launch and the check launch; its cost is about that of a plain call of 2n pairs.  The packed
+ * inputs and raw outputs live in engine-owned scratch, allocated by the first LR call for max_batch pairs of its input
+ * format (regrown once for a larger format, never in a steady loop); a first LR call on a capturing stream returns
+ * SMX_ERR_UNSUPPORTED (make one outside capture first).  Plain calls give the same bits before and after LR calls.
+ * n pairs, same layouts as the *_batch entries, 1 <= n and 2*n <= cfg.max_batch (else SMX_ERR_INVALID_ARG).
+ * out: [n][H][W], checked left map.  right_out: [n][H][W] un-checked right-view map D_R, or NULL.  The inputs must not
+ * overlap out / right_out, nor out right_out (SMX_ERR_INVALID_ARG).  max_diff must be finite and >= 0, invalid_disparity
+ * finite (SMX_ERR_INVALID_ARG).  stream = SMX_STREAM_ENGINE: SMX_ERR_UNSUPPORTED (LR calls run on a caller's stream).
+ * Every argument is checked before the device is touched. */
+int smx_compute_lr_gray_batch(smx_engine *engine, int n, const float *left_nhw, const float *right_nhw, float *out_nhw,
+                              float *right_out_nhw, float max_diff, float invalid_disparity, void *stream);
+int smx_compute_lr_gray_u8_batch(smx_engine *engine, int n, const uint8_t *left_nhw, const uint8_t *right_nhw,
+                                 float *out_nhw, float *right_out_nhw, float max_diff, float invalid_disparity,
+                                 void *stream);
+int smx_compute_lr_rgb_batch(smx_engine *engine, int n, const float *left_nchw, const float *right_nchw, float *out_nhw,
+                             float *right_out_nhw, float max_diff, float invalid_disparity, void *stream);
+int smx_compute_lr_rgb_u8_batch(smx_engine *engine, int n, const uint8_t *left_nchw, const uint8_t *right_nchw,
+                                float *out_nhw, float *right_out_nhw, float max_diff, float invalid_disparity,
+                                void *stream);
+/* Standalone check of maps the caller already has (e.g. from another backend): the same rule, D_R given un-mirrored.
+ * left/right/out: [n][H][W] f32 device pointers on device_id; out may alias left (the same buffer), not right.
+ * stream: a caller's stream. */
+int smx_lr_check(int device_id, int n, int H, int W, const float *left_disp, const float *right_disp, float *out,
+                 float max_diff, float invalid_disparity, void *stream);
 
 #ifdef __cplusplus
 }

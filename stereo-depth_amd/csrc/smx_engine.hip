@@ -8,6 +8,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see build.py).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -207,6 +208,12 @@ struct smx_engine {
     std::vector<OutRange> out_live[LANES];
     bool detached_pending = false;                // SMX_STREAM_ENGINE calls not yet joined into a caller stream
     int overlap_min = 0;
+    // Left-right check (smx_compute_lr_*): the packed inputs of the 2n internal pairs, in the entry's own format, and
+    // their raw outputs.  Allocated by the first LR call for max_batch pairs of its format, regrown only when a format with
+    // more bytes per pair arrives; engines that never make an LR call hold none of it.
+    void *lr_in_l = nullptr, *lr_in_r = nullptr;  // [B] pairs of lr_pair_bytes
+    size_t lr_pair_bytes = 0;
+    float *lr_raw = nullptr;                      // [B][H][W]
 };
 
 namespace {
@@ -226,7 +233,8 @@ void free_events(smx_engine *e) {
 
 void free_buffers(smx_engine *e) {
     void *ptrs[] = {e->gray_l, e->gray_r, e->down_l, e->down_r, e->wta,     e->refined,  e->costs,
-                    e->vol,    e->flags,  e->gray8_l, e->gray8_r, e->slices, e->cand,    e->stats_dev, e->tickets, e->fast_stats_dev};
+                    e->vol,    e->flags,  e->gray8_l, e->gray8_r, e->slices, e->cand,    e->stats_dev, e->tickets, e->fast_stats_dev,
+                    e->lr_in_l, e->lr_in_r, e->lr_raw};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (e->hints) (void)hipHostFree(e->hints);
@@ -910,6 +918,78 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     return rc;
 }
 
+bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    if (!a || !b) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+int check_lr_scalars(float max_diff, float invalid) {
+    if (!(std::isfinite(max_diff) && max_diff >= 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "max_diff must be finite and >= 0, got %g", (double)max_diff);
+    if (!std::isfinite(invalid))
+        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
+                    (double)invalid);
+    return SMX_OK;
+}
+
+// Left-right check: ONE engine call of 2n internal pairs on the caller's stream -- (L_i, R_i) for i < n, (flip R_i, flip L_i)
+// for n + i -- between the pack / mirror launch and the check launch (k_lr.h).
+int enqueue_lr(smx_engine *e, int in_mode, int n, const void *left, const void *right, float *out, float *right_out,
+               float max_diff, float invalid, void *stream) {
+    if (int rc = check_lr_scalars(max_diff, invalid)) return rc;
+    if (!e) return fail(SMX_ERR_INVALID_ARG, "engine is NULL");
+    if (!left || !right || !out) return fail(SMX_ERR_INVALID_ARG, "left, right and out must be non-NULL");
+    if (n < 1 || 2L * n > e->B)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "LR batch size %d: the check runs the mirrored problem too, i.e. 2n = %ld internal pairs, which must "
+                    "lie in [2, max_batch=%d] (n <= max_batch / 2)", n, 2L * n, e->B);
+    if (stream == SMX_STREAM_ENGINE)
+        return fail(SMX_ERR_UNSUPPORTED, "LR calls run on a caller's stream only (SMX_STREAM_ENGINE is not supported)");
+    const smx_dims &d = e->dm;
+    const bool rgb = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
+    const bool u8 = in_mode == smx::IN_GRAY_U8 || in_mode == smx::IN_RGB_U8;
+    const int planes = rgb ? 3 : 1, es = u8 ? 1 : (int)sizeof(float);
+    const size_t hw = (size_t)d.H * d.W, pair_bytes = hw * planes * es;
+    const size_t in_bytes = (size_t)n * pair_bytes, out_bytes = (size_t)n * hw * sizeof(float);
+    if (ranges_overlap(left, in_bytes, out, out_bytes) || ranges_overlap(right, in_bytes, out, out_bytes) ||
+        ranges_overlap(left, in_bytes, right_out, out_bytes) || ranges_overlap(right, in_bytes, right_out, out_bytes) ||
+        ranges_overlap(out, out_bytes, right_out, out_bytes))
+        return fail(SMX_ERR_INVALID_ARG, "LR call: the inputs, out and right_out must not overlap");
+    DeviceGuard guard(e->cfg.device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", e->cfg.device_id);
+    hipStream_t s = (hipStream_t)stream;
+    const bool capturing = stream_capturing(s);
+    if (!e->lr_raw || e->lr_pair_bytes < pair_bytes) {
+        if (capturing)
+            return fail(SMX_ERR_UNSUPPORTED, "stream capture: the LR scratch of this input format is not allocated yet "
+                                             "(make one LR call outside capture first)");
+        if (e->lr_pair_bytes < pair_bytes) {
+            if (e->lr_in_l || e->lr_in_r) {                      // a larger format: earlier LR calls may still read the old ones
+                SMX_HIP(hipDeviceSynchronize());
+                (void)hipFree(e->lr_in_l);
+                (void)hipFree(e->lr_in_r);
+                e->lr_in_l = e->lr_in_r = nullptr;
+                e->lr_pair_bytes = 0;
+            }
+            SMX_HIP(hipMalloc(&e->lr_in_l, (size_t)e->B * pair_bytes));
+            SMX_HIP(hipMalloc(&e->lr_in_r, (size_t)e->B * pair_bytes));
+            e->lr_pair_bytes = pair_bytes;
+        }
+        if (!e->lr_raw) SMX_HIP(hipMalloc((void **)&e->lr_raw, (size_t)e->B * hw * sizeof(float)));
+    }
+    if (capturing && (e->detached_pending || e->epoch == 0x7fffffff))
+        return fail(SMX_ERR_UNSUPPORTED,
+                    "stream capture: the engine has work on its own streams that is not joined yet (call smx_join on a "
+                    "stream outside the capture first), or its call counter is about to wrap");
+    smx::launch_lr_pack(es, left, right, e->lr_in_l, e->lr_in_r, (long)n * planes * d.H, d.W, s);
+    SMX_HIP(hipGetLastError());
+    if (int rc = enqueue(e, in_mode, 2 * n, e->lr_in_l, e->lr_in_r, e->lr_raw, stream)) return rc;
+    smx::launch_lr_check(true, e->lr_raw, e->lr_raw + (size_t)n * hw, out, right_out, n, d.H, d.W, max_diff, invalid, s);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1187,6 +1267,40 @@ int smx_compute_gray_u8_batch(smx_engine *e, int n, const uint8_t *l, const uint
 }
 int smx_compute_rgb_u8_batch(smx_engine *e, int n, const uint8_t *l, const uint8_t *r, float *out, void *stream) {
     return enqueue(e, smx::IN_RGB_U8, n, l, r, out, stream);
+}
+
+int smx_compute_lr_gray_batch(smx_engine *e, int n, const float *l, const float *r, float *out, float *right_out,
+                              float max_diff, float invalid, void *stream) {
+    return enqueue_lr(e, smx::IN_GRAY_F32, n, l, r, out, right_out, max_diff, invalid, stream);
+}
+int smx_compute_lr_gray_u8_batch(smx_engine *e, int n, const uint8_t *l, const uint8_t *r, float *out, float *right_out,
+                                 float max_diff, float invalid, void *stream) {
+    return enqueue_lr(e, smx::IN_GRAY_U8, n, l, r, out, right_out, max_diff, invalid, stream);
+}
+int smx_compute_lr_rgb_batch(smx_engine *e, int n, const float *l, const float *r, float *out, float *right_out,
+                             float max_diff, float invalid, void *stream) {
+    return enqueue_lr(e, smx::IN_RGB_F32, n, l, r, out, right_out, max_diff, invalid, stream);
+}
+int smx_compute_lr_rgb_u8_batch(smx_engine *e, int n, const uint8_t *l, const uint8_t *r, float *out, float *right_out,
+                                float max_diff, float invalid, void *stream) {
+    return enqueue_lr(e, smx::IN_RGB_U8, n, l, r, out, right_out, max_diff, invalid, stream);
+}
+
+int smx_lr_check(int device_id, int n, int H, int W, const float *left, const float *right, float *out, float max_diff,
+                 float invalid, void *stream) {
+    if (int rc = check_lr_scalars(max_diff, invalid)) return rc;
+    if (!left || !right || !out) return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: left, right and out must be non-NULL");
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
+        return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", n, H, W);
+    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "smx_lr_check needs a caller stream");
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    if (ranges_overlap(right, bytes, out, bytes) || (out != left && ranges_overlap(left, bytes, out, bytes)))
+        return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: out must not overlap right_disp, and overlap left_disp only as the same buffer");
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
+    smx::launch_lr_check(false, left, right, out, nullptr, n, H, W, max_diff, invalid, (hipStream_t)stream);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
 }
 
 size_t smx_stage_bytes(const smx_engine *e, int stage) {

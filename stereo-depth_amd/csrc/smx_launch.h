@@ -78,6 +78,13 @@ void launch_match_filter_24(const MatchParams &p, const FilterParams &f, int n, 
 void launch_match_filter_27(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s);
 void launch_match_filter_32(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s);
 
+// ---- tu_lr.hip: left-right consistency check (k_lr.h) ----------------------------------------------------
+// rows = n * planes * H rows of W elements of elem_bytes (1 or 4) per input; pl / pr: [2n] pairs, the second n mirrored
+void launch_lr_pack(int elem_bytes, const void *l, const void *r, void *pl, void *pr, long rows, int W, hipStream_t s);
+// mirrored: `right` holds the raw output of the mirrored internal pairs (flip(D_R)); right_out may be NULL
+void launch_lr_check(bool mirrored, const float *left, const float *right, float *out, float *right_out, int n, int H, int W,
+                     float max_diff, float invalid, hipStream_t s);
+
 #ifdef SMX_EXPERIMENTAL
 // ---- tu_experimental.hip: measured negative results kept for A/B runs (NOTES.md) --------------------------
 bool wide_applicable(const MatchParams &p, int n);

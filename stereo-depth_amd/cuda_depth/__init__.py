@@ -15,6 +15,7 @@ TORCH_CHECK failures do in the reference (stereo_matching.cc:13-15).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -76,6 +77,47 @@ def _check_input(name: str, t: torch.Tensor) -> None:
         raise RuntimeError(f"{name} must be contiguous")
 
 
+def _check_lr_scalars(max_diff, invalid_disparity) -> None:
+    for name, v in (("max_diff", max_diff), ("invalid_disparity", invalid_disparity)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{name} must be a number")
+    if not (math.isfinite(max_diff) and max_diff >= 0):
+        raise RuntimeError(f"max_diff must be finite and >= 0, got {max_diff}")
+    if not math.isfinite(invalid_disparity):
+        raise RuntimeError(f"invalid_disparity must be finite (a NaN marker never compares equal), got {invalid_disparity}")
+
+
+def left_right_check(left_disp: torch.Tensor, right_disp: torch.Tensor, *, max_diff: float = 1.0,
+                     invalid_disparity: float = -1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Left-right consistency check of maps the caller already has (smx_lr_check): left_disp referenced to the left
+    image, right_disp to the right image, both [H,W] or [n,H,W] float32 on one device.  Returns left_disp with every
+    pixel whose match does not point back to it within max_diff replaced by invalid_disparity.  `out` may be left_disp."""
+    _check_input("left_disp", left_disp)
+    _check_input("right_disp", right_disp)
+    if left_disp.dtype != torch.float32 or right_disp.dtype != torch.float32:
+        raise RuntimeError("left_disp and right_disp must be torch.float32")
+    if left_disp.dim() not in (2, 3) or tuple(right_disp.shape) != tuple(left_disp.shape):
+        raise RuntimeError(f"left_disp and right_disp must both be [H,W] or [n,H,W] of one shape, got "
+                           f"{tuple(left_disp.shape)} / {tuple(right_disp.shape)}")
+    if right_disp.device != left_disp.device:
+        raise RuntimeError("left_disp and right_disp must live on the same device")
+    _check_lr_scalars(max_diff, invalid_disparity)
+    if out is None:
+        out = torch.empty_like(left_disp)
+    else:
+        _check_input("out", out)
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(left_disp.shape) or out.device != left_disp.device:
+            raise RuntimeError(f"out must be float32 {tuple(left_disp.shape)} on {left_disp.device}")
+    n = 1 if left_disp.dim() == 2 else int(left_disp.shape[0])
+    H, W = int(left_disp.shape[-2]), int(left_disp.shape[-1])
+    if left_disp.numel() == 0:
+        raise RuntimeError("left_disp is empty")
+    dev = left_disp.device.index
+    check(LIB.smx_lr_check(dev, n, H, W, left_disp.data_ptr(), right_disp.data_ptr(), out.data_ptr(), float(max_diff),
+                           float(invalid_disparity), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
 class StereoMatching:
     """torch_extension_module.cc:22-26.  `compute_disparity_map` is the reference method;
     the keyword-only constructor extras and the *_gray / *_batch methods are additions that
@@ -113,6 +155,7 @@ class StereoMatching:
         # the reference returns an alias of its persistent output buffer (stereo_matching.cc:42)
         self._output = torch.zeros((d.H, d.W), dtype=torch.float32, device=dev)
         self._batch_output: Optional[torch.Tensor] = None
+        self._lr_output: Optional[torch.Tensor] = None
         self._out_parity = 0
 
     # ------------------------------------------------------------------ lifetime
@@ -214,6 +257,45 @@ class StereoMatching:
             fn = LIB.smx_compute_gray_batch if gray else LIB.smx_compute_rgb_batch
         check(fn(self._handle, n, left.data_ptr(), right.data_ptr(), out.data_ptr(),
                  _native.STREAM_ENGINE if engine_streams else self._stream()))
+        return out
+
+    def compute_disparity_map_batch_lr(self, left: torch.Tensor, right: torch.Tensor,
+                                       out: Optional[torch.Tensor] = None, *, right_out: Optional[torch.Tensor] = None,
+                                       max_diff: float = 1.0, invalid_disparity: float = -1.0) -> torch.Tensor:
+        """Left-right checked disparity maps (smx_compute_lr_*_batch): same inputs as compute_disparity_map_batch, at most
+        max_batch // 2 pairs (the right-view maps are computed in the same call, as n more pairs).  Pixels whose match
+        in the right image does not point back to them within max_diff pixels become invalid_disparity.  right_out
+        ([n,H,W] float32) receives the un-checked right-view maps.  The default `out` is a buffer of its own (valid
+        until the next LR call), not the one of the plain batch method."""
+        d = self._dims
+        if not isinstance(left, torch.Tensor) or left.dim() not in (3, 4):
+            raise RuntimeError("left_image must be [n,H,W] or [n,3,H,W]")
+        n = int(left.shape[0])
+        if not (1 <= n <= self._max_batch // 2):
+            raise RuntimeError(f"LR batch size {n} outside [1, max_batch // 2 = {self._max_batch // 2}]: the right-view "
+                               f"maps double the pairs of the call (create the engine with max_batch >= {2 * n})")
+        gray = left.dim() == 3
+        shape = (n, d.H, d.W) if gray else (n, 3, d.H, d.W)
+        dtype = torch.uint8 if left.dtype == torch.uint8 else torch.float32
+        self._validate("left_image", left, shape, dtype)
+        self._validate("right_image", right, shape, dtype)
+        _check_lr_scalars(max_diff, invalid_disparity)
+        if out is None:
+            if self._lr_output is None:
+                self._lr_output = torch.zeros((self._max_batch // 2, d.H, d.W), dtype=torch.float32,
+                                              device=torch.device("cuda", self._device))
+            out = self._lr_output[:n]
+        else:
+            self._validate("out", out, (n, d.H, d.W))
+        if right_out is not None:
+            self._validate("right_out", right_out, (n, d.H, d.W))
+        if dtype == torch.uint8:
+            fn = LIB.smx_compute_lr_gray_u8_batch if gray else LIB.smx_compute_lr_rgb_u8_batch
+        else:
+            fn = LIB.smx_compute_lr_gray_batch if gray else LIB.smx_compute_lr_rgb_batch
+        check(fn(self._handle, n, left.data_ptr(), right.data_ptr(), out.data_ptr(),
+                 right_out.data_ptr() if right_out is not None else None, float(max_diff), float(invalid_disparity),
+                 self._stream()))
         return out
 
     def join(self) -> None:

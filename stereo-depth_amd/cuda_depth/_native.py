@@ -80,6 +80,18 @@ EXPORTS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smx_eval_metrics": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
                                    C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    # left-right consistency check: (engine, n, left, right, out, right_out, max_diff, invalid_disparity, stream)
+    "smx_compute_lr_gray_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_float, C.c_float, C.c_void_p]),
+    "smx_compute_lr_gray_u8_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_float, C.c_float, C.c_void_p]),
+    "smx_compute_lr_rgb_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_float, C.c_void_p]),
+    "smx_compute_lr_rgb_u8_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_float, C.c_float, C.c_void_p]),
+    # (device_id, n, H, W, left_disp, right_disp, out, max_diff, invalid_disparity, stream)
+    "smx_lr_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                               C.c_float, C.c_void_p]),
 }
 
 STREAM_ENGINE = C.c_void_p(-1)          # SMX_STREAM_ENGINE: the engine's own streams

@@ -25,12 +25,27 @@ def _device_frame(image: torch.Tensor) -> torch.Tensor:
 
 
 class CudaStereoMatchingBackend(StereoMatching):
+    """left_right_check=True: every map is left-right checked (StereoMatching.compute_disparity_map_batch_lr, one pair
+    plus its mirrored twin per call, hence max_batch=2): pixels whose match in the right image does not point back to
+    them within lr_max_diff pixels -- occlusions, the band left of min_disparity -- become invalid_disparity."""
 
-    def __init__(self, configuration: Optional["cuda_depth.StereoMatchingConfiguration"] = None):
-        self._stereo_algo = cuda_depth.StereoMatching(configuration or cuda_depth.StereoMatchingConfiguration())
+    def __init__(self, configuration: Optional["cuda_depth.StereoMatchingConfiguration"] = None, *,
+                 left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0):
+        configuration = configuration or cuda_depth.StereoMatchingConfiguration()
+        self._left_right_check = bool(left_right_check)
+        self._lr_max_diff = float(lr_max_diff)
+        self._invalid_disparity = float(invalid_disparity)
+        if self._left_right_check:
+            self._stereo_algo = cuda_depth.StereoMatching(configuration, max_batch=2)
+        else:
+            self._stereo_algo = cuda_depth.StereoMatching(configuration)
 
     def process(self, left_image: torch.Tensor, right_image: torch.Tensor) -> torch.Tensor:
         left, right = _device_frame(left_image), _device_frame(right_image)
         if left.dtype != right.dtype:                       # mixed inputs: fall back to float for both
             left, right = left.float(), right.float()
+        if self._left_right_check:
+            return self._stereo_algo.compute_disparity_map_batch_lr(
+                left.unsqueeze(0), right.unsqueeze(0), max_diff=self._lr_max_diff,
+                invalid_disparity=self._invalid_disparity)[0]
         return self._stereo_algo.compute_disparity_map(left, right)

@@ -1,7 +1,7 @@
 """Pipeline facade: the direct caller of the backend boundary.
 
 Same public surface as /root/reference/src/python/pipeline/depth_estimation_pipeline.py:14-87
-(`DepthEstimationPipelineConfig` with its six fields and `update`, `DepthEstimationResult`,
+(`DepthEstimationPipelineConfig` with its six fields -- plus the opt-in left-right check -- and `update`, `DepthEstimationResult`,
 `DepthEstimationPipelineContext`, `DepthEstimationPipeline.process / get_configuration`) for the
 'cuda' backend.  Right-view synthesis (Deep3D) and the traced-DNN backends are out of scope
 (SURVEY.md section 2): `right_image` is mandatory here and the other backend names raise.
@@ -29,6 +29,10 @@ class DepthEstimationPipelineConfig:
     invalid_disparity: float = -1.0
     stereo_matching_backend: str = "cuda"          # one of "cuda", "msnet2d", "msnet3d", "gwcnet"
     log_perf_time: bool = False
+    # additions (no counterpart in the reference): left-right consistency check of the 'cuda' backend -- pixels whose
+    # match in the right image does not point back to them within lr_max_diff pixels become invalid_disparity
+    left_right_check: bool = False
+    lr_max_diff: float = 1.0
 
     def update(self, **changes: Any) -> "DepthEstimationPipelineConfig":
         """In-place update that rejects unknown fields (reference :23-28); returns self."""
@@ -68,7 +72,9 @@ class DepthEstimationPipelineContext:
 def _make_backend(config: DepthEstimationPipelineConfig) -> StereoMatching:
     name = config.stereo_matching_backend
     if name == "cuda":
-        return CudaStereoMatchingBackend(configuration=config.engine_configuration())
+        return CudaStereoMatchingBackend(configuration=config.engine_configuration(),
+                                         left_right_check=config.left_right_check, lr_max_diff=config.lr_max_diff,
+                                         invalid_disparity=config.invalid_disparity)
     if name in AVAILABLE_DNN_BACKENDS:
         raise RuntimeError(f"Stereo matching backend '{name}' (traced DNN) is not part of this build; use 'cuda'.")
     raise RuntimeError(f"Unsupported stereo matching backend: {name}")

@@ -20,6 +20,7 @@
  *   -- (independent pairs, one launch set)                smx_compute_gray_batch / _rgb_batch
  *                                                         / _gray_u8_batch / _rgb_u8_batch
  *   -- (left-right consistency check)                     smx_compute_lr_*_batch, smx_lr_check
+ *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -353,6 +354,49 @@ int smx_compute_lr_rgb_u8_batch(smx_engine *engine, int n, const uint8_t *left_n
  * stream: a caller's stream. */
 int smx_lr_check(int device_id, int n, int H, int W, const float *left_disp, const float *right_disp, float *out,
                  float max_diff, float invalid_disparity, void *stream);
+
+/* Post-processing of checked maps: speckle filter and background hole fill.  Maps are [n][H][W] float32 on the device;
+ * the n maps are independent (nothing connects across map boundaries).  A pixel value d is VALID iff
+ * isfinite(d) && d != invalid_disparity (float comparison, so -0.0 == 0.0).
+ *
+ * Speckle filter:
+ *   - Two 4-neighbours p, q of the same map are LINKED iff both are valid and fabsf(d_p - d_q) <= max_diff.  The
+ *     subtraction is in float32.  There is no multiply, so there is no contraction question.
+ *   - A REGION is a connected component of the linked relation: the transitive closure, 4-connectivity, no wrap-around.
+ *   - Every pixel of a region with size <= max_speckle_size becomes invalid_disparity.  This is the <= of
+ *     cv::filterSpeckles.  Every other pixel is copied unchanged, bit for bit, including non-valid ones such as NaN
+ *     payloads.
+ *   - max_speckle_size = 0 is a plain copy.
+ *
+ * Hole fill (background interpolation), two passes.
+ *   Row pass, on the input:
+ *   - For each non-valid pixel (x, y), let a be the nearest valid column < y in the same row and b the nearest valid
+ *     column > y.
+ *   - If both exist, the value is (D[x][a] <= D[x][b]) ? D[x][a] : D[x][b].  The left value wins ties, which pins
+ *     -0.0 / +0.0.
+ *   - If only one exists, use its value.
+ *   - If neither exists, leave the pixel unchanged.
+ *   Column pass, on the result of the row pass:
+ *   - Every row with at least one valid input pixel is now fully valid.
+ *   - For each row with no valid input pixel, let r1 be the nearest non-empty row above and r2 the nearest non-empty
+ *     row below.
+ *   - If both exist, each pixel takes (D[r1][y] <= D[r2][y]) ? D[r1][y] : D[r2][y].  The row above wins ties.
+ *   - If only one exists, copy it.
+ *   - If the whole map is non-valid, the map is copied unchanged.
+ *
+ * Both entries are engine-free.  in / out: [n][H][W] f32 device pointers on device_id; out may be in (in place) but
+ * must not overlap it otherwise.  workspace: device memory of at least smx_postprocess_workspace_bytes(n, H, W) bytes,
+ * overlapping neither map; its layout is implementation-defined and it holds nothing between calls (any contents give
+ * the same result).  Each call enqueues a fixed sequence of launches on `stream` (a caller's stream, not
+ * SMX_STREAM_ENGINE), with no host synchronisation and no allocation, so it can be captured into a HIP graph.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL pointer, n < 1, H or W outside 1..32768,
+ * max_speckle_size < 0, max_diff not finite or < 0, invalid_disparity not finite, workspace_bytes below the query,
+ * the overlaps above, stream == SMX_STREAM_ENGINE. */
+size_t smx_postprocess_workspace_bytes(int n, int H, int W);   /* 0 for n < 1 or H, W outside 1..32768 */
+int smx_filter_speckles(int device_id, int n, int H, int W, const float *in, float *out, int max_speckle_size,
+                        float max_diff, float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
+int smx_fill_invalid(int device_id, int n, int H, int W, const float *in, float *out, float invalid_disparity,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1303,6 +1303,64 @@ int smx_lr_check(int device_id, int n, int H, int W, const float *left, const fl
     return SMX_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The checks shared by smx_filter_speckles and smx_fill_invalid (after their own scalar checks).
+int check_post_args(const char *fn, int n, int H, int W, const float *in, const float *out, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+    if (!in || !out || !workspace) return fail(SMX_ERR_INVALID_ARG, "%s: in, out and workspace must be non-NULL", fn);
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", fn, n, H, W);
+    const size_t need = smx::post_workspace_bytes(n, H, W);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_postprocess_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    if (out != in && ranges_overlap(in, bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in other than as the same buffer", fn);
+    if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in or out", fn);
+    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
+    return SMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t smx_postprocess_workspace_bytes(int n, int H, int W) {
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return 0;
+    return smx::post_workspace_bytes(n, H, W);
+}
+
+int smx_filter_speckles(int device_id, int n, int H, int W, const float *in, float *out, int max_speckle_size,
+                        float max_diff, float invalid, void *workspace, size_t workspace_bytes, void *stream) {
+    if (max_speckle_size < 0)
+        return fail(SMX_ERR_INVALID_ARG, "smx_filter_speckles: max_speckle_size must be >= 0, got %d", max_speckle_size);
+    if (int rc = check_lr_scalars(max_diff, invalid)) return rc;
+    if (int rc = check_post_args("smx_filter_speckles", n, H, W, in, out, workspace, workspace_bytes, stream)) return rc;
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
+    smx::launch_filter_speckles(n, H, W, in, out, max_speckle_size, max_diff, invalid, workspace, (hipStream_t)stream);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
+int smx_fill_invalid(int device_id, int n, int H, int W, const float *in, float *out, float invalid, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    if (!std::isfinite(invalid))
+        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
+                    (double)invalid);
+    if (int rc = check_post_args("smx_fill_invalid", n, H, W, in, out, workspace, workspace_bytes, stream)) return rc;
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
+    smx::launch_fill_invalid(n, H, W, in, out, invalid, workspace, (hipStream_t)stream);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
 size_t smx_stage_bytes(const smx_engine *e, int stage) {
     if (!e) return 0;
     const smx_dims &d = e->dm;

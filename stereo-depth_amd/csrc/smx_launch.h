@@ -85,6 +85,13 @@ void launch_lr_pack(int elem_bytes, const void *l, const void *r, void *pl, void
 void launch_lr_check(bool mirrored, const float *left, const float *right, float *out, float *right_out, int n, int H, int W,
                      float max_diff, float invalid, hipStream_t s);
 
+// ---- tu_post.hip: speckle filter and hole fill (k_post.h) --------------------------------------------------------
+// workspace: post_workspace_bytes(n, H, W) bytes, layout private to tu_post.hip; nothing in it survives a call
+size_t post_workspace_bytes(int n, int H, int W);
+void launch_filter_speckles(int n, int H, int W, const float *in, float *out, int max_size, float max_diff, float invalid,
+                            void *workspace, hipStream_t s);
+void launch_fill_invalid(int n, int H, int W, const float *in, float *out, float invalid, void *workspace, hipStream_t s);
+
 #ifdef SMX_EXPERIMENTAL
 // ---- tu_experimental.hip: measured negative results kept for A/B runs (NOTES.md) --------------------------
 bool wide_applicable(const MatchParams &p, int n);

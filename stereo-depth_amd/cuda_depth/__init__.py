@@ -118,6 +118,76 @@ def left_right_check(left_disp: torch.Tensor, right_disp: torch.Tensor, *, max_d
     return out
 
 
+def _postprocess_operands(disp: torch.Tensor, out: Optional[torch.Tensor]):
+    """Shared checks of filter_speckles / fill_invalid: (out, n, H, W)."""
+    _check_input("disp", disp)
+    if disp.dtype != torch.float32:
+        raise RuntimeError("disp must be torch.float32")
+    if disp.dim() not in (2, 3) or disp.numel() == 0:
+        raise RuntimeError(f"disp must be a non-empty [H,W] or [n,H,W] map, got {tuple(disp.shape)}")
+    if out is None:
+        out = torch.empty_like(disp)
+    else:
+        _check_input("out", out)
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(disp.shape) or out.device != disp.device:
+            raise RuntimeError(f"out must be float32 {tuple(disp.shape)} on {disp.device}")
+    n = 1 if disp.dim() == 2 else int(disp.shape[0])
+    return out, n, int(disp.shape[-2]), int(disp.shape[-1])
+
+
+def _postprocess_workspace(n: int, H: int, W: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of smx_postprocess_workspace_bytes(n, H, W) bytes for smx_filter_speckles / smx_fill_invalid."""
+    nbytes = int(LIB.smx_postprocess_workspace_bytes(n, H, W))
+    if nbytes == 0:
+        raise RuntimeError(f"post-processing: need 1 <= H, W <= 32768 (got {H} x {W})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _launch_filter_speckles(disp, out, n, H, W, max_speckle_size, max_diff, invalid_disparity, workspace) -> None:
+    dev = disp.device.index
+    check(LIB.smx_filter_speckles(dev, n, H, W, disp.data_ptr(), out.data_ptr(), int(max_speckle_size), float(max_diff),
+                                  float(invalid_disparity), workspace.data_ptr(), workspace.numel(),
+                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def _launch_fill_invalid(disp, out, n, H, W, invalid_disparity, workspace) -> None:
+    dev = disp.device.index
+    check(LIB.smx_fill_invalid(dev, n, H, W, disp.data_ptr(), out.data_ptr(), float(invalid_disparity),
+                               workspace.data_ptr(), workspace.numel(),
+                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def _check_speckle_size(max_speckle_size) -> None:
+    if isinstance(max_speckle_size, bool) or not isinstance(max_speckle_size, int):
+        raise TypeError("max_speckle_size must be an int")
+    if not 0 <= max_speckle_size <= 2**31 - 1:
+        raise RuntimeError(f"max_speckle_size must be in [0, 2**31 - 1], got {max_speckle_size}")
+
+
+def filter_speckles(disp: torch.Tensor, *, max_speckle_size: int, max_diff: float = 1.0,
+                    invalid_disparity: float = -1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Speckle filter (smx_filter_speckles) on the current stream: every connected region of valid pixels whose
+    4-neighbours differ by at most max_diff, of max_speckle_size pixels or fewer, becomes invalid_disparity; every other
+    pixel is copied.  disp: [H,W] or [n,H,W] float32 on a GPU (the n maps are independent).  `out` may be disp."""
+    _check_speckle_size(max_speckle_size)
+    _check_lr_scalars(max_diff, invalid_disparity)
+    out, n, H, W = _postprocess_operands(disp, out)
+    _launch_filter_speckles(disp, out, n, H, W, max_speckle_size, max_diff, invalid_disparity,
+                            _postprocess_workspace(n, H, W, disp.device))
+    return out
+
+
+def fill_invalid(disp: torch.Tensor, *, invalid_disparity: float = -1.0,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Background hole fill (smx_fill_invalid) on the current stream: every non-valid pixel takes the smaller of the
+    nearest valid values to its left and right in its row; rows without a valid pixel take the smaller of the nearest
+    non-empty rows above and below.  disp: [H,W] or [n,H,W] float32 on a GPU.  `out` may be disp."""
+    _check_lr_scalars(0.0, invalid_disparity)
+    out, n, H, W = _postprocess_operands(disp, out)
+    _launch_fill_invalid(disp, out, n, H, W, invalid_disparity, _postprocess_workspace(n, H, W, disp.device))
+    return out
+
+
 class StereoMatching:
     """torch_extension_module.cc:22-26.  `compute_disparity_map` is the reference method;
     the keyword-only constructor extras and the *_gray / *_batch methods are additions that

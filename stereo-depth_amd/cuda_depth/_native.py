@@ -92,6 +92,14 @@ EXPORTS = {
     # (device_id, n, H, W, left_disp, right_disp, out, max_diff, invalid_disparity, stream)
     "smx_lr_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                C.c_float, C.c_void_p]),
+    # post-processing: (n, H, W) -> workspace bytes;
+    # (device_id, n, H, W, in, out, max_speckle_size, max_diff, invalid_disparity, workspace, workspace_bytes, stream)
+    "smx_postprocess_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_filter_speckles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (device_id, n, H, W, in, out, invalid_disparity, workspace, workspace_bytes, stream)
+    "smx_fill_invalid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
 }
 
 STREAM_ENGINE = C.c_void_p(-1)          # SMX_STREAM_ENGINE: the engine's own streams

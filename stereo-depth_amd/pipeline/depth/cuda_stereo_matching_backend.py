@@ -27,14 +27,25 @@ def _device_frame(image: torch.Tensor) -> torch.Tensor:
 class CudaStereoMatchingBackend(StereoMatching):
     """left_right_check=True: every map is left-right checked (StereoMatching.compute_disparity_map_batch_lr, one pair
     plus its mirrored twin per call, hence max_batch=2): pixels whose match in the right image does not point back to
-    them within lr_max_diff pixels -- occlusions, the band left of min_disparity -- become invalid_disparity."""
+    them within lr_max_diff pixels -- occlusions, the band left of min_disparity -- become invalid_disparity.
+    speckle_max_size > 0: then the speckle filter (cuda_depth.filter_speckles) removes every region of speckle_max_size
+    pixels or fewer whose 4-neighbours differ by at most speckle_max_diff.  fill_invalid=True: then the background hole
+    fill (cuda_depth.fill_invalid) makes the map dense again.  Both run in place on the returned map, on the current
+    stream, with a workspace allocated once; with the defaults neither runs."""
 
     def __init__(self, configuration: Optional["cuda_depth.StereoMatchingConfiguration"] = None, *,
-                 left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0):
+                 left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0,
+                 speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)
         self._invalid_disparity = float(invalid_disparity)
+        cuda_depth._check_speckle_size(speckle_max_size)
+        cuda_depth._check_lr_scalars(speckle_max_diff, invalid_disparity)
+        self._speckle_max_size = speckle_max_size
+        self._speckle_max_diff = float(speckle_max_diff)
+        self._fill_invalid = bool(fill_invalid)
+        self._post_workspace: Optional[torch.Tensor] = None
         if self._left_right_check:
             self._stereo_algo = cuda_depth.StereoMatching(configuration, max_batch=2)
         else:
@@ -45,7 +56,22 @@ class CudaStereoMatchingBackend(StereoMatching):
         if left.dtype != right.dtype:                       # mixed inputs: fall back to float for both
             left, right = left.float(), right.float()
         if self._left_right_check:
-            return self._stereo_algo.compute_disparity_map_batch_lr(
+            disparity = self._stereo_algo.compute_disparity_map_batch_lr(
                 left.unsqueeze(0), right.unsqueeze(0), max_diff=self._lr_max_diff,
                 invalid_disparity=self._invalid_disparity)[0]
-        return self._stereo_algo.compute_disparity_map(left, right)
+        else:
+            disparity = self._stereo_algo.compute_disparity_map(left, right)
+        if self._speckle_max_size > 0 or self._fill_invalid:
+            self._postprocess(disparity)
+        return disparity
+
+    def _postprocess(self, disparity: torch.Tensor) -> None:
+        H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
+        if self._post_workspace is None:
+            self._post_workspace = cuda_depth._postprocess_workspace(1, H, W, disparity.device)
+        if self._speckle_max_size > 0:
+            cuda_depth._launch_filter_speckles(disparity, disparity, 1, H, W, self._speckle_max_size,
+                                               self._speckle_max_diff, self._invalid_disparity, self._post_workspace)
+        if self._fill_invalid:
+            cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,
+                                            self._post_workspace)

@@ -69,12 +69,12 @@ class DepthEstimationPipelineContext:
     frame_index: int
 
 
-def _make_backend(config: DepthEstimationPipelineConfig) -> StereoMatching:
+def _make_backend(config: DepthEstimationPipelineConfig, **post: Any) -> StereoMatching:
     name = config.stereo_matching_backend
     if name == "cuda":
         return CudaStereoMatchingBackend(configuration=config.engine_configuration(),
                                          left_right_check=config.left_right_check, lr_max_diff=config.lr_max_diff,
-                                         invalid_disparity=config.invalid_disparity)
+                                         invalid_disparity=config.invalid_disparity, **post)
     if name in AVAILABLE_DNN_BACKENDS:
         raise RuntimeError(f"Stereo matching backend '{name}' (traced DNN) is not part of this build; use 'cuda'.")
     raise RuntimeError(f"Unsupported stereo matching backend: {name}")
@@ -82,9 +82,13 @@ def _make_backend(config: DepthEstimationPipelineConfig) -> StereoMatching:
 
 class DepthEstimationPipeline:
 
-    def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None):
+    def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
+                 speckle_max_diff: float = 1.0, fill_invalid: bool = False):
+        """speckle_max_size / speckle_max_diff / fill_invalid: post-processing of the 'cuda' backend's map, after the
+        left-right check if configured (CudaStereoMatchingBackend); with the defaults the map is returned as computed."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
-        self._stereo_matching = _make_backend(self._config)
+        self._stereo_matching = _make_backend(self._config, speckle_max_size=speckle_max_size,
+                                              speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
     def get_configuration(self) -> DepthEstimationPipelineConfig:

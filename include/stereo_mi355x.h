@@ -238,7 +238,7 @@ typedef enum smx_match_kernel {
     SMX_KERNEL_EXACT_ONLY = 0,      /* configuration outside the FAST_GRID envelope                         */
     SMX_KERNEL_FAST_WINDOW = 1,     /* one 64-column window per wave, tall bands                             */
     SMX_KERNEL_FAST_SPLIT = 2,      /* few pairs in flight: short bands, disparity range split over 4 waves  */
-    SMX_KERNEL_FAST_WIDE = 3        /* one workgroup per CU, 12 waves exchanging through workgroup-wide rows  */
+    SMX_KERNEL_FAST_WIDE = 3        /* reserved (a removed workgroup-wide kernel, NOTES.md): never reported  */
 } smx_match_kernel;
 typedef struct smx_match_geometry {
     int32_t kernel;                 /* smx_match_kernel */
@@ -249,9 +249,9 @@ typedef struct smx_match_geometry {
 } smx_match_geometry;
 int smx_get_match_geometry(const smx_engine *engine, int n, smx_match_geometry *out);
 
-/* What the library was built with: SMX_FEATURE_EXPERIMENTAL = the two opt-in negative-result kernels (workgroup-wide
- * aggregation, fused steps 6-9; NOTES.md) are compiled in and can be switched on through SMX_ENABLE_WIDE=1 /
- * SMX_FUSED_REFINE_FILL=1 (read once, in smx_create).  The product build has neither. */
+/* Optional features the library was built with, as a bit set.  No optional feature is currently compiled in: the
+ * result is 0.  SMX_FEATURE_EXPERIMENTAL is reserved (it marked builds with two negative-result kernels, since removed;
+ * NOTES.md) and never reported. */
 #define SMX_FEATURE_EXPERIMENTAL 1
 int smx_build_features(void);
 

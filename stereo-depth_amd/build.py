@@ -1,12 +1,10 @@
 """Builds libstereo_mi355x.so (hand-written HIP for gfx950) in-tree with hipcc.
 
-    python stereo-depth_amd/build.py [--force] [--experimental] [-v]
+    python stereo-depth_amd/build.py [--force] [-v]
 
 Every csrc/*.hip is one translation unit (the engine plus one per kernel family, smx_launch.h); they are
 compiled in parallel into csrc/build/*.o and linked.  A unit is rebuilt when it, one of the headers it
-includes (hipcc -MD) or the flags changed.  --experimental (or SMX_EXPERIMENTAL=1) adds -DSMX_EXPERIMENTAL: the two
-opt-in negative-result kernels (k_match_wide.h, k_refine_fill.h) are then compiled in; the product library holds
-neither.
+includes (hipcc -MD) or the flags changed.
 
 -ffp-contract=off is part of the numerical contract: the kernels must evaluate
 a*b+c exactly like the CPU oracle, i.e. without fused multiply-add.
@@ -46,9 +44,9 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
-def _flags(experimental: bool):
+def _flags():
     extra = os.environ.get("SMX_EXTRA_FLAGS", "").split()      # kernel tuning experiments only
-    return FLAGS + (["-DSMX_EXPERIMENTAL"] if experimental else []) + extra + ["-I", INCLUDE]
+    return FLAGS + extra + ["-I", INCLUDE]
 
 
 def _deps(depfile: str):
@@ -74,16 +72,14 @@ def _stale(src: str, obj: str, stamp: str) -> bool:
     return any((not os.path.exists(d)) or os.path.getmtime(d) > t for d in deps + [src])
 
 
-def build(force: bool = False, verbose: bool = False, experimental: bool | None = None, variant: str = "") -> str:
+def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
     """variant: kernel experiments -- the library goes to libstereo_mi355x.<variant>.so (objects to csrc/build/<variant>/),
     built with SMX_EXTRA_FLAGS; load it through SMX_LIB_PATH (cuda_depth/_native.py).  The product library has no variant."""
     global LIB, OBJ
-    if experimental is None:
-        experimental = os.environ.get("SMX_EXPERIMENTAL") == "1"
     if variant:
         LIB = os.path.join(HERE, f"libstereo_mi355x.{variant}.so")
         OBJ = os.path.join(CSRC, "build", variant)
-    cc, flags = hipcc(), _flags(experimental)
+    cc, flags = hipcc(), _flags()
     stamp = hashlib.sha256(" ".join([cc] + flags + [repr(sorted(PER_FILE_FLAGS.items()))]).encode()).hexdigest()
     # fast path (the GPU box gets the built library but not the object files): the library is newer than every
     # source and was linked with these flags
@@ -131,5 +127,4 @@ def build(force: bool = False, verbose: bool = False, experimental: bool | None 
 
 if __name__ == "__main__":
     variant = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--variant=")), "")
-    print(build(force="--force" in sys.argv, verbose="-v" in sys.argv or "--force" in sys.argv,
-                experimental=True if "--experimental" in sys.argv else None, variant=variant))
+    print(build(force="--force" in sys.argv, verbose="-v" in sys.argv or "--force" in sys.argv, variant=variant))

@@ -424,8 +424,8 @@ __global__ __launch_bounds__(256) void k_refine_int(RefineParams p) {
 // to pairs of rows (13 rows per 2 pixels) and then to the per-pixel route (surface edges, noise).
 constexpr int RV = 4;
 
-// The RV pooled pixels (xg .. xg+RV-1, y) of pair b (xg: the same for all lanes of a wave); xg may be -1 (the halo row of the first tile row of the
-// fused refine + fill kernel): rows outside the image are computed as shadows and not delivered.
+// The RV pooled pixels (xg .. xg+RV-1, y) of pair b (xg: the same for all lanes of a wave); rows outside the image, below
+// (xg = -1 is clamped to row 0) or past it, are computed as shadows and not delivered.
 // sink(v, x, value) receives the refined value of pixel (x = xg + v, y).
 template <int KT, bool SX, typename SINK>
 __device__ __forceinline__ void refine_int_v_core(const RefineParams &p, int b, int y, int xg_lane, SINK &&sink) {

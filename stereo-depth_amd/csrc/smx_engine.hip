@@ -27,9 +27,6 @@
 #include "k_match_filter.h"
 #include "k_match_capture.h"
 #include "k_match_fast.h"
-#ifdef SMX_EXPERIMENTAL
-#include "k_match_wide.h"
-#endif
 #include "k_prologue.h"
 #include "k_refine.h"
 #include "smx_common.h"
@@ -107,6 +104,65 @@ struct HostHints {
     unsigned long long fast_density[2];     // per stream lane: (seq << 32) | float bits: second-pass marches / first-pass marches of the last sparse fast launch
 };
 
+// A launch-plan choice between a default and an alternative route that follows what earlier calls' kernels reported through
+// one HostHints word per stream lane.  Above `hi` the engine takes the alternative and probes the default route every
+// `period` calls (16, doubling to 64 while the probes keep failing); below `lo` it comes back.  A forced choice is the
+// caller's business: it does not call decide(), so the countdown stands still, and reports are observed all the same.
+struct ContentSwitch {
+    static constexpr int LANES = 2;               // one report word per stream lane (smx_engine::LANES)
+    float hi, lo;
+    bool on = false;                              // the alternative is the current choice
+    int period = 16, countdown = 0;
+    bool pending = false;                         // a probe call has been issued and its report has not been evaluated yet
+    unsigned seq = 0, seen[LANES] = {0, 0};       // last sequence number handed to a launch / seen per lane
+    float last = -1.f;                            // the last observation, -1: none yet
+
+    // Takes the reports that have arrived by now (no synchronisation: whatever has arrived, has arrived).  The two halves
+    // of a split call report separately: they are ONE observation.  Returns whether anything was fresh.
+    bool observe(const unsigned long long (&words)[LANES]) {
+        float sum = 0.f;
+        int fresh = 0;
+        for (int k = 0; k < LANES; ++k) {
+            const unsigned long long w = *(const volatile unsigned long long *)&words[k];
+            const unsigned sq = (unsigned)(w >> 32);
+            if (sq == 0 || sq == seen[k]) continue;
+            seen[k] = sq;
+            const unsigned bits = (unsigned)(w & 0xffffffffull);
+            float v;
+            std::memcpy(&v, &bits, sizeof(v));
+            sum += v;
+            fresh++;
+        }
+        if (!fresh) return false;
+        last = sum / (float)fresh;
+        if (!on && last > hi) {
+            on = true;
+            period = 16;
+            countdown = period;
+        } else if (on && last < lo) {
+            on = false;
+        } else if (on && pending && period < 64) {   // a probe that failed: look again later (once per probe,
+            period *= 2;                              // however many reports its halves send, whenever they arrive)
+        }
+        pending = false;
+        return true;
+    }
+    // The route of the call being enqueued: true = the alternative.  While `on`, every period-th call is a probe: it takes
+    // the default route, which reports what it found.
+    bool decide() {
+        if (!on) return false;
+        if (--countdown > 0) return true;
+        countdown = period;
+        pending = true;
+        return false;
+    }
+    // Sequence number for the next reporting launch (0 means "nothing reported").
+    unsigned next_seq() {
+        if (++seq == 0) seq = 1;
+        return seq;
+    }
+};
+
 struct smx_engine {
     smx_config cfg;
     smx_dims dm;
@@ -146,35 +202,31 @@ struct smx_engine {
     bool last_gray_owned = false;                 // false after the f32 gray entry: those are the caller's buffers
     size_t last_gplane = 0;
     // environment switches, read once in smx_create
-    bool opt_wide = false;                        // SMX_ENABLE_WIDE=1 (library built with SMX_EXPERIMENTAL only)
-    bool opt_fused_refine_fill = false;           // SMX_FUSED_REFINE_FILL=1 (ditto)
     int opt_lane_priority = 1;                    // SMX_LANE_PRIORITY=0: lane streams at default priority (A/B runs)
+    int opt_fast_dense = -1;                      // SMX_FAST_DENSE=1 / 0: always / never the dense form of the fast kernel (tests, A/B); -1: by content
+    int opt_fast_dense_small = -1;                // SMX_FAST_DENSE_SMALL=1 / 0: the latency shape at 12-row bands always / never takes its dense form (tests, A/B); -1: by content
+    bool opt_debug_hints = false;                 // SMX_DEBUG_HINTS: print every report of the sparse fast kernel to stderr
+    HostHints *hints = nullptr, *hints_dev = nullptr;     // pinned host memory / its device address
     // Content-aware route of off-grid (RGB) batches.  The filtered route pays a fixed filter pass to evaluate fewer
     // disparities in exact order; on real scenes (flat cost curves in untextured and occluded regions) the candidate
     // sets cover most of the range and the dense kernel alone is faster.  The sparse kernel reports the density of
-    // every filtered launch through `hints`; above FILTER_RHO_HI the engine goes dense and probes the filtered route
-    // every probe_period calls (16, doubling to 64 while the probes keep failing), below FILTER_RHO_LO it comes back.
-    HostHints *hints = nullptr, *hints_dev = nullptr;     // pinned host memory / its device address
+    // every filtered launch (hints->filter_density); filt.on: the dense route.
+    // Break-even density, measured (profiles/r03_rgb_routes.txt, 32 pairs per call): the filter's two passes cost 0.89-0.93 ms,
+    // the sparse kernel 0.19 ms + 1.1 x density x the dense kernel's 2.24-2.7 ms: the routes tie at a density of 0.45 (C5,
+    // 96 disparities) to 0.56 (the reference's pair at its calibrated range, which reports 0.65 and loses 12 % filtered).
+    ContentSwitch filt{0.50f, 0.40f};             // hi, lo
     unsigned *stats_dev = nullptr;                // [LANES][2] counters of the sparse kernel
-    bool route_dense = false;
-    int probe_period = 16, probe_countdown = 0;
-    bool probe_pending = false;                   // a probe call has been issued and its report has not been evaluated yet
-    unsigned filt_seq = 0, seen_seq[2] = {0, 0};
-    float last_density = -1.f;
     bool call_use_filter = true;                  // decision for the call being enqueued (both halves alike)
-    int opt_fast_dense = -1;                      // SMX_FAST_DENSE=1 / 0: always / never the dense form of the fast kernel (tests, A/B); -1: by content
-    int opt_fast_dense_small = -1;                // SMX_FAST_DENSE_SMALL=1 / 0: the latency shape at 12-row bands always / never takes its dense form (tests, A/B); -1: by content
-    bool call_fast_dense = false;                 // ... decision for the call being enqueued
-    // By content: the sparse form reports which share of the disparities its second pass revisited (banded surfaces 0.05,
-    // scene-like 0.17, real texture / noise ~1).  The dense form costs what ~0.13 costs the sparse one: above FAST_DENSE_HI the
-    // engine switches to it, probes the sparse form every fast_probe_period calls (16, doubling to 64 while the probes keep
-    // saying "dense") and comes back below FAST_DENSE_LO.
+    // Form of the fast kernel by content: the sparse form reports which share of the disparities its second pass revisited
+    // (hints->fast_density; banded surfaces 0.05, scene-like 0.17, real texture / noise ~1); fast.on: the dense form.
+    // Measured per 64 C2 pairs (tools/content_breakdown.py, SMX_DEBUG_HINTS=1): the sparse form takes 0.68 ms at a ratio of 0.047
+    // (banded surfaces), 0.85 at 0.166 (scene-like ramp) and 1.20 at 0.97 (noise) -- the first marches of the second pass are the
+    // expensive ones, they deliver to many rows -- the dense form 0.80 ms whatever the content: the curves cross near 0.13.
+    // (The latency shape's curves cross lower -- its dense form costs a banded C2 frame 0.3 us and saves a scene-like one 8 -- and
+    // its windows are 12 rows, not 27: the same ramp reports 0.133 there.  One pair of thresholds a little below the crossing.)
+    ContentSwitch fast{0.10f, 0.07f};             // hi, lo
     unsigned long long *fast_stats_dev = nullptr; // [LANES] device counters of the sparse form's report
-    bool fast_dense = false;
-    int fast_probe_period = 16, fast_probe_countdown = 0;
-    bool fast_probe_pending = false;
-    unsigned fast_seq = 0, fast_seen_seq[2] = {0, 0};
-    float fast_last_ratio = -1.f;
+    bool call_fast_dense = false;                 // decision for the call being enqueued
     bool fast_stats_pending = false;              // the aggregation launch of the half being enqueued reports: its fill launch publishes
     bool call_on_lanes = false;                   // the call being enqueued runs on the stream lanes
     int call_grid_hint = -1;                      // f32 gray, few pairs: the last reported call was on (0) / off (1) the exact grid; -1: no report yet
@@ -215,13 +267,9 @@ struct smx_engine {
     size_t lr_pair_bytes = 0;
     float *lr_raw = nullptr;                      // [B][H][W]
 };
+static_assert(ContentSwitch::LANES == smx_engine::LANES, "one report word per stream lane");
 
 namespace {
-
-// Break-even density, measured (profiles/r03_rgb_routes.txt, 32 pairs per call): the filter's two passes cost 0.89-0.93 ms,
-// the sparse kernel 0.19 ms + 1.1 x density x the dense kernel's 2.24-2.7 ms: the routes tie at a density of 0.45 (C5,
-// 96 disparities) to 0.56 (the reference's pair at its calibrated range, which reports 0.65 and loses 12 % filtered).
-constexpr float FILTER_RHO_HI = 0.50f, FILTER_RHO_LO = 0.40f;
 
 void free_events(smx_engine *e) {
     for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
@@ -273,9 +321,6 @@ hipError_t raise_lds_caps(int device) {
         if (d == device) return hipSuccess;
     if (hipError_t e = smx::exact_raise_lds_caps(SMX_EXACT2_LDS_CAP + (int)((smx::E2_CAPBITS + 2 * smx::E2_SPARSE_WORDS) * sizeof(unsigned)));
         e != hipSuccess) return e;
-#ifdef SMX_EXPERIMENTAL
-    if (hipError_t e = smx::wide_raise_caps(); e != hipSuccess) return e;
-#endif
     if (hipError_t e = smx::match_auto_raise_caps(); e != hipSuccess) return e;
     done.push_back(device);
     return hipSuccess;
@@ -286,12 +331,6 @@ bool env_is(const char *name, char c) {
     return v && v[0] == c;
 }
 
-#ifdef SMX_EXPERIMENTAL
-bool use_wide(const smx_engine *e, const smx::MatchParams &mp, int n) { return e->opt_wide && smx::wide_applicable(mp, n); }
-#endif
-
-// FAST_GRID aggregation: the wave-per-window kernel (short bands / disparity split for few pairs in flight,
-// right-tile chunks for wide ranges); experimental builds: the workgroup-wide kernel on request.
 // Which form of the fast kernel a call takes (k_match_fast.h DENSE: the pass that keeps the winner's neighbours instead of
 // fetching them in a sparse second pass; min_disparity = 0 only), and -- for the sparse form -- where its second pass reports
 // how much it revisited.  Both shapes that have a dense form follow the same per-call decision (call_fast_dense): the
@@ -318,15 +357,11 @@ void plan_fast_form(smx_engine *e, smx::MatchParams &mp, int n) {
     e->fast_stats_pending = true;            // ... published by this call's fill launch (enqueue_range)
 }
 
+// FAST_GRID aggregation: the wave-per-window kernel (short bands / disparity split for few pairs in flight,
+// right-tile chunks for wide ranges).
 void launch_fast(smx_engine *e, const smx::MatchParams &mp_in, int n, hipStream_t s) {
     smx::MatchParams mp = mp_in;
     plan_fast_form(e, mp, n);
-#ifdef SMX_EXPERIMENTAL
-    if (use_wide(e, mp, n)) {
-        smx::launch_match_wide_tu(mp, n, s);
-        return;
-    }
-#endif
     smx::launch_match_fast(mp, n, e->cus, s);
 }
 
@@ -391,80 +426,14 @@ bool stream_capturing(hipStream_t s) {
     return st != hipStreamCaptureStatusNone;
 }
 
-// Reads the hint words the kernels of earlier calls have published by now and settles the launch plans of the call
-// that is about to be enqueued (no synchronisation: whatever has arrived, has arrived).
-// Second-pass marches per first-pass march above which the dense form of the fast kernel is the faster one, with hysteresis.
-// Measured per 64 C2 pairs (tools/content_breakdown.py, SMX_DEBUG_HINTS=1): the sparse form takes 0.68 ms at a ratio of 0.047
-// (banded surfaces), 0.85 at 0.166 (scene-like ramp) and 1.20 at 0.97 (noise) -- the first marches of the second pass are the
-// expensive ones, they deliver to many rows -- the dense form 0.80 ms whatever the content: the curves cross near 0.13.
-// (The latency shape's curves cross lower -- its dense form costs a banded C2 frame 0.3 us and saves a scene-like one 8 -- and
-// its windows are 12 rows, not 27: the same ramp reports 0.133 there.  One pair of thresholds a little below the crossing.)
-constexpr float FAST_DENSE_HI = 0.10f, FAST_DENSE_LO = 0.07f;
-
+// Reads the hint words the kernels of earlier calls have published by now into the state the launch plans of the next
+// call follow: the two content switches and the grid hint.
 void read_hints(smx_engine *e) {
     if (!e->hints) return;
-    // the two halves of a split call report separately (one word per lane): they are ONE observation
-    float rho_sum = 0.f;
-    int fresh = 0;
-    for (int k = 0; k < smx_engine::LANES; ++k) {
-        const unsigned long long w = *(volatile unsigned long long *)&e->hints->filter_density[k];
-        const unsigned seq = (unsigned)(w >> 32);
-        if (seq == 0 || seq == e->seen_seq[k]) continue;
-        e->seen_seq[k] = seq;
-        unsigned bits = (unsigned)(w & 0xffffffffull);
-        float rho;
-        std::memcpy(&rho, &bits, sizeof(rho));
-        rho_sum += rho;
-        fresh++;
-    }
-    if (fresh) {
-        const float rho = rho_sum / (float)fresh;
-        e->last_density = rho;
-        if (!e->route_dense) {
-            if (rho > FILTER_RHO_HI) {
-                e->route_dense = true;
-                e->probe_period = 16;
-                e->probe_countdown = e->probe_period;
-            }
-        } else if (rho < FILTER_RHO_LO) {
-            e->route_dense = false;
-        } else if (e->probe_pending && e->probe_period < 64) {       // a probe that failed: look again later (once per probe,
-            e->probe_period *= 2;                                    // however many reports its halves send, whenever they arrive)
-        }
-        e->probe_pending = false;
-    }
-    {   // the sparse fast kernel's report (the two halves of a split call are ONE observation)
-        float sum = 0.f;
-        int got = 0;
-        for (int k = 0; k < smx_engine::LANES; ++k) {
-            const unsigned long long w = *(volatile unsigned long long *)&e->hints->fast_density[k];
-            const unsigned seq = (unsigned)(w >> 32);
-            if (seq == 0 || seq == e->fast_seen_seq[k]) continue;
-            e->fast_seen_seq[k] = seq;
-            unsigned bits = (unsigned)(w & 0xffffffffull);
-            float r;
-            std::memcpy(&r, &bits, sizeof(r));
-            sum += r;
-            got++;
-        }
-        if (got) {
-            const float r = sum / (float)got;
-            e->fast_last_ratio = r;
-            if (std::getenv("SMX_DEBUG_HINTS")) std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", r, e->fast_dense ? 1 : 0);
-            if (!e->fast_dense) {
-                if (r > FAST_DENSE_HI) {
-                    e->fast_dense = true;
-                    e->fast_probe_period = 16;
-                    e->fast_probe_countdown = e->fast_probe_period;
-                }
-            } else if (r < FAST_DENSE_LO) {
-                e->fast_dense = false;
-            } else if (e->fast_probe_pending && e->fast_probe_period < 64) {
-                e->fast_probe_period *= 2;
-            }
-            e->fast_probe_pending = false;
-        }
-    }
+    e->filt.observe(e->hints->filter_density);
+    const bool was_dense = e->fast.on;
+    if (e->fast.observe(e->hints->fast_density) && e->opt_debug_hints)
+        std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", e->fast.last, was_dense ? 1 : 0);
     const unsigned long long g = *(volatile unsigned long long *)&e->hints->grid;
     e->call_grid_hint = g == 0ull ? -1 : (int)(g & 1ull);      // (the word carries the call counter, which starts at 1: 0 = nothing reported)
 }
@@ -564,10 +533,9 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
         }
         SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
         const int lane = e->cur_lane;
-        if (++e->filt_seq == 0) e->filt_seq = 1;
         smx::launch_exact2_sparse(e->xp, mp, n, v.cand, e->cand_cw, (const int *)v.flags2,
                                   e->stats_dev ? e->stats_dev + 2 * lane : nullptr,
-                                  e->hints_dev ? &e->hints_dev->filter_density[lane] : nullptr, e->filt_seq, s);
+                                  e->hints_dev ? &e->hints_dev->filter_density[lane] : nullptr, e->filt.next_seq(), s);
         if (e->capture) smx::launch_exact2_capture(e->xp, mp, n, false, e->cus, s);   // dmin > 0: the lookups of step 6
     } else if (mode == SMX_MATCH_EXACT_ORDER) {
         SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
@@ -627,28 +595,16 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     fp.K = d.K; fp.h = d.h; fp.w = d.w; fp.thr = (float)e->cfg.threshold;
     fp.log2k = 0;
     while ((1 << fp.log2k) < d.K) fp.log2k++;
-    bool filled = false;          // steps 7-9 already done by the fused refine + fill launch (experimental builds)
     {
         SlotTimer tm(e, s, SMX_KERNEL_REFINE);
         const int kt = (rp.R == 5 && (d.K == 1 || d.K == 2 || d.K == 4)) ? d.K : 0;
-        auto fused = [&](bool auto_mode) -> bool {
-#ifdef SMX_EXPERIMENTAL
-            if (n > 4 && e->opt_fused_refine_fill) {
-                smx::launch_refine_fill(auto_mode, d.K, rp, fp, n, s);
-                filled = true;
-                return true;
-            }
-#endif
-            (void)auto_mode;
-            return false;
-        };
         // integer-valued gray -> v_sad_u8 kernel; otherwise the float kernel (same results)
         if (kt == 0 || e->pitch8 == 0 || rgb_in) {
             smx::launch_refine(smx::REFINE_FLOAT, kt, apron, rp, n, s);
         } else if (in_mode == smx::IN_GRAY_U8) {
             // u8 is integer-valued by construction; the prologue wrote the padded copy.  Batches: four pooled rows per
             // thread share their row SADs (k_refine_int_v)
-            if (!fused(false)) smx::launch_refine(n > 4 ? smx::REFINE_INT_V : smx::REFINE_INT, kt, false, rp, n, s);
+            smx::launch_refine(n > 4 ? smx::REFINE_INT_V : smx::REFINE_INT, kt, false, rp, n, s);
         } else if (n <= 4) {   // f32 gray, few pairs: one launch picks per pair (k_refine_auto) and reports the grid flag
             rp.grid_flags = v.flags;
             rp.grid_hint = (whole_call && e->hints_dev) ? &e->hints_dev->grid : nullptr;
@@ -656,18 +612,17 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
         } else {   // f32 gray batches: the prologue wrote u8 copies and the per-pair integrality flag; one launch
             // branches on it per pair (k_refine_auto_v: a gated-out launch of the float kernel still has to be placed on
             // a chip the other lane fills, and the lane's chain waits for it)
-            if (!fused(true)) smx::launch_refine(smx::REFINE_AUTO_V, kt, false, rp, n, s);
+            smx::launch_refine(smx::REFINE_AUTO_V, kt, false, rp, n, s);
         }
     }
-    if (e->fast_stats_pending && !filled && e->hints_dev) {
-        if (++e->fast_seq == 0) e->fast_seq = 1;
+    if (e->fast_stats_pending && e->hints_dev) {
         fp.fast_stats = e->fast_stats_dev + e->cur_lane;
         fp.fast_stats_host = &e->hints_dev->fast_density[e->cur_lane];
-        fp.fast_seq = e->fast_seq;
+        fp.fast_seq = e->fast.next_seq();
         fp.fast_pass1 = (d.Dd + 1) / 2;
     }
     e->fast_stats_pending = false;
-    if (!filled) {
+    {
         SlotTimer tm(e, s, SMX_KERNEL_FILL);
         smx::launch_fill(fp, n, e->call_on_lanes && n > 4 ? 4 : 8, s);
     }
@@ -809,25 +764,9 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     e->call_on_lanes = detached;
     // launch plans that depend on what earlier calls saw (hints only: every plan gives the same bits)
     read_hints(e);
-    e->call_fast_dense = e->opt_fast_dense == 1;
-    if (e->opt_fast_dense < 0 && e->fast_dense) {
-        e->call_fast_dense = true;
-        if (--e->fast_probe_countdown <= 0) {    // probe: one call in the sparse form, which reports what it found
-            e->fast_probe_countdown = e->fast_probe_period;
-            e->call_fast_dense = false;
-            e->fast_probe_pending = true;
-        }
-    }
-    e->call_use_filter = true;
-    if (e->cfg.exact_filter < 0) e->call_use_filter = false;
-    else if (e->cfg.exact_filter == 0 && e->route_dense) {
-        e->call_use_filter = false;
-        if (--e->probe_countdown <= 0) {         // probe: has the content changed?
-            e->probe_countdown = e->probe_period;
-            e->call_use_filter = true;
-            e->probe_pending = true;
-        }
-    }
+    // (a forced choice -- SMX_FAST_DENSE, exact_filter = 1 / -1 -- leaves its switch's countdown alone)
+    e->call_fast_dense = e->opt_fast_dense >= 0 ? e->opt_fast_dense == 1 : e->fast.decide();
+    e->call_use_filter = e->cfg.exact_filter == 0 ? !e->filt.decide() : e->cfg.exact_filter > 0;
     // The two lanes run unordered against each other, which is safe only while they work on disjoint pairs of the engine's
     // buffers (steady state: lane 0 always [0, n/2), lane 1 always [n/2, n)).  When a call's split differs from what the
     // other lane has in flight, that lane's tail is waited for first.
@@ -1118,16 +1057,14 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     // environment switches are read here, once (never per call)
     e->overlap_min = cfg->overlap_min_pairs < 0 ? 0
                      : (cfg->overlap_min_pairs > 0 ? (cfg->overlap_min_pairs < 2 ? 2 : cfg->overlap_min_pairs) : overlap_min_pairs_default(d, e->cus));
-    e->opt_wide = env_is("SMX_ENABLE_WIDE", '1');
-    e->opt_fused_refine_fill = env_is("SMX_FUSED_REFINE_FILL", '1');
     e->opt_lane_priority = env_is("SMX_LANE_PRIORITY", '0') ? 0 : 1;
     e->opt_fast_dense = env_is("SMX_FAST_DENSE", '1') ? 1 : (env_is("SMX_FAST_DENSE", '0') ? 0 : -1);
     e->opt_fast_dense_small = env_is("SMX_FAST_DENSE_SMALL", '1') ? 1 : (env_is("SMX_FAST_DENSE_SMALL", '0') ? 0 : -1);
+    e->opt_debug_hints = std::getenv("SMX_DEBUG_HINTS") != nullptr;
     if (const char *v = std::getenv("SMX_TEST_EPOCH_START")) {      // tests only: start the call counter near its wrap
         const long k = std::atol(v);
         if (k > 0 && k < 0x7fffffffL) e->epoch = (int)k;
     }
-    const bool filter_env_off = env_is("SMX_FILTERED_EXACT", '0');      // A/B runs: never the filtered route
     const size_t B = (size_t)e->B, hw = (size_t)d.h * d.w;
     hipError_t err = hipSuccess;
     auto alloc = [&](void **p, size_t bytes) {
@@ -1188,7 +1125,7 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     // (k_match_filter.h: filter_error_bound_units) is derived for exactly these radii -- 63 / 63 / 81 taps of a 3x3
     // cost -- and for grid units up to 64 (exact integer sums below 2^24): anything else takes the dense kernel.
     static_assert(smx::FILTER_TILE_H == smx::E2_TH && smx::FILTER_TILE_W == smx::E2_TW, "the filter marks exact-order tiles");
-    e->filter_ok = cfg->exact_filter >= 0 && !filter_env_off && e->fast_ok_host && e->default_radii && K * K <= 64 &&
+    e->filter_ok = cfg->exact_filter >= 0 && e->fast_ok_host && e->default_radii && K * K <= 64 &&
                    smx::filter_cand_words(d.Dd) <= smx::E2_SPARSE_WORDS;       // (&& no aggregated volume: checked below)
     if (e->filter_ok) {
         e->cand_tiles_x = (d.w + smx::E2_TW - 1) / smx::E2_TW;
@@ -1447,26 +1384,15 @@ int smx_get_match_geometry(const smx_engine *e, int n, smx_match_geometry *g) {
     mp.h = d.h; mp.w = d.w; mp.Dd = d.Dd; mp.dmin = d.dmin; mp.vol = e->vol; mp.pass1_only = e->capture ? 1 : 0;
     mp.on_lanes = e->call_on_lanes ? 1 : 0;        // the shape the engine's LAST call ran with (lanes or a caller's stream)
     if (mp.on_lanes && smx_overlap_lanes(e, n) == 2) n = (n + 1) / 2;      // ... a split call launches its halves
-    long waves, wgs;
-#ifdef SMX_EXPERIMENTAL
-    if (use_wide(e, mp, n)) {
-        g->kernel = SMX_KERNEL_FAST_WIDE;
-        g->band_rows = smx::MW_TH;
-        g->waves_per_workgroup = smx::MW_WAVES;
-        wgs = (long)((d.w + smx::MW_OUT - 1) / smx::MW_OUT) * ((d.h + smx::MW_NB * smx::MW_TH - 1) / (smx::MW_NB * smx::MW_TH));
-    } else
-#endif
-    {
-        const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
-        g->kernel = pl.small ? SMX_KERNEL_FAST_SPLIT : SMX_KERNEL_FAST_WINDOW;
-        g->band_rows = pl.th;
-        g->waves_per_workgroup = pl.small ? smx::FA_DS_WAVES : smx::FA_WAVES;
-        const int cols_per_wg = smx::FA_VALID * (pl.small ? 1 : smx::FA_WAVES);
-        wgs = (long)((d.w + cols_per_wg - 1) / cols_per_wg) * ((d.h + pl.th - 1) / pl.th);
-    }
+    const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
+    g->kernel = pl.small ? SMX_KERNEL_FAST_SPLIT : SMX_KERNEL_FAST_WINDOW;
+    g->band_rows = pl.th;
+    g->waves_per_workgroup = pl.small ? smx::FA_DS_WAVES : smx::FA_WAVES;
+    const int cols_per_wg = smx::FA_VALID * (pl.small ? 1 : smx::FA_WAVES);
+    const long wgs = (long)((d.w + cols_per_wg - 1) / cols_per_wg) * ((d.h + pl.th - 1) / pl.th);
     g->rows_marched = g->band_rows + 22;
     g->workgroups = (int)(wgs * n);
-    waves = wgs * g->waves_per_workgroup;
+    const long waves = wgs * g->waves_per_workgroup;
     // the disparity-split kernel spends its 4 waves on one window: a quarter of the range each
     const double lane_rows = (double)waves * 64.0 * g->rows_marched / (g->kernel == SMX_KERNEL_FAST_SPLIT ? (double)smx::FA_DS_WAVES : 1.0);
     g->useful_fraction = (double)d.h * d.w / lane_rows;
@@ -1475,26 +1401,20 @@ int smx_get_match_geometry(const smx_engine *e, int n, smx_match_geometry *g) {
     return SMX_OK;
 }
 
-int smx_build_features(void) {
-#ifdef SMX_EXPERIMENTAL
-    return SMX_FEATURE_EXPERIMENTAL;
-#else
-    return 0;
-#endif
-}
+int smx_build_features(void) { return 0; }
 
 int smx_get_route_info(smx_engine *e, smx_route_info *info) {
     if (!e || !info) return fail(SMX_ERR_INVALID_ARG, "smx_get_route_info: NULL argument");
     read_hints(e);
     std::memset(info, 0, sizeof(*info));
     info->filter_available = e->filter_ok ? 1 : 0;
-    info->route_dense = e->route_dense ? 1 : 0;
+    info->route_dense = e->filt.on ? 1 : 0;
     info->last_call_filtered = e->call_use_filter ? 1 : 0;
-    info->probe_period = e->probe_period;
-    info->candidate_density = e->last_density;
+    info->probe_period = e->filt.period;
+    info->candidate_density = e->filt.last;
     info->offgrid_hint = e->call_grid_hint;
     info->compute_units = e->cus;
-    info->fast_dense = e->fast_dense ? 1 : 0;
+    info->fast_dense = e->fast.on ? 1 : 0;
     return SMX_OK;
 }
 

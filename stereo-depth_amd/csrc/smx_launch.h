@@ -92,12 +92,4 @@ void launch_filter_speckles(int n, int H, int W, const float *in, float *out, in
                             void *workspace, hipStream_t s);
 void launch_fill_invalid(int n, int H, int W, const float *in, float *out, float invalid, void *workspace, hipStream_t s);
 
-#ifdef SMX_EXPERIMENTAL
-// ---- tu_experimental.hip: measured negative results kept for A/B runs (NOTES.md) --------------------------
-bool wide_applicable(const MatchParams &p, int n);
-void launch_match_wide_tu(const MatchParams &p, int n, hipStream_t s);
-hipError_t wide_raise_caps();
-void launch_refine_fill(bool auto_mode, int K, const RefineParams &rp, const FillParams &fp, int n, hipStream_t s);
-#endif
-
 }  // namespace smx

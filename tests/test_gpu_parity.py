@@ -628,9 +628,11 @@ def test_min_disparity_without_volume(cd, oracle_omp, case):
             assert np.array_equal(out[i], ref_out), f"pair {i}"
 
 
-# --- the workgroup-wide kernel (k_match_wide.h): one workgroup of 2 bands x 6 column waves per CU.  Correct but,
-#     with its wave-to-wave waits, not faster than the window-per-wave kernel (NOTES.md section 3.5): opt-in.
-WIDE_CASES = [
+# --- edge geometries of the throughput shape of the fast kernel (one 64-column window per wave, tall bands): column groups
+#     and bands that are nearly empty, the widest range one right tile holds, every K, an unpaired last disparity, noise.
+#     (The ids and row comments count in the geometry of a removed workgroup-wide kernel -- 342-column groups, two bands of
+#     24 rows, NOTES.md section 3.5; for 42-column windows the shapes leave partial last windows and bands as well.)
+THROUGHPUT_EDGE_CASES = [
     # id, H, W, K, dmin, dmax, n, kind, checked pairs
     ("two_column_groups_last_nearly_empty", 96, 700, 2, 0, 31, 128, "synthetic", (0, 1)),   # w = 350 = 342 + 8
     ("k1_partial_second_band", 30, 343, 1, 0, 68, 128, "odd", (0, 1)),                      # Dd = 69 (the most one right tile holds), h = 30: band 1 has 6 rows
@@ -641,11 +643,8 @@ WIDE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", WIDE_CASES, ids=[c[0] for c in WIDE_CASES])
-def test_wide_kernel(cd, oracle_omp, case, monkeypatch):
-    if not cd.build_features()["experimental"]:
-        pytest.skip("library built without SMX_EXPERIMENTAL (python stereo-depth_amd/build.py --experimental)")
-    monkeypatch.setenv("SMX_ENABLE_WIDE", "1")                       # read once, when the engine is created
+@pytest.mark.parametrize("case", THROUGHPUT_EDGE_CASES, ids=[c[0] for c in THROUGHPUT_EDGE_CASES])
+def test_throughput_shape_edge_cases(cd, oracle_omp, case):
     _, H, W, K, dmin, dmax, n, kind, check = case
     cfg, ocfg = _cfgs(cd, H, W, K, dmin, dmax)
     uniq = max(check) + 1
@@ -662,7 +661,7 @@ def test_wide_kernel(cd, oracle_omp, case, monkeypatch):
     L = np.stack([Ls[i % uniq] for i in range(n)])
     R = np.stack([Rs[i % uniq] for i in range(n)])
     sm = cd.StereoMatching(cfg, max_batch=n, overlap_min_pairs=-1)     # one launch for the whole batch
-    assert sm.match_geometry(n)["kernel"] == "fast_wide"
+    assert sm.match_geometry(n)["kernel"] == "fast_window"
     out = sm.compute_disparity_map_batch(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda())
     from cuda_depth import _native as N
     for i in check:
@@ -674,7 +673,7 @@ def test_wide_kernel(cd, oracle_omp, case, monkeypatch):
     o = out.cpu().numpy()
     for i in range(uniq, n):
         assert np.array_equal(o[i], o[i % uniq]), f"replica {i}"
-    # small batches of the same engine still take the wave-per-window kernels, with the same result
+    # a single pair on the same engine (the latency shape) gives the same result
     one = sm.compute_disparity_map_batch(torch.from_numpy(L[:1]).cuda(), torch.from_numpy(R[:1]).cuda()).cpu().numpy()
     assert sm.match_geometry(1)["kernel"] in ("fast_split", "fast_window")
     assert np.array_equal(one[0], o[0])

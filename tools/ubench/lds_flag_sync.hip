@@ -1,4 +1,4 @@
-// Do LDS progress counters order data between the waves of a workgroup?  (question raised by k_match_wide.h)
+// Do LDS progress counters order data between the waves of a workgroup?  (question raised by the workgroup-wide aggregation kernel, NOTES.md §3.5)
 // Workgroup of NW waves in a row; every step each wave waits until both neighbours have published
 // step-1, reads its neighbours' rows of step-1 (two buffers, alternating), checks their stamps, writes
 // its own row of this step and publishes.  Prints the number of stale / early reads.

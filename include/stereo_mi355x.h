@@ -21,6 +21,7 @@
  *                                                         / _gray_u8_batch / _rgb_u8_batch
  *   -- (left-right consistency check)                     smx_compute_lr_*_batch, smx_lr_check
  *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
+ *   -- (image-guided weighted median)                     smx_weighted_median
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -397,6 +398,34 @@ int smx_filter_speckles(int device_id, int n, int H, int W, const float *in, flo
                         float max_diff, float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
 int smx_fill_invalid(int device_id, int n, int H, int W, const float *in, float *out, float invalid_disparity,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* Image-guided weighted median (Rhemann et al. CVPR 2011; Hosni et al. TPAMI 2013), normally run on the pixels the
+ * hole fill wrote.  Every operand is [n][H][W] f32 on the device; the n maps are independent.  VALID is as above.
+ *   - Weights are integers.  range_weight[256] and spatial_weight[(radius+1)^2] are host tables of uint16 values in
+ *     0..1023.  For a centre p and a sample q at offset (dy, dx) in its window,
+ *       w = spatial_weight[|dy| * (radius+1) + |dx|] * range_weight[k],
+ *     where a = fabsf(guide[p] - guide[q]) in float32 and k = (isnan(a) || a >= 255) ? 255 : (int)a (truncation).
+ *     Every sum of weights is below 2^30, so all sums are exact in uint32 in any order.
+ *   - Window: (2 radius + 1)^2 pixels, radius in 1..15, clipped to the map (no padding, no wrap-around).  The SAMPLES
+ *     are the window pixels q that are valid in `in` and have w > 0; T is the sum of their weights.
+ *   - Filtered set F: with holes == NULL, the pixels valid in `in`; otherwise the pixels NOT valid in `holes` (the
+ *     pixels the fill wrote).  Every pixel outside F, and every pixel of F whose T is 0, is copied bit for bit from in.
+ *   - Median: with u = bits(d) and key(d) = (u & 0x80000000) ? ~u : (u | 0x80000000) (a total order, -0.0 < +0.0),
+ *     out[p] is the sample value with the smallest key K such that 2 * sum(w_q : key(d_q) <= K) >= T.  It is a value
+ *     that occurs in the window, so every implementation gives the same bits.
+ * out must not overlap in or guide.  out may be exactly holes (overwrite the pre-fill map) but must not overlap it
+ * otherwise.  in, holes and guide may alias each other (holes == in: a weighted-median fill of the non-valid pixels,
+ * with no background fill before it).  The tables are read during the call (passed by value in the kernel arguments).
+ * workspace: NULL or device memory of at least smx_median_workspace_bytes(n, H, W) bytes (which may be 0) overlapping
+ * no operand; its contents do not affect the result.  One launch on `stream` (a caller's stream), with no host
+ * synchronisation and no allocation, so it can be captured into a HIP graph.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL in, guide, out or table, n < 1, H or W outside
+ * 1..32768, radius outside 1..15, a table value above 1023, invalid_disparity not finite, workspace_bytes below the query
+ * or workspace NULL with workspace_bytes > 0, the overlaps above, stream == SMX_STREAM_ENGINE. */
+size_t smx_median_workspace_bytes(int n, int H, int W);        /* may be 0; 0 for n < 1 or H, W outside 1..32768 */
+int smx_weighted_median(int device_id, int n, int H, int W, const float *in, const float *holes, const float *guide,
+                        float *out, int radius, const uint16_t range_weight[256], const uint16_t spatial_weight[],
+                        float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1298,6 +1298,55 @@ int smx_fill_invalid(int device_id, int n, int H, int W, const float *in, float 
     return SMX_OK;
 }
 
+size_t smx_median_workspace_bytes(int n, int H, int W) {
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return 0;
+    return smx::median_workspace_bytes(n, H, W);
+}
+
+int smx_weighted_median(int device_id, int n, int H, int W, const float *in, const float *holes, const float *guide,
+                        float *out, int radius, const uint16_t range_weight[256], const uint16_t spatial_weight[],
+                        float invalid, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_weighted_median";
+    if (!in || !guide || !out)
+        return fail(SMX_ERR_INVALID_ARG, "%s: in, guide and out must be non-NULL", fn);
+    if (!range_weight || !spatial_weight)
+        return fail(SMX_ERR_INVALID_ARG, "%s: range_weight and spatial_weight must be non-NULL", fn);
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", fn, n, H, W);
+    if (radius < 1 || radius > 15) return fail(SMX_ERR_INVALID_ARG, "%s: radius must be in 1..15, got %d", fn, radius);
+    for (int k = 0; k < 256; ++k)
+        if (range_weight[k] > 1023)
+            return fail(SMX_ERR_INVALID_ARG, "%s: range_weight[%d] = %d is above 1023", fn, k, (int)range_weight[k]);
+    for (int k = 0; k < (radius + 1) * (radius + 1); ++k)
+        if (spatial_weight[k] > 1023)
+            return fail(SMX_ERR_INVALID_ARG, "%s: spatial_weight[%d] = %d is above 1023", fn, k, (int)spatial_weight[k]);
+    if (!std::isfinite(invalid))
+        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
+                    (double)invalid);
+    const size_t need = smx::median_workspace_bytes(n, H, W);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_median_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    if (!workspace && workspace_bytes > 0)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace is NULL but workspace_bytes is %zu", fn, workspace_bytes);
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(guide, bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in or guide", fn);
+    if (holes && out != holes && ranges_overlap(holes, bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap holes other than as the same buffer", fn);
+    if (workspace_bytes > 0 &&
+        (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
+         ranges_overlap(workspace, workspace_bytes, guide, bytes) || ranges_overlap(workspace, workspace_bytes, holes, bytes)))
+        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, holes, guide or out", fn);
+    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
+    smx::launch_weighted_median(n, H, W, in, holes, guide, out, radius, range_weight, spatial_weight, invalid,
+                                (hipStream_t)stream);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
 size_t smx_stage_bytes(const smx_engine *e, int stage) {
     if (!e) return 0;
     const smx_dims &d = e->dm;

@@ -92,4 +92,10 @@ void launch_filter_speckles(int n, int H, int W, const float *in, float *out, in
                             void *workspace, hipStream_t s);
 void launch_fill_invalid(int n, int H, int W, const float *in, float *out, float invalid, void *workspace, hipStream_t s);
 
+// ---- tu_median.hip: image-guided weighted median (k_median.h) ------------------------------------------------------
+// range / spatial: the host tables, copied into the kernel arguments (spatial holds (radius+1)^2 entries)
+size_t median_workspace_bytes(int n, int H, int W);
+void launch_weighted_median(int n, int H, int W, const float *in, const float *holes, const float *guide, float *out,
+                            int radius, const uint16_t *range, const uint16_t *spatial, float invalid, hipStream_t s);
+
 }  // namespace smx

@@ -188,6 +188,82 @@ def fill_invalid(disp: torch.Tensor, *, invalid_disparity: float = -1.0,
     return out
 
 
+def _check_median_params(radius, sigma_color, sigma_space) -> None:
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise TypeError("radius must be an int")
+    if not 1 <= radius <= 15:
+        raise RuntimeError(f"radius must be in 1..15, got {radius}")
+    for name, v in (("sigma_color", sigma_color), ("sigma_space", sigma_space)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{name} must be a number")
+        if not (math.isfinite(v) and v > 0):
+            raise RuntimeError(f"{name} must be finite and > 0, got {v}")
+
+
+def median_weight_tables(radius: int, sigma_color: float, sigma_space: float):
+    """The integer weight tables of smx_weighted_median, in float64:
+    range[k] = floor(1023 exp(-k^2 / (2 sigma_color^2)) + 0.5) for k in 0..255 and
+    spatial[|dy| (radius+1) + |dx|] = floor(1023 exp(-(dx^2 + dy^2) / (2 sigma_space^2)) + 0.5).
+    Returns (range uint16[256], spatial uint16[(radius+1)^2]) as numpy arrays."""
+    import numpy as np
+    _check_median_params(radius, sigma_color, sigma_space)
+    sc2, ss2 = 2.0 * float(sigma_color) ** 2, 2.0 * float(sigma_space) ** 2
+    rng = np.array([math.floor(1023.0 * math.exp(-(k * k) / sc2) + 0.5) for k in range(256)], np.uint16)
+    spatial = np.array([math.floor(1023.0 * math.exp(-(dx * dx + dy * dy) / ss2) + 0.5)
+                        for dy in range(radius + 1) for dx in range(radius + 1)], np.uint16)
+    return rng, spatial
+
+
+def _median_operand(name: str, t: torch.Tensor, disp: torch.Tensor) -> None:
+    _check_input(name, t)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(disp.shape) or t.device != disp.device:
+        raise RuntimeError(f"{name} must be float32 {tuple(disp.shape)} on {disp.device}")
+
+
+def _median_workspace(n: int, H: int, W: int, device: torch.device) -> Optional[torch.Tensor]:
+    """Device scratch of smx_median_workspace_bytes(n, H, W) bytes, or None when the query is 0."""
+    nbytes = int(LIB.smx_median_workspace_bytes(n, H, W))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _launch_weighted_median(disp, holes, guide, out, n, H, W, radius, range_weight, spatial_weight, invalid_disparity,
+                            workspace) -> None:
+    """smx_weighted_median on the current stream; range_weight / spatial_weight: numpy uint16 host tables."""
+    import numpy as np
+    dev = disp.device.index
+    rw = np.ascontiguousarray(range_weight, np.uint16)
+    sw = np.ascontiguousarray(spatial_weight, np.uint16)
+    if rw.shape != (256,) or sw.shape != ((radius + 1) ** 2,):
+        raise RuntimeError(f"weight tables must be uint16[256] and uint16[{(radius + 1) ** 2}], got {rw.shape} and "
+                           f"{sw.shape}")
+    check(LIB.smx_weighted_median(dev, n, H, W, disp.data_ptr(), holes.data_ptr() if holes is not None else None,
+                                  guide.data_ptr(), out.data_ptr(), int(radius), rw.ctypes.data, sw.ctypes.data,
+                                  float(invalid_disparity), workspace.data_ptr() if workspace is not None else None,
+                                  workspace.numel() if workspace is not None else 0,
+                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def weighted_median(disp: torch.Tensor, guide: torch.Tensor, *, radius: int, sigma_color: float, sigma_space: float,
+                    holes: Optional[torch.Tensor] = None, invalid_disparity: float = -1.0,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Image-guided weighted median (smx_weighted_median) on the current stream, with the tables of
+    median_weight_tables(radius, sigma_color, sigma_space).  Each filtered pixel becomes the weighted median of the valid
+    values of disp in its (2 radius + 1)^2 window, a sample weighing more the closer it lies and the closer its guide
+    intensity is to the centre's.  holes=None filters every valid pixel of disp; otherwise only the pixels that are not
+    valid in holes (the pre-fill map: the pixels the fill wrote), and every other pixel is copied.  disp, guide, holes,
+    out: [H,W] or [n,H,W] float32 on one GPU.  out must not overlap disp or guide; it may be holes."""
+    _check_median_params(radius, sigma_color, sigma_space)
+    _check_lr_scalars(0.0, invalid_disparity)
+    out, n, H, W = _postprocess_operands(disp, out)
+    _median_operand("guide", guide, disp)
+    if holes is not None:
+        _median_operand("holes", holes, disp)
+    rw, sw = median_weight_tables(radius, sigma_color, sigma_space)
+    _launch_weighted_median(disp, holes, guide, out, n, H, W, radius, rw, sw, invalid_disparity,
+                            _median_workspace(n, H, W, disp.device))
+    return out
+
+
 class StereoMatching:
     """torch_extension_module.cc:22-26.  `compute_disparity_map` is the reference method;
     the keyword-only constructor extras and the *_gray / *_batch methods are additions that
@@ -372,14 +448,21 @@ class StereoMatching:
         """Orders the current stream behind every engine_streams=True call made so far (smx_join)."""
         check(LIB.smx_join(self._handle, self._stream()))
 
-    def intermediate(self, stage: int, pair_index: int = 0) -> torch.Tensor:
-        """Copy of an intermediate of the last call (parity tests)."""
+    def intermediate(self, stage: int, pair_index: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Copy of an intermediate of the last call (parity tests), on the current stream.  out: an existing
+        contiguous buffer of the stage's size and dtype to copy into (e.g. a persistent guide image)."""
         d = self._dims
         nbytes = int(LIB.smx_stage_bytes(self._handle, stage))
         if nbytes == 0:
             raise RuntimeError(f"stage {stage} is not available for this configuration")
         dtype = torch.int32 if stage == _native.STAGE_GRID_FLAG else torch.float32
-        buf = torch.empty(nbytes // 4, dtype=dtype, device=torch.device("cuda", self._device))
+        if out is None:
+            buf = torch.empty(nbytes // 4, dtype=dtype, device=torch.device("cuda", self._device))
+        else:
+            _check_input("out", out)
+            if out.dtype != dtype or out.numel() * 4 != nbytes or out.device != torch.device("cuda", self._device):
+                raise RuntimeError(f"out must be {dtype} of {nbytes // 4} elements on cuda:{self._device}")
+            buf = out.view(-1)
         check(LIB.smx_get_intermediate(self._handle, stage, pair_index, buf.data_ptr(), nbytes, self._stream()))
         shapes = {
             _native.STAGE_GRAY_LEFT: (d.H, d.W), _native.STAGE_GRAY_RIGHT: (d.H, d.W),

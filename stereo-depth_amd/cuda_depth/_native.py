@@ -100,6 +100,12 @@ EXPORTS = {
     # (device_id, n, H, W, in, out, invalid_disparity, workspace, workspace_bytes, stream)
     "smx_fill_invalid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    # weighted median: (n, H, W) -> workspace bytes; (device_id, n, H, W, in, holes, guide, out, radius, range_weight,
+    # spatial_weight, invalid_disparity, workspace, workspace_bytes, stream); the tables are host uint16 arrays
+    "smx_median_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_weighted_median": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
 }
 
 STREAM_ENGINE = C.c_void_p(-1)          # SMX_STREAM_ENGINE: the engine's own streams

@@ -31,11 +31,16 @@ class CudaStereoMatchingBackend(StereoMatching):
     speckle_max_size > 0: then the speckle filter (cuda_depth.filter_speckles) removes every region of speckle_max_size
     pixels or fewer whose 4-neighbours differ by at most speckle_max_diff.  fill_invalid=True: then the background hole
     fill (cuda_depth.fill_invalid) makes the map dense again.  Both run in place on the returned map, on the current
-    stream, with a workspace allocated once; with the defaults neither runs."""
+    stream, with a workspace allocated once; with the defaults neither runs.
+    median_radius > 0: last, the image-guided weighted median (cuda_depth.weighted_median, tables from median_sigma_color
+    and median_sigma_space), guided by the engine's own left gray plane.  With fill_invalid it filters only the pixels
+    the fill wrote (the fill runs into a scratch map, the median writes the returned map); without, every valid pixel.
+    With median_radius = 0 (the default) it does not run."""
 
     def __init__(self, configuration: Optional["cuda_depth.StereoMatchingConfiguration"] = None, *,
                  left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0,
-                 speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False):
+                 speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False,
+                 median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)
@@ -46,6 +51,15 @@ class CudaStereoMatchingBackend(StereoMatching):
         self._speckle_max_diff = float(speckle_max_diff)
         self._fill_invalid = bool(fill_invalid)
         self._post_workspace: Optional[torch.Tensor] = None
+        if isinstance(median_radius, bool) or not isinstance(median_radius, int):
+            raise TypeError("median_radius must be an int")
+        if median_radius != 0:                              # 0: off; otherwise 1..15 with finite, positive sigmas
+            self._median_tables = cuda_depth.median_weight_tables(median_radius, median_sigma_color, median_sigma_space)
+        else:
+            cuda_depth._check_median_params(1, median_sigma_color, median_sigma_space)
+        self._median_radius = median_radius
+        self._median_guide: Optional[torch.Tensor] = None   # the left gray plane of the last call
+        self._median_scratch: Optional[torch.Tensor] = None
         if self._left_right_check:
             self._stereo_algo = cuda_depth.StereoMatching(configuration, max_batch=2)
         else:
@@ -61,17 +75,33 @@ class CudaStereoMatchingBackend(StereoMatching):
                 invalid_disparity=self._invalid_disparity)[0]
         else:
             disparity = self._stereo_algo.compute_disparity_map(left, right)
-        if self._speckle_max_size > 0 or self._fill_invalid:
+        if self._speckle_max_size > 0 or self._fill_invalid or self._median_radius > 0:
             self._postprocess(disparity)
         return disparity
 
     def _postprocess(self, disparity: torch.Tensor) -> None:
         H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
-        if self._post_workspace is None:
+        if self._post_workspace is None and (self._speckle_max_size > 0 or self._fill_invalid):
             self._post_workspace = cuda_depth._postprocess_workspace(1, H, W, disparity.device)
         if self._speckle_max_size > 0:
             cuda_depth._launch_filter_speckles(disparity, disparity, 1, H, W, self._speckle_max_size,
                                                self._speckle_max_diff, self._invalid_disparity, self._post_workspace)
-        if self._fill_invalid:
-            cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,
-                                            self._post_workspace)
+        if self._median_radius == 0:
+            if self._fill_invalid:
+                cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,
+                                                self._post_workspace)
+            return
+        if self._median_guide is None:
+            self._median_guide = torch.empty_like(disparity)
+            self._median_scratch = torch.empty_like(disparity)
+        self._stereo_algo.intermediate(cuda_depth._native.STAGE_GRAY_LEFT, 0, out=self._median_guide)
+        scratch = self._median_scratch
+        if self._fill_invalid:                              # filled -> scratch; the median rewrites the filled pixels
+            cuda_depth._launch_fill_invalid(disparity, scratch, 1, H, W, self._invalid_disparity, self._post_workspace)
+            holes = disparity
+        else:                                               # every valid pixel
+            scratch.copy_(disparity)
+            holes = None
+        cuda_depth._launch_weighted_median(scratch, holes, self._median_guide, disparity, 1, H, W, self._median_radius,
+                                           *self._median_tables, self._invalid_disparity,
+                                           cuda_depth._median_workspace(1, H, W, disparity.device))

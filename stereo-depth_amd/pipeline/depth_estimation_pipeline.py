@@ -83,12 +83,16 @@ def _make_backend(config: DepthEstimationPipelineConfig, **post: Any) -> StereoM
 class DepthEstimationPipeline:
 
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
-                 speckle_max_diff: float = 1.0, fill_invalid: bool = False):
-        """speckle_max_size / speckle_max_diff / fill_invalid: post-processing of the 'cuda' backend's map, after the
-        left-right check if configured (CudaStereoMatchingBackend); with the defaults the map is returned as computed."""
+                 speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
+                 median_sigma_color: float = 10.0, median_sigma_space: float = 5.0):
+        """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
+        post-processing of the 'cuda' backend's map, after the left-right check if configured
+        (CudaStereoMatchingBackend); with the defaults the map is returned as computed."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         self._stereo_matching = _make_backend(self._config, speckle_max_size=speckle_max_size,
-                                              speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid)
+                                              speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
+                                              median_radius=median_radius, median_sigma_color=median_sigma_color,
+                                              median_sigma_space=median_sigma_space)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
     def get_configuration(self) -> DepthEstimationPipelineConfig:

@@ -22,6 +22,7 @@
  *   -- (left-right consistency check)                     smx_compute_lr_*_batch, smx_lr_check
  *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
  *   -- (image-guided weighted median)                     smx_weighted_median
+ *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -426,6 +427,41 @@ size_t smx_median_workspace_bytes(int n, int H, int W);        /* may be 0; 0 fo
 int smx_weighted_median(int device_id, int n, int H, int W, const float *in, const float *holes, const float *guide,
                         float *out, int radius, const uint16_t range_weight[256], const uint16_t spatial_weight[],
                         float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Rectification of raw frames: a bilinear remap through a precomputed map, with an integer-defined rule, so that every
+ * implementation gives the same bits.
+ *   - Map: [H_out][W_out][2] int32, interleaved (x, y), in units of 1/32 pixel (5 fractional bits, OpenCV's
+ *     INTER_BITS).  The map is input data: every int32 value is legal and defined, and no value reads outside the input.
+ *   - Per output pixel, with (qx, qy) its map entry: x0 = qx >> 5, y0 = qy >> 5 (arithmetic shifts: floor), fx = qx & 31,
+ *     fy = qy & 31.  The four taps are (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1), with the weights
+ *     w00 = (32-fx)(32-fy), w01 = fx(32-fy), w10 = (32-fx)fy, w11 = fx*fy, which sum to 1024.  x0 + 1 and y0 + 1 are at
+ *     most 2^26: no tap coordinate overflows.
+ *   - SMX_BORDER_CONSTANT: a tap outside the input reads border_value (OpenCV's BORDER_CONSTANT, per tap).
+ *     SMX_BORDER_REPLICATE: each tap coordinate is clamped to the input.
+ *   - uint8: out = (w00 p00 + w01 p01 + w10 p10 + w11 p11 + 512) >> 10 in integers: the exact bilinear value, rounded
+ *     half up.  border_value must be an integer in 0..255.
+ *   - float32: out = ((w00 p00 + w01 p01) + (w10 p10 + w11 p11)) * 0.0009765625f, every operation a float32
+ *     round-to-nearest with no fused operation.  A tap whose weight is 0 is not read and contributes +0.0, so an inf or
+ *     NaN behind a zero weight does not reach the result.  A NaN result is stored as the canonical quiet NaN
+ *     0x7FC00000, whatever the sign and payload of the NaNs it came from.  border_value must be finite.
+ *   - Not OpenCV bit for bit: OpenCV's 8-bit remap uses 15-bit rounded weight tables; this rule is the exact rational
+ *     value, rounded.
+ * Images are planar [n][C][H][W] (as the engine's CHW entries), C in 1..4, every channel with the same taps; each view
+ * has its own map, shared by the n images of that view.  left_* is required; right_in, right_map and right_out are all
+ * NULL (left view only) or all non-NULL.  One launch on `stream` (a caller's stream), with no host synchronisation and
+ * no allocation, so it can be captured into a HIP graph.  Engine-free: device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL left operand, a partially-NULL right triple, n < 1
+ * (or n frames larger than the address space),
+ * a size outside 1..32768, channels outside 1..4, an unknown dtype or border mode, a non-finite border_value or, for
+ * uint8, one that is not an integer in 0..255, an output overlapping any input or map or the other output,
+ * stream == SMX_STREAM_ENGINE. */
+#define SMX_BORDER_CONSTANT  0
+#define SMX_BORDER_REPLICATE 1
+#define SMX_DTYPE_U8  0
+#define SMX_DTYPE_F32 1
+int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
+                    const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
+                    void *left_out, void *right_out, int border_mode, float border_value, void *stream);
 
 #ifdef __cplusplus
 }

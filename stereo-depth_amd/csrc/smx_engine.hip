@@ -1347,6 +1347,54 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
     return SMX_OK;
 }
 
+int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
+                    const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
+                    void *left_out, void *right_out, int border_mode, float border_value, void *stream) {
+    const char *fn = "smx_remap_pairs";
+    if (!left_in || !left_map || !left_out)
+        return fail(SMX_ERR_INVALID_ARG, "%s: left_in, left_map and left_out must be non-NULL", fn);
+    const int right_set = (right_in != nullptr) + (right_map != nullptr) + (right_out != nullptr);
+    if (right_set != 0 && right_set != 3)
+        return fail(SMX_ERR_INVALID_ARG, "%s: right_in, right_map and right_out must be all NULL or all non-NULL", fn);
+    if (n < 1) return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1, got %d", fn, n);
+    if (H_in < 1 || W_in < 1 || H_out < 1 || W_out < 1 || H_in > 32768 || W_in > 32768 || H_out > 32768 || W_out > 32768)
+        return fail(SMX_ERR_INVALID_ARG, "%s: sizes must be in 1..32768 (got in %dx%d, out %dx%d)", fn, H_in, W_in, H_out,
+                    W_out);
+    if (channels < 1 || channels > 4) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be in 1..4, got %d", fn, channels);
+    if (dtype != SMX_DTYPE_U8 && dtype != SMX_DTYPE_F32) return fail(SMX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (border_mode != SMX_BORDER_CONSTANT && border_mode != SMX_BORDER_REPLICATE)
+        return fail(SMX_ERR_INVALID_ARG, "%s: unknown border mode %d", fn, border_mode);
+    if (!std::isfinite(border_value))
+        return fail(SMX_ERR_INVALID_ARG, "%s: border_value must be finite, got %g", fn, (double)border_value);
+    if (dtype == SMX_DTYPE_U8 && !(border_value >= 0.0f && border_value <= 255.0f && border_value == std::floor(border_value)))
+        return fail(SMX_ERR_INVALID_ARG, "%s: a uint8 border_value must be an integer in 0..255, got %g", fn,
+                    (double)border_value);
+    const size_t es = dtype == SMX_DTYPE_F32 ? 4 : 1;
+    const size_t frame = (size_t)channels * (size_t)(H_in > H_out ? H_in : H_out) * (size_t)(W_in > W_out ? W_in : W_out) * es;
+    if ((size_t)n > SIZE_MAX / frame)                       // frame < 2^34: the byte sizes below do not overflow
+        return fail(SMX_ERR_INVALID_ARG, "%s: n = %d frames do not fit the address space", fn, n);
+    const size_t in_bytes = (size_t)n * channels * H_in * W_in * es;
+    const size_t out_bytes = (size_t)n * channels * H_out * W_out * es;
+    const size_t map_bytes = (size_t)H_out * W_out * 2 * sizeof(int32_t);
+    const void *outs[2] = {left_out, right_out};
+    for (const void *o : outs) {
+        if (!o) continue;
+        if (ranges_overlap(o, out_bytes, left_in, in_bytes) || ranges_overlap(o, out_bytes, right_in, in_bytes) ||
+            ranges_overlap(o, out_bytes, left_map, map_bytes) || ranges_overlap(o, out_bytes, right_map, map_bytes))
+            return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or a map", fn);
+    }
+    if (ranges_overlap(left_out, out_bytes, right_out, out_bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: left_out and right_out overlap", fn);
+    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
+    smx::launch_remap_pairs(n, channels, dtype == SMX_DTYPE_F32, H_in, W_in, H_out, W_out, left_in, right_in, left_map,
+                            right_map, left_out, right_out, border_mode == SMX_BORDER_REPLICATE, border_value,
+                            (hipStream_t)stream);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
 size_t smx_stage_bytes(const smx_engine *e, int stage) {
     if (!e) return 0;
     const smx_dims &d = e->dm;

@@ -98,4 +98,10 @@ size_t median_workspace_bytes(int n, int H, int W);
 void launch_weighted_median(int n, int H, int W, const float *in, const float *holes, const float *guide, float *out,
                             int radius, const uint16_t *range, const uint16_t *spatial, float invalid, hipStream_t s);
 
+// ---- tu_remap.hip: bilinear remap / rectification (k_remap.h) -------------------------------------------------------
+// in_r / map_r / out_r NULL: left view only; arguments checked by smx_remap_pairs
+void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, const void *in_l, const void *in_r,
+                        const int32_t *map_l, const int32_t *map_r, void *out_l, void *out_r, bool replicate,
+                        float border_value, hipStream_t s);
+
 }  // namespace smx

@@ -264,6 +264,181 @@ def weighted_median(disp: torch.Tensor, guide: torch.Tensor, *, radius: int, sig
     return out
 
 
+def _shape2(name: str, shape) -> tuple:
+    try:
+        h, w = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise TypeError(f"{name} must be a (height, width) pair") from None
+    if not (1 <= h <= 32768 and 1 <= w <= 32768):
+        raise ValueError(f"{name} must lie in 1..32768, got {(h, w)}")
+    return h, w
+
+
+def rectification_map(K, dist, R, P, in_shape, out_shape):
+    """The float64 rectification map of one camera, in the model and formula order of OpenCV's initUndistortRectifyMap:
+    for each output pixel (u, v), X = inv(P[:, :3] @ R) @ [u, v, 1], x = X0 / X2, y = X1 / X2, then the radial
+    (k1, k2, k3) and tangential (p1, p2) distortion of dist = (k1, k2, p1, p2[, k3]), then K.  A pixel with X2 <= 0 or a
+    non-finite result is marked outside (NaN, which quantize_map sends outside the input).
+    K: 3x3 raw intrinsics; R: 3x3 rectifying rotation; P: 3x3 or 3x4 rectified projection (only P[:, :3] is used).
+    in_shape / out_shape: (height, width) of the raw and rectified images.  Returns (map_x, map_y), float64 [H_out, W_out]
+    of raw-image pixel coordinates."""
+    import numpy as np
+    _shape2("in_shape", in_shape)
+    Ho, Wo = _shape2("out_shape", out_shape)
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    P = np.asarray(P, np.float64)
+    if P.shape not in ((3, 3), (3, 4)):
+        P = P.reshape(3, -1)
+    d = np.zeros(5)
+    dist = np.asarray(dist if dist is not None else [], np.float64).reshape(-1)
+    if dist.size not in (0, 4, 5):
+        raise ValueError(f"dist must hold 4 or 5 entries (k1, k2, p1, p2[, k3]), got {dist.size}")
+    d[:dist.size] = dist
+    k1, k2, p1, p2, k3 = d
+    iR = np.linalg.inv(P[:, :3] @ R)
+    v, u = np.meshgrid(np.arange(Ho, dtype=np.float64), np.arange(Wo, dtype=np.float64), indexing="ij")
+    X0 = iR[0, 0] * u + iR[0, 1] * v + iR[0, 2]
+    X1 = iR[1, 0] * u + iR[1, 1] * v + iR[1, 2]
+    X2 = iR[2, 0] * u + iR[2, 1] * v + iR[2, 2]
+    with np.errstate(all="ignore"):
+        x, y = X0 / X2, X1 / X2
+        x2, y2 = x * x, y * y
+        r2 = x2 + y2
+        xy2 = 2 * x * y
+        kr = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+        xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2)
+        yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2
+        map_x = K[0, 0] * xd + K[0, 1] * yd + K[0, 2]
+        map_y = K[1, 1] * yd + K[1, 2]
+    bad = ~(X2 > 0) | ~np.isfinite(map_x) | ~np.isfinite(map_y)
+    map_x[bad] = np.nan
+    map_y[bad] = np.nan
+    return map_x, map_y
+
+
+def quantize_map(map_x, map_y, in_shape):
+    """float maps of raw-image pixel coordinates -> the int32 [H_out, W_out, 2] map of smx_remap_pairs, (x, y) in 1/32
+    pixel: q = floor(m * 32 + 0.5), clamped to [-64, (W_in + 1) * 32] for x and [-64, (H_in + 1) * 32] for y (outside
+    the input, every tap lies outside too); a non-finite entry becomes -64.  Takes any float map, e.g. one of OpenCV."""
+    import numpy as np
+    Hi, Wi = _shape2("in_shape", in_shape)
+    mx, my = np.asarray(map_x, np.float64), np.asarray(map_y, np.float64)
+    if mx.ndim != 2 or mx.shape != my.shape:
+        raise ValueError(f"map_x and map_y must be 2-D of one shape, got {mx.shape} and {my.shape}")
+    q = np.empty(mx.shape + (2,), np.int32)
+    for k, (m, hi) in enumerate(((mx, (Wi + 1) * 32), (my, (Hi + 1) * 32))):
+        with np.errstate(all="ignore"):
+            f = np.floor(m * 32.0 + 0.5)
+        f = np.where(np.isfinite(f), np.clip(f, -64, hi), -64)
+        q[..., k] = f.astype(np.int32)
+    return q
+
+
+def _valid_taps(qmap, in_shape):
+    """bool [H_out, W_out]: every tap of non-zero weight of the quantised map lies inside the input (a tap of weight 0
+    is not read, so it does not count)."""
+    import numpy as np
+    Hi, Wi = in_shape
+    q = np.asarray(qmap, np.int64)
+    x0, y0, fx, fy = q[..., 0] >> 5, q[..., 1] >> 5, q[..., 0] & 31, q[..., 1] & 31
+    x1 = np.where(fx > 0, x0 + 1, x0)
+    y1 = np.where(fy > 0, y0 + 1, y0)
+    return (x0 >= 0) & (x1 < Wi) & (y0 >= 0) & (y1 < Hi)
+
+
+_BORDERS = {"constant": _native.BORDER_CONSTANT, "replicate": _native.BORDER_REPLICATE}
+
+
+class StereoRectification:
+    """Rectification of raw stereo frames on the GPU (smx_remap_pairs): both views of a batch in one launch, each
+    through its own int32 map (quantize_map).  left_map / right_map: int32 [H_out, W_out, 2] (numpy or tensor);
+    in_shape / out_shape: (height, width) of the raw and rectified frames; border_mode 'constant' (taps outside read
+    border_value) or 'replicate' (taps clamped to the image).  left_valid: device bool [H_out, W_out], the output pixels
+    whose left-view taps of non-zero weight all lie inside the raw image."""
+
+    def __init__(self, left_map, right_map, in_shape, out_shape, *, border_mode: str = "constant",
+                 border_value: float = 0.0, device=None):
+        import numpy as np
+        self.in_shape = _shape2("in_shape", in_shape)
+        self.out_shape = _shape2("out_shape", out_shape)
+        if border_mode not in _BORDERS:
+            raise ValueError(f"border_mode must be 'constant' or 'replicate', got {border_mode!r}")
+        if isinstance(border_value, bool) or not isinstance(border_value, (int, float)):
+            raise TypeError("border_value must be a number")
+        if not math.isfinite(border_value):
+            raise ValueError(f"border_value must be finite, got {border_value}")
+        self.border_mode = border_mode
+        self.border_value = float(border_value)
+        device = torch.device("cuda" if device is None else device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        maps = []
+        for name, m in (("left_map", left_map), ("right_map", right_map)):
+            m = m.cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+            if m.dtype != np.int32 or m.shape != self.out_shape + (2,):
+                raise ValueError(f"{name} must be int32 {self.out_shape + (2,)}, got {m.dtype} {m.shape}")
+            maps.append(m)
+        self.left_map = torch.from_numpy(np.ascontiguousarray(maps[0])).to(self.device)
+        self.right_map = torch.from_numpy(np.ascontiguousarray(maps[1])).to(self.device)
+        self.left_valid = torch.from_numpy(_valid_taps(maps[0], self.in_shape)).to(self.device)
+
+    @classmethod
+    def from_calibration(cls, left, right, in_shape, out_shape, **kwargs) -> "StereoRectification":
+        """left / right: (K, dist, R, P) of each camera, as rectification_map takes them."""
+        maps = [quantize_map(*rectification_map(*cam, in_shape, out_shape), in_shape) for cam in (left, right)]
+        return cls(maps[0], maps[1], in_shape, out_shape, **kwargs)
+
+    def _out(self, name, t, like, shape):
+        if t is None:
+            return torch.empty(shape, dtype=like.dtype, device=like.device)
+        _check_input(name, t)
+        if t.dtype != like.dtype or tuple(t.shape) != shape or t.device != like.device:
+            raise RuntimeError(f"{name} must be {like.dtype} {shape} on {like.device}")
+        return t
+
+    def rectify(self, left: torch.Tensor, right: Optional[torch.Tensor] = None, out=None):
+        """Rectifies one pair ([C,H,W]) or a batch ([n,C,H,W]), uint8 or float32, C in 1..4, on the current stream.
+        Returns (left_out, right_out) of the same dtype and rank, [.., C, H_out, W_out]; with right=None only the left
+        frames are rectified and left_out alone is returned.  out: the output tensor(s) to write, in the same form."""
+        _check_input("left", left)
+        if left.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError(f"frames must be uint8 or float32, got {left.dtype}")
+        if left.dim() not in (3, 4) or not 1 <= int(left.shape[-3]) <= 4:
+            raise RuntimeError(f"frames must be [C,H,W] or [n,C,H,W] with C in 1..4, got {tuple(left.shape)}")
+        if tuple(left.shape[-2:]) != self.in_shape:
+            raise RuntimeError(f"frames must be {self.in_shape[0]}x{self.in_shape[1]} (in_shape), got "
+                               f"{tuple(left.shape[-2:])}")
+        if left.device != self.device:
+            raise RuntimeError(f"frames must live on {self.device}, got {left.device}")
+        if left.numel() == 0:
+            raise RuntimeError("left is empty")
+        if right is not None:
+            _check_input("right", right)
+            if right.dtype != left.dtype or tuple(right.shape) != tuple(left.shape) or right.device != left.device:
+                raise RuntimeError(f"right must be {left.dtype} {tuple(left.shape)} on {left.device}")
+        if left.dtype == torch.uint8 and not (0 <= self.border_value <= 255 and self.border_value.is_integer()):
+            raise RuntimeError(f"a uint8 border_value must be an integer in 0..255, got {self.border_value}")
+        shape = tuple(left.shape[:-2]) + self.out_shape
+        if right is None:
+            lo, ro = self._out("out", out, left, shape), None
+        else:
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise TypeError("out must be a (left_out, right_out) pair")
+            lo = self._out("out[0]", None if out is None else out[0], left, shape)
+            ro = self._out("out[1]", None if out is None else out[1], left, shape)
+        n = 1 if left.dim() == 3 else int(left.shape[0])
+        dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
+        dev = left.device.index
+        check(LIB.smx_remap_pairs(dev, n, int(left.shape[-3]), dt, *self.in_shape, *self.out_shape, left.data_ptr(),
+                                  None if right is None else right.data_ptr(), self.left_map.data_ptr(),
+                                  None if right is None else self.right_map.data_ptr(), lo.data_ptr(),
+                                  None if ro is None else ro.data_ptr(), _BORDERS[self.border_mode],
+                                  self.border_value, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return lo if right is None else (lo, ro)
+
+
 class StereoMatching:
     """torch_extension_module.cc:22-26.  `compute_disparity_map` is the reference method;
     the keyword-only constructor extras and the *_gray / *_batch methods are additions that

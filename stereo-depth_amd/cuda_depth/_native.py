@@ -106,8 +106,15 @@ EXPORTS = {
     "smx_weighted_median": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    # rectification: (device_id, n, channels, dtype, H_in, W_in, H_out, W_out, left_in, right_in, left_map, right_map,
+    # left_out, right_out, border_mode, border_value, stream)
+    "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                  C.c_void_p]),
 }
 
+BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*
+DTYPE_U8, DTYPE_F32 = 0, 1                 # SMX_DTYPE_*
 STREAM_ENGINE = C.c_void_p(-1)          # SMX_STREAM_ENGINE: the engine's own streams
 KERNEL_SLOTS = ("prologue", "match_fast", "match_exact", "refine", "fill")
 

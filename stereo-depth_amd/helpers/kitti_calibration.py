@@ -48,6 +48,28 @@ def focal_length_and_baseline(calib_dir: str) -> Tuple[float, float]:
     return float(p2[0, 0]), float(offset3 - offset2)
 
 
+def stereo_rectification(calib_dir: str, cams: Tuple[int, int] = (2, 3), **kwargs):
+    """cuda_depth.StereoRectification of a raw ("extract") drive's camera pair from calib_cam_to_cam.txt: for camera x,
+    the map of K_0x, D_0x (k1 k2 p1 p2 k3), R_rect_0x and P_rect_0x, from the raw size S_0x to the rectified size
+    S_rect_0x (both stored as width height).  kwargs: border_mode, border_value, device."""
+    import cuda_depth
+    cal = read_calibration(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
+
+    def size(key: str) -> Tuple[int, int]:
+        w, h = (int(round(float(v))) for v in np.asarray(cal[key]).reshape(2))
+        return h, w
+
+    in_shapes = {size(f"S_0{c}") for c in cams}
+    out_shapes = {size(f"S_rect_0{c}") for c in cams}
+    if len(in_shapes) != 1 or len(out_shapes) != 1:
+        raise ValueError(f"cameras {cams} differ in raw or rectified size: {sorted(in_shapes)} / {sorted(out_shapes)}")
+    in_shape, out_shape = in_shapes.pop(), out_shapes.pop()
+    geometry = [(np.asarray(cal[f"K_0{c}"]).reshape(3, 3), np.asarray(cal[f"D_0{c}"]).reshape(5),
+                 np.asarray(cal[f"R_rect_0{c}"]).reshape(3, 3), np.asarray(cal[f"P_rect_0{c}"]).reshape(3, 4))
+                for c in cams]
+    return cuda_depth.StereoRectification.from_calibration(geometry[0], geometry[1], in_shape, out_shape, **kwargs)
+
+
 def velodyne_to_image_projection(calib_dir: str, cam: int = 2) -> np.ndarray:
     """3x4 matrix taking homogeneous velodyne points to pixels of rectified camera `cam`
     (velodyne_points_helpers.py:58-68)."""

@@ -35,13 +35,26 @@ class CudaStereoMatchingBackend(StereoMatching):
     median_radius > 0: last, the image-guided weighted median (cuda_depth.weighted_median, tables from median_sigma_color
     and median_sigma_space), guided by the engine's own left gray plane.  With fill_invalid it filters only the pixels
     the fill wrote (the fill runs into a scratch map, the median writes the returned map); without, every valid pixel.
-    With median_radius = 0 (the default) it does not run."""
+    With median_radius = 0 (the default) it does not run.
+    rectification (a cuda_depth.StereoRectification, default None): both raw frames are rectified on the current stream
+    before matching (its out_shape must be the configuration's image size), and the pixels of the final map outside its
+    left_valid mask become invalid_disparity."""
 
     def __init__(self, configuration: Optional["cuda_depth.StereoMatchingConfiguration"] = None, *,
                  left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0,
                  speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False,
-                 median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0):
+                 median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                 rectification: Optional["cuda_depth.StereoRectification"] = None):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
+        if rectification is not None:
+            if not isinstance(rectification, cuda_depth.StereoRectification):
+                raise TypeError("rectification must be a cuda_depth.StereoRectification")
+            size = (configuration._values["height"], configuration._values["width"])
+            if tuple(rectification.out_shape) != size:
+                raise ValueError(f"rectification.out_shape {tuple(rectification.out_shape)} differs from the image "
+                                 f"size {size}")
+        self._rectification = rectification
+        self._rectified: Optional[tuple] = None             # persistent output frames of the rectification
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)
         self._invalid_disparity = float(invalid_disparity)
@@ -69,6 +82,8 @@ class CudaStereoMatchingBackend(StereoMatching):
         left, right = _device_frame(left_image), _device_frame(right_image)
         if left.dtype != right.dtype:                       # mixed inputs: fall back to float for both
             left, right = left.float(), right.float()
+        if self._rectification is not None:
+            left, right = self._rectify(left, right)
         if self._left_right_check:
             disparity = self._stereo_algo.compute_disparity_map_batch_lr(
                 left.unsqueeze(0), right.unsqueeze(0), max_diff=self._lr_max_diff,
@@ -77,7 +92,21 @@ class CudaStereoMatchingBackend(StereoMatching):
             disparity = self._stereo_algo.compute_disparity_map(left, right)
         if self._speckle_max_size > 0 or self._fill_invalid or self._median_radius > 0:
             self._postprocess(disparity)
+        if self._rectification is not None:
+            disparity.masked_fill_(~self._rectification.left_valid, self._invalid_disparity)
         return disparity
+
+    def rectified_frames(self) -> Optional[tuple]:
+        """(left, right) rectified frames of the last process() call (persistent buffers, overwritten by the next
+        call), or None without rectification."""
+        return self._rectified if self._rectification is not None else None
+
+    def _rectify(self, left: torch.Tensor, right: torch.Tensor):
+        shape = tuple(left.shape[:-2]) + tuple(self._rectification.out_shape)
+        if self._rectified is None or self._rectified[0].dtype != left.dtype or tuple(self._rectified[0].shape) != shape:
+            self._rectified = (torch.empty(shape, dtype=left.dtype, device=left.device),
+                               torch.empty(shape, dtype=left.dtype, device=left.device))
+        return self._rectification.rectify(left, right, out=self._rectified)
 
     def _postprocess(self, disparity: torch.Tensor) -> None:
         H, W = int(disparity.shape[-2]), int(disparity.shape[-1])

@@ -84,15 +84,19 @@ class DepthEstimationPipeline:
 
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
                  speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
-                 median_sigma_color: float = 10.0, median_sigma_space: float = 5.0):
+                 median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                 rectification: Optional["cuda_depth.StereoRectification"] = None):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the 'cuda' backend's map, after the left-right check if configured
-        (CudaStereoMatchingBackend); with the defaults the map is returned as computed."""
+        (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  rectification: a
+        cuda_depth.StereoRectification whose out_shape is config.image_shape; the raw frames are rectified on the GPU
+        before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
+        rectified)."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         self._stereo_matching = _make_backend(self._config, speckle_max_size=speckle_max_size,
                                               speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
                                               median_radius=median_radius, median_sigma_color=median_sigma_color,
-                                              median_sigma_space=median_sigma_space)
+                                              median_sigma_space=median_sigma_space, rectification=rectification)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
     def get_configuration(self) -> DepthEstimationPipelineConfig:
@@ -100,10 +104,15 @@ class DepthEstimationPipeline:
 
     def process(self, left_image: torch.Tensor, right_image: Optional[torch.Tensor] = None) -> DepthEstimationResult:
         """One frame.  The returned disparity map aliases the engine's persistent output buffer
-        (stereo_matching.cc:42): clone it before processing the next frame if it must survive."""
+        (stereo_matching.cc:42): clone it before processing the next frame if it must survive.  With rectification=,
+        the result's left_image / right_image are the rectified frames the map was computed on (out_shape, same
+        geometry as the map; persistent buffers too), not the raw frames passed in."""
         if right_image is None:
             raise RuntimeError("right_image is required: right-view synthesis (Deep3D) is not part of this build.")
         left_on_device = left_image.cuda()
         with cuda_perf_clock("Stereo matching", self._config.log_perf_time):
             disparity = self._stereo_matching.process(left_on_device, right_image)
+        rectified = getattr(self._stereo_matching, "rectified_frames", lambda: None)()
+        if rectified is not None:
+            left_on_device, right_image = rectified
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity)

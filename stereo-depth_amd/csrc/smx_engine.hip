@@ -1,4 +1,4 @@
-// smx_engine.hip -- the C ABI of include/stereo_mi355x.h over the gfx950 kernels.
+// smx_engine.hip -- the engine behind the C ABI of include/stereo_mi355x.h; the engine-free entries are in smx_maps.hip.
 //
 // Replaces, behind a plain C boundary, the reference's native engine:
 //   depth/stereo_matching.{hh,cc}      (9-step sequencer)      -> smx_engine + enqueue()
@@ -8,7 +8,6 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see build.py).
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -31,39 +30,11 @@
 #include "k_refine.h"
 #include "smx_common.h"
 #include "smx_launch.h"
+#include "smx_status.h"
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define SMX_HIP(call)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? SMX_ERR_OUT_OF_MEMORY : SMX_ERR_HIP, \
-                        "%s failed: %s", #call, hipGetErrorString(e_));                 \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) ok = true;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+using smx::check_lr_scalars, smx::DeviceGuard, smx::fail, smx::ranges_overlap;
 
 int compute_dims(const smx_config *c, smx_dims *d) {
     // reference device_buffer.cc:3-12 and stereo_matching.cc:61-62 (Q18: unsigned division,
@@ -857,21 +828,6 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     return rc;
 }
 
-bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    if (!a || !b) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-int check_lr_scalars(float max_diff, float invalid) {
-    if (!(std::isfinite(max_diff) && max_diff >= 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "max_diff must be finite and >= 0, got %g", (double)max_diff);
-    if (!std::isfinite(invalid))
-        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
-                    (double)invalid);
-    return SMX_OK;
-}
-
 // Left-right check: ONE engine call of 2n internal pairs on the caller's stream -- (L_i, R_i) for i < n, (flip R_i, flip L_i)
 // for n + i -- between the pack / mirror launch and the check launch (k_lr.h).
 int enqueue_lr(smx_engine *e, int in_mode, int n, const void *left, const void *right, float *out, float *right_out,
@@ -930,6 +886,18 @@ int enqueue_lr(smx_engine *e, int in_mode, int n, const void *left, const void *
 }
 
 }  // namespace
+
+static thread_local std::string g_last_error;
+
+int smx::fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    return code;
+}
 
 extern "C" {
 
@@ -1223,178 +1191,6 @@ int smx_compute_lr_rgb_u8_batch(smx_engine *e, int n, const uint8_t *l, const ui
     return enqueue_lr(e, smx::IN_RGB_U8, n, l, r, out, right_out, max_diff, invalid, stream);
 }
 
-int smx_lr_check(int device_id, int n, int H, int W, const float *left, const float *right, float *out, float max_diff,
-                 float invalid, void *stream) {
-    if (int rc = check_lr_scalars(max_diff, invalid)) return rc;
-    if (!left || !right || !out) return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: left, right and out must be non-NULL");
-    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", n, H, W);
-    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "smx_lr_check needs a caller stream");
-    const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (ranges_overlap(right, bytes, out, bytes) || (out != left && ranges_overlap(left, bytes, out, bytes)))
-        return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: out must not overlap right_disp, and overlap left_disp only as the same buffer");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    smx::launch_lr_check(false, left, right, out, nullptr, n, H, W, max_diff, invalid, (hipStream_t)stream);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The checks shared by smx_filter_speckles and smx_fill_invalid (after their own scalar checks).
-int check_post_args(const char *fn, int n, int H, int W, const float *in, const float *out, void *workspace,
-                    size_t workspace_bytes, void *stream) {
-    if (!in || !out || !workspace) return fail(SMX_ERR_INVALID_ARG, "%s: in, out and workspace must be non-NULL", fn);
-    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", fn, n, H, W);
-    const size_t need = smx::post_workspace_bytes(n, H, W);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_postprocess_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
-    const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (out != in && ranges_overlap(in, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in other than as the same buffer", fn);
-    if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in or out", fn);
-    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
-    return SMX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t smx_postprocess_workspace_bytes(int n, int H, int W) {
-    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return 0;
-    return smx::post_workspace_bytes(n, H, W);
-}
-
-int smx_filter_speckles(int device_id, int n, int H, int W, const float *in, float *out, int max_speckle_size,
-                        float max_diff, float invalid, void *workspace, size_t workspace_bytes, void *stream) {
-    if (max_speckle_size < 0)
-        return fail(SMX_ERR_INVALID_ARG, "smx_filter_speckles: max_speckle_size must be >= 0, got %d", max_speckle_size);
-    if (int rc = check_lr_scalars(max_diff, invalid)) return rc;
-    if (int rc = check_post_args("smx_filter_speckles", n, H, W, in, out, workspace, workspace_bytes, stream)) return rc;
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    smx::launch_filter_speckles(n, H, W, in, out, max_speckle_size, max_diff, invalid, workspace, (hipStream_t)stream);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int smx_fill_invalid(int device_id, int n, int H, int W, const float *in, float *out, float invalid, void *workspace,
-                     size_t workspace_bytes, void *stream) {
-    if (!std::isfinite(invalid))
-        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
-                    (double)invalid);
-    if (int rc = check_post_args("smx_fill_invalid", n, H, W, in, out, workspace, workspace_bytes, stream)) return rc;
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    smx::launch_fill_invalid(n, H, W, in, out, invalid, workspace, (hipStream_t)stream);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-size_t smx_median_workspace_bytes(int n, int H, int W) {
-    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return 0;
-    return smx::median_workspace_bytes(n, H, W);
-}
-
-int smx_weighted_median(int device_id, int n, int H, int W, const float *in, const float *holes, const float *guide,
-                        float *out, int radius, const uint16_t range_weight[256], const uint16_t spatial_weight[],
-                        float invalid, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "smx_weighted_median";
-    if (!in || !guide || !out)
-        return fail(SMX_ERR_INVALID_ARG, "%s: in, guide and out must be non-NULL", fn);
-    if (!range_weight || !spatial_weight)
-        return fail(SMX_ERR_INVALID_ARG, "%s: range_weight and spatial_weight must be non-NULL", fn);
-    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1 and 1 <= H, W <= 32768 (got n %d, H %d, W %d)", fn, n, H, W);
-    if (radius < 1 || radius > 15) return fail(SMX_ERR_INVALID_ARG, "%s: radius must be in 1..15, got %d", fn, radius);
-    for (int k = 0; k < 256; ++k)
-        if (range_weight[k] > 1023)
-            return fail(SMX_ERR_INVALID_ARG, "%s: range_weight[%d] = %d is above 1023", fn, k, (int)range_weight[k]);
-    for (int k = 0; k < (radius + 1) * (radius + 1); ++k)
-        if (spatial_weight[k] > 1023)
-            return fail(SMX_ERR_INVALID_ARG, "%s: spatial_weight[%d] = %d is above 1023", fn, k, (int)spatial_weight[k]);
-    if (!std::isfinite(invalid))
-        return fail(SMX_ERR_INVALID_ARG, "invalid_disparity must be finite (a NaN marker never compares equal), got %g",
-                    (double)invalid);
-    const size_t need = smx::median_workspace_bytes(n, H, W);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_median_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
-    if (!workspace && workspace_bytes > 0)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace is NULL but workspace_bytes is %zu", fn, workspace_bytes);
-    const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(guide, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in or guide", fn);
-    if (holes && out != holes && ranges_overlap(holes, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap holes other than as the same buffer", fn);
-    if (workspace_bytes > 0 &&
-        (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
-         ranges_overlap(workspace, workspace_bytes, guide, bytes) || ranges_overlap(workspace, workspace_bytes, holes, bytes)))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, holes, guide or out", fn);
-    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    smx::launch_weighted_median(n, H, W, in, holes, guide, out, radius, range_weight, spatial_weight, invalid,
-                                (hipStream_t)stream);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
-                    const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
-                    void *left_out, void *right_out, int border_mode, float border_value, void *stream) {
-    const char *fn = "smx_remap_pairs";
-    if (!left_in || !left_map || !left_out)
-        return fail(SMX_ERR_INVALID_ARG, "%s: left_in, left_map and left_out must be non-NULL", fn);
-    const int right_set = (right_in != nullptr) + (right_map != nullptr) + (right_out != nullptr);
-    if (right_set != 0 && right_set != 3)
-        return fail(SMX_ERR_INVALID_ARG, "%s: right_in, right_map and right_out must be all NULL or all non-NULL", fn);
-    if (n < 1) return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1, got %d", fn, n);
-    if (H_in < 1 || W_in < 1 || H_out < 1 || W_out < 1 || H_in > 32768 || W_in > 32768 || H_out > 32768 || W_out > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "%s: sizes must be in 1..32768 (got in %dx%d, out %dx%d)", fn, H_in, W_in, H_out,
-                    W_out);
-    if (channels < 1 || channels > 4) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be in 1..4, got %d", fn, channels);
-    if (dtype != SMX_DTYPE_U8 && dtype != SMX_DTYPE_F32) return fail(SMX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
-    if (border_mode != SMX_BORDER_CONSTANT && border_mode != SMX_BORDER_REPLICATE)
-        return fail(SMX_ERR_INVALID_ARG, "%s: unknown border mode %d", fn, border_mode);
-    if (!std::isfinite(border_value))
-        return fail(SMX_ERR_INVALID_ARG, "%s: border_value must be finite, got %g", fn, (double)border_value);
-    if (dtype == SMX_DTYPE_U8 && !(border_value >= 0.0f && border_value <= 255.0f && border_value == std::floor(border_value)))
-        return fail(SMX_ERR_INVALID_ARG, "%s: a uint8 border_value must be an integer in 0..255, got %g", fn,
-                    (double)border_value);
-    const size_t es = dtype == SMX_DTYPE_F32 ? 4 : 1;
-    const size_t frame = (size_t)channels * (size_t)(H_in > H_out ? H_in : H_out) * (size_t)(W_in > W_out ? W_in : W_out) * es;
-    if ((size_t)n > SIZE_MAX / frame)                       // frame < 2^34: the byte sizes below do not overflow
-        return fail(SMX_ERR_INVALID_ARG, "%s: n = %d frames do not fit the address space", fn, n);
-    const size_t in_bytes = (size_t)n * channels * H_in * W_in * es;
-    const size_t out_bytes = (size_t)n * channels * H_out * W_out * es;
-    const size_t map_bytes = (size_t)H_out * W_out * 2 * sizeof(int32_t);
-    const void *outs[2] = {left_out, right_out};
-    for (const void *o : outs) {
-        if (!o) continue;
-        if (ranges_overlap(o, out_bytes, left_in, in_bytes) || ranges_overlap(o, out_bytes, right_in, in_bytes) ||
-            ranges_overlap(o, out_bytes, left_map, map_bytes) || ranges_overlap(o, out_bytes, right_map, map_bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or a map", fn);
-    }
-    if (ranges_overlap(left_out, out_bytes, right_out, out_bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: left_out and right_out overlap", fn);
-    if (stream == SMX_STREAM_ENGINE) return fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn);
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    smx::launch_remap_pairs(n, channels, dtype == SMX_DTYPE_F32, H_in, W_in, H_out, W_out, left_in, right_in, left_map,
-                            right_map, left_out, right_out, border_mode == SMX_BORDER_REPLICATE, border_value,
-                            (hipStream_t)stream);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
 size_t smx_stage_bytes(const smx_engine *e, int stage) {
     if (!e) return 0;
     const smx_dims &d = e->dm;
@@ -1532,32 +1328,6 @@ int smx_join(smx_engine *e, void *stream) {
 int smx_overlap_lanes(const smx_engine *e, int n) {
     if (!e || n < 1) return SMX_ERR_INVALID_ARG;
     return (e->overlap_min > 0 && n >= e->overlap_min && n <= e->B) ? smx_engine::LANES : 1;
-}
-
-int smx_disparity_to_points(int device_id, const float *disp, int H, int W, float bf, float invalid,
-                            float *depth, float *points, int *count_dev, int *workspace, void *stream) {
-    if (!disp || !points || !count_dev || !workspace || H < 1 || W < 1 || H > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "smx_disparity_to_points: NULL pointer or bad size");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    hipStream_t s = (hipStream_t)stream;
-    smx::launch_points(disp, H, W, bf, invalid, depth, points, count_dev, workspace, s);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int smx_eval_metrics(int device_id, int n, const float *est, const float *gt, const uint8_t *mask,
-                     size_t pixels, float max_disparity, const float thresholds[4], double *out_sums,
-                     void *stream) {
-    if (!est || !gt || !out_sums || !thresholds || n < 1 || pixels == 0)
-        return fail(SMX_ERR_INVALID_ARG, "smx_eval_metrics: NULL pointer, n < 1 or no pixels");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", device_id);
-    hipStream_t s = (hipStream_t)stream;
-    SMX_HIP(hipMemsetAsync(out_sums, 0, sizeof(double) * 8 * (size_t)n, s));
-    smx::launch_metrics(n, est, gt, mask, pixels, max_disparity, thresholds, out_sums, s);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
 }
 
 int smx_profile_begin(smx_engine *e, int max_calls) {

@@ -1,7 +1,7 @@
-// smx_launch.h -- host-side launch interface between the engine (smx_engine.hip) and the kernel
+// smx_launch.h -- host-side launch interface between the C ABI (smx_engine.hip, smx_maps.hip) and the kernel
 // translation units (tu_*.hip).  Every kernel family is compiled in its own translation unit so that the
-// library builds in parallel and a change to one kernel recompiles one file; the engine never instantiates
-// a kernel template itself.  All functions enqueue on `s` and return without synchronising.
+// library builds in parallel and a change to one kernel recompiles one file; the C ABI's units never instantiate
+// a kernel template themselves.  All functions enqueue on `s` and return without synchronising.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -77,10 +77,30 @@ def _check_input(name: str, t: torch.Tensor) -> None:
         raise RuntimeError(f"{name} must be contiguous")
 
 
+def _check_like(name: str, t: torch.Tensor, dtype: torch.dtype, shape: tuple, device: torch.device) -> None:
+    """An operand that must match a reference tensor's dtype, shape and device."""
+    _check_input(name, t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise RuntimeError(f"{name} must be {str(dtype).removeprefix('torch.')} {tuple(shape)} on {device}")
+
+
+def _int_arg(name: str, v) -> None:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError(f"{name} must be an int")
+
+
+def _number_arg(name: str, v) -> None:
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError(f"{name} must be a number")
+
+
+def _stream(device_index: int) -> C.c_void_p:
+    return C.c_void_p(torch.cuda.current_stream(device_index).cuda_stream)
+
+
 def _check_lr_scalars(max_diff, invalid_disparity) -> None:
-    for name, v in (("max_diff", max_diff), ("invalid_disparity", invalid_disparity)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise TypeError(f"{name} must be a number")
+    _number_arg("max_diff", max_diff)
+    _number_arg("invalid_disparity", invalid_disparity)
     if not (math.isfinite(max_diff) and max_diff >= 0):
         raise RuntimeError(f"max_diff must be finite and >= 0, got {max_diff}")
     if not math.isfinite(invalid_disparity):
@@ -105,16 +125,14 @@ def left_right_check(left_disp: torch.Tensor, right_disp: torch.Tensor, *, max_d
     if out is None:
         out = torch.empty_like(left_disp)
     else:
-        _check_input("out", out)
-        if out.dtype != torch.float32 or tuple(out.shape) != tuple(left_disp.shape) or out.device != left_disp.device:
-            raise RuntimeError(f"out must be float32 {tuple(left_disp.shape)} on {left_disp.device}")
+        _check_like("out", out, torch.float32, left_disp.shape, left_disp.device)
     n = 1 if left_disp.dim() == 2 else int(left_disp.shape[0])
     H, W = int(left_disp.shape[-2]), int(left_disp.shape[-1])
     if left_disp.numel() == 0:
         raise RuntimeError("left_disp is empty")
     dev = left_disp.device.index
     check(LIB.smx_lr_check(dev, n, H, W, left_disp.data_ptr(), right_disp.data_ptr(), out.data_ptr(), float(max_diff),
-                           float(invalid_disparity), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                           float(invalid_disparity), _stream(dev)))
     return out
 
 
@@ -128,9 +146,7 @@ def _postprocess_operands(disp: torch.Tensor, out: Optional[torch.Tensor]):
     if out is None:
         out = torch.empty_like(disp)
     else:
-        _check_input("out", out)
-        if out.dtype != torch.float32 or tuple(out.shape) != tuple(disp.shape) or out.device != disp.device:
-            raise RuntimeError(f"out must be float32 {tuple(disp.shape)} on {disp.device}")
+        _check_like("out", out, torch.float32, disp.shape, disp.device)
     n = 1 if disp.dim() == 2 else int(disp.shape[0])
     return out, n, int(disp.shape[-2]), int(disp.shape[-1])
 
@@ -146,20 +162,17 @@ def _postprocess_workspace(n: int, H: int, W: int, device: torch.device) -> torc
 def _launch_filter_speckles(disp, out, n, H, W, max_speckle_size, max_diff, invalid_disparity, workspace) -> None:
     dev = disp.device.index
     check(LIB.smx_filter_speckles(dev, n, H, W, disp.data_ptr(), out.data_ptr(), int(max_speckle_size), float(max_diff),
-                                  float(invalid_disparity), workspace.data_ptr(), workspace.numel(),
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                  float(invalid_disparity), workspace.data_ptr(), workspace.numel(), _stream(dev)))
 
 
 def _launch_fill_invalid(disp, out, n, H, W, invalid_disparity, workspace) -> None:
     dev = disp.device.index
     check(LIB.smx_fill_invalid(dev, n, H, W, disp.data_ptr(), out.data_ptr(), float(invalid_disparity),
-                               workspace.data_ptr(), workspace.numel(),
-                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                               workspace.data_ptr(), workspace.numel(), _stream(dev)))
 
 
 def _check_speckle_size(max_speckle_size) -> None:
-    if isinstance(max_speckle_size, bool) or not isinstance(max_speckle_size, int):
-        raise TypeError("max_speckle_size must be an int")
+    _int_arg("max_speckle_size", max_speckle_size)
     if not 0 <= max_speckle_size <= 2**31 - 1:
         raise RuntimeError(f"max_speckle_size must be in [0, 2**31 - 1], got {max_speckle_size}")
 
@@ -189,13 +202,11 @@ def fill_invalid(disp: torch.Tensor, *, invalid_disparity: float = -1.0,
 
 
 def _check_median_params(radius, sigma_color, sigma_space) -> None:
-    if isinstance(radius, bool) or not isinstance(radius, int):
-        raise TypeError("radius must be an int")
+    _int_arg("radius", radius)
     if not 1 <= radius <= 15:
         raise RuntimeError(f"radius must be in 1..15, got {radius}")
     for name, v in (("sigma_color", sigma_color), ("sigma_space", sigma_space)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise TypeError(f"{name} must be a number")
+        _number_arg(name, v)
         if not (math.isfinite(v) and v > 0):
             raise RuntimeError(f"{name} must be finite and > 0, got {v}")
 
@@ -212,12 +223,6 @@ def median_weight_tables(radius: int, sigma_color: float, sigma_space: float):
     spatial = np.array([math.floor(1023.0 * math.exp(-(dx * dx + dy * dy) / ss2) + 0.5)
                         for dy in range(radius + 1) for dx in range(radius + 1)], np.uint16)
     return rng, spatial
-
-
-def _median_operand(name: str, t: torch.Tensor, disp: torch.Tensor) -> None:
-    _check_input(name, t)
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(disp.shape) or t.device != disp.device:
-        raise RuntimeError(f"{name} must be float32 {tuple(disp.shape)} on {disp.device}")
 
 
 def _median_workspace(n: int, H: int, W: int, device: torch.device) -> Optional[torch.Tensor]:
@@ -239,8 +244,7 @@ def _launch_weighted_median(disp, holes, guide, out, n, H, W, radius, range_weig
     check(LIB.smx_weighted_median(dev, n, H, W, disp.data_ptr(), holes.data_ptr() if holes is not None else None,
                                   guide.data_ptr(), out.data_ptr(), int(radius), rw.ctypes.data, sw.ctypes.data,
                                   float(invalid_disparity), workspace.data_ptr() if workspace is not None else None,
-                                  workspace.numel() if workspace is not None else 0,
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                  workspace.numel() if workspace is not None else 0, _stream(dev)))
 
 
 def weighted_median(disp: torch.Tensor, guide: torch.Tensor, *, radius: int, sigma_color: float, sigma_space: float,
@@ -255,9 +259,9 @@ def weighted_median(disp: torch.Tensor, guide: torch.Tensor, *, radius: int, sig
     _check_median_params(radius, sigma_color, sigma_space)
     _check_lr_scalars(0.0, invalid_disparity)
     out, n, H, W = _postprocess_operands(disp, out)
-    _median_operand("guide", guide, disp)
+    _check_like("guide", guide, torch.float32, disp.shape, disp.device)
     if holes is not None:
-        _median_operand("holes", holes, disp)
+        _check_like("holes", holes, torch.float32, disp.shape, disp.device)
     rw, sw = median_weight_tables(radius, sigma_color, sigma_space)
     _launch_weighted_median(disp, holes, guide, out, n, H, W, radius, rw, sw, invalid_disparity,
                             _median_workspace(n, H, W, disp.device))
@@ -364,8 +368,7 @@ class StereoRectification:
         self.out_shape = _shape2("out_shape", out_shape)
         if border_mode not in _BORDERS:
             raise ValueError(f"border_mode must be 'constant' or 'replicate', got {border_mode!r}")
-        if isinstance(border_value, bool) or not isinstance(border_value, (int, float)):
-            raise TypeError("border_value must be a number")
+        _number_arg("border_value", border_value)
         if not math.isfinite(border_value):
             raise ValueError(f"border_value must be finite, got {border_value}")
         self.border_mode = border_mode
@@ -393,9 +396,7 @@ class StereoRectification:
     def _out(self, name, t, like, shape):
         if t is None:
             return torch.empty(shape, dtype=like.dtype, device=like.device)
-        _check_input(name, t)
-        if t.dtype != like.dtype or tuple(t.shape) != shape or t.device != like.device:
-            raise RuntimeError(f"{name} must be {like.dtype} {shape} on {like.device}")
+        _check_like(name, t, like.dtype, shape, like.device)
         return t
 
     def rectify(self, left: torch.Tensor, right: Optional[torch.Tensor] = None, out=None):
@@ -415,9 +416,7 @@ class StereoRectification:
         if left.numel() == 0:
             raise RuntimeError("left is empty")
         if right is not None:
-            _check_input("right", right)
-            if right.dtype != left.dtype or tuple(right.shape) != tuple(left.shape) or right.device != left.device:
-                raise RuntimeError(f"right must be {left.dtype} {tuple(left.shape)} on {left.device}")
+            _check_like("right", right, left.dtype, left.shape, left.device)
         if left.dtype == torch.uint8 and not (0 <= self.border_value <= 255 and self.border_value.is_integer()):
             raise RuntimeError(f"a uint8 border_value must be an integer in 0..255, got {self.border_value}")
         shape = tuple(left.shape[:-2]) + self.out_shape
@@ -435,7 +434,7 @@ class StereoRectification:
                                   None if right is None else right.data_ptr(), self.left_map.data_ptr(),
                                   None if right is None else self.right_map.data_ptr(), lo.data_ptr(),
                                   None if ro is None else ro.data_ptr(), _BORDERS[self.border_mode],
-                                  self.border_value, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                  self.border_value, _stream(dev)))
         return lo if right is None else (lo, ro)
 
 
@@ -495,7 +494,7 @@ class StereoMatching:
         return self._dims
 
     def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        return _stream(self._device)
 
     def _validate(self, name: str, t: torch.Tensor, shape, dtype=torch.float32) -> None:
         _check_input(name, t)

@@ -64,8 +64,7 @@ class CudaStereoMatchingBackend(StereoMatching):
         self._speckle_max_diff = float(speckle_max_diff)
         self._fill_invalid = bool(fill_invalid)
         self._post_workspace: Optional[torch.Tensor] = None
-        if isinstance(median_radius, bool) or not isinstance(median_radius, int):
-            raise TypeError("median_radius must be an int")
+        cuda_depth._int_arg("median_radius", median_radius)
         if median_radius != 0:                              # 0: off; otherwise 1..15 with finite, positive sigmas
             self._median_tables = cuda_depth.median_weight_tables(median_radius, median_sigma_color, median_sigma_space)
         else:

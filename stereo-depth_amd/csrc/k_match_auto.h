@@ -54,6 +54,41 @@ inline int match_auto_nsplit(const MatchParams &p, int th) {
     return ns;
 }
 
+// Floats of slice records the off-grid branch of a one-launch call of n pairs writes: [nsplit][SMX_SLICE_WORDS][n][h][w].
+// One rule for the buffer and the launch: slice_region_floats sizes each stream lane's region with it, and
+// match_auto_small_applicable refuses a call whose records do not fit (it takes the two gated launches instead).
+inline size_t match_auto_slice_floats(const MatchParams &p, int n, int th) {
+    return (size_t)match_auto_nsplit(p, th) * (size_t)n * SMX_SLICE_WORDS * (size_t)p.h * (size_t)p.w;
+}
+
+// Floats of one stream lane's region of the slice buffer (smx_create; two small calls may be in flight at once): the
+// largest disparity split launch_exact can pick (calls of up to 4 pairs) and, if the engine can take the one-launch AUTO
+// kernel (one_launch), the records of its calls of up to 16 pairs in the latency shape, on a caller's stream or on the
+// lanes.  Larger calls that would need more room take the two gated launches, whose split is 1 beyond 4 pairs.
+// p: the engine's h, w and Dd; cus: the device's CU count.
+inline size_t slice_region_floats(MatchParams p, int B, int cus, bool one_launch) {
+    const int tiles = ((p.w + E2_TW - 1) / E2_TW) * ((p.h + E2_TH - 1) / E2_TH);
+    const size_t hw = (size_t)p.h * p.w;
+    size_t floats = 0;
+    for (int n = 1; n <= B && n <= 4; ++n) {
+        const int sp = exact_split(tiles, n, p.Dd, cus);
+        const size_t need = (size_t)sp * n * SMX_SLICE_WORDS * hw;
+        if (sp > 1 && need > floats) floats = need;
+    }
+    if (one_launch) {
+        p.pass1_only = 0;                       // (the one-launch kernel never serves the capture route)
+        for (int n = 1; n <= B && n <= 16; ++n) {
+            for (int lanes = 0; lanes < 2; ++lanes) {
+                p.on_lanes = lanes;
+                const FastPlan pl = match_fast_plan(p, n, cus);
+                const size_t need = pl.small ? match_auto_slice_floats(p, n, pl.th) : 0;
+                if (need > floats) floats = need;
+            }
+        }
+    }
+    return floats;
+}
+
 // Dynamic-LDS limit the engine raises these kernels to once per device (max of the fast split tile and the 64 KB exact tile;
 // the split tile's needed-set table grows with the range: 73 KB + 32 B per disparity up to 2048 disparities at 8-row bands,
 // 97 KB + 32 B at 12-row bands -- those run one workgroup per CU by design).
@@ -61,12 +96,14 @@ constexpr int MATCH_AUTO_LDS_CAP = 128 * 1024;
 
 // workgroups per pair of the disparity-split fast kernel / of the exact-order kernel; ranges whose tile would not fit
 // the raised limit (more than ~780 disparities) take the two gated launches instead
-// th: the band height match_fast_plan chose for this call (FA_TH_SMALL or FA_TH_SMALL_TALL)
-inline bool match_auto_small_applicable(const MatchParams &p, int th) {
+// th: the band height match_fast_plan chose for this call of n pairs; slices_floats: the floats of this lane's region of
+// the slice buffer (the records of the off-grid branch must fit it)
+inline bool match_auto_small_applicable(const MatchParams &p, int th, int n, size_t slices_floats) {
     const long fast_wgs = (long)((p.w + FA_VALID - 1) / FA_VALID) * ((p.h + th - 1) / th);
     const long tiles = (long)((p.w + E2_TW - 1) / E2_TW) * ((p.h + E2_TH - 1) / E2_TH);
     const size_t lds = p.Dd <= 256 - 64 + 1 ? fast_lds_bytes<256>(th, p.Dd, true) : fast_lds_bytes<320>(th, p.Dd, true);
-    return fast_wgs >= tiles && !p.pass1_only && !p.vol && lds <= (size_t)MATCH_AUTO_LDS_CAP && p.tickets != nullptr && p.slices != nullptr;
+    return fast_wgs >= tiles && !p.pass1_only && !p.vol && lds <= (size_t)MATCH_AUTO_LDS_CAP && p.tickets != nullptr && p.slices != nullptr &&
+           match_auto_slice_floats(p, n, th) <= slices_floats;
 }
 
 template <int TH, int PR>

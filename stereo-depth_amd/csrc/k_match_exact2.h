@@ -34,6 +34,31 @@ template <int NR> struct E2K {
     static constexpr int WAVES = E2_TH / NR;          // waves per workgroup: 4 or 8
     static constexpr int THREADS = 64 * WAVES;
 };
+
+// Disparity slices per pair for the register-tiled exact kernel (calls of up to 4 pairs): the split that minimises
+// rounds of workgroups x disparities per workgroup.  A CU holds two of these workgroups (80 KB of LDS, 191 registers), so
+// a round is 2 * cus workgroups; a split launch pays its merge kernel (about two slices' worth).  C2-shaped pair: 60 tiles
+// -> 8 slices of 8 (480 workgroups, one round); the reference's default 1080p configuration: 272 tiles x 95 disparities
+// -> 7 slices of 14 in 4 rounds = 56 slice times instead of 95 in one round with half of the slots empty.
+inline int exact_split(int tiles, int n, int Dd, int cus) {
+    if (n > 4 || Dd < 16) return 1;
+    const long slots = 2L * cus, wgs = (long)tiles * n;
+    int best = 1;
+    long best_cost = ((wgs + slots - 1) / slots) * Dd;
+#ifndef SMX_E2_MIN_PER
+#define SMX_E2_MIN_PER 8
+#endif
+#ifndef SMX_E2_MAX_SPLIT
+#define SMX_E2_MAX_SPLIT 8
+#endif
+    for (int sp = 2; sp <= SMX_E2_MAX_SPLIT && Dd / sp >= SMX_E2_MIN_PER; ++sp) {
+        const long per = (Dd + sp - 1) / sp;
+        const long cost = ((wgs * sp + slots - 1) / slots) * per + 2;
+        if (cost < best_cost) { best_cost = cost; best = sp; }
+    }
+    return best;
+}
+
 constexpr int E2_RL = 10, E2_RM = 4, E2_RS = 1, E2_RN = 1;
 constexpr int E2_HL = E2_RL + E2_RN;      // 11
 constexpr int E2_LROWS = E2_TH + 2 * E2_HL;       // 38 staged rows
@@ -415,9 +440,12 @@ template <bool DEV> __device__ __forceinline__ void e2_merge_pixel(const MatchPa
 template <int THREADS>
 __device__ __forceinline__ void e2_merge_by_last_arriver(const MatchParams &p, int b, int tile, int tiles, int tiles_x) {
     __shared__ int is_last;
-    // the records were written with device-scope stores: once every wave's stores have completed (workgroup-scope release +
-    // barrier) the ticket may be taken; no L2 write-back, and the merging workgroup reads them with device-scope loads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    // The records were written with device-scope (sc1, write-through) stores; the ticket may be taken only once every
+    // wave's stores have completed.  Each wave drains its own vector stores (s_waitcnt vmcnt(0)) before the barrier, so
+    // when thread 0 passes the barrier all of the workgroup's records have landed.  A workgroup-scope release would not
+    // do it: on this chip it emits no vmcnt wait, and the ticket could become visible before the records.  No L2
+    // write-back is needed, and the merging workgroup reads the records with device-scope (sc1) loads.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned *t = p.tickets + (size_t)b * tiles + tile;

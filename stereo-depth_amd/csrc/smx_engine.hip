@@ -23,6 +23,7 @@
 #include "k_fill.h"
 #include "k_match_exact.h"
 #include "k_match_exact2.h"
+#include "k_match_auto.h"
 #include "k_match_filter.h"
 #include "k_match_capture.h"
 #include "k_match_fast.h"
@@ -519,7 +520,7 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
         mp.gate = 0;
         launch_fast(e, mp, n, s);
         if (e->capture) smx::launch_match_capture_tu(mp, n, e->cus, s);
-    } else if (e->default_radii && small && e->call_grid_hint == 0 && smx::match_auto_small_ok(mp, n, e->cus)) {
+    } else if (e->default_radii && small && e->call_grid_hint == 0 && smx::match_auto_small_ok(mp, n, e->cus, xp.slices_floats)) {
         // AUTO, few pairs in flight, the last reported call on the grid: one launch that branches on the device-side
         // flag (k_match_auto.h).  Its exact-order branch (the disparity-split register-tiled kernel on the fast kernel's
         // grid, merged by the last workgroup of a tile) is ~1.4 x slower than the two gated launches below, so those serve
@@ -1066,24 +1067,17 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
         alloc((void **)&e->gray8_r, B * (size_t)d.H * e->pitch8);
     }
     if (e->default_radii) {
-        // disparity-split exact kernel (few pairs in flight): room for the largest split launch_exact can pick
+        // slice records of the disparity-split exact kernel and of the one-launch AUTO kernel's off-grid branch (few pairs
+        // in flight): one region per stream lane, sized by the rule the launches check against (k_match_auto.h)
+        smx::MatchParams sp{};
+        sp.h = d.h; sp.w = d.w; sp.Dd = d.Dd;
+        const size_t floats = smx::slice_region_floats(sp, e->B, e->cus, e->fast_ok_host);
         const int tiles = ((d.w + smx::E2_TW - 1) / smx::E2_TW) * ((d.h + smx::E2_TH - 1) / smx::E2_TH);
-        size_t recs = 0;
-        for (int n = 1; n <= e->B && n <= 4; ++n) {
-            const int sp = smx::exact_split(tiles, n, d.Dd, e->cus);
-            if (sp > 1 && (size_t)sp * n > recs) recs = (size_t)sp * n;
-        }
-        // the one-launch AUTO kernel splits its off-grid branch into up to 8 slices per tile (k_match_auto.h), for calls of
-        // up to ~12 pairs (the latency shape)
-        if (e->fast_ok_host) {
-            const size_t nmax = (size_t)(e->B < 16 ? e->B : 16);
-            if (8 * nmax > recs) recs = 8 * nmax;
-        }
         // arrival tickets per (pair slot, tile): the last slice of a tile merges it inside the split launch
         e->e2_tiles = tiles;
         alloc((void **)&e->tickets, B * (size_t)tiles * sizeof(unsigned));
-        if (recs) {
-            e->xp.slices_floats = recs * smx::SMX_SLICE_WORDS * hw;
+        if (floats) {
+            e->xp.slices_floats = floats;
             // one region per stream lane: two small calls may be in flight at once (alternating lanes, see enqueue)
             alloc((void **)&e->slices, smx_engine::LANES * e->xp.slices_floats * sizeof(float));
             e->xp.slices = e->slices;

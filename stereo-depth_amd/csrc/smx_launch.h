@@ -51,7 +51,6 @@ struct ExactPlan {
     float *slices;           // partial arg-max states of the disparity-split launch
     size_t slices_floats;
 };
-int exact_split(int tiles, int n, int Dd, int cus);
 // 0 = enqueued; 1 = the slice buffer is too small for the split this launch would choose (internal error)
 int launch_exact(const ExactPlan &pl, MatchParams p, int n, bool allow_split, int cus, hipStream_t s);
 void launch_exact2_capture(const ExactPlan &pl, MatchParams p, int n, bool allow_split, int cus, hipStream_t s);
@@ -65,7 +64,8 @@ void launch_match_fast(const MatchParams &p, int n, int cus, hipStream_t s);
 void launch_match_fast_tall_24(const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_27(const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_32(const MatchParams &p, int n, hipStream_t s);
-bool match_auto_small_ok(const MatchParams &p, int n, int cus);
+// slices_floats: this lane's region of the slice buffer (k_match_auto.h: slice_region_floats)
+bool match_auto_small_ok(const MatchParams &p, int n, int cus, size_t slices_floats);
 void launch_match_auto_small_tu(const MatchParams &p, int n, int cus, hipStream_t s);
 hipError_t match_auto_raise_caps();       // k_match_auto.h: MATCH_AUTO_LDS_CAP
 

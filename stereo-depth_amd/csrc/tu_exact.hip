@@ -6,30 +6,6 @@
 
 namespace smx {
 
-// Disparity slices per pair for the register-tiled exact kernel (calls of up to 4 pairs): the split that minimises
-// rounds of workgroups x disparities per workgroup.  A CU holds two of these workgroups (80 KB of LDS, 191 registers), so
-// a round is 2 * cus workgroups; a split launch pays its merge kernel (about two slices' worth).  C2-shaped pair: 60 tiles
-// -> 8 slices of 8 (480 workgroups, one round); the reference's default 1080p configuration: 272 tiles x 95 disparities
-// -> 7 slices of 14 in 4 rounds = 56 slice times instead of 95 in one round with half of the slots empty.
-int exact_split(int tiles, int n, int Dd, int cus) {
-    if (n > 4 || Dd < 16) return 1;
-    const long slots = 2L * cus, wgs = (long)tiles * n;
-    int best = 1;
-    long best_cost = ((wgs + slots - 1) / slots) * Dd;
-#ifndef SMX_E2_MIN_PER
-#define SMX_E2_MIN_PER 8
-#endif
-#ifndef SMX_E2_MAX_SPLIT
-#define SMX_E2_MAX_SPLIT 8
-#endif
-    for (int sp = 2; sp <= SMX_E2_MAX_SPLIT && Dd / sp >= SMX_E2_MIN_PER; ++sp) {
-        const long per = (Dd + sp - 1) / sp;
-        const long cost = ((wgs * sp + slots - 1) / slots) * per + 2;
-        if (cost < best_cost) { best_cost = cost; best = sp; }
-    }
-    return best;
-}
-
 int launch_exact(const ExactPlan &pl, MatchParams p, int n, bool allow_split, int cus, hipStream_t s) {
     const bool vol = p.vol != nullptr;
     if (!vol && p.rn == 1 && p.rs == 1 && p.rm == 4 && p.rl == 10) {

@@ -23,6 +23,7 @@
  *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
  *   -- (image-guided weighted median)                     smx_weighted_median
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
+ *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -462,6 +463,48 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
 int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
                     const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
                     void *left_out, void *right_out, int border_mode, float border_value, void *stream);
+
+/* Semi-global matching (Hirschmueller, TPAMI 2008) with a census cost: a second matcher beside the engine, engine-free.
+ * The rule is integer up to one float32 division, so every implementation gives the same bits.
+ *   - Input: n pairs of planar [C][H][W] frames, C in {1, 3}, SMX_DTYPE_U8 or SMX_DTYPE_F32.  Candidate i in 0..D-1
+ *     (D = num_disparities, 1..256) means disparity dmin + i (dmin = min_disparity, 0..32768): the left pixel (y, x)
+ *     matches the right pixel (y, x - dmin - i).
+ *   - Gray: for C = 3, (0.2989f*r + 0.5870f*g) + 0.1140f*b in float32 with no contraction (the engine's step 1, on the
+ *     values or on float(u8)); for C = 1, the values themselves.
+ *   - Census: a 9 wide x 7 high window; bit k is set when the k-th of its 62 neighbours (row-major, centre skipped) is
+ *     < the centre under IEEE < (a NaN gives 0).  Neighbour coordinates are clamped into the image.
+ *   - Cost: C(p, i) = popcount(cL(y, x) ^ cR(y, x - dmin - i)), and 64 when x - dmin - i < 0.
+ *   - Paths: 4, the directions (0,+1), (0,-1), (+1,0), (-1,0), or 8, which add the four diagonals.  With q = p - r the
+ *     predecessor of p on path r: L_r(p,i) = C(p,i) when q lies outside the image, otherwise
+ *       L_r(p,i) = C(p,i) + min(L_r(q,i), L_r(q,i-1) + P1, L_r(q,i+1) + P1, M_r(q) + P2) - M_r(q),
+ *     M_r(q) = min_k L_r(q,k); a neighbour i+-1 outside 0..D-1 is left out of the min.  0 <= P1 <= P2 <= 191, so
+ *     L_r <= 255 and S = sum_r L_r <= 2040.
+ *   - Winner: i* is the smallest i minimising S(p, i); d* = dmin + i*.
+ *   - Invalid (the pixel is invalid_disparity): (a) x - d* < 0; (b) uniqueness u in 1..99 (0: off) and some i with
+ *     |i - i*| > 1 has S(i) * (100 - u) < S(i*) * 100; (c) lr_max_diff >= 0 and |dmin + iR(y, x - d*) - d*| >
+ *     lr_max_diff, where iR(y, x') is the smallest i minimising S(y, x' + dmin + i, i) over the i with
+ *     x' + dmin + i <= W - 1 (the right-view winner, from the same S).  A negative lr_max_diff turns (c) off.
+ *   - Value: with subpixel != 0 and 0 < i* < D-1, den = S(i*-1) + S(i*+1) - 2 S(i*); if den > 0 the output is
+ *     f32(d*) + f32(S(i*-1) - S(i*+1)) / f32(2 den) (one correctly rounded division, then one add), else f32(d*).
+ *   - gray_left_out (NULL: not written): the f32 [n][H][W] gray planes of the left frames, the weighted median's guide.
+ * left / right: [n][C][H][W] device frames; out: [n][H][W] f32.  out and gray_left_out must not overlap an input, the
+ * workspace or each other.  workspace: device memory of at least smx_sgm_workspace_bytes(n, H, W, D, paths) bytes; its
+ * contents on entry do not matter.  With P = n*H*W, Dp = D rounded up to a multiple of (D <= 64 ? 1 : D <= 128 ? 2 : 4)
+ * and R(v) = v rounded up to a multiple of 256, the size is
+ *     R(8 P) + R(8 P) + R(2 Dp P) + R(2 P)
+ * (two census planes, the u16 volume S and the right-view winners; the same for 4 and 8 paths).  It is 0 for
+ * arguments smx_sgm would reject by size.  A batch whose n * (H + W) exceeds 2^31 must be split by the caller.
+ * A fixed sequence of 4 to 7 launches on `stream` (a caller's stream), with no host synchronisation and no allocation,
+ * so it can be captured into a HIP graph.  Engine-free: device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL left, right, out or workspace, n < 1, H or W
+ * outside 1..32768, n * (H + W) > 2^31, channels not 1 or 3, an unknown dtype, min_disparity outside 0..32768,
+ * num_disparities outside 1..256, paths not 4 or 8, not 0 <= P1 <= P2 <= 191, uniqueness outside 0..99, a non-finite
+ * lr_max_diff or invalid_disparity, workspace_bytes below the query, the overlaps above, stream == SMX_STREAM_ENGINE. */
+size_t smx_sgm_workspace_bytes(int n, int H, int W, int num_disparities, int paths);
+int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const void *left, const void *right,
+            int min_disparity, int num_disparities, int paths, int P1, int P2, int uniqueness, float lr_max_diff,
+            int subpixel, float invalid_disparity, float *out, float *gray_left_out, void *workspace,
+            size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

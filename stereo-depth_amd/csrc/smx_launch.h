@@ -104,4 +104,11 @@ void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, 
                         const int32_t *map_l, const int32_t *map_r, void *out_l, void *out_r, bool replicate,
                         float border_value, hipStream_t s);
 
+// ---- tu_sgm.hip: semi-global matching (k_sgm.h) ----------------------------------------------------------------------
+// workspace: sgm_workspace_bytes(n, H, W, D) bytes (smx_sgm_workspace_bytes); arguments checked by smx_sgm
+size_t sgm_workspace_bytes(int n, int H, int W, int D);
+void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const void *right, int dmin, int D, int paths,
+                int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
+                float *gray_out, void *workspace, hipStream_t s);
+
 }  // namespace smx

@@ -174,6 +174,68 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
     });
 }
 
+// The size rules of smx_sgm that the workspace query shares: 0 = accepted.
+static int sgm_size_error(int n, int H, int W, int D, int paths) {
+    if (!map_dims_ok(n, H, W)) return 1;
+    if (D < 1 || D > 256) return 2;
+    if (paths != 4 && paths != 8) return 3;
+    if ((size_t)n * (size_t)(H + W) > ((size_t)1 << 31)) return 4;
+    return 0;
+}
+
+size_t smx_sgm_workspace_bytes(int n, int H, int W, int num_disparities, int paths) {
+    return sgm_size_error(n, H, W, num_disparities, paths) ? 0 : smx::sgm_workspace_bytes(n, H, W, num_disparities);
+}
+
+int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const void *left, const void *right,
+            int min_disparity, int num_disparities, int paths, int P1, int P2, int uniqueness, float lr_max_diff,
+            int subpixel, float invalid_disparity, float *out, float *gray_left_out, void *workspace,
+            size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_sgm";
+    if (!left || !right || !out || !workspace)
+        return fail(SMX_ERR_INVALID_ARG, "%s: left, right, out and workspace must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if ((size_t)n * (size_t)(H + W) > ((size_t)1 << 31))
+        return fail(SMX_ERR_INVALID_ARG, "%s: n * (H + W) = %zu exceeds 2^31: split the batch", fn,
+                    (size_t)n * (size_t)(H + W));
+    if (channels != 1 && channels != 3) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be 1 or 3, got %d", fn, channels);
+    if (dtype != SMX_DTYPE_U8 && dtype != SMX_DTYPE_F32) return fail(SMX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (min_disparity < 0 || min_disparity > 32768)
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_disparity must be in 0..32768, got %d", fn, min_disparity);
+    if (num_disparities < 1 || num_disparities > 256)
+        return fail(SMX_ERR_INVALID_ARG, "%s: num_disparities must be in 1..256, got %d", fn, num_disparities);
+    if (paths != 4 && paths != 8) return fail(SMX_ERR_INVALID_ARG, "%s: paths must be 4 or 8, got %d", fn, paths);
+    if (!(0 <= P1 && P1 <= P2 && P2 <= 191))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 0 <= P1 <= P2 <= 191, got P1 %d, P2 %d", fn, P1, P2);
+    if (uniqueness < 0 || uniqueness > 99)
+        return fail(SMX_ERR_INVALID_ARG, "%s: uniqueness must be in 0..99 (percent, 0: off), got %d", fn, uniqueness);
+    if (!std::isfinite(lr_max_diff))
+        return fail(SMX_ERR_INVALID_ARG, "%s: lr_max_diff must be finite (negative: no LR check), got %g", fn,
+                    (double)lr_max_diff);
+    if (int rc = check_finite_marker(invalid_disparity)) return rc;
+    const size_t need = smx::sgm_workspace_bytes(n, H, W, num_disparities);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_sgm_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t in_bytes = (size_t)n * channels * H * W * (dtype == SMX_DTYPE_F32 ? 4 : 1);
+    const size_t map_bytes = (size_t)n * H * W * sizeof(float);
+    const void *outs[2] = {out, gray_left_out};
+    for (const void *o : outs)
+        if (ranges_overlap(o, map_bytes, left, in_bytes) || ranges_overlap(o, map_bytes, right, in_bytes) ||
+            ranges_overlap(o, map_bytes, workspace, workspace_bytes))
+            return fail(SMX_ERR_INVALID_ARG, "%s: out and gray_left_out must not overlap left, right or the workspace", fn);
+    if (ranges_overlap(out, map_bytes, gray_left_out, map_bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out and gray_left_out overlap", fn);
+    if (ranges_overlap(workspace, workspace_bytes, left, in_bytes) || ranges_overlap(workspace, workspace_bytes, right, in_bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap left or right", fn);
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_sgm(n, channels, dtype == SMX_DTYPE_F32, H, W, left, right, min_disparity, num_disparities, paths, P1,
+                        P2, uniqueness, lr_max_diff, subpixel != 0, invalid_disparity, out, gray_left_out, workspace,
+                        (hipStream_t)stream);
+    });
+}
+
 int smx_disparity_to_points(int device_id, const float *disp, int H, int W, float bf, float invalid,
                             float *depth, float *points, int *count_dev, int *workspace, void *stream) {
     if (!disp || !points || !count_dev || !workspace || H < 1 || W < 1 || H > 32768)

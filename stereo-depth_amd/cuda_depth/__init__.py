@@ -438,6 +438,91 @@ class StereoRectification:
         return lo if right is None else (lo, ro)
 
 
+class StereoSGM:
+    """Semi-global matching with a census 9x7 cost (smx_sgm; the rule is in include/stereo_mi355x.h), a second matcher
+    beside StereoMatching.  Candidates are min_disparity..max_disparity (at most 256); paths 4 or 8; 0 <= P1 <= P2 <= 191;
+    uniqueness in 0..99 percent (0: off); lr_max_diff None (no check) or a finite value >= 0: pixels whose right-view
+    match does not point back within it become invalid_disparity; subpixel: parabola through the winner's neighbours."""
+
+    def __init__(self, min_disparity: int = 0, max_disparity: int = 127, *, paths: int = 8, P1: int = 10,
+                 P2: int = 120, uniqueness: int = 0, lr_max_diff: Optional[float] = None, subpixel: bool = True,
+                 invalid_disparity: float = -1.0):
+        for name, v in (("min_disparity", min_disparity), ("max_disparity", max_disparity), ("paths", paths),
+                        ("P1", P1), ("P2", P2), ("uniqueness", uniqueness)):
+            _int_arg(name, v)
+        if not 0 <= min_disparity <= 32768:
+            raise RuntimeError(f"min_disparity must be in 0..32768, got {min_disparity}")
+        if not 1 <= max_disparity - min_disparity + 1 <= 256:
+            raise RuntimeError(f"need 1 <= max_disparity - min_disparity + 1 <= 256, got {min_disparity}..{max_disparity}")
+        if paths not in (4, 8):
+            raise RuntimeError(f"paths must be 4 or 8, got {paths}")
+        if not 0 <= P1 <= P2 <= 191:
+            raise RuntimeError(f"need 0 <= P1 <= P2 <= 191, got P1 {P1}, P2 {P2}")
+        if not 0 <= uniqueness <= 99:
+            raise RuntimeError(f"uniqueness must be in 0..99 (percent, 0: off), got {uniqueness}")
+        if lr_max_diff is not None:
+            _number_arg("lr_max_diff", lr_max_diff)
+            if not (math.isfinite(lr_max_diff) and lr_max_diff >= 0):
+                raise RuntimeError(f"lr_max_diff must be None or finite and >= 0, got {lr_max_diff}")
+        if not isinstance(subpixel, bool):
+            raise TypeError("subpixel must be a bool")
+        _number_arg("invalid_disparity", invalid_disparity)
+        if not math.isfinite(invalid_disparity):
+            raise RuntimeError(f"invalid_disparity must be finite (a NaN marker never compares equal), got "
+                               f"{invalid_disparity}")
+        self.min_disparity, self.max_disparity = min_disparity, max_disparity
+        self.num_disparities = max_disparity - min_disparity + 1
+        self.paths, self.P1, self.P2, self.uniqueness = paths, P1, P2, uniqueness
+        self.lr_max_diff = None if lr_max_diff is None else float(lr_max_diff)
+        self.subpixel = subpixel
+        self.invalid_disparity = float(invalid_disparity)
+        self._workspace: dict = {}                          # (device, n, H, W) -> uint8 tensor
+
+    def workspace(self, n: int, H: int, W: int, device: torch.device) -> torch.Tensor:
+        """The cached device workspace of smx_sgm for n pairs of H x W frames on `device`."""
+        key = (device, n, H, W)
+        ws = self._workspace.get(key)
+        if ws is None:
+            nbytes = int(LIB.smx_sgm_workspace_bytes(n, H, W, self.num_disparities, self.paths))
+            if nbytes == 0:
+                raise RuntimeError(f"StereoSGM: need 1 <= H, W <= 32768 and n * (H + W) <= 2**31 (got n {n}, {H} x {W})")
+            ws = self._workspace[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
+
+    def compute(self, left: torch.Tensor, right: torch.Tensor, out: Optional[torch.Tensor] = None,
+                gray_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """left, right: [C,H,W] or [n,C,H,W], uint8 or float32, C in {1, 3}, on one GPU.  Returns the float32 disparity
+        map(s), [H,W] or [n,H,W], computed on the current stream.  out: the map tensor to write; gray_out: a float32
+        tensor of the map's shape that receives the left frames' gray planes (the weighted median's guide)."""
+        _check_input("left", left)
+        _check_input("right", right)
+        if left.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError(f"frames must be uint8 or float32, got {left.dtype}")
+        if left.dim() not in (3, 4) or int(left.shape[-3]) not in (1, 3):
+            raise RuntimeError(f"frames must be [C,H,W] or [n,C,H,W] with C in (1, 3), got {tuple(left.shape)}")
+        if left.numel() == 0:
+            raise RuntimeError("left is empty")
+        _check_like("right", right, left.dtype, left.shape, left.device)
+        shape = (tuple(left.shape[:1]) if left.dim() == 4 else ()) + tuple(left.shape[-2:])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=left.device)
+        else:
+            _check_like("out", out, torch.float32, shape, left.device)
+        if gray_out is not None:
+            _check_like("gray_out", gray_out, torch.float32, shape, left.device)
+        n = 1 if left.dim() == 3 else int(left.shape[0])
+        H, W = int(left.shape[-2]), int(left.shape[-1])
+        ws = self.workspace(n, H, W, left.device)
+        dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
+        dev = left.device.index
+        check(LIB.smx_sgm(dev, n, int(left.shape[-3]), dt, H, W, left.data_ptr(), right.data_ptr(), self.min_disparity,
+                          self.num_disparities, self.paths, self.P1, self.P2, self.uniqueness,
+                          -1.0 if self.lr_max_diff is None else self.lr_max_diff, int(self.subpixel),
+                          self.invalid_disparity, out.data_ptr(), None if gray_out is None else gray_out.data_ptr(),
+                          ws.data_ptr(), ws.numel(), _stream(dev)))
+        return out
+
+
 class StereoMatching:
     """torch_extension_module.cc:22-26.  `compute_disparity_map` is the reference method;
     the keyword-only constructor extras and the *_gray / *_batch methods are additions that

@@ -111,6 +111,13 @@ EXPORTS = {
     "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                   C.c_void_p]),
+    # semi-global matching: (n, H, W, num_disparities, paths) -> workspace bytes; (device_id, n, channels, dtype, H, W,
+    # left, right, min_disparity, num_disparities, paths, P1, P2, uniqueness, lr_max_diff, subpixel, invalid_disparity,
+    # out, gray_left_out, workspace, workspace_bytes, stream)
+    "smx_sgm_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "smx_sgm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

@@ -1,0 +1,115 @@
+"""What the stereo-matching backends share around their matcher: rectification of the raw frames before matching, and
+the post-processing of the map after it (speckle filter, background hole fill, image-guided weighted median, the
+rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
+from __future__ import annotations
+
+from typing import Callable, Optional
+
+import torch
+
+import cuda_depth
+
+
+def device_frame(image: torch.Tensor) -> torch.Tensor:
+    """Contiguous, on the GPU, uint8 kept, everything else as float32."""
+    image = image.cuda()
+    if image.dtype != torch.uint8:
+        image = image.float()
+    return image.contiguous()
+
+
+class MapPostprocessing:
+    """Mixin of the backends: _init_postprocessing() in the constructor, _rectify() before matching, _finish() after.
+    speckle_max_size > 0: the speckle filter (cuda_depth.filter_speckles) removes every region of speckle_max_size
+    pixels or fewer whose 4-neighbours differ by at most speckle_max_diff.  fill_invalid=True: then the background hole
+    fill (cuda_depth.fill_invalid) makes the map dense again.  Both run in place on the map.
+    median_radius > 0: last, the image-guided weighted median (cuda_depth.weighted_median, tables from median_sigma_color
+    and median_sigma_space), guided by the left gray plane of the matcher.  With fill_invalid it filters only the pixels
+    the fill wrote (the fill runs into a scratch map, the median writes the map); without, every valid pixel.
+    rectification (a cuda_depth.StereoRectification, or None): both raw frames are rectified before matching (its
+    out_shape must be image_size), and the pixels of the final map outside its left_valid mask become invalid_disparity."""
+
+    def _init_postprocessing(self, image_size: tuple, *, invalid_disparity: float = -1.0, speckle_max_size: int = 0,
+                             speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
+                             median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                             rectification: Optional["cuda_depth.StereoRectification"] = None) -> None:
+        if rectification is not None:
+            if not isinstance(rectification, cuda_depth.StereoRectification):
+                raise TypeError("rectification must be a cuda_depth.StereoRectification")
+            size = tuple(image_size)
+            if tuple(rectification.out_shape) != size:
+                raise ValueError(f"rectification.out_shape {tuple(rectification.out_shape)} differs from the image "
+                                 f"size {size}")
+        self._rectification = rectification
+        self._rectified: Optional[tuple] = None             # persistent output frames of the rectification
+        self._invalid_disparity = float(invalid_disparity)
+        cuda_depth._check_speckle_size(speckle_max_size)
+        cuda_depth._check_lr_scalars(speckle_max_diff, invalid_disparity)
+        self._speckle_max_size = speckle_max_size
+        self._speckle_max_diff = float(speckle_max_diff)
+        self._fill_invalid = bool(fill_invalid)
+        self._post_workspace: Optional[torch.Tensor] = None
+        cuda_depth._int_arg("median_radius", median_radius)
+        if median_radius != 0:                              # 0: off; otherwise 1..15 with finite, positive sigmas
+            self._median_tables = cuda_depth.median_weight_tables(median_radius, median_sigma_color, median_sigma_space)
+        else:
+            cuda_depth._check_median_params(1, median_sigma_color, median_sigma_space)
+        self._median_radius = median_radius
+        self._median_guide: Optional[torch.Tensor] = None   # the left gray plane of the last call
+        self._median_scratch: Optional[torch.Tensor] = None
+
+    def _guide_buffer(self, like: torch.Tensor) -> torch.Tensor:
+        """The persistent [H, W] float32 buffer the matcher's left gray plane goes into (median_radius > 0)."""
+        if self._median_guide is None:
+            self._median_guide = torch.empty_like(like)
+            self._median_scratch = torch.empty_like(like)
+        return self._median_guide
+
+    def _rectify(self, left: torch.Tensor, right: torch.Tensor):
+        """Both frames through the rectification (into persistent buffers), or unchanged without one."""
+        if self._rectification is None:
+            return left, right
+        shape = tuple(left.shape[:-2]) + tuple(self._rectification.out_shape)
+        if self._rectified is None or self._rectified[0].dtype != left.dtype or tuple(self._rectified[0].shape) != shape:
+            self._rectified = (torch.empty(shape, dtype=left.dtype, device=left.device),
+                               torch.empty(shape, dtype=left.dtype, device=left.device))
+        return self._rectification.rectify(left, right, out=self._rectified)
+
+    def rectified_frames(self) -> Optional[tuple]:
+        """(left, right) rectified frames of the last process() call (persistent buffers, overwritten by the next
+        call), or None without rectification."""
+        return self._rectified if self._rectification is not None else None
+
+    def _finish(self, disparity: torch.Tensor, write_guide: Optional[Callable[[torch.Tensor], None]] = None) -> None:
+        """Post-processes the [H, W] map in place.  write_guide(buffer): writes the left gray plane into the guide
+        buffer when the median runs (None: the matcher already wrote _guide_buffer())."""
+        if self._speckle_max_size > 0 or self._fill_invalid or self._median_radius > 0:
+            self._postprocess(disparity, write_guide)
+        if self._rectification is not None:
+            disparity.masked_fill_(~self._rectification.left_valid, self._invalid_disparity)
+
+    def _postprocess(self, disparity: torch.Tensor, write_guide) -> None:
+        H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
+        if self._post_workspace is None and (self._speckle_max_size > 0 or self._fill_invalid):
+            self._post_workspace = cuda_depth._postprocess_workspace(1, H, W, disparity.device)
+        if self._speckle_max_size > 0:
+            cuda_depth._launch_filter_speckles(disparity, disparity, 1, H, W, self._speckle_max_size,
+                                               self._speckle_max_diff, self._invalid_disparity, self._post_workspace)
+        if self._median_radius == 0:
+            if self._fill_invalid:
+                cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,
+                                                self._post_workspace)
+            return
+        guide = self._guide_buffer(disparity)
+        if write_guide is not None:
+            write_guide(guide)
+        scratch = self._median_scratch
+        if self._fill_invalid:                              # filled -> scratch; the median rewrites the filled pixels
+            cuda_depth._launch_fill_invalid(disparity, scratch, 1, H, W, self._invalid_disparity, self._post_workspace)
+            holes = disparity
+        else:                                               # every valid pixel
+            scratch.copy_(disparity)
+            holes = None
+        cuda_depth._launch_weighted_median(scratch, holes, guide, disparity, 1, H, W, self._median_radius,
+                                           *self._median_tables, self._invalid_disparity,
+                                           cuda_depth._median_workspace(1, H, W, disparity.device))

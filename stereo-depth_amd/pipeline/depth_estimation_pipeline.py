@@ -3,7 +3,7 @@
 Same public surface as /root/reference/src/python/pipeline/depth_estimation_pipeline.py:14-87
 (`DepthEstimationPipelineConfig` with its six fields -- plus the opt-in left-right check -- and `update`, `DepthEstimationResult`,
 `DepthEstimationPipelineContext`, `DepthEstimationPipeline.process / get_configuration`) for the
-'cuda' backend.  Right-view synthesis (Deep3D) and the traced-DNN backends are out of scope
+'cuda' and 'sgm' backends.  Right-view synthesis (Deep3D) and the traced-DNN backends are out of scope
 (SURVEY.md section 2): `right_image` is mandatory here and the other backend names raise.
 """
 from __future__ import annotations
@@ -15,9 +15,9 @@ import torch
 
 import cuda_depth
 from helpers.torch_helpers import cuda_perf_clock
-from pipeline.depth import AVAILABLE_DNN_BACKENDS, CudaStereoMatchingBackend, StereoMatching
+from pipeline.depth import AVAILABLE_DNN_BACKENDS, CudaStereoMatchingBackend, SgmStereoMatchingBackend, StereoMatching
 
-_BACKENDS = ("cuda",) + AVAILABLE_DNN_BACKENDS
+_BACKENDS = ("cuda", "sgm") + AVAILABLE_DNN_BACKENDS
 
 
 @dataclasses.dataclass
@@ -27,10 +27,11 @@ class DepthEstimationPipelineConfig:
     min_disparity: int = 1
     max_disparity: int = 64
     invalid_disparity: float = -1.0
-    stereo_matching_backend: str = "cuda"          # one of "cuda", "msnet2d", "msnet3d", "gwcnet"
+    stereo_matching_backend: str = "cuda"          # one of "cuda", "sgm", "msnet2d", "msnet3d", "gwcnet"
     log_perf_time: bool = False
-    # additions (no counterpart in the reference): left-right consistency check of the 'cuda' backend -- pixels whose
-    # match in the right image does not point back to them within lr_max_diff pixels become invalid_disparity
+    # additions (no counterpart in the reference): left-right consistency check of the 'cuda' and 'sgm' backends --
+    # pixels whose match in the right image does not point back to them within lr_max_diff pixels become
+    # invalid_disparity
     left_right_check: bool = False
     lr_max_diff: float = 1.0
 
@@ -69,12 +70,28 @@ class DepthEstimationPipelineContext:
     frame_index: int
 
 
-def _make_backend(config: DepthEstimationPipelineConfig, **post: Any) -> StereoMatching:
+def _check_sgm_keywords(paths: Any, p1: Any, p2: Any, uniqueness: Any) -> None:
+    for name, v in (("sgm_paths", paths), ("sgm_p1", p1), ("sgm_p2", p2), ("sgm_uniqueness", uniqueness)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name} must be an int")
+    if paths not in (4, 8):
+        raise ValueError(f"sgm_paths must be 4 or 8, got {paths}")
+    if not 0 <= p1 <= p2 <= 191:
+        raise ValueError(f"need 0 <= sgm_p1 <= sgm_p2 <= 191, got {p1}, {p2}")
+    if not 0 <= uniqueness <= 99:
+        raise ValueError(f"sgm_uniqueness must be in 0..99 (percent, 0: off), got {uniqueness}")
+
+
+def _make_backend(config: DepthEstimationPipelineConfig, sgm: dict, **post: Any) -> StereoMatching:
     name = config.stereo_matching_backend
     if name == "cuda":
         return CudaStereoMatchingBackend(configuration=config.engine_configuration(),
                                          left_right_check=config.left_right_check, lr_max_diff=config.lr_max_diff,
                                          invalid_disparity=config.invalid_disparity, **post)
+    if name == "sgm":
+        return SgmStereoMatchingBackend(config.image_shape, config.min_disparity, config.max_disparity, **sgm,
+                                        left_right_check=config.left_right_check, lr_max_diff=config.lr_max_diff,
+                                        invalid_disparity=config.invalid_disparity, **post)
     if name in AVAILABLE_DNN_BACKENDS:
         raise RuntimeError(f"Stereo matching backend '{name}' (traced DNN) is not part of this build; use 'cuda'.")
     raise RuntimeError(f"Unsupported stereo matching backend: {name}")
@@ -85,15 +102,20 @@ class DepthEstimationPipeline:
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
                  speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
                  median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
-                 rectification: Optional["cuda_depth.StereoRectification"] = None):
+                 rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
+                 sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
-        post-processing of the 'cuda' backend's map, after the left-right check if configured
+        post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  rectification: a
         cuda_depth.StereoRectification whose out_shape is config.image_shape; the raw frames are rectified on the GPU
         before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
-        rectified)."""
+        rectified).  sgm_paths / sgm_p1 / sgm_p2 / sgm_uniqueness: the tuning of the 'sgm' backend (4 or 8 paths,
+        0 <= P1 <= P2 <= 191, uniqueness 0..99 percent, 0 = off), which matches at image_shape over min_disparity..
+        max_disparity with the same post-processing; checked whatever the backend."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
-        self._stereo_matching = _make_backend(self._config, speckle_max_size=speckle_max_size,
+        _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
+        sgm = dict(paths=sgm_paths, P1=sgm_p1, P2=sgm_p2, uniqueness=sgm_uniqueness)
+        self._stereo_matching = _make_backend(self._config, sgm, speckle_max_size=speckle_max_size,
                                               speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
                                               median_radius=median_radius, median_sigma_color=median_sigma_color,
                                               median_sigma_space=median_sigma_space, rectification=rectification)

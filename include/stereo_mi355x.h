@@ -22,6 +22,7 @@
  *   -- (left-right consistency check)                     smx_compute_lr_*_batch, smx_lr_check
  *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
  *   -- (image-guided weighted median)                     smx_weighted_median
+ *   -- (image-guided weighted least squares filter)       smx_wls_filter, smx_wls_workspace_bytes
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
  *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
@@ -428,6 +429,45 @@ size_t smx_median_workspace_bytes(int n, int H, int W);        /* may be 0; 0 fo
 int smx_weighted_median(int device_id, int n, int H, int W, const float *in, const float *holes, const float *guide,
                         float *out, int radius, const uint16_t range_weight[256], const uint16_t spatial_weight[],
                         float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Image-guided weighted least squares filter: the fast global smoother of Min et al. (TIP 2014) as a confidence-weighted
+ * disparity filter.  It makes a checked map dense, smooth inside surfaces, with edges that follow the guide's.  Every
+ * operand is [n][H][W] f32 on the device; the n maps are independent.  VALID is as above.
+ *   1. Confidence: c(p) = 0 where p is not valid; otherwise 1.0f with confidence == NULL, else
+ *      (conf > 0) ? fminf(conf, 1.0f) : 0.0f (a NaN confidence gives 0).
+ *   2. Planes: U(p) = valid ? d * c : 0.0f (one float32 product), V(p) = c(p).
+ *   3. Edge weight between horizontal or vertical neighbours p, q: a = fabsf(guide[p] - guide[q]) in float32,
+ *      k = (isnan(a) || a >= 255) ? 255 : (int)a (as in the weighted median), w = range_weight[k]; range_weight is a host
+ *      table of 256 finite float32 values in [0, 1].
+ *   4. Iterations t = 0 .. T-1, T = num_iterations in 1..8, lambda = lambdas[t] (host table of finite float32 values,
+ *      0 <= lambda <= 2^20): first every row of U and every row of V is solved, then every column of U and of V; each
+ *      result replaces its line.
+ *   5. One line solve of f_0 .. f_{N-1} with guide g_0 .. g_{N-1}: s_j = lambda * w(g_j, g_{j+1}) for j < N-1;
+ *      L_j = j > 0 ? s_{j-1} : 0, R_j = j < N-1 ? s_j : 0, b_j = (1.0f + L_j) + R_j.  Forward: r_0 = 1.0f / b_0,
+ *      e_0 = R_0 * r_0, y_0 = f_0 * r_0; for j >= 1 r_j = 1.0f / (b_j - L_j * e_{j-1}), e_j = R_j * r_j,
+ *      y_j = (f_j + L_j * y_{j-1}) * r_j.  Back: x_{N-1} = y_{N-1}, x_j = y_j + e_j * x_{j+1}.  This is the Thomas
+ *      algorithm for (I + lambda A_w) x = f.  Every operation is one float32 round-to-nearest with no fused operation,
+ *      the division is the correctly rounded one, and denormals are kept.  In exact arithmetic every pivot is
+ *      >= 1 + R_j; lambda <= 2^20 keeps the rounded pivots well above 0.
+ *   6. out(p) = (V > min_weight) ? U / V : invalid_disparity (a NaN V gives invalid_disparity); a NaN quotient is stored
+ *      as 0x7FC00000.  Every pixel is rewritten, valid ones included.
+ *   Consequences: lambda = 0 gives back every valid pixel's value (bit for bit, except that a -0.0 may come back as
+ *   +0.0) and marks the others invalid; a guide edge whose weight is 0 decouples its two sides exactly.
+ * in, confidence (NULL: every valid pixel has confidence 1) and guide may alias each other.  out may be exactly in but
+ * must not overlap it otherwise, nor confidence or guide.  The tables are read during the call (passed by value in the
+ * kernel arguments).  workspace: device memory of at least smx_wls_workspace_bytes(n, H, W) bytes overlapping no
+ * operand; with R(v) = v rounded up to a multiple of 256 the size is 3 R(4 n H W) (the U, V and forward-sweep planes);
+ * its contents on entry do not matter.  2 num_iterations launches on `stream` (a caller's stream), with no host
+ * synchronisation and no allocation, so the call can be captured into a HIP graph.  Engine-free: device_id only selects
+ * the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL in, guide, out, lambdas or range_weight, n < 1, H
+ * or W outside 1..32768, num_iterations outside 1..8, a lambda that is not finite in [0, 2^20], a range weight that is
+ * not finite in [0, 1], min_weight not finite or < 0, invalid_disparity not finite, a NULL workspace or workspace_bytes
+ * below the query, the overlaps above, stream == SMX_STREAM_ENGINE. */
+size_t smx_wls_workspace_bytes(int n, int H, int W);           /* 0 for n < 1 or H, W outside 1..32768 */
+int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const float *confidence, const float *guide,
+                   float *out, int num_iterations, const float lambdas[], const float range_weight[256],
+                   float min_weight, float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Rectification of raw frames: a bilinear remap through a precomputed map, with an integer-defined rule, so that every
  * implementation gives the same bits.

@@ -98,6 +98,14 @@ size_t median_workspace_bytes(int n, int H, int W);
 void launch_weighted_median(int n, int H, int W, const float *in, const float *holes, const float *guide, float *out,
                             int radius, const uint16_t *range, const uint16_t *spatial, float invalid, hipStream_t s);
 
+// ---- tu_wls.hip: image-guided weighted least squares filter (k_wls.h) ----------------------------------------------
+// workspace: wls_workspace_bytes(n, H, W) bytes; lambdas[iterations] and range[256]: the host tables, copied into the
+// kernel arguments; arguments checked by smx_wls_filter
+size_t wls_workspace_bytes(int n, int H, int W);
+void launch_wls(int n, int H, int W, const float *in, const float *conf, const float *guide, float *out, int iterations,
+                const float *lambdas, const float *range, float min_weight, float invalid, void *workspace,
+                hipStream_t s);
+
 // ---- tu_remap.hip: bilinear remap / rectification (k_remap.h) -------------------------------------------------------
 // in_r / map_r / out_r NULL: left view only; arguments checked by smx_remap_pairs
 void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, const void *in_l, const void *in_r,

@@ -128,6 +128,49 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
     });
 }
 
+size_t smx_wls_workspace_bytes(int n, int H, int W) {
+    return map_dims_ok(n, H, W) ? smx::wls_workspace_bytes(n, H, W) : 0;
+}
+
+int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const float *confidence, const float *guide,
+                   float *out, int num_iterations, const float lambdas[], const float range_weight[256],
+                   float min_weight, float invalid, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_wls_filter";
+    if (!in || !guide || !out) return fail(SMX_ERR_INVALID_ARG, "%s: in, guide and out must be non-NULL", fn);
+    if (!lambdas || !range_weight) return fail(SMX_ERR_INVALID_ARG, "%s: lambdas and range_weight must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (num_iterations < 1 || num_iterations > 8)
+        return fail(SMX_ERR_INVALID_ARG, "%s: num_iterations must be in 1..8, got %d", fn, num_iterations);
+    for (int t = 0; t < num_iterations; ++t)
+        if (!(std::isfinite(lambdas[t]) && lambdas[t] >= 0.0f && lambdas[t] <= 1048576.0f))
+            return fail(SMX_ERR_INVALID_ARG, "%s: lambdas[%d] = %g is not finite in [0, 2^20]", fn, t, (double)lambdas[t]);
+    for (int k = 0; k < 256; ++k)
+        if (!(std::isfinite(range_weight[k]) && range_weight[k] >= 0.0f && range_weight[k] <= 1.0f))
+            return fail(SMX_ERR_INVALID_ARG, "%s: range_weight[%d] = %g is not finite in [0, 1]", fn, k,
+                        (double)range_weight[k]);
+    if (!(std::isfinite(min_weight) && min_weight >= 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and >= 0, got %g", fn, (double)min_weight);
+    if (int rc = check_finite_marker(invalid)) return rc;
+    const size_t need = smx::wls_workspace_bytes(n, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace is NULL or workspace_bytes %zu is below smx_wls_workspace_bytes = %zu",
+                    fn, workspace_bytes, need);
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    if ((out != in && ranges_overlap(in, bytes, out, bytes)) || ranges_overlap(confidence, bytes, out, bytes) ||
+        ranges_overlap(guide, bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap confidence or guide, and overlap in only as the same buffer",
+                    fn);
+    if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
+        ranges_overlap(workspace, workspace_bytes, guide, bytes) ||
+        ranges_overlap(workspace, workspace_bytes, confidence, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, confidence, guide or out", fn);
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_wls(n, H, W, in, confidence, guide, out, num_iterations, lambdas, range_weight, min_weight, invalid,
+                        workspace, (hipStream_t)stream);
+    });
+}
+
 int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
                     const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
                     void *left_out, void *right_out, int border_mode, float border_value, void *stream) {

@@ -268,6 +268,88 @@ def weighted_median(disp: torch.Tensor, guide: torch.Tensor, *, radius: int, sig
     return out
 
 
+def _check_wls_params(lam, sigma_color, iterations, attenuation) -> None:
+    _number_arg("lam", lam)
+    if not (math.isfinite(lam) and 0 <= lam <= 2.0 ** 20):
+        raise RuntimeError(f"lam must be finite in [0, 2**20], got {lam}")
+    _number_arg("sigma_color", sigma_color)
+    if not (math.isfinite(sigma_color) and sigma_color > 0):
+        raise RuntimeError(f"sigma_color must be finite and > 0, got {sigma_color}")
+    _int_arg("iterations", iterations)
+    if not 1 <= iterations <= 8:
+        raise RuntimeError(f"iterations must be in 1..8, got {iterations}")
+    _number_arg("attenuation", attenuation)
+    if not (math.isfinite(attenuation) and 0 < attenuation <= 1):
+        raise RuntimeError(f"attenuation must be in (0, 1], got {attenuation}")
+
+
+def wls_tables(lam: float, sigma_color: float, iterations: int = 3, attenuation: float = 0.25):
+    """The float32 tables of smx_wls_filter, each computed in float64 and rounded once: lambdas[t] =
+    lam * attenuation**t for t in 0..iterations-1 (the lambda schedule of the fast global smoother) and
+    range_weight[k] = exp(-k / sigma_color) for k in 0..255.  Returns (lambdas float32[iterations],
+    range_weight float32[256]) as numpy arrays."""
+    import numpy as np
+    _check_wls_params(lam, sigma_color, iterations, attenuation)
+    lambdas = np.array([float(lam) * float(attenuation) ** t for t in range(iterations)], np.float64).astype(np.float32)
+    rw = np.array([math.exp(-k / float(sigma_color)) for k in range(256)], np.float64).astype(np.float32)
+    return lambdas, rw
+
+
+def _wls_workspace(n: int, H: int, W: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of smx_wls_workspace_bytes(n, H, W) bytes for smx_wls_filter."""
+    nbytes = int(LIB.smx_wls_workspace_bytes(n, H, W))
+    if nbytes == 0:
+        raise RuntimeError(f"wls_filter: need 1 <= H, W <= 32768 (got {H} x {W})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _launch_wls(disp, confidence, guide, out, n, H, W, lambdas, range_weight, min_weight, invalid_disparity,
+                workspace) -> None:
+    """smx_wls_filter on the current stream; lambdas / range_weight: numpy float32 host tables."""
+    import numpy as np
+    dev = disp.device.index
+    lam = np.ascontiguousarray(lambdas, np.float32)
+    rw = np.ascontiguousarray(range_weight, np.float32)
+    if lam.ndim != 1 or rw.shape != (256,):
+        raise RuntimeError(f"tables must be float32[iterations] and float32[256], got {lam.shape} and {rw.shape}")
+    check(LIB.smx_wls_filter(dev, n, H, W, disp.data_ptr(), confidence.data_ptr() if confidence is not None else None,
+                             guide.data_ptr(), out.data_ptr(), int(lam.size), lam.ctypes.data, rw.ctypes.data,
+                             float(min_weight), float(invalid_disparity), workspace.data_ptr(), workspace.numel(),
+                             _stream(dev)))
+
+
+def _check_min_weight(min_weight) -> None:
+    _number_arg("min_weight", min_weight)
+    if not (math.isfinite(min_weight) and min_weight >= 0):
+        raise RuntimeError(f"min_weight must be finite and >= 0, got {min_weight}")
+
+
+def wls_filter(disp: torch.Tensor, guide: torch.Tensor, *, lam: float = 8000.0, sigma_color: float = 1.5,
+               iterations: int = 3, attenuation: float = 0.25, confidence: Optional[torch.Tensor] = None,
+               min_weight: float = 1e-3, invalid_disparity: float = -1.0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Image-guided weighted least squares filter (smx_wls_filter) on the current stream, with the tables of
+    wls_tables(lam, sigma_color, iterations, attenuation).  Every pixel is rewritten: the confidence-weighted average of
+    the valid pixels, spread along each row and column by `iterations` tridiagonal solves whose coupling across a guide
+    step of k grey levels is lam * exp(-k / sigma_color).  The result is dense, smooth inside surfaces, with edges that
+    follow the guide's; a pixel whose accumulated weight is at most min_weight (far from any valid pixel) becomes
+    invalid_disparity.  confidence: None (every valid pixel weighs 1) or per-pixel weights, clamped to [0, 1].
+    disp, guide, confidence, out: [H,W] or [n,H,W] float32 on one GPU (the n maps are independent); out may be disp.
+    The defaults lam = 8000, sigma_color = 1.5 and min_weight = 1e-3 are judgement calls in the range OpenCV's
+    DisparityWLSFilter users take, not the result of a measurement on this project's data."""
+    _check_wls_params(lam, sigma_color, iterations, attenuation)
+    _check_min_weight(min_weight)
+    _check_lr_scalars(0.0, invalid_disparity)
+    out, n, H, W = _postprocess_operands(disp, out)
+    _check_like("guide", guide, torch.float32, disp.shape, disp.device)
+    if confidence is not None:
+        _check_like("confidence", confidence, torch.float32, disp.shape, disp.device)
+    lambdas, rw = wls_tables(lam, sigma_color, iterations, attenuation)
+    _launch_wls(disp, confidence, guide, out, n, H, W, lambdas, rw, min_weight, invalid_disparity,
+                _wls_workspace(n, H, W, disp.device))
+    return out
+
+
 def _shape2(name: str, shape) -> tuple:
     try:
         h, w = (int(v) for v in shape)

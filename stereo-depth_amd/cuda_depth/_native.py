@@ -106,6 +106,13 @@ EXPORTS = {
     "smx_weighted_median": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    # weighted least squares filter: (n, H, W) -> workspace bytes; (device_id, n, H, W, in, confidence, guide, out,
+    # num_iterations, lambdas, range_weight, min_weight, invalid_disparity, workspace, workspace_bytes, stream); the
+    # tables are host float32 arrays
+    "smx_wls_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_wls_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
     # rectification: (device_id, n, channels, dtype, H_in, W_in, H_out, W_out, left_in, right_in, left_map, right_map,
     # left_out, right_out, border_mode, border_value, stream)
     "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

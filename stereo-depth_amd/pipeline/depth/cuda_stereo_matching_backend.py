@@ -29,6 +29,10 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
     and median_sigma_space), guided by the engine's own left gray plane.  With fill_invalid it filters only the pixels
     the fill wrote (the fill runs into a scratch map, the median writes the returned map); without, every valid pixel.
     With median_radius = 0 (the default) it does not run.
+    wls_lambda > 0: after the speckle filter, the image-guided weighted least squares filter (cuda_depth.wls_filter,
+    tables from wls_lambda, wls_sigma_color and wls_iterations, binary confidence), guided by the same gray plane; it
+    fills the map itself, so fill_invalid=True or median_radius > 0 with it raise ValueError.  With wls_lambda = 0 (the
+    default) it does not run.
     rectification (a cuda_depth.StereoRectification, default None): both raw frames are rectified on the current stream
     before matching (its out_shape must be the configuration's image size), and the pixels of the final map outside its
     left_valid mask become invalid_disparity."""
@@ -37,12 +41,14 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
                  left_right_check: bool = False, lr_max_diff: float = 1.0, invalid_disparity: float = -1.0,
                  speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False,
                  median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                 wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                  rectification: Optional["cuda_depth.StereoRectification"] = None):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
         self._init_postprocessing(
             (configuration._values["height"], configuration._values["width"]), invalid_disparity=invalid_disparity,
             speckle_max_size=speckle_max_size, speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
             median_radius=median_radius, median_sigma_color=median_sigma_color, median_sigma_space=median_sigma_space,
+            wls_lambda=wls_lambda, wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
             rectification=rectification)
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)

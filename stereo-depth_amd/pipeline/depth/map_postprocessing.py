@@ -1,6 +1,6 @@
 """What the stereo-matching backends share around their matcher: rectification of the raw frames before matching, and
-the post-processing of the map after it (speckle filter, background hole fill, image-guided weighted median, the
-rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
+the post-processing of the map after it (speckle filter, background hole fill, image-guided weighted median or weighted
+least squares filter, the rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -26,12 +26,17 @@ class MapPostprocessing:
     median_radius > 0: last, the image-guided weighted median (cuda_depth.weighted_median, tables from median_sigma_color
     and median_sigma_space), guided by the left gray plane of the matcher.  With fill_invalid it filters only the pixels
     the fill wrote (the fill runs into a scratch map, the median writes the map); without, every valid pixel.
+    wls_lambda > 0: after the speckle filter, the image-guided weighted least squares filter (cuda_depth.wls_filter with
+    lam=wls_lambda, sigma_color=wls_sigma_color, iterations=wls_iterations and binary confidence: every valid pixel
+    weighs 1), guided by the same left gray plane, in place.  It fills the map itself, so it excludes fill_invalid and
+    the median (ValueError).
     rectification (a cuda_depth.StereoRectification, or None): both raw frames are rectified before matching (its
     out_shape must be image_size), and the pixels of the final map outside its left_valid mask become invalid_disparity."""
 
     def _init_postprocessing(self, image_size: tuple, *, invalid_disparity: float = -1.0, speckle_max_size: int = 0,
                              speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
                              median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                             wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                              rectification: Optional["cuda_depth.StereoRectification"] = None) -> None:
         if rectification is not None:
             if not isinstance(rectification, cuda_depth.StereoRectification):
@@ -55,15 +60,26 @@ class MapPostprocessing:
         else:
             cuda_depth._check_median_params(1, median_sigma_color, median_sigma_space)
         self._median_radius = median_radius
+        cuda_depth._check_wls_params(wls_lambda, wls_sigma_color, wls_iterations, 0.25)
+        if wls_lambda > 0 and (self._fill_invalid or median_radius > 0):
+            raise ValueError("wls_lambda > 0 fills the map itself: it cannot be combined with fill_invalid=True or "
+                             "median_radius > 0")
+        self._wls_tables = cuda_depth.wls_tables(wls_lambda, wls_sigma_color, wls_iterations) if wls_lambda > 0 else None
+        self._wls_workspace: Optional[torch.Tensor] = None
         self._median_guide: Optional[torch.Tensor] = None   # the left gray plane of the last call
         self._median_scratch: Optional[torch.Tensor] = None
 
     def _guide_buffer(self, like: torch.Tensor) -> torch.Tensor:
-        """The persistent [H, W] float32 buffer the matcher's left gray plane goes into (median_radius > 0)."""
+        """The persistent [H, W] float32 buffer the matcher's left gray plane goes into (median_radius > 0 or
+        wls_lambda > 0)."""
         if self._median_guide is None:
             self._median_guide = torch.empty_like(like)
             self._median_scratch = torch.empty_like(like)
         return self._median_guide
+
+    def _uses_guide(self) -> bool:
+        """Whether a post-processing step needs the left gray plane (the median or the WLS filter)."""
+        return self._median_radius > 0 or self._wls_tables is not None
 
     def _rectify(self, left: torch.Tensor, right: torch.Tensor):
         """Both frames through the rectification (into persistent buffers), or unchanged without one."""
@@ -83,7 +99,7 @@ class MapPostprocessing:
     def _finish(self, disparity: torch.Tensor, write_guide: Optional[Callable[[torch.Tensor], None]] = None) -> None:
         """Post-processes the [H, W] map in place.  write_guide(buffer): writes the left gray plane into the guide
         buffer when the median runs (None: the matcher already wrote _guide_buffer())."""
-        if self._speckle_max_size > 0 or self._fill_invalid or self._median_radius > 0:
+        if self._speckle_max_size > 0 or self._fill_invalid or self._uses_guide():
             self._postprocess(disparity, write_guide)
         if self._rectification is not None:
             disparity.masked_fill_(~self._rectification.left_valid, self._invalid_disparity)
@@ -95,6 +111,15 @@ class MapPostprocessing:
         if self._speckle_max_size > 0:
             cuda_depth._launch_filter_speckles(disparity, disparity, 1, H, W, self._speckle_max_size,
                                                self._speckle_max_diff, self._invalid_disparity, self._post_workspace)
+        if self._wls_tables is not None:
+            guide = self._guide_buffer(disparity)
+            if write_guide is not None:
+                write_guide(guide)
+            if self._wls_workspace is None:
+                self._wls_workspace = cuda_depth._wls_workspace(1, H, W, disparity.device)
+            cuda_depth._launch_wls(disparity, None, guide, disparity, 1, H, W, *self._wls_tables, 1e-3,
+                                   self._invalid_disparity, self._wls_workspace)
+            return
         if self._median_radius == 0:
             if self._fill_invalid:
                 cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,

@@ -101,12 +101,15 @@ class DepthEstimationPipeline:
 
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
                  speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
-                 median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
+                 median_sigma_color: float = 10.0, median_sigma_space: float = 5.0, wls_lambda: float = 0.0,
+                 wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                  rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
                  sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
-        (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  rectification: a
+        (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
+        wls_sigma_color / wls_iterations: wls_lambda > 0 runs the image-guided weighted least squares filter after the
+        speckle filter in place of the fill and the median (combining them raises ValueError).  rectification: a
         cuda_depth.StereoRectification whose out_shape is config.image_shape; the raw frames are rectified on the GPU
         before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
         rectified).  sgm_paths / sgm_p1 / sgm_p2 / sgm_uniqueness: the tuning of the 'sgm' backend (4 or 8 paths,
@@ -118,7 +121,9 @@ class DepthEstimationPipeline:
         self._stereo_matching = _make_backend(self._config, sgm, speckle_max_size=speckle_max_size,
                                               speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
                                               median_radius=median_radius, median_sigma_color=median_sigma_color,
-                                              median_sigma_space=median_sigma_space, rectification=rectification)
+                                              median_sigma_space=median_sigma_space, wls_lambda=wls_lambda,
+                                              wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
+                                              rectification=rectification)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
     def get_configuration(self) -> DepthEstimationPipelineConfig:

@@ -23,8 +23,10 @@
  *   -- (speckle filter, hole fill)                        smx_filter_speckles, smx_fill_invalid
  *   -- (image-guided weighted median)                     smx_weighted_median
  *   -- (image-guided weighted least squares filter)       smx_wls_filter, smx_wls_workspace_bytes
+ *   -- (per-pixel confidence: LR agreement x texture)     smx_confidence_map
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
- *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes
+ *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes,
+ *                                                         smx_sgm_with_right_map
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -469,6 +471,33 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
                    float *out, int num_iterations, const float lambdas[], const float range_weight[256],
                    float min_weight, float invalid_disparity, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Per-pixel confidence in [0, 1] of a disparity map, the input of smx_wls_filter's confidence and of any thresholding
+ * downstream.  Every operand is [n][H][W] f32 on the device; the n maps are independent.  VALID is as above.  For a
+ * pixel (X, Y) with d = D_L[X][Y]:
+ *   1. d not VALID: conf = 0.0f.
+ *   2. LR term.  right_disp == NULL: c_lr = 1.0f.  Otherwise t = floorf(d + 0.5f); !(t >= 0 && t <= Y): conf = 0 (the
+ *      index rule of smx_lr_check); r = D_R[X][Y - (int)t]; r not VALID: conf = 0; otherwise e = fabsf(d - r) and
+ *      c_lr = fmaxf(0.0f, 1.0f - e / lr_scale).
+ *   3. Texture term.  guide == NULL: c_tex = 1.0f.  Otherwise, over the (2R+1) x (2R+1) guide values around the pixel
+ *      (R = radius, 1..15; coordinates clamped into the image), range = max - min of the non-NaN values (one float32
+ *      subtraction; -0.0 and +0.0 count as equal, so a zero range is +0.0) and c_tex = fminf(1.0f, range / texture_scale);
+ *      c_tex = 0 when every value of the window is NaN or the range is NaN (+inf - +inf).  Max and min do not depend on
+ *      the order of evaluation, so the result does not depend on how an implementation splits the window.
+ *   4. conf = c_lr * c_tex (one float32 product).  Every zero above is +0.0f.
+ * Every operation is one float32 round-to-nearest with no fused operation, the divisions are the correctly rounded
+ * ones and denormals are kept, so every implementation gives the same bits.  Suggested starting points, not tuned
+ * values: lr_scale = 1 (disparity px), radius = 2, texture_scale = 10 (gray levels).
+ * right_disp (the un-checked right-view map, e.g. the right_out of smx_compute_lr_*_batch or smx_sgm_with_right_map)
+ * and guide (e.g. the left gray plane) may each be NULL; the inputs may alias each other; out must not overlap any of
+ * them.  One launch on `stream` (a caller's stream), with no host synchronisation and no allocation, so the call can be
+ * captured into a HIP graph.  Engine-free: device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL left_disp or out, n < 1, H or W outside 1..32768,
+ * radius outside 1..15 with a guide, lr_scale or texture_scale not finite and > 0, invalid_disparity not finite, the
+ * overlaps above, stream == SMX_STREAM_ENGINE. */
+int smx_confidence_map(int device_id, int n, int H, int W, const float *left_disp, const float *right_disp,
+                       const float *guide, int radius, float lr_scale, float texture_scale, float invalid_disparity,
+                       float *out, void *stream);
+
 /* Rectification of raw frames: a bilinear remap through a precomputed map, with an integer-defined rule, so that every
  * implementation gives the same bits.
  *   - Map: [H_out][W_out][2] int32, interleaved (x, y), in units of 1/32 pixel (5 fractional bits, OpenCV's
@@ -545,6 +574,17 @@ int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const v
             int min_disparity, int num_disparities, int paths, int P1, int P2, int uniqueness, float lr_max_diff,
             int subpixel, float invalid_disparity, float *out, float *gray_left_out, void *workspace,
             size_t workspace_bytes, void *stream);
+/* smx_sgm that also writes the right-view map: right_out ([n][H][W] f32, required) receives f32(dmin + iR(y, x')) where
+ * iR >= 0 and invalid_disparity where no candidate lies in the image (iR = -1), iR as above, whether or not lr_max_diff
+ * is negative (the right-view winners are then found for this map alone).  out and gray_left_out are the same bits as
+ * smx_sgm's for the same arguments, and the workspace query is the same.  right_out must not overlap an input, the
+ * workspace, out or gray_left_out.  The other arguments and their checks are smx_sgm's; a NULL right_out is
+ * SMX_ERR_INVALID_ARG. */
+int smx_sgm_with_right_map(int device_id, int n, int channels, int dtype, int H, int W, const void *left,
+                           const void *right, int min_disparity, int num_disparities, int paths, int P1, int P2,
+                           int uniqueness, float lr_max_diff, int subpixel, float invalid_disparity, float *out,
+                           float *gray_left_out, float *right_out, void *workspace, size_t workspace_bytes,
+                           void *stream);
 
 #ifdef __cplusplus
 }

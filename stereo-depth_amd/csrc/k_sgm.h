@@ -8,7 +8,8 @@
 //      The cost is XOR + popcount of the census on the fly, the neighbours i-1 / i+1 come across lanes by shuffle, and
 //      M_r(q) is one wave min reduction per step.  Each pixel lies on exactly one line per axis, so a wave owns its
 //      S cells for the whole launch: the first pass of the call stores L_r, every other pass adds L_r to S (u16).
-//   3. k_sgm_right_wta<DPL> (LR check on): iR(y, x') for every right-view pixel, one wave per pixel.
+//   3. k_sgm_right_wta<DPL> (LR check on, or the right-view map asked for): iR(y, x') for every right-view pixel, one
+//      wave per pixel, and the right-view map f32(dmin + iR) when asked for.
 //   4. k_sgm_select<DPL>: winner, uniqueness, LR test and subpixel value, one wave per pixel.
 // Every value is an integer until the one float32 division of the subpixel step, so the result does not depend on
 // how the work is split.
@@ -221,6 +222,7 @@ struct SgmSelectArgs {
     const uint16_t *S;
     int16_t *iR;                  // [n][H][W]: right-view winner, -1 where no candidate lies in the image
     float *out;
+    float *right_out;             // [n][H][W] f32(dmin + iR), invalid where iR = -1; NULL: not written
     int n, H, W, dmin, D, Dp;
     int uniqueness, lr, subpixel;
     float lr_max_diff, invalid;
@@ -230,6 +232,7 @@ struct SgmSelectArgs {
 __device__ __forceinline__ unsigned sgm_key(unsigned s, int i) { return (s << 8) | (unsigned)i; }
 
 // iR(y, x') = the smallest i minimising S(y, x' + dmin + i, i) over x' + dmin + i <= W - 1.  One wave per pixel.
+// With right_out, the right-view map is written beside it.
 template <int DPL>
 __global__ __launch_bounds__(SGM_THREADS) void k_sgm_right_wta(SgmSelectArgs a) {
     const int lane = threadIdx.x & 63;
@@ -245,7 +248,11 @@ __global__ __launch_bounds__(SGM_THREADS) void k_sgm_right_wta(SgmSelectArgs a) 
             if (i < a.D && xl <= a.W - 1) key = min(key, sgm_key(a.S[(p + (xl - x)) * a.Dp + i], i));
         }
         key = __ockl_wfred_min_u32(key);
-        if (lane == 0) a.iR[p] = key == 0xFFFFFFFFu ? (int16_t)-1 : (int16_t)(key & 0xFFu);
+        if (lane == 0) {
+            const bool none = key == 0xFFFFFFFFu;
+            a.iR[p] = none ? (int16_t)-1 : (int16_t)(key & 0xFFu);
+            if (a.right_out) a.right_out[p] = none ? a.invalid : (float)(a.dmin + (int)(key & 0xFFu));
+        }
     }
 }
 

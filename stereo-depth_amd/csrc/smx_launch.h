@@ -106,6 +106,11 @@ void launch_wls(int n, int H, int W, const float *in, const float *conf, const f
                 const float *lambdas, const float *range, float min_weight, float invalid, void *workspace,
                 hipStream_t s);
 
+// ---- tu_confidence.hip: per-pixel confidence (k_confidence.h) -----------------------------------------------------
+// right / guide NULL: no LR / texture term; arguments checked by smx_confidence_map
+void launch_confidence(int n, int H, int W, const float *left, const float *right, const float *guide, int radius,
+                       float lr_scale, float texture_scale, float invalid, float *out, hipStream_t s);
+
 // ---- tu_remap.hip: bilinear remap / rectification (k_remap.h) -------------------------------------------------------
 // in_r / map_r / out_r NULL: left view only; arguments checked by smx_remap_pairs
 void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, const void *in_l, const void *in_r,
@@ -113,10 +118,11 @@ void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, 
                         float border_value, hipStream_t s);
 
 // ---- tu_sgm.hip: semi-global matching (k_sgm.h) ----------------------------------------------------------------------
-// workspace: sgm_workspace_bytes(n, H, W, D) bytes (smx_sgm_workspace_bytes); arguments checked by smx_sgm
+// workspace: sgm_workspace_bytes(n, H, W, D) bytes (smx_sgm_workspace_bytes); right_out NULL: not written (the
+// right-view WTA runs only for the LR check); arguments checked by smx_sgm / smx_sgm_with_right_map
 size_t sgm_workspace_bytes(int n, int H, int W, int D);
 void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const void *right, int dmin, int D, int paths,
                 int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
-                float *gray_out, void *workspace, hipStream_t s);
+                float *gray_out, float *right_out, void *workspace, hipStream_t s);
 
 }  // namespace smx

@@ -171,6 +171,30 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
     });
 }
 
+int smx_confidence_map(int device_id, int n, int H, int W, const float *left_disp, const float *right_disp,
+                       const float *guide, int radius, float lr_scale, float texture_scale, float invalid,
+                       float *out, void *stream) {
+    const char *fn = "smx_confidence_map";
+    if (!left_disp || !out) return fail(SMX_ERR_INVALID_ARG, "%s: left_disp and out must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (guide && (radius < 1 || radius > 15))
+        return fail(SMX_ERR_INVALID_ARG, "%s: radius must be in 1..15 with a guide, got %d", fn, radius);
+    if (!(std::isfinite(lr_scale) && lr_scale > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: lr_scale must be finite and > 0, got %g", fn, (double)lr_scale);
+    if (!(std::isfinite(texture_scale) && texture_scale > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: texture_scale must be finite and > 0, got %g", fn, (double)texture_scale);
+    if (int rc = check_finite_marker(invalid)) return rc;
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    if (ranges_overlap(left_disp, bytes, out, bytes) || ranges_overlap(right_disp, bytes, out, bytes) ||
+        ranges_overlap(guide, bytes, out, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap left_disp, right_disp or guide", fn);
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_confidence(n, H, W, left_disp, right_disp, guide, radius, lr_scale, texture_scale, invalid, out,
+                               (hipStream_t)stream);
+    });
+}
+
 int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
                     const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
                     void *left_out, void *right_out, int border_mode, float border_value, void *stream) {
@@ -230,11 +254,11 @@ size_t smx_sgm_workspace_bytes(int n, int H, int W, int num_disparities, int pat
     return sgm_size_error(n, H, W, num_disparities, paths) ? 0 : smx::sgm_workspace_bytes(n, H, W, num_disparities);
 }
 
-int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const void *left, const void *right,
-            int min_disparity, int num_disparities, int paths, int P1, int P2, int uniqueness, float lr_max_diff,
-            int subpixel, float invalid_disparity, float *out, float *gray_left_out, void *workspace,
-            size_t workspace_bytes, void *stream) {
-    const char *fn = "smx_sgm";
+// smx_sgm and smx_sgm_with_right_map: right_out NULL is smx_sgm.
+static int sgm_entry(const char *fn, int device_id, int n, int channels, int dtype, int H, int W, const void *left,
+                     const void *right, int min_disparity, int num_disparities, int paths, int P1, int P2,
+                     int uniqueness, float lr_max_diff, int subpixel, float invalid_disparity, float *out,
+                     float *gray_left_out, float *right_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (!left || !right || !out || !workspace)
         return fail(SMX_ERR_INVALID_ARG, "%s: left, right, out and workspace must be non-NULL", fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
@@ -262,21 +286,44 @@ int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const v
                     workspace_bytes, need);
     const size_t in_bytes = (size_t)n * channels * H * W * (dtype == SMX_DTYPE_F32 ? 4 : 1);
     const size_t map_bytes = (size_t)n * H * W * sizeof(float);
-    const void *outs[2] = {out, gray_left_out};
+    const void *outs[3] = {out, gray_left_out, right_out};
     for (const void *o : outs)
         if (ranges_overlap(o, map_bytes, left, in_bytes) || ranges_overlap(o, map_bytes, right, in_bytes) ||
             ranges_overlap(o, map_bytes, workspace, workspace_bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: out and gray_left_out must not overlap left, right or the workspace", fn);
+            return fail(SMX_ERR_INVALID_ARG, "%s: the outputs must not overlap left, right or the workspace", fn);
     if (ranges_overlap(out, map_bytes, gray_left_out, map_bytes))
         return fail(SMX_ERR_INVALID_ARG, "%s: out and gray_left_out overlap", fn);
+    if (ranges_overlap(right_out, map_bytes, out, map_bytes) || ranges_overlap(right_out, map_bytes, gray_left_out, map_bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: right_out overlaps out or gray_left_out", fn);
     if (ranges_overlap(workspace, workspace_bytes, left, in_bytes) || ranges_overlap(workspace, workspace_bytes, right, in_bytes))
         return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap left or right", fn);
     if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_sgm(n, channels, dtype == SMX_DTYPE_F32, H, W, left, right, min_disparity, num_disparities, paths, P1,
-                        P2, uniqueness, lr_max_diff, subpixel != 0, invalid_disparity, out, gray_left_out, workspace,
-                        (hipStream_t)stream);
+                        P2, uniqueness, lr_max_diff, subpixel != 0, invalid_disparity, out, gray_left_out, right_out,
+                        workspace, (hipStream_t)stream);
     });
+}
+
+int smx_sgm(int device_id, int n, int channels, int dtype, int H, int W, const void *left, const void *right,
+            int min_disparity, int num_disparities, int paths, int P1, int P2, int uniqueness, float lr_max_diff,
+            int subpixel, float invalid_disparity, float *out, float *gray_left_out, void *workspace,
+            size_t workspace_bytes, void *stream) {
+    return sgm_entry("smx_sgm", device_id, n, channels, dtype, H, W, left, right, min_disparity, num_disparities, paths,
+                     P1, P2, uniqueness, lr_max_diff, subpixel, invalid_disparity, out, gray_left_out, nullptr,
+                     workspace, workspace_bytes, stream);
+}
+
+int smx_sgm_with_right_map(int device_id, int n, int channels, int dtype, int H, int W, const void *left,
+                           const void *right, int min_disparity, int num_disparities, int paths, int P1, int P2,
+                           int uniqueness, float lr_max_diff, int subpixel, float invalid_disparity, float *out,
+                           float *gray_left_out, float *right_out, void *workspace, size_t workspace_bytes,
+                           void *stream) {
+    const char *fn = "smx_sgm_with_right_map";
+    if (!right_out) return fail(SMX_ERR_INVALID_ARG, "%s: right_out must be non-NULL", fn);
+    return sgm_entry(fn, device_id, n, channels, dtype, H, W, left, right, min_disparity, num_disparities, paths, P1, P2,
+                     uniqueness, lr_max_diff, subpixel, invalid_disparity, out, gray_left_out, right_out, workspace,
+                     workspace_bytes, stream);
 }
 
 int smx_disparity_to_points(int device_id, const float *disp, int H, int W, float bf, float invalid,

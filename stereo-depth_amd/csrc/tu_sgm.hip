@@ -44,7 +44,7 @@ void launch_dpl(const SgmPathArgs &base, int paths, const SgmSelectArgs &sel, hi
     const size_t pixels = (size_t)sel.n * sel.H * sel.W;
     const size_t groups = (pixels + SGM_THREADS / 64 - 1) / (SGM_THREADS / 64);
     const unsigned grid = (unsigned)(groups < ((size_t)1 << 20) ? groups : ((size_t)1 << 20));   // grid-stride beyond
-    if (sel.lr) hipLaunchKernelGGL((k_sgm_right_wta<DPL>), dim3(grid), dim3(SGM_THREADS), 0, s, sel);
+    if (sel.lr || sel.right_out) hipLaunchKernelGGL((k_sgm_right_wta<DPL>), dim3(grid), dim3(SGM_THREADS), 0, s, sel);
     hipLaunchKernelGGL((k_sgm_select<DPL>), dim3(grid), dim3(SGM_THREADS), 0, s, sel);
 }
 
@@ -54,7 +54,7 @@ size_t sgm_workspace_bytes(int n, int H, int W, int D) { return sgm_layout(n, H,
 
 void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const void *right, int dmin, int D, int paths,
                 int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
-                float *gray_out, void *workspace, hipStream_t s) {
+                float *gray_out, float *right_out, void *workspace, hipStream_t s) {
     const SgmLayout l = sgm_layout(n, H, W, D);
     char *ws = (char *)workspace;
     uint64_t *cen_l = (uint64_t *)(ws + l.cen_l), *cen_r = (uint64_t *)(ws + l.cen_r);
@@ -74,6 +74,7 @@ void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const vo
     sel.S = S;
     sel.iR = iR;
     sel.out = out;
+    sel.right_out = right_out;
     sel.n = n, sel.H = H, sel.W = W, sel.dmin = dmin, sel.D = D, sel.Dp = a.Dp;
     sel.uniqueness = uniqueness, sel.lr = lr_max_diff >= 0.0f, sel.subpixel = subpixel;
     sel.lr_max_diff = lr_max_diff, sel.invalid = invalid;

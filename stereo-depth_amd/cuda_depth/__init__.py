@@ -350,6 +350,51 @@ def wls_filter(disp: torch.Tensor, guide: torch.Tensor, *, lam: float = 8000.0, 
     return out
 
 
+def _check_confidence_params(radius, lr_scale, texture_scale, invalid_disparity, radius_zero_ok: bool = False) -> None:
+    """The scalar rules of smx_confidence_map, checked before the device is touched (radius 0: no texture term, where
+    the caller allows it)."""
+    _int_arg("radius", radius)
+    if not ((radius_zero_ok and radius == 0) or 1 <= radius <= 15):
+        raise RuntimeError(f"radius must be in {'0..15' if radius_zero_ok else '1..15'}, got {radius}")
+    for name, v in (("lr_scale", lr_scale), ("texture_scale", texture_scale)):
+        _number_arg(name, v)
+        if not (math.isfinite(v) and v > 0):
+            raise RuntimeError(f"{name} must be finite and > 0, got {v}")
+    _number_arg("invalid_disparity", invalid_disparity)
+    if not math.isfinite(invalid_disparity):
+        raise RuntimeError(f"invalid_disparity must be finite (a NaN marker never compares equal), got {invalid_disparity}")
+
+
+def _launch_confidence(disp, right_disp, guide, out, n, H, W, radius, lr_scale, texture_scale,
+                       invalid_disparity) -> None:
+    """smx_confidence_map on the current stream; right_disp / guide may be None."""
+    dev = disp.device.index
+    check(LIB.smx_confidence_map(dev, n, H, W, disp.data_ptr(), None if right_disp is None else right_disp.data_ptr(),
+                                 None if guide is None else guide.data_ptr(), int(radius), float(lr_scale),
+                                 float(texture_scale), float(invalid_disparity), out.data_ptr(), _stream(dev)))
+
+
+def confidence_map(disp: torch.Tensor, right_disp: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None,
+                   *, radius: int = 2, lr_scale: float = 1.0, texture_scale: float = 10.0,
+                   invalid_disparity: float = -1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-pixel confidence in [0, 1] of a disparity map (smx_confidence_map; the rule is in include/stereo_mi355x.h), on
+    the current stream: 0 on every non-valid pixel, otherwise c_lr * c_tex.  right_disp (the un-checked right-view map,
+    e.g. compute_disparity_map_batch_lr's right_out or StereoSGM.compute's right_out): c_lr = max(0, 1 - |d - r| /
+    lr_scale) with r the right-view value the pixel points at (0 where it points outside the image or at a non-valid
+    value); None: c_lr = 1.  guide (e.g. the left gray plane): c_tex = min(1, (max - min) / texture_scale) over the
+    (2 radius + 1)^2 window; None: c_tex = 1.  disp, right_disp, guide, out: [H,W] or [n,H,W] float32 on one GPU (the n
+    maps are independent); out must not overlap the inputs.  The defaults lr_scale = 1 px, radius = 2 and
+    texture_scale = 10 gray levels are starting points, not values tuned on this project's data."""
+    _check_confidence_params(radius, lr_scale, texture_scale, invalid_disparity)
+    out, n, H, W = _postprocess_operands(disp, out)
+    if right_disp is not None:
+        _check_like("right_disp", right_disp, torch.float32, disp.shape, disp.device)
+    if guide is not None:
+        _check_like("guide", guide, torch.float32, disp.shape, disp.device)
+    _launch_confidence(disp, right_disp, guide, out, n, H, W, radius, lr_scale, texture_scale, invalid_disparity)
+    return out
+
+
 def _shape2(name: str, shape) -> tuple:
     try:
         h, w = (int(v) for v in shape)
@@ -572,10 +617,12 @@ class StereoSGM:
         return ws
 
     def compute(self, left: torch.Tensor, right: torch.Tensor, out: Optional[torch.Tensor] = None,
-                gray_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                gray_out: Optional[torch.Tensor] = None, right_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """left, right: [C,H,W] or [n,C,H,W], uint8 or float32, C in {1, 3}, on one GPU.  Returns the float32 disparity
         map(s), [H,W] or [n,H,W], computed on the current stream.  out: the map tensor to write; gray_out: a float32
-        tensor of the map's shape that receives the left frames' gray planes (the weighted median's guide)."""
+        tensor of the map's shape that receives the left frames' gray planes (the weighted median's guide); right_out: a
+        float32 tensor of the map's shape that receives the right-view winner maps (smx_sgm_with_right_map: integer
+        disparities, invalid_disparity where no candidate lies in the image), the right_disp of confidence_map."""
         _check_input("left", left)
         _check_input("right", right)
         if left.dtype not in (torch.uint8, torch.float32):
@@ -592,16 +639,21 @@ class StereoSGM:
             _check_like("out", out, torch.float32, shape, left.device)
         if gray_out is not None:
             _check_like("gray_out", gray_out, torch.float32, shape, left.device)
+        if right_out is not None:
+            _check_like("right_out", right_out, torch.float32, shape, left.device)
         n = 1 if left.dim() == 3 else int(left.shape[0])
         H, W = int(left.shape[-2]), int(left.shape[-1])
         ws = self.workspace(n, H, W, left.device)
         dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
         dev = left.device.index
-        check(LIB.smx_sgm(dev, n, int(left.shape[-3]), dt, H, W, left.data_ptr(), right.data_ptr(), self.min_disparity,
-                          self.num_disparities, self.paths, self.P1, self.P2, self.uniqueness,
-                          -1.0 if self.lr_max_diff is None else self.lr_max_diff, int(self.subpixel),
-                          self.invalid_disparity, out.data_ptr(), None if gray_out is None else gray_out.data_ptr(),
-                          ws.data_ptr(), ws.numel(), _stream(dev)))
+        args = (dev, n, int(left.shape[-3]), dt, H, W, left.data_ptr(), right.data_ptr(), self.min_disparity,
+                self.num_disparities, self.paths, self.P1, self.P2, self.uniqueness,
+                -1.0 if self.lr_max_diff is None else self.lr_max_diff, int(self.subpixel), self.invalid_disparity,
+                out.data_ptr(), None if gray_out is None else gray_out.data_ptr())
+        if right_out is None:
+            check(LIB.smx_sgm(*args, ws.data_ptr(), ws.numel(), _stream(dev)))
+        else:
+            check(LIB.smx_sgm_with_right_map(*args, right_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
         return out
 
 

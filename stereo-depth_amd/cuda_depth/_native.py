@@ -113,6 +113,10 @@ EXPORTS = {
     "smx_wls_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
+    # per-pixel confidence: (device_id, n, H, W, left_disp, right_disp, guide, radius, lr_scale, texture_scale,
+    # invalid_disparity, out, stream)
+    "smx_confidence_map": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     # rectification: (device_id, n, channels, dtype, H_in, W_in, H_out, W_out, left_in, right_in, left_map, right_map,
     # left_out, right_out, border_mode, border_value, stream)
     "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -125,6 +129,11 @@ EXPORTS = {
     "smx_sgm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    # smx_sgm plus right_out, after gray_left_out
+    "smx_sgm_with_right_map": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

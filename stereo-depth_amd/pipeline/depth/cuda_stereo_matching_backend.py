@@ -33,6 +33,9 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
     tables from wls_lambda, wls_sigma_color and wls_iterations, binary confidence), guided by the same gray plane; it
     fills the map itself, so fill_invalid=True or median_radius > 0 with it raise ValueError.  With wls_lambda = 0 (the
     default) it does not run.
+    confidence=True (with confidence_lr_scale, confidence_radius, confidence_texture_scale): the per-pixel confidence
+    of MapPostprocessing, confidence_map(); with left_right_check its LR term reads the engine's right-view map of the
+    same call.
     rectification (a cuda_depth.StereoRectification, default None): both raw frames are rectified on the current stream
     before matching (its out_shape must be the configuration's image size), and the pixels of the final map outside its
     left_valid mask become invalid_disparity."""
@@ -42,6 +45,8 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
                  speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False,
                  median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                  wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
+                 confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
+                 confidence_texture_scale: float = 10.0,
                  rectification: Optional["cuda_depth.StereoRectification"] = None):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
         self._init_postprocessing(
@@ -49,7 +54,8 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
             speckle_max_size=speckle_max_size, speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
             median_radius=median_radius, median_sigma_color=median_sigma_color, median_sigma_space=median_sigma_space,
             wls_lambda=wls_lambda, wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
-            rectification=rectification)
+            confidence=confidence, confidence_lr_scale=confidence_lr_scale, confidence_radius=confidence_radius,
+            confidence_texture_scale=confidence_texture_scale, rectification=rectification)
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)
         self._invalid_disparity = float(invalid_disparity)
@@ -63,12 +69,16 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
         if left.dtype != right.dtype:                       # mixed inputs: fall back to float for both
             left, right = left.float(), right.float()
         left, right = self._rectify(left, right)
+        right_map = None
         if self._left_right_check:
+            if self._confidence:
+                d = self._stereo_algo.dims
+                right_map = self._right_map_buffer((1, d.H, d.W), left.device)
             disparity = self._stereo_algo.compute_disparity_map_batch_lr(
-                left.unsqueeze(0), right.unsqueeze(0), max_diff=self._lr_max_diff,
+                left.unsqueeze(0), right.unsqueeze(0), right_out=right_map, max_diff=self._lr_max_diff,
                 invalid_disparity=self._invalid_disparity)[0]
         else:
             disparity = self._stereo_algo.compute_disparity_map(left, right)
         self._finish(disparity, lambda guide: self._stereo_algo.intermediate(
-            cuda_depth._native.STAGE_GRAY_LEFT, 0, out=guide))
+            cuda_depth._native.STAGE_GRAY_LEFT, 0, out=guide), None if right_map is None else right_map[0])
         return disparity

@@ -1,6 +1,6 @@
 """What the stereo-matching backends share around their matcher: rectification of the raw frames before matching, and
-the post-processing of the map after it (speckle filter, background hole fill, image-guided weighted median or weighted
-least squares filter, the rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
+the post-processing of the map after it (speckle filter, per-pixel confidence, background hole fill, image-guided
+weighted median or weighted least squares filter, the rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -30,6 +30,12 @@ class MapPostprocessing:
     lam=wls_lambda, sigma_color=wls_sigma_color, iterations=wls_iterations and binary confidence: every valid pixel
     weighs 1), guided by the same left gray plane, in place.  It fills the map itself, so it excludes fill_invalid and
     the median (ValueError).
+    confidence=True: after the speckle filter and before the fill, the median or the WLS filter, the per-pixel
+    confidence of the map (cuda_depth.confidence_map) into a persistent buffer, confidence_map(): the LR term from the
+    right-view map the matcher hands over (left_right_check only; otherwise the map is texture-only) with
+    confidence_lr_scale, the texture term over the same left gray plane with confidence_radius (0: none) and
+    confidence_texture_scale.  Removed speckles and, with a rectification, the pixels outside its left_valid mask get 0;
+    the pixels the fill writes keep 0.  With wls_lambda > 0 the WLS filter weighs each pixel by it.
     rectification (a cuda_depth.StereoRectification, or None): both raw frames are rectified before matching (its
     out_shape must be image_size), and the pixels of the final map outside its left_valid mask become invalid_disparity."""
 
@@ -37,6 +43,8 @@ class MapPostprocessing:
                              speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
                              median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                              wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
+                             confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
+                             confidence_texture_scale: float = 10.0,
                              rectification: Optional["cuda_depth.StereoRectification"] = None) -> None:
         if rectification is not None:
             if not isinstance(rectification, cuda_depth.StereoRectification):
@@ -68,6 +76,16 @@ class MapPostprocessing:
         self._wls_workspace: Optional[torch.Tensor] = None
         self._median_guide: Optional[torch.Tensor] = None   # the left gray plane of the last call
         self._median_scratch: Optional[torch.Tensor] = None
+        if not isinstance(confidence, bool):
+            raise TypeError("confidence must be a bool")
+        cuda_depth._check_confidence_params(confidence_radius, confidence_lr_scale, confidence_texture_scale,
+                                            invalid_disparity, radius_zero_ok=True)
+        self._confidence = confidence
+        self._confidence_lr_scale = float(confidence_lr_scale)
+        self._confidence_radius = confidence_radius
+        self._confidence_texture_scale = float(confidence_texture_scale)
+        self._confidence_map: Optional[torch.Tensor] = None     # the confidence of the last call
+        self._right_map: Optional[torch.Tensor] = None          # the matcher's right-view map (confidence, LR check)
 
     def _guide_buffer(self, like: torch.Tensor) -> torch.Tensor:
         """The persistent [H, W] float32 buffer the matcher's left gray plane goes into (median_radius > 0 or
@@ -78,8 +96,22 @@ class MapPostprocessing:
         return self._median_guide
 
     def _uses_guide(self) -> bool:
-        """Whether a post-processing step needs the left gray plane (the median or the WLS filter)."""
-        return self._median_radius > 0 or self._wls_tables is not None
+        """Whether a post-processing step needs the left gray plane (the median, the WLS filter or the confidence's
+        texture term)."""
+        return self._median_radius > 0 or self._wls_tables is not None or (self._confidence and
+                                                                            self._confidence_radius > 0)
+
+    def _right_map_buffer(self, shape: tuple, device: torch.device) -> torch.Tensor:
+        """The persistent float32 buffer of `shape` the matcher's right-view map goes into (confidence=True with the
+        left-right check)."""
+        if self._right_map is None or tuple(self._right_map.shape) != tuple(shape) or self._right_map.device != device:
+            self._right_map = torch.empty(shape, dtype=torch.float32, device=device)
+        return self._right_map
+
+    def confidence_map(self) -> Optional[torch.Tensor]:
+        """The [H, W] float32 confidence of the last process() call (a persistent buffer, overwritten by the next call),
+        or None with confidence=False."""
+        return self._confidence_map if self._confidence else None
 
     def _rectify(self, left: torch.Tensor, right: torch.Tensor):
         """Both frames through the rectification (into persistent buffers), or unchanged without one."""
@@ -96,28 +128,35 @@ class MapPostprocessing:
         call), or None without rectification."""
         return self._rectified if self._rectification is not None else None
 
-    def _finish(self, disparity: torch.Tensor, write_guide: Optional[Callable[[torch.Tensor], None]] = None) -> None:
+    def _finish(self, disparity: torch.Tensor, write_guide: Optional[Callable[[torch.Tensor], None]] = None,
+                right_disp: Optional[torch.Tensor] = None) -> None:
         """Post-processes the [H, W] map in place.  write_guide(buffer): writes the left gray plane into the guide
-        buffer when the median runs (None: the matcher already wrote _guide_buffer())."""
-        if self._speckle_max_size > 0 or self._fill_invalid or self._uses_guide():
-            self._postprocess(disparity, write_guide)
+        buffer when a step needs it (None: the matcher already wrote _guide_buffer()).  right_disp: the matcher's
+        un-checked [H, W] right-view map for the confidence's LR term, or None."""
+        if self._speckle_max_size > 0 or self._fill_invalid or self._uses_guide() or self._confidence:
+            self._postprocess(disparity, write_guide, right_disp)
         if self._rectification is not None:
             disparity.masked_fill_(~self._rectification.left_valid, self._invalid_disparity)
 
-    def _postprocess(self, disparity: torch.Tensor, write_guide) -> None:
+    def _postprocess(self, disparity: torch.Tensor, write_guide, right_disp) -> None:
         H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
         if self._post_workspace is None and (self._speckle_max_size > 0 or self._fill_invalid):
             self._post_workspace = cuda_depth._postprocess_workspace(1, H, W, disparity.device)
         if self._speckle_max_size > 0:
             cuda_depth._launch_filter_speckles(disparity, disparity, 1, H, W, self._speckle_max_size,
                                                self._speckle_max_diff, self._invalid_disparity, self._post_workspace)
-        if self._wls_tables is not None:
+        guide = None
+        if self._uses_guide():
             guide = self._guide_buffer(disparity)
             if write_guide is not None:
                 write_guide(guide)
+        confidence = None
+        if self._confidence:
+            confidence = self._compute_confidence(disparity, right_disp, guide)
+        if self._wls_tables is not None:
             if self._wls_workspace is None:
                 self._wls_workspace = cuda_depth._wls_workspace(1, H, W, disparity.device)
-            cuda_depth._launch_wls(disparity, None, guide, disparity, 1, H, W, *self._wls_tables, 1e-3,
+            cuda_depth._launch_wls(disparity, confidence, guide, disparity, 1, H, W, *self._wls_tables, 1e-3,
                                    self._invalid_disparity, self._wls_workspace)
             return
         if self._median_radius == 0:
@@ -125,9 +164,6 @@ class MapPostprocessing:
                 cuda_depth._launch_fill_invalid(disparity, disparity, 1, H, W, self._invalid_disparity,
                                                 self._post_workspace)
             return
-        guide = self._guide_buffer(disparity)
-        if write_guide is not None:
-            write_guide(guide)
         scratch = self._median_scratch
         if self._fill_invalid:                              # filled -> scratch; the median rewrites the filled pixels
             cuda_depth._launch_fill_invalid(disparity, scratch, 1, H, W, self._invalid_disparity, self._post_workspace)
@@ -138,3 +174,18 @@ class MapPostprocessing:
         cuda_depth._launch_weighted_median(scratch, holes, guide, disparity, 1, H, W, self._median_radius,
                                            *self._median_tables, self._invalid_disparity,
                                            cuda_depth._median_workspace(1, H, W, disparity.device))
+
+    def _compute_confidence(self, disparity: torch.Tensor, right_disp: Optional[torch.Tensor],
+                            guide: Optional[torch.Tensor]) -> torch.Tensor:
+        """The confidence of the [H, W] map as it stands (after the speckle filter) into the persistent buffer; 0 outside
+        the rectification's left_valid mask."""
+        if self._confidence_map is None or self._confidence_map.device != disparity.device:
+            self._confidence_map = torch.empty_like(disparity)
+        H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
+        radius = self._confidence_radius
+        cuda_depth._launch_confidence(disparity, right_disp, guide if radius > 0 else None, self._confidence_map, 1, H,
+                                      W, radius, self._confidence_lr_scale, self._confidence_texture_scale,
+                                      self._invalid_disparity)
+        if self._rectification is not None:
+            self._confidence_map.masked_fill_(~self._rectification.left_valid, 0.0)
+        return self._confidence_map

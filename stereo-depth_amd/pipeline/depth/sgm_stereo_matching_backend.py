@@ -16,7 +16,8 @@ class SgmStereoMatchingBackend(MapPostprocessing, StereoMatching):
     P1, P2, uniqueness and subpixel as cuda_depth.StereoSGM takes them.  image_shape: (height, width) of the frames it
     matches (after rectification).  left_right_check=True: the in-kernel left-right check of StereoSGM with
     lr_max_diff.  The post-processing and rectification keywords are those of CudaStereoMatchingBackend; the guide of the
-    weighted median and of the WLS filter is the left gray plane StereoSGM writes beside the map."""
+    weighted median, of the WLS filter and of the confidence's texture term is the left gray plane StereoSGM writes
+    beside the map; with left_right_check, the confidence's LR term reads the right-view map StereoSGM writes too."""
 
     def __init__(self, image_shape=(384, 1280), min_disparity: int = 0, max_disparity: int = 127, *, paths: int = 8,
                  P1: int = 10, P2: int = 120, uniqueness: int = 0, subpixel: bool = True,
@@ -24,13 +25,18 @@ class SgmStereoMatchingBackend(MapPostprocessing, StereoMatching):
                  speckle_max_size: int = 0, speckle_max_diff: float = 1.0, fill_invalid: bool = False,
                  median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                  wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
+                 confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
+                 confidence_texture_scale: float = 10.0,
                  rectification: Optional["cuda_depth.StereoRectification"] = None):
         self._image_shape = cuda_depth._shape2("image_shape", image_shape)
         self._init_postprocessing(
             self._image_shape, invalid_disparity=invalid_disparity, speckle_max_size=speckle_max_size,
             speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid, median_radius=median_radius,
             median_sigma_color=median_sigma_color, median_sigma_space=median_sigma_space, wls_lambda=wls_lambda,
-            wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations, rectification=rectification)
+            wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations, confidence=confidence,
+            confidence_lr_scale=confidence_lr_scale, confidence_radius=confidence_radius,
+            confidence_texture_scale=confidence_texture_scale, rectification=rectification)
+        self._left_right_check = bool(left_right_check)
         self._sgm = cuda_depth.StereoSGM(min_disparity, max_disparity, paths=paths, P1=P1, P2=P2,
                                          uniqueness=uniqueness,
                                          lr_max_diff=float(lr_max_diff) if left_right_check else None,
@@ -48,6 +54,9 @@ class SgmStereoMatchingBackend(MapPostprocessing, StereoMatching):
         if self._disparity is None or self._disparity.device != left.device:
             self._disparity = torch.empty(self._image_shape, dtype=torch.float32, device=left.device)
         guide = self._guide_buffer(self._disparity) if self._uses_guide() else None
-        self._sgm.compute(left, right, out=self._disparity, gray_out=guide)
-        self._finish(self._disparity)
+        right_map = None
+        if self._confidence and self._left_right_check:
+            right_map = self._right_map_buffer(self._image_shape, left.device)
+        self._sgm.compute(left, right, out=self._disparity, gray_out=guide, right_out=right_map)
+        self._finish(self._disparity, right_disp=right_map)
         return self._disparity

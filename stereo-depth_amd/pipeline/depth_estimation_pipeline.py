@@ -59,6 +59,9 @@ class DepthEstimationResult:
     left_image: torch.Tensor
     right_image: torch.Tensor
     disparity_map: torch.Tensor
+    # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
+    # None otherwise
+    confidence_map: Optional[torch.Tensor] = None
 
 
 @dataclasses.dataclass
@@ -102,14 +105,19 @@ class DepthEstimationPipeline:
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
                  speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
                  median_sigma_color: float = 10.0, median_sigma_space: float = 5.0, wls_lambda: float = 0.0,
-                 wls_sigma_color: float = 1.5, wls_iterations: int = 3,
+                 wls_sigma_color: float = 1.5, wls_iterations: int = 3, confidence: bool = False,
+                 confidence_lr_scale: float = 1.0, confidence_radius: int = 2, confidence_texture_scale: float = 10.0,
                  rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
                  sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
         wls_sigma_color / wls_iterations: wls_lambda > 0 runs the image-guided weighted least squares filter after the
-        speckle filter in place of the fill and the median (combining them raises ValueError).  rectification: a
+        speckle filter in place of the fill and the median (combining them raises ValueError).  confidence /
+        confidence_lr_scale / confidence_radius / confidence_texture_scale: confidence=True computes the per-pixel
+        confidence of the map after the speckle filter (cuda_depth.confidence_map: the left-right term with
+        config.left_right_check, the texture term over the left gray plane with confidence_radius > 0), returns it as
+        DepthEstimationResult.confidence_map and weighs the WLS filter's pixels by it.  rectification: a
         cuda_depth.StereoRectification whose out_shape is config.image_shape; the raw frames are rectified on the GPU
         before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
         rectified).  sgm_paths / sgm_p1 / sgm_p2 / sgm_uniqueness: the tuning of the 'sgm' backend (4 or 8 paths,
@@ -123,6 +131,9 @@ class DepthEstimationPipeline:
                                               median_radius=median_radius, median_sigma_color=median_sigma_color,
                                               median_sigma_space=median_sigma_space, wls_lambda=wls_lambda,
                                               wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
+                                              confidence=confidence, confidence_lr_scale=confidence_lr_scale,
+                                              confidence_radius=confidence_radius,
+                                              confidence_texture_scale=confidence_texture_scale,
                                               rectification=rectification)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
@@ -133,7 +144,8 @@ class DepthEstimationPipeline:
         """One frame.  The returned disparity map aliases the engine's persistent output buffer
         (stereo_matching.cc:42): clone it before processing the next frame if it must survive.  With rectification=,
         the result's left_image / right_image are the rectified frames the map was computed on (out_shape, same
-        geometry as the map; persistent buffers too), not the raw frames passed in."""
+        geometry as the map; persistent buffers too), not the raw frames passed in.  With confidence=True the result's
+        confidence_map aliases a persistent buffer in the same way."""
         if right_image is None:
             raise RuntimeError("right_image is required: right-view synthesis (Deep3D) is not part of this build.")
         left_on_device = left_image.cuda()
@@ -142,4 +154,6 @@ class DepthEstimationPipeline:
         rectified = getattr(self._stereo_matching, "rectified_frames", lambda: None)()
         if rectified is not None:
             left_on_device, right_image = rectified
-        return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity)
+        confidence = getattr(self._stereo_matching, "confidence_map", lambda: None)()
+        return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
+                                     confidence_map=confidence)

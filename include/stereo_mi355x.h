@@ -24,6 +24,7 @@
  *   -- (image-guided weighted median)                     smx_weighted_median
  *   -- (image-guided weighted least squares filter)       smx_wls_filter, smx_wls_workspace_bytes
  *   -- (per-pixel confidence: LR agreement x texture)     smx_confidence_map
+ *   -- (motion-gated temporal filter of map streams)      smx_temporal_filter
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
  *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes,
  *                                                         smx_sgm_with_right_map
@@ -497,6 +498,43 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
 int smx_confidence_map(int device_id, int n, int H, int W, const float *left_disp, const float *right_disp,
                        const float *guide, int radius, float lr_scale, float texture_scale, float invalid_disparity,
                        float *out, void *stream);
+
+/* Motion-gated temporal filter of disparity-map streams: blends each pixel's new measurement with its history where the
+ * guide image has not changed around it, and resets everywhere else (no motion compensation, so no ghosting).  Every
+ * operand is [n][H][W] f32 on the device; the n maps are n independent streams.  VALID is as above.  Inputs: disp (d),
+ * confidence (c, may be NULL), guide (g, the current left gray plane), prev_guide (G, the previous frame's).  State, read
+ * and written at the same pixel only: state_disp (D), state_weight (A); start it with A = 0 (D is then never read as a
+ * value).  Outputs: out, and guide_out (may be NULL), which receives a copy of g for the next call.  Per pixel p:
+ *   1. Motion.  e(q) = fabsf(g(q) - G(q)), q clamped into the image; R = motion_radius.  Each window row gives
+ *      r(dy) = (...(e(-R) + e(-R+1)) + ...) + e(R), summed in dx order; then S = (...(r(-R) + r(-R+1)) + ...) + r(R),
+ *      summed in dy order.  STATIC iff S <= T with T = motion_threshold * (float)(2R+1)^2 (one float32 product).  A NaN
+ *      or inf anywhere in the window makes S NaN or +inf, so the pixel is not STATIC (while T is finite).  The fixed
+ *      order makes the sum separable and reproducible; an implementation must not use another.
+ *   2. Measurement weight.  w = 0 if d is not VALID; otherwise w = 1.0f with confidence == NULL, else
+ *      (c > 0) ? fminf(c, 1.0f) : 0.0f (step 1 of smx_wls_filter).
+ *   3. a = A * decay; hist = (a > 0) && STATIC && VALID(D).
+ *   4. VALID(d), hist and fabsf(d - D) <= max_diff: out = (a*D + w*d) / (a + w), A' = fminf(a + w, max_weight).
+ *      VALID(d) otherwise (no history, or disagreement): out = d, A' = w.
+ *      d not VALID, hist and a >= min_weight: out = D, A' = a (hold, with a decaying weight).
+ *      Otherwise: out = invalid_disparity, A' = 0.
+ *   5. D' = out; guide_out = g if guide_out is non-NULL.
+ * Every operation is one float32 round-to-nearest with no fused operation, the division is the correctly rounded one
+ * and denormals are kept, so every implementation gives the same bits.  With A = 0 everywhere (after a reset) the call
+ * returns d at the VALID pixels and invalid_disparity elsewhere.  Suggested starting points, not tuned values:
+ * motion_radius = 1, motion_threshold = 4 (gray levels per window pixel), decay = 0.8, max_diff = 1 (disparity px),
+ * max_weight = 8, min_weight = 0.25.
+ * Ranges: motion_radius 0..7; motion_threshold finite and >= 0; decay in (0, 1]; max_diff finite and >= 0; max_weight
+ * finite and > 0; min_weight finite and >= 0; invalid_disparity finite.  Overlaps: the inputs may alias each other;
+ * out is exactly disp or does not overlap it, and does not overlap any other operand; state_disp and state_weight do not
+ * overlap each other or any input; guide_out does not overlap guide, prev_guide or any other operand.  One launch on
+ * `stream` (a caller's stream), with no host synchronisation and no allocation, so the call can be captured into a HIP
+ * graph.  Engine-free: device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL disp, guide, prev_guide, state_disp, state_weight or
+ * out, n < 1, H or W outside 1..32768, a parameter outside its range, the overlaps above, stream == SMX_STREAM_ENGINE. */
+int smx_temporal_filter(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                        const float *guide, const float *prev_guide, float *state_disp, float *state_weight,
+                        float *guide_out, float *out, int motion_radius, float motion_threshold, float decay,
+                        float max_diff, float max_weight, float min_weight, float invalid_disparity, void *stream);
 
 /* Rectification of raw frames: a bilinear remap through a precomputed map, with an integer-defined rule, so that every
  * implementation gives the same bits.

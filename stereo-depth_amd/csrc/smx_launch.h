@@ -111,6 +111,14 @@ void launch_wls(int n, int H, int W, const float *in, const float *conf, const f
 void launch_confidence(int n, int H, int W, const float *left, const float *right, const float *guide, int radius,
                        float lr_scale, float texture_scale, float invalid, float *out, hipStream_t s);
 
+// ---- tu_temporal.hip: motion-gated temporal filter (k_temporal.h) ---------------------------------------------------
+// conf / guide_out NULL: every valid measurement weighs 1 / no copy of the guide; arguments checked by
+// smx_temporal_filter
+void launch_temporal(int n, int H, int W, const float *disp, const float *conf, const float *guide,
+                     const float *prev_guide, float *state_disp, float *state_weight, float *guide_out, float *out,
+                     int radius, float threshold, float decay, float max_diff, float max_weight, float min_weight,
+                     float invalid, hipStream_t s);
+
 // ---- tu_remap.hip: bilinear remap / rectification (k_remap.h) -------------------------------------------------------
 // in_r / map_r / out_r NULL: left view only; arguments checked by smx_remap_pairs
 void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, const void *in_l, const void *in_r,

@@ -195,6 +195,54 @@ int smx_confidence_map(int device_id, int n, int H, int W, const float *left_dis
     });
 }
 
+int smx_temporal_filter(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                        const float *guide, const float *prev_guide, float *state_disp, float *state_weight,
+                        float *guide_out, float *out, int motion_radius, float motion_threshold, float decay,
+                        float max_diff, float max_weight, float min_weight, float invalid, void *stream) {
+    const char *fn = "smx_temporal_filter";
+    if (!disp || !guide || !prev_guide || !state_disp || !state_weight || !out)
+        return fail(SMX_ERR_INVALID_ARG, "%s: disp, guide, prev_guide, state_disp, state_weight and out must be non-NULL",
+                    fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (motion_radius < 0 || motion_radius > 7)
+        return fail(SMX_ERR_INVALID_ARG, "%s: motion_radius must be in 0..7, got %d", fn, motion_radius);
+    if (!(std::isfinite(motion_threshold) && motion_threshold >= 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: motion_threshold must be finite and >= 0, got %g", fn,
+                    (double)motion_threshold);
+    if (!(decay > 0.0f && decay <= 1.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: decay must be in (0, 1], got %g", fn, (double)decay);
+    if (!(std::isfinite(max_diff) && max_diff >= 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: max_diff must be finite and >= 0, got %g", fn, (double)max_diff);
+    if (!(std::isfinite(max_weight) && max_weight > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: max_weight must be finite and > 0, got %g", fn, (double)max_weight);
+    if (!(std::isfinite(min_weight) && min_weight >= 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and >= 0, got %g", fn, (double)min_weight);
+    if (int rc = check_finite_marker(invalid)) return rc;
+    const size_t bytes = (size_t)n * H * W * sizeof(float);
+    const void *inputs[4] = {disp, confidence, guide, prev_guide};
+    if (out != disp && ranges_overlap(out, bytes, disp, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap disp other than as the same buffer", fn);
+    const void *others[6] = {confidence, guide, prev_guide, state_disp, state_weight, guide_out};
+    for (const void *o : others)
+        if (ranges_overlap(out, bytes, o, bytes))
+            return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap an operand other than disp", fn);
+    for (const void *i : inputs)
+        if (ranges_overlap(state_disp, bytes, i, bytes) || ranges_overlap(state_weight, bytes, i, bytes))
+            return fail(SMX_ERR_INVALID_ARG, "%s: the state buffers must not overlap an input", fn);
+    if (ranges_overlap(state_disp, bytes, state_weight, bytes))
+        return fail(SMX_ERR_INVALID_ARG, "%s: state_disp and state_weight overlap", fn);
+    const void *not_guide_out[6] = {disp, confidence, guide, prev_guide, state_disp, state_weight};
+    for (const void *o : not_guide_out)
+        if (ranges_overlap(guide_out, bytes, o, bytes))
+            return fail(SMX_ERR_INVALID_ARG, "%s: guide_out must not overlap another operand", fn);
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_temporal(n, H, W, disp, confidence, guide, prev_guide, state_disp, state_weight, guide_out, out,
+                             motion_radius, motion_threshold, decay, max_diff, max_weight, min_weight, invalid,
+                             (hipStream_t)stream);
+    });
+}
+
 int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
                     const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
                     void *left_out, void *right_out, int border_mode, float border_value, void *stream) {

@@ -395,6 +395,123 @@ def confidence_map(disp: torch.Tensor, right_disp: Optional[torch.Tensor] = None
     return out
 
 
+def _check_temporal_params(motion_radius, motion_threshold, decay, max_diff, max_weight, min_weight,
+                           invalid_disparity) -> None:
+    """The scalar rules of smx_temporal_filter, checked before the device is touched."""
+    _int_arg("motion_radius", motion_radius)
+    if not 0 <= motion_radius <= 7:
+        raise RuntimeError(f"motion_radius must be in 0..7, got {motion_radius}")
+    for name, v in (("motion_threshold", motion_threshold), ("decay", decay), ("max_diff", max_diff),
+                    ("max_weight", max_weight), ("min_weight", min_weight), ("invalid_disparity", invalid_disparity)):
+        _number_arg(name, v)
+    for name, v in (("motion_threshold", motion_threshold), ("max_diff", max_diff), ("min_weight", min_weight)):
+        if not (math.isfinite(v) and v >= 0):
+            raise RuntimeError(f"{name} must be finite and >= 0, got {v}")
+    if not 0 < decay <= 1:
+        raise RuntimeError(f"decay must be in (0, 1], got {decay}")
+    if not (math.isfinite(max_weight) and max_weight > 0):
+        raise RuntimeError(f"max_weight must be finite and > 0, got {max_weight}")
+    if not math.isfinite(invalid_disparity):
+        raise RuntimeError(f"invalid_disparity must be finite (a NaN marker never compares equal), got {invalid_disparity}")
+
+
+def _launch_temporal(disp, confidence, guide, prev_guide, state_disp, state_weight, guide_out, out, n, H, W,
+                     motion_radius, motion_threshold, decay, max_diff, max_weight, min_weight,
+                     invalid_disparity) -> None:
+    """smx_temporal_filter on the current stream; confidence / guide_out may be None."""
+    dev = disp.device.index
+    check(LIB.smx_temporal_filter(dev, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(),
+                                  guide.data_ptr(), prev_guide.data_ptr(), state_disp.data_ptr(),
+                                  state_weight.data_ptr(), None if guide_out is None else guide_out.data_ptr(),
+                                  out.data_ptr(), int(motion_radius), float(motion_threshold), float(decay),
+                                  float(max_diff), float(max_weight), float(min_weight), float(invalid_disparity),
+                                  _stream(dev)))
+
+
+class TemporalFilter:
+    """Motion-gated temporal filter of n independent disparity-map streams (smx_temporal_filter; the rule is in
+    include/stereo_mi355x.h).  Where the guide (the left gray plane) has not changed around a pixel since the previous
+    call (the mean |g - G| over the (2 motion_radius + 1)^2 window is at most motion_threshold), a valid measurement is
+    blended with the pixel's history if they agree within max_diff, and an invalid one holds the history while its
+    weight, decayed by `decay` per call, stays at least min_weight.  Everywhere else the measurement is taken as it is
+    and the history restarts: without motion compensation the filter does little on a moving camera, but never smears.
+    The history's weight is capped at max_weight.  The filter keeps the state (D, A) and the previous guide (two
+    ping-pong buffers), so a caller only passes each frame's map and guide.  The defaults are starting points, not values
+    tuned on this project's data."""
+
+    def __init__(self, n: int, H: int, W: int, *, device=None, motion_radius: int = 1, motion_threshold: float = 4.0,
+                 decay: float = 0.8, max_diff: float = 1.0, max_weight: float = 8.0, min_weight: float = 0.25,
+                 invalid_disparity: float = -1.0):
+        for name, v in (("n", n), ("H", H), ("W", W)):
+            _int_arg(name, v)
+        if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768):
+            raise RuntimeError(f"need n >= 1 and 1 <= H, W <= 32768 (got n {n}, H {H}, W {W})")
+        _check_temporal_params(motion_radius, motion_threshold, decay, max_diff, max_weight, min_weight,
+                               invalid_disparity)
+        device = torch.device("cuda") if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"TemporalFilter needs a GPU device, got {device}")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.n, self.H, self.W, self.device = n, H, W, device
+        self.motion_radius = motion_radius
+        self.motion_threshold, self.decay, self.max_diff = float(motion_threshold), float(decay), float(max_diff)
+        self.max_weight, self.min_weight = float(max_weight), float(min_weight)
+        self.invalid_disparity = float(invalid_disparity)
+        shape = (n, H, W)
+        self._state_disp = torch.full(shape, self.invalid_disparity, dtype=torch.float32, device=device)
+        self._state_weight = torch.zeros(shape, dtype=torch.float32, device=device)
+        self._guides = torch.zeros((2,) + shape, dtype=torch.float32, device=device)
+        self._prev = 0                                  # _guides[_prev] holds the previous call's guide
+
+    @property
+    def state(self):
+        """(D, A): [n, H, W] views of the filtered map and its weight after the last call."""
+        return self._state_disp, self._state_weight
+
+    def reset(self, streams=None) -> None:
+        """Forgets the history of every stream (None) or of the listed stream indices: their next call returns the
+        measurement at the valid pixels and invalid_disparity elsewhere.  Runs on the current stream."""
+        if streams is None:
+            self._state_weight.zero_()
+            self._state_disp.fill_(self.invalid_disparity)
+            return
+        idx = list(streams)
+        for i in idx:
+            _int_arg("stream index", i)
+            if not 0 <= i < self.n:
+                raise RuntimeError(f"stream index must be in 0..{self.n - 1}, got {i}")
+        for i in idx:
+            self._state_weight[i].zero_()
+            self._state_disp[i].fill_(self.invalid_disparity)
+
+    def apply(self, disp: torch.Tensor, guide: torch.Tensor, confidence: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Filters one frame of every stream on the current stream and returns the filtered map(s).  disp, guide,
+        confidence, out: float32 [n, H, W] on the filter's device ([H, W] also for n = 1).  confidence: None (every valid
+        pixel weighs 1) or per-pixel weights, clamped to [0, 1], e.g. cuda_depth.confidence_map.  out=disp filters in
+        place; out must not overlap guide or confidence."""
+        _check_input("disp", disp)
+        shape = (self.n, self.H, self.W)
+        if not (tuple(disp.shape) == shape or (self.n == 1 and tuple(disp.shape) == shape[1:])):
+            raise RuntimeError(f"disp must be float32 {shape} on {self.device}" +
+                               (f" or {shape[1:]}" if self.n == 1 else "") + f", got {tuple(disp.shape)}")
+        _check_like("disp", disp, torch.float32, disp.shape, self.device)
+        _check_like("guide", guide, torch.float32, disp.shape, self.device)
+        if confidence is not None:
+            _check_like("confidence", confidence, torch.float32, disp.shape, self.device)
+        if out is None:
+            out = torch.empty_like(disp)
+        else:
+            _check_like("out", out, torch.float32, disp.shape, self.device)
+        prev, nxt = self._guides[self._prev], self._guides[1 - self._prev]
+        _launch_temporal(disp, confidence, guide, prev, self._state_disp, self._state_weight, nxt, out, self.n, self.H,
+                         self.W, self.motion_radius, self.motion_threshold, self.decay, self.max_diff, self.max_weight,
+                         self.min_weight, self.invalid_disparity)
+        self._prev = 1 - self._prev
+        return out
+
+
 def _shape2(name: str, shape) -> tuple:
     try:
         h, w = (int(v) for v in shape)

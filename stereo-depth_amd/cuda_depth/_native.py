@@ -117,6 +117,11 @@ EXPORTS = {
     # invalid_disparity, out, stream)
     "smx_confidence_map": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    # temporal filter: (device_id, n, H, W, disp, confidence, guide, prev_guide, state_disp, state_weight, guide_out,
+    # out, motion_radius, motion_threshold, decay, max_diff, max_weight, min_weight, invalid_disparity, stream)
+    "smx_temporal_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     # rectification: (device_id, n, channels, dtype, H_in, W_in, H_out, W_out, left_in, right_in, left_map, right_map,
     # left_out, right_out, border_mode, border_value, stream)
     "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

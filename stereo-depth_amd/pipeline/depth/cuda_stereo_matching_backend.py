@@ -36,6 +36,9 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
     confidence=True (with confidence_lr_scale, confidence_radius, confidence_texture_scale): the per-pixel confidence
     of MapPostprocessing, confidence_map(); with left_right_check its LR term reads the engine's right-view map of the
     same call.
+    temporal=True (with temporal_motion_radius, temporal_motion_threshold, temporal_decay, temporal_max_diff,
+    temporal_max_weight, temporal_min_weight): the motion-gated temporal filter of MapPostprocessing, last, guided by the
+    engine's left gray plane; reset_temporal() forgets its history.
     rectification (a cuda_depth.StereoRectification, default None): both raw frames are rectified on the current stream
     before matching (its out_shape must be the configuration's image size), and the pixels of the final map outside its
     left_valid mask become invalid_disparity."""
@@ -46,7 +49,9 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
                  median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                  wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                  confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
-                 confidence_texture_scale: float = 10.0,
+                 confidence_texture_scale: float = 10.0, temporal: bool = False, temporal_motion_radius: int = 1,
+                 temporal_motion_threshold: float = 4.0, temporal_decay: float = 0.8, temporal_max_diff: float = 1.0,
+                 temporal_max_weight: float = 8.0, temporal_min_weight: float = 0.25,
                  rectification: Optional["cuda_depth.StereoRectification"] = None):
         configuration = configuration or cuda_depth.StereoMatchingConfiguration()
         self._init_postprocessing(
@@ -55,7 +60,11 @@ class CudaStereoMatchingBackend(MapPostprocessing, StereoMatching):
             median_radius=median_radius, median_sigma_color=median_sigma_color, median_sigma_space=median_sigma_space,
             wls_lambda=wls_lambda, wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
             confidence=confidence, confidence_lr_scale=confidence_lr_scale, confidence_radius=confidence_radius,
-            confidence_texture_scale=confidence_texture_scale, rectification=rectification)
+            confidence_texture_scale=confidence_texture_scale, temporal=temporal,
+            temporal_motion_radius=temporal_motion_radius, temporal_motion_threshold=temporal_motion_threshold,
+            temporal_decay=temporal_decay, temporal_max_diff=temporal_max_diff,
+            temporal_max_weight=temporal_max_weight, temporal_min_weight=temporal_min_weight,
+            rectification=rectification)
         self._left_right_check = bool(left_right_check)
         self._lr_max_diff = float(lr_max_diff)
         self._invalid_disparity = float(invalid_disparity)

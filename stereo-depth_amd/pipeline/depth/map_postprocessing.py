@@ -1,6 +1,7 @@
 """What the stereo-matching backends share around their matcher: rectification of the raw frames before matching, and
 the post-processing of the map after it (speckle filter, per-pixel confidence, background hole fill, image-guided
-weighted median or weighted least squares filter, the rectification's validity mask).  Every step runs on the current stream with buffers allocated once."""
+weighted median or weighted least squares filter, the rectification's validity mask, the temporal filter).  Every step
+runs on the current stream with buffers allocated once."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -37,14 +38,22 @@ class MapPostprocessing:
     confidence_texture_scale.  Removed speckles and, with a rectification, the pixels outside its left_valid mask get 0;
     the pixels the fill writes keep 0.  With wls_lambda > 0 the WLS filter weighs each pixel by it.
     rectification (a cuda_depth.StereoRectification, or None): both raw frames are rectified before matching (its
-    out_shape must be image_size), and the pixels of the final map outside its left_valid mask become invalid_disparity."""
+    out_shape must be image_size), and the pixels of the final map outside its left_valid mask become invalid_disparity.
+    temporal=True: last, after the rectification's mask, the motion-gated temporal filter (cuda_depth.TemporalFilter with
+    temporal_motion_radius, temporal_motion_threshold, temporal_decay, temporal_max_diff, temporal_max_weight and
+    temporal_min_weight) in place on the map, guided by the same left gray plane, with its history carried from one
+    process() call to the next; reset_temporal() forgets it.  With confidence=True the confidence map is the
+    measurement's weight, so the pixels the fill or the WLS filter wrote (confidence 0) keep their history."""
 
     def _init_postprocessing(self, image_size: tuple, *, invalid_disparity: float = -1.0, speckle_max_size: int = 0,
                              speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
                              median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                              wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                              confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
-                             confidence_texture_scale: float = 10.0,
+                             confidence_texture_scale: float = 10.0, temporal: bool = False,
+                             temporal_motion_radius: int = 1, temporal_motion_threshold: float = 4.0,
+                             temporal_decay: float = 0.8, temporal_max_diff: float = 1.0,
+                             temporal_max_weight: float = 8.0, temporal_min_weight: float = 0.25,
                              rectification: Optional["cuda_depth.StereoRectification"] = None) -> None:
         if rectification is not None:
             if not isinstance(rectification, cuda_depth.StereoRectification):
@@ -86,6 +95,14 @@ class MapPostprocessing:
         self._confidence_texture_scale = float(confidence_texture_scale)
         self._confidence_map: Optional[torch.Tensor] = None     # the confidence of the last call
         self._right_map: Optional[torch.Tensor] = None          # the matcher's right-view map (confidence, LR check)
+        if not isinstance(temporal, bool):
+            raise TypeError("temporal must be a bool")
+        self._temporal_params = dict(motion_radius=temporal_motion_radius, motion_threshold=temporal_motion_threshold,
+                                     decay=temporal_decay, max_diff=temporal_max_diff,
+                                     max_weight=temporal_max_weight, min_weight=temporal_min_weight)
+        cuda_depth._check_temporal_params(**self._temporal_params, invalid_disparity=invalid_disparity)
+        self._temporal = temporal
+        self._temporal_filter: Optional["cuda_depth.TemporalFilter"] = None   # created at the first frame
 
     def _guide_buffer(self, like: torch.Tensor) -> torch.Tensor:
         """The persistent [H, W] float32 buffer the matcher's left gray plane goes into (median_radius > 0 or
@@ -96,10 +113,10 @@ class MapPostprocessing:
         return self._median_guide
 
     def _uses_guide(self) -> bool:
-        """Whether a post-processing step needs the left gray plane (the median, the WLS filter or the confidence's
-        texture term)."""
+        """Whether a post-processing step needs the left gray plane (the median, the WLS filter, the confidence's
+        texture term or the temporal filter)."""
         return self._median_radius > 0 or self._wls_tables is not None or (self._confidence and
-                                                                            self._confidence_radius > 0)
+                                                                            self._confidence_radius > 0) or self._temporal
 
     def _right_map_buffer(self, shape: tuple, device: torch.device) -> torch.Tensor:
         """The persistent float32 buffer of `shape` the matcher's right-view map goes into (confidence=True with the
@@ -137,6 +154,24 @@ class MapPostprocessing:
             self._postprocess(disparity, write_guide, right_disp)
         if self._rectification is not None:
             disparity.masked_fill_(~self._rectification.left_valid, self._invalid_disparity)
+        if self._temporal:
+            self._apply_temporal(disparity)
+
+    def _apply_temporal(self, disparity: torch.Tensor) -> None:
+        """The temporal filter on the finished [H, W] map, in place, guided by the left gray plane _postprocess wrote."""
+        H, W = int(disparity.shape[-2]), int(disparity.shape[-1])
+        f = self._temporal_filter
+        if f is None or f.device != disparity.device or (f.H, f.W) != (H, W):
+            f = self._temporal_filter = cuda_depth.TemporalFilter(1, H, W, device=disparity.device,
+                                                                  invalid_disparity=self._invalid_disparity,
+                                                                  **self._temporal_params)
+        f.apply(disparity, self._median_guide, confidence=self._confidence_map if self._confidence else None,
+                out=disparity)
+
+    def reset_temporal(self) -> None:
+        """Forgets the temporal filter's history: the next frame's map is returned as the other steps leave it."""
+        if self._temporal_filter is not None:
+            self._temporal_filter.reset()
 
     def _postprocess(self, disparity: torch.Tensor, write_guide, right_disp) -> None:
         H, W = int(disparity.shape[-2]), int(disparity.shape[-1])

@@ -26,7 +26,9 @@ class SgmStereoMatchingBackend(MapPostprocessing, StereoMatching):
                  median_radius: int = 0, median_sigma_color: float = 10.0, median_sigma_space: float = 5.0,
                  wls_lambda: float = 0.0, wls_sigma_color: float = 1.5, wls_iterations: int = 3,
                  confidence: bool = False, confidence_lr_scale: float = 1.0, confidence_radius: int = 2,
-                 confidence_texture_scale: float = 10.0,
+                 confidence_texture_scale: float = 10.0, temporal: bool = False, temporal_motion_radius: int = 1,
+                 temporal_motion_threshold: float = 4.0, temporal_decay: float = 0.8, temporal_max_diff: float = 1.0,
+                 temporal_max_weight: float = 8.0, temporal_min_weight: float = 0.25,
                  rectification: Optional["cuda_depth.StereoRectification"] = None):
         self._image_shape = cuda_depth._shape2("image_shape", image_shape)
         self._init_postprocessing(
@@ -35,7 +37,11 @@ class SgmStereoMatchingBackend(MapPostprocessing, StereoMatching):
             median_sigma_color=median_sigma_color, median_sigma_space=median_sigma_space, wls_lambda=wls_lambda,
             wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations, confidence=confidence,
             confidence_lr_scale=confidence_lr_scale, confidence_radius=confidence_radius,
-            confidence_texture_scale=confidence_texture_scale, rectification=rectification)
+            confidence_texture_scale=confidence_texture_scale, temporal=temporal,
+            temporal_motion_radius=temporal_motion_radius, temporal_motion_threshold=temporal_motion_threshold,
+            temporal_decay=temporal_decay, temporal_max_diff=temporal_max_diff,
+            temporal_max_weight=temporal_max_weight, temporal_min_weight=temporal_min_weight,
+            rectification=rectification)
         self._left_right_check = bool(left_right_check)
         self._sgm = cuda_depth.StereoSGM(min_disparity, max_disparity, paths=paths, P1=P1, P2=P2,
                                          uniqueness=uniqueness,

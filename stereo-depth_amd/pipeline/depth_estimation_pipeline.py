@@ -107,6 +107,9 @@ class DepthEstimationPipeline:
                  median_sigma_color: float = 10.0, median_sigma_space: float = 5.0, wls_lambda: float = 0.0,
                  wls_sigma_color: float = 1.5, wls_iterations: int = 3, confidence: bool = False,
                  confidence_lr_scale: float = 1.0, confidence_radius: int = 2, confidence_texture_scale: float = 10.0,
+                 temporal: bool = False, temporal_motion_radius: int = 1, temporal_motion_threshold: float = 4.0,
+                 temporal_decay: float = 0.8, temporal_max_diff: float = 1.0, temporal_max_weight: float = 8.0,
+                 temporal_min_weight: float = 0.25,
                  rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
                  sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
@@ -117,7 +120,11 @@ class DepthEstimationPipeline:
         confidence_lr_scale / confidence_radius / confidence_texture_scale: confidence=True computes the per-pixel
         confidence of the map after the speckle filter (cuda_depth.confidence_map: the left-right term with
         config.left_right_check, the texture term over the left gray plane with confidence_radius > 0), returns it as
-        DepthEstimationResult.confidence_map and weighs the WLS filter's pixels by it.  rectification: a
+        DepthEstimationResult.confidence_map and weighs the WLS filter's pixels by it.  temporal / temporal_motion_radius /
+        temporal_motion_threshold / temporal_decay / temporal_max_diff / temporal_max_weight / temporal_min_weight:
+        temporal=True runs the motion-gated temporal filter (cuda_depth.TemporalFilter) last, in place on the map, with
+        its history carried across process() calls (reset_temporal() forgets it); with confidence=True the confidence
+        map is the measurement's weight.  rectification: a
         cuda_depth.StereoRectification whose out_shape is config.image_shape; the raw frames are rectified on the GPU
         before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
         rectified).  sgm_paths / sgm_p1 / sgm_p2 / sgm_uniqueness: the tuning of the 'sgm' backend (4 or 8 paths,
@@ -133,9 +140,18 @@ class DepthEstimationPipeline:
                                               wls_sigma_color=wls_sigma_color, wls_iterations=wls_iterations,
                                               confidence=confidence, confidence_lr_scale=confidence_lr_scale,
                                               confidence_radius=confidence_radius,
-                                              confidence_texture_scale=confidence_texture_scale,
+                                              confidence_texture_scale=confidence_texture_scale, temporal=temporal,
+                                              temporal_motion_radius=temporal_motion_radius,
+                                              temporal_motion_threshold=temporal_motion_threshold,
+                                              temporal_decay=temporal_decay, temporal_max_diff=temporal_max_diff,
+                                              temporal_max_weight=temporal_max_weight,
+                                              temporal_min_weight=temporal_min_weight,
                                               rectification=rectification)
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
+
+    def reset_temporal(self) -> None:
+        """Forgets the temporal filter's history (temporal=True), e.g. at a cut in the stream; a no-op otherwise."""
+        self._stereo_matching.reset_temporal()
 
     def get_configuration(self) -> DepthEstimationPipelineConfig:
         return self._config

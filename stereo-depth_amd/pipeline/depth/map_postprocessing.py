@@ -21,6 +21,8 @@ def device_frame(image: torch.Tensor) -> torch.Tensor:
 
 class MapPostprocessing:
     """Mixin of the backends: _init_postprocessing() in the constructor, _rectify() before matching, _finish() after.
+    The backends take uint8 frames as uint8 and every other dtype as float32; a pair of different dtypes is taken as
+    float32 for both, before the rectification.
     speckle_max_size > 0: the speckle filter (cuda_depth.filter_speckles) removes every region of speckle_max_size
     pixels or fewer whose 4-neighbours differ by at most speckle_max_diff.  fill_invalid=True: then the background hole
     fill (cuda_depth.fill_invalid) makes the map dense again.  Both run in place on the map.

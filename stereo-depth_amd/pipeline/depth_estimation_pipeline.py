@@ -161,7 +161,8 @@ class DepthEstimationPipeline:
         (stereo_matching.cc:42): clone it before processing the next frame if it must survive.  With rectification=,
         the result's left_image / right_image are the rectified frames the map was computed on (out_shape, same
         geometry as the map; persistent buffers too), not the raw frames passed in.  With confidence=True the result's
-        confidence_map aliases a persistent buffer in the same way."""
+        confidence_map aliases a persistent buffer in the same way.  Frames are matched (and rectified) as uint8 when
+        both are uint8 and as float32 otherwise: a uint8 frame beside a float32 one is converted to float32 first."""
         if right_image is None:
             raise RuntimeError("right_image is required: right-view synthesis (Deep3D) is not part of this build.")
         left_on_device = left_image.cuda()

@@ -1,6 +1,6 @@
 """Left-right consistency check, the parts that need no GPU: the five C-ABI symbols, argument checks that return before
 the device is touched, the pipeline's new config fields, and known answers of the NumPy twin of the rule
-(include/stereo_mi355x.h: smx_compute_lr_*) that the GPU tests compare the kernels against."""
+(include/stereo_mi355x.h: smx_compute_lr_*; lr_ref.lr_rule) that the GPU tests compare the kernels against."""
 import ctypes as C
 import os
 import re
@@ -8,23 +8,12 @@ import re
 import numpy as np
 import pytest
 
+from lr_ref import lr_rule
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 LR_SYMBOLS = ("smx_compute_lr_gray_batch", "smx_compute_lr_gray_u8_batch", "smx_compute_lr_rgb_batch",
               "smx_compute_lr_rgb_u8_batch", "smx_lr_check")
-
-
-def lr_rule(dl: np.ndarray, dr: np.ndarray, max_diff: float = 1.0, invalid_disparity: float = -1.0) -> np.ndarray:
-    """NumPy twin of the check: dl = left-referenced map, dr = right-referenced map, both [..., H, W] float32."""
-    dl = np.asarray(dl, np.float32)
-    dr = np.asarray(dr, np.float32)
-    with np.errstate(invalid="ignore"):
-        t = np.floor(dl + np.float32(0.5))
-        Y = np.arange(dl.shape[-1])
-        ok = np.isfinite(t) & (t >= 0) & (t <= Y)
-        yr = Y - np.where(ok, t, 0).astype(np.int64)
-        ok &= np.abs(dl - np.take_along_axis(dr, yr, -1)) <= np.float32(max_diff)
-    return np.where(ok, dl, np.float32(invalid_disparity)).astype(np.float32)
 
 
 @pytest.fixture(scope="module")

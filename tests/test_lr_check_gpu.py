@@ -1,6 +1,6 @@
 """Left-right consistency check on the device (include/stereo_mi355x.h: smx_compute_lr_*, smx_lr_check).
 
-Every expected value comes from the CPU oracle and the NumPy twin of the rule (test_lr_check_cpu.lr_rule):
+Every expected value comes from the CPU oracle and the NumPy twin of the rule (lr_ref.lr_rule):
   D_L = oracle(L, R),  D_R = flip(oracle(flip R, flip L)),  out = rule(D_L, D_R)
 and is compared bit for bit.  The occlusion scene at the end is the one behavioural test (thresholds in its docstring)."""
 
@@ -14,7 +14,7 @@ torch = pytest.importorskip("torch")
 import stereo_synthetic as syn                      # noqa: E402
 from oracle_lib import OracleConfig                 # noqa: E402
 from parity_inputs import float_pair, odd_disparity_pair   # noqa: E402
-from test_lr_check_cpu import lr_rule               # noqa: E402
+from lr_ref import lr_rule                          # noqa: E402
 
 
 @pytest.fixture(scope="module")

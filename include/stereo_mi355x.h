@@ -28,6 +28,8 @@
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
  *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes,
  *                                                         smx_sgm_with_right_map
+ *   -- (metric 3D points, coloured, compacted)            smx_reproject_points, smx_reproject_workspace_bytes
+ *   -- (voxel-grid downsampling of those points)          smx_voxel_downsample, smx_voxel_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -623,6 +625,64 @@ int smx_sgm_with_right_map(int device_id, int n, int channels, int dtype, int H,
                            int uniqueness, float lr_max_diff, int subpixel, float invalid_disparity, float *out,
                            float *gray_left_out, float *right_out, void *workspace, size_t workspace_bytes,
                            void *stream);
+
+/* ---- Metric 3D point clouds -------------------------------------------------------------------------------------------
+ * smx_reproject_points: n disparity maps disp [n][H][W] f32 -> one compacted list of 3D points for the batch.
+ * Geometry: Q is a host 4x4 row-major matrix in OpenCV's reprojectImageTo3D convention, [X' Y' Z' W'] = Q [u v d 1], with
+ * u = (float)column and v = (float)row.  Every step is ONE float32 operation (no fused multiply-add, correctly rounded
+ * division), in this order, on every implementation:
+ *   R'   = ((Q[r][0]*u + Q[r][1]*v) + Q[r][2]*d) + Q[r][3]          for r = 0..3  (X', Y', Z', W')
+ *   X = X'/W', Y = Y'/W', Z = Z'/W'
+ * A pixel becomes a point iff d is finite and d != invalid_disparity, W' > 0, X, Y and Z are finite,
+ * z_min <= Z <= z_max, and (with a confidence map) c >= min_confidence (a NaN c excludes the pixel).
+ * Colour (image != NULL): gray [n][H][W] (image_channels 1, copied to R, G and B) or planar RGB [n][3][H][W]
+ * (image_channels 3), SMX_DTYPE_U8 or SMX_DTYPE_F32; an f32 value v becomes (uint8)clamp(floorf(v + 0.5f), 0, 255),
+ * NaN -> 0.
+ * Outputs (capacity n*H*W points; the caller allocates it): offsets [n+1] int32 on the device -- the points of map i are
+ * [offsets[i], offsets[i+1]), in row-major pixel order; points [cap][3] f32; colors [cap][3] u8 (NULL: none; needs an
+ * image); indices [cap] int32 (NULL: none), the pixel's row-major index y*W + x within its map; xyz_map
+ * [n][H][W][3] f32 (NULL: none), the organised cloud with NaN at every excluded pixel.  Entries past offsets[n] are not
+ * written.  workspace: smx_reproject_workspace_bytes(n, H, W) bytes (0 for sizes the call rejects).
+ * Three launches on `stream` (a caller's stream), no host synchronisation and no allocation: graph-capturable.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL disp, Q, points, offsets or workspace; n < 1; H or W
+ * outside 1..32768; n*H*W > 2^30; a non-finite Q entry; a NaN z bound or z_min > z_max; a non-finite min_confidence or
+ * invalid_disparity; an image whose channels are not 1 or 3 or whose dtype is unknown; colors without an image;
+ * workspace_bytes below the query; an output overlapping an input, the workspace or another output; stream ==
+ * SMX_STREAM_ENGINE. */
+size_t smx_reproject_workspace_bytes(int n, int H, int W);
+int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, const float Q[16],
+                         const float *confidence, float min_confidence, float z_min, float z_max,
+                         float invalid_disparity, const void *image, int image_channels, int image_dtype,
+                         float *points, uint8_t *colors, int32_t *indices, float *xyz_map, int32_t *offsets,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_voxel_downsample: one point per occupied voxel of every map of a compacted list (smx_reproject_points' output:
+ * points [capacity][3] f32, colors [capacity][3] u8 or NULL, offsets [n+1] int32 on the device).  The device offsets are
+ * used clamped to a non-decreasing sequence in [0, capacity].
+ *   voxel index per axis: i = (int)floorf(coord / voxel_size); a point with any index outside -2^20 <= i < 2^20 (or a
+ *   NaN coordinate) is dropped and counted in dropped[map].
+ *   A voxel with cnt < min_points points is dropped and its cnt points are counted in dropped[map].
+ *   Per map, the kept voxels are written in ascending (ix, iy, iz) order from out_offsets[map]:
+ *     centroid  = S / (float)cnt per axis, S summed over the voxel's points in their input (pixel) order: sequentially
+ *                 within consecutive chunks of 64 points, s_c = ((p_0 + p_1) + p_2) + ... (starting from p_0, not
+ *                 0), then sequentially over the chunk sums, S = ((s_0 + s_1) + s_2) + ...; one point returns itself.
+ *     colour    = (sum of c + cnt/2) / cnt per channel, in integers (out_colors; only with colors)
+ *     out_counts = cnt
+ *   out_offsets [n+1] int32, dropped [n] int32; the sum of out_counts of map i plus dropped[i] is its input count.
+ * The result is bit-identical from run to run, and map i's is independent of n and of the other maps: there are no
+ * float atomics (a stable LSD radix sort of each map's voxel keys, then one thread per voxel).
+ * workspace: smx_voxel_workspace_bytes(n, capacity) bytes (0 for sizes the call rejects); about 36 bytes per point.
+ * A fixed sequence of launches on `stream` (a caller's stream; sort passes beyond the key's width return at once), no host
+ * synchronisation and no allocation: graph-capturable.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL points, offsets, out_points, out_counts,
+ * out_offsets, dropped or workspace; exactly one of colors / out_colors NULL; n outside 1..65536; capacity outside
+ * 1..2^30; voxel_size not finite and > 0; min_points < 1; workspace_bytes below the query; an output overlapping an input,
+ * the workspace or another output; stream == SMX_STREAM_ENGINE. */
+size_t smx_voxel_workspace_bytes(int n, int capacity);
+int smx_voxel_downsample(int device_id, int n, int capacity, const float *points, const uint8_t *colors,
+                         const int32_t *offsets, float voxel_size, int min_points, float *out_points,
+                         uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -133,4 +133,19 @@ void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const vo
                 int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
                 float *gray_out, float *right_out, void *workspace, hipStream_t s);
 
+// ---- tu_reproject.hip: metric 3D points and voxel-grid downsampling (k_reproject.h) ------------------------------------
+// q: the host's 4x4 matrix, copied into the kernel arguments; conf / image / colors / indices / xyz_map may be NULL;
+// arguments checked by smx_reproject_points
+size_t reproject_workspace_bytes(int n, int H);
+void launch_reproject(int n, int H, int W, const float *disp, const float q[16], const float *conf, float min_conf,
+                      float zmin, float zmax, float invalid, const void *image, int channels, bool img_f32,
+                      float *points, uint8_t *colors, int32_t *indices, float *xyz_map, int32_t *offsets,
+                      void *workspace, hipStream_t s);
+// colors / out_colors NULL: no colour; arguments checked by smx_voxel_downsample
+size_t voxel_workspace_bytes(int n, int capacity);
+hipError_t launch_voxel_downsample(int n, int capacity, const float *points, const uint8_t *colors,
+                                   const int32_t *offsets, float voxel_size, int min_points, float *out_points,
+                                   uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
+                                   void *workspace, hipStream_t s);
+
 }  // namespace smx

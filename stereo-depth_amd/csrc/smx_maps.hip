@@ -396,4 +396,115 @@ int smx_eval_metrics(int device_id, int n, const float *est, const float *gt, co
     });
 }
 
+// ---- metric 3D points ----------------------------------------------------------------------------------------------------
+static constexpr long SMX_POINTS_MAX = 1L << 30;     // n*H*W (reprojection) and the capacity (downsampling)
+
+size_t smx_reproject_workspace_bytes(int n, int H, int W) {
+    if (!map_dims_ok(n, H, W) || (long)n * H * W > SMX_POINTS_MAX) return 0;
+    return smx::reproject_workspace_bytes(n, H);
+}
+
+int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, const float Q[16],
+                         const float *confidence, float min_confidence, float z_min, float z_max,
+                         float invalid_disparity, const void *image, int image_channels, int image_dtype,
+                         float *points, uint8_t *colors, int32_t *indices, float *xyz_map, int32_t *offsets,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_reproject_points";
+    if (!disp || !Q || !points || !offsets || !workspace)
+        return fail(SMX_ERR_INVALID_ARG, "%s: disp, Q, points, offsets and workspace must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    const long cap = (long)n * H * W;
+    if (cap > SMX_POINTS_MAX)
+        return fail(SMX_ERR_INVALID_ARG, "%s: n * H * W = %ld exceeds 2^30: split the batch", fn, cap);
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(Q[k])) return fail(SMX_ERR_INVALID_ARG, "%s: Q[%d] = %g is not finite", fn, k, (double)Q[k]);
+    if (std::isnan(z_min) || std::isnan(z_max) || z_min > z_max)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need z_min <= z_max, got %g, %g", fn, (double)z_min, (double)z_max);
+    if (!std::isfinite(min_confidence))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_confidence must be finite, got %g", fn, (double)min_confidence);
+    if (int rc = check_finite_marker(invalid_disparity)) return rc;
+    if (image) {
+        if (image_channels != 1 && image_channels != 3)
+            return fail(SMX_ERR_INVALID_ARG, "%s: image_channels must be 1 or 3 with an image, got %d", fn, image_channels);
+        if (image_dtype != SMX_DTYPE_U8 && image_dtype != SMX_DTYPE_F32)
+            return fail(SMX_ERR_INVALID_ARG, "%s: unknown image dtype %d", fn, image_dtype);
+    } else if (colors) {
+        return fail(SMX_ERR_INVALID_ARG, "%s: colors needs an image", fn);
+    }
+    const size_t need = smx::reproject_workspace_bytes(n, H);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_reproject_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t px = (size_t)cap;
+    const size_t map_bytes = px * sizeof(float);
+    const size_t img_bytes = image ? px * image_channels * (image_dtype == SMX_DTYPE_F32 ? 4 : 1) : 0;
+    const void *ins[4] = {disp, confidence, image, workspace};
+    const size_t in_bytes[4] = {map_bytes, map_bytes, img_bytes, workspace_bytes};
+    void *outs[5] = {points, colors, indices, xyz_map, offsets};
+    const size_t out_bytes[5] = {px * 3 * sizeof(float), px * 3, px * sizeof(int32_t), px * 3 * sizeof(float),
+                                 ((size_t)n + 1) * sizeof(int32_t)};
+    for (int i = 0; i < 5; ++i) {
+        for (int j = 0; j < 4; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or the workspace", fn);
+        for (int j = i + 1; j < 5; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
+    }
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_reproject(n, H, W, disp, Q, confidence, min_confidence, z_min, z_max, invalid_disparity, image,
+                              image_channels, image_dtype == SMX_DTYPE_F32, points, colors, indices, xyz_map, offsets,
+                              workspace, (hipStream_t)stream);
+    });
+}
+
+static bool voxel_dims_ok(int n, int capacity) { return n >= 1 && n <= 65536 && capacity >= 1 && capacity <= SMX_POINTS_MAX; }
+
+size_t smx_voxel_workspace_bytes(int n, int capacity) {
+    return voxel_dims_ok(n, capacity) ? smx::voxel_workspace_bytes(n, capacity) : 0;
+}
+
+int smx_voxel_downsample(int device_id, int n, int capacity, const float *points, const uint8_t *colors,
+                         const int32_t *offsets, float voxel_size, int min_points, float *out_points,
+                         uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_voxel_downsample";
+    if (!points || !offsets || !out_points || !out_counts || !out_offsets || !dropped || !workspace)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: points, offsets, out_points, out_counts, out_offsets, dropped and workspace must be non-NULL", fn);
+    if ((colors == nullptr) != (out_colors == nullptr))
+        return fail(SMX_ERR_INVALID_ARG, "%s: colors and out_colors must be both NULL or both non-NULL", fn);
+    if (!voxel_dims_ok(n, capacity))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= n <= 65536 and 1 <= capacity <= 2^30 (got n %d, capacity %d)", fn,
+                    n, capacity);
+    if (!(std::isfinite(voxel_size) && voxel_size > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: voxel_size must be finite and > 0, got %g", fn, (double)voxel_size);
+    if (min_points < 1) return fail(SMX_ERR_INVALID_ARG, "%s: min_points must be >= 1, got %d", fn, min_points);
+    const size_t need = smx::voxel_workspace_bytes(n, capacity);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_voxel_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t cap = (size_t)capacity, offs = ((size_t)n + 1) * sizeof(int32_t);
+    const void *ins[4] = {points, colors, offsets, workspace};
+    const size_t in_bytes[4] = {cap * 3 * sizeof(float), cap * 3, offs, workspace_bytes};
+    void *outs[5] = {out_points, out_colors, out_counts, out_offsets, dropped};
+    const size_t out_bytes[5] = {cap * 3 * sizeof(float), cap * 3, cap * sizeof(int32_t), offs, (size_t)n * sizeof(int32_t)};
+    for (int i = 0; i < 5; ++i) {
+        for (int j = 0; j < 4; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or the workspace", fn);
+        for (int j = i + 1; j < 5; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
+    }
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&]() -> int {
+        SMX_HIP(smx::launch_voxel_downsample(n, capacity, points, colors, offsets, voxel_size, min_points, out_points,
+                                             out_colors, out_counts, out_offsets, dropped, workspace,
+                                             (hipStream_t)stream));
+        return SMX_OK;
+    });
+}
+
 }  // extern "C"

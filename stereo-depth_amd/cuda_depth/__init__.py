@@ -15,9 +15,11 @@ TORCH_CHECK failures do in the reference (stereo_matching.cc:13-15).
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
-from typing import Optional
+from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _native
@@ -1018,3 +1020,243 @@ class StereoMatching:
     def last_match_mode(self) -> str:
         code = LIB.smx_last_match_mode(self._handle)
         return {v: k for k, v in _native.MATCH_MODES.items()}[code]
+
+
+# ---- metric 3D point clouds ----------------------------------------------------------------------------------------------
+
+@dataclasses.dataclass
+class PointCloud:
+    """One map's point cloud; a field is None where it does not apply.  points: [N, 3] float32 (X, Y, Z in the units of
+    the reprojection matrix's baseline); colors: [N, 3] uint8 RGB (with an image); indices: [N] int32, the row-major pixel
+    index y * W + x of each point (reproject_to_3d); counts: [N] int32, the points per voxel (voxel_downsample);
+    xyz_map: [H, W, 3] float32, the organised cloud with NaN at the excluded pixels (reproject_to_3d(organized=True))."""
+    points: torch.Tensor
+    colors: Optional[torch.Tensor] = None
+    indices: Optional[torch.Tensor] = None
+    counts: Optional[torch.Tensor] = None
+    xyz_map: Optional[torch.Tensor] = None
+
+
+def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
+                        cx_right: Optional[float] = None) -> np.ndarray:
+    """The float32 4x4 Q of a rectified pair in OpenCV's reprojectImageTo3D convention, [X' Y' Z' W'] = Q [u v d 1]:
+        [[1, 0,     0,     -cx        ],
+         [0, fx/fy, 0,     -cy fx/fy  ],
+         [0, 0,     0,      fx        ],
+         [0, 0,     1/B,   (cx_right - cx)/B]]
+    so Z = fx B / (d + cx_right - cx), X = (u - cx) Z / fx, Y = (v - cy) Z / fy.  fy defaults to fx, cx_right (the right
+    camera's principal point) to cx; with Middlebury's doffs, cx_right = cx + doffs.  Units follow the baseline's.
+    Computed in float64, rounded once to float32."""
+    fy = fx if fy is None else fy
+    cx_right = cx if cx_right is None else cx_right
+    for name, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("baseline", baseline), ("cx_right", cx_right)):
+        _number_arg(name, v)
+        if not math.isfinite(v):
+            raise RuntimeError(f"{name} must be finite, got {v}")
+    if fx <= 0 or fy <= 0:
+        raise RuntimeError(f"fx and fy must be > 0, got {fx}, {fy}")
+    if baseline == 0:
+        raise RuntimeError("baseline must not be 0")
+    fx, fy, cx, cy, b, cxr = (float(v) for v in (fx, fy, cx, cy, baseline, cx_right))
+    q = np.array([[1.0, 0.0, 0.0, -cx],
+                  [0.0, fx / fy, 0.0, -cy * fx / fy],
+                  [0.0, 0.0, 0.0, fx],
+                  [0.0, 0.0, 1.0 / b, (cxr - cx) / b]], dtype=np.float64)
+    return q.astype(np.float32)
+
+
+def _check_q(Q) -> np.ndarray:
+    q = np.asarray(Q.detach().cpu() if isinstance(Q, torch.Tensor) else Q)
+    if q.shape != (4, 4) or not np.issubdtype(q.dtype, np.number):
+        raise RuntimeError(f"Q must be a numeric 4x4 matrix, got shape {q.shape}")
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    if not np.isfinite(q).all():
+        raise RuntimeError("Q must be finite (in float32)")
+    return q
+
+
+def _check_reproject_params(min_confidence, depth_range, invalid_disparity) -> Tuple[float, float]:
+    _number_arg("min_confidence", min_confidence)
+    if not math.isfinite(min_confidence):
+        raise RuntimeError(f"min_confidence must be finite, got {min_confidence}")
+    _number_arg("invalid_disparity", invalid_disparity)
+    if not math.isfinite(invalid_disparity):
+        raise RuntimeError(f"invalid_disparity must be finite (a NaN marker never compares equal), got {invalid_disparity}")
+    try:
+        z_min, z_max = depth_range
+    except (TypeError, ValueError):
+        raise TypeError("depth_range must be a pair (z_min, z_max)") from None
+    _number_arg("depth_range[0]", z_min)
+    _number_arg("depth_range[1]", z_max)
+    if math.isnan(z_min) or math.isnan(z_max) or z_min > z_max:
+        raise RuntimeError(f"depth_range must satisfy z_min <= z_max, got {depth_range}")
+    return float(z_min), float(z_max)
+
+
+def _check_colour_image(image: torch.Tensor, n: int, H: int, W: int, batched: bool, device) -> int:
+    """The number of channels (1 or 3) of a colour source for n maps of H x W."""
+    _check_input("image", image)
+    if image.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"image must be uint8 or float32, got {image.dtype}")
+    if image.device != device:
+        raise RuntimeError(f"image must be on {device}, got {image.device}")
+    lead = (n,) if batched else ()
+    shape = tuple(image.shape)
+    for ch, want in ((1, lead + (H, W)), (1, lead + (1, H, W)), (3, lead + (3, H, W))):
+        if shape == want:
+            return ch
+    raise RuntimeError(f"image must be {lead + (H, W)}, {lead + (1, H, W)} or {lead + (3, H, W)}, got {shape}")
+
+
+def reproject_to_3d_batched(disp: torch.Tensor, Q, *, image: Optional[torch.Tensor] = None,
+                            confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0,
+                            depth_range=(0.0, math.inf), invalid_disparity: float = -1.0, organized: bool = False,
+                            indices: bool = True):
+    """reproject_to_3d of n maps [n, H, W] without synchronising (smx_reproject_points, on the current stream): returns
+    (points [n H W, 3] f32, colors [n H W, 3] u8 or None, indices [n H W] int32 or None, offsets [n + 1] int32,
+    xyz_map [n, H, W, 3] f32 or None), fresh tensors padded to the capacity n H W; the points of map i are rows
+    offsets[i]..offsets[i+1] (device values) in row-major pixel order.  image: [n, H, W], [n, 1, H, W] (gray) or
+    [n, 3, H, W] (RGB), uint8 or float32."""
+    q = _check_q(Q)
+    z_min, z_max = _check_reproject_params(min_confidence, depth_range, invalid_disparity)
+    _check_input("disp", disp)
+    if disp.dtype != torch.float32 or disp.dim() != 3:
+        raise RuntimeError(f"disp must be float32 [n, H, W], got {disp.dtype} {tuple(disp.shape)}")
+    n, H, W = disp.shape
+    if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768 and n * H * W <= 2 ** 30):
+        raise RuntimeError(f"need n >= 1, 1 <= H, W <= 32768 and n * H * W <= 2^30, got {tuple(disp.shape)}")
+    if confidence is not None:
+        _check_like("confidence", confidence, torch.float32, disp.shape, disp.device)
+    channels = 0 if image is None else _check_colour_image(image, n, H, W, True, disp.device)
+    dev, cap = disp.device, n * H * W
+    points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    colors = None if image is None else torch.empty((cap, 3), dtype=torch.uint8, device=dev)
+    idx = torch.empty(cap, dtype=torch.int32, device=dev) if indices else None
+    xyz = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev) if organized else None
+    offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    ws_bytes = LIB.smx_reproject_workspace_bytes(n, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    qc = (C.c_float * 16)(*q.reshape(-1).tolist())
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    dtype = _native.DTYPE_F32 if image is not None and image.dtype == torch.float32 else _native.DTYPE_U8
+    check(LIB.smx_reproject_points(dev.index, n, H, W, disp.data_ptr(), qc, ptr(confidence), float(min_confidence),
+                                   z_min, z_max, float(invalid_disparity), ptr(image), channels, dtype,
+                                   points.data_ptr(), ptr(colors), ptr(idx), ptr(xyz), offsets.data_ptr(),
+                                   ws.data_ptr(), ws_bytes, _stream(dev.index)))
+    return points, colors, idx, offsets, xyz
+
+
+def reproject_to_3d(disp: torch.Tensor, Q, *, image: Optional[torch.Tensor] = None,
+                    confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0,
+                    depth_range=(0.0, math.inf), invalid_disparity: float = -1.0, organized: bool = False):
+    """Metric 3D points of a disparity map [H, W] (-> PointCloud) or of n maps [n, H, W] (-> a list of n PointClouds),
+    float32 on one GPU (smx_reproject_points; the rule is in include/stereo_mi355x.h).  Q: the 4x4 reprojection matrix
+    (reprojection_matrix(), helpers.kitti_calibration.reprojection_matrix, MiddleBuryStereoCameraCalibration.
+    reprojection_matrix()).  A pixel becomes a point where its disparity is finite and != invalid_disparity, W' > 0, the
+    point is finite, depth_range[0] <= Z <= depth_range[1] and, with a confidence map, confidence >= min_confidence.
+    image: the colour source, [H, W] / [1, H, W] (gray) or [3, H, W] (RGB) per map ([n, ...] for n maps), uint8 or float32
+    (rounded and clamped to 0..255).  The points keep row-major pixel order; PointCloud.indices holds their pixel indices;
+    organized=True adds PointCloud.xyz_map.  Runs on the current stream and SYNCHRONISES ONCE, to read the point counts;
+    reproject_to_3d_batched is the asynchronous form.  Returns new tensors."""
+    single = isinstance(disp, torch.Tensor) and disp.dim() == 2
+    if isinstance(disp, torch.Tensor) and disp.dim() not in (2, 3):
+        raise RuntimeError(f"disp must be [H, W] or [n, H, W], got {tuple(disp.shape)}")
+    if single:
+        _check_input("disp", disp)
+        H, W = disp.shape
+        if image is not None:
+            _check_colour_image(image, 1, H, W, False, disp.device)
+            image = image.unsqueeze(0)
+        if confidence is not None:
+            _check_like("confidence", confidence, torch.float32, disp.shape, disp.device)
+            confidence = confidence.unsqueeze(0)
+        disp = disp.unsqueeze(0)
+    points, colors, idx, offsets, xyz = reproject_to_3d_batched(
+        disp, Q, image=image, confidence=confidence, min_confidence=min_confidence, depth_range=depth_range,
+        invalid_disparity=invalid_disparity, organized=organized)
+    off = offsets.cpu().tolist()                                   # the one synchronisation
+    clouds = [PointCloud(points=points[a:b], colors=None if colors is None else colors[a:b], indices=idx[a:b],
+                         xyz_map=None if xyz is None else xyz[i])
+              for i, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+    return clouds[0] if single else clouds
+
+
+def _check_voxel_params(voxel_size, min_points) -> None:
+    _number_arg("voxel_size", voxel_size)
+    if not (math.isfinite(voxel_size) and voxel_size > 0):
+        raise RuntimeError(f"voxel_size must be finite and > 0, got {voxel_size}")
+    _int_arg("min_points", min_points)
+    if min_points < 1:
+        raise RuntimeError(f"min_points must be >= 1, got {min_points}")
+
+
+def voxel_downsample_batched(points: torch.Tensor, offsets: torch.Tensor, voxel_size: float, *,
+                             colors: Optional[torch.Tensor] = None, min_points: int = 1):
+    """voxel_downsample of a compacted batch without synchronising (smx_voxel_downsample, on the current stream).
+    points: [cap, 3] float32, colors: [cap, 3] uint8 or None, offsets: [n + 1] int32 on the same device (the points of
+    map i are rows offsets[i]..offsets[i+1]), e.g. reproject_to_3d_batched's.  Returns (points [cap, 3], colors or None,
+    counts [cap] int32, offsets [n + 1] int32, dropped [n] int32), fresh tensors padded to cap: map i's voxels are rows
+    offsets[i]..offsets[i+1] in ascending voxel-index order; dropped[i] counts its points outside the index range or in
+    voxels below min_points."""
+    _check_voxel_params(voxel_size, min_points)
+    _check_input("points", points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise RuntimeError(f"points must be float32 [cap >= 1, 3], got {points.dtype} {tuple(points.shape)}")
+    cap, dev = points.shape[0], points.device
+    if cap > 2 ** 30:
+        raise RuntimeError(f"at most 2^30 points, got {cap}")
+    _check_input("offsets", offsets)
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or not 2 <= offsets.shape[0] <= 65537 or offsets.device != dev:
+        raise RuntimeError(f"offsets must be int32 [n + 1] with 1 <= n <= 65536 on {dev}")
+    if colors is not None:
+        _check_like("colors", colors, torch.uint8, (cap, 3), dev)
+    n = offsets.shape[0] - 1
+    out_points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    out_colors = None if colors is None else torch.empty((cap, 3), dtype=torch.uint8, device=dev)
+    counts = torch.empty(cap, dtype=torch.int32, device=dev)
+    out_offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    dropped = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_bytes = LIB.smx_voxel_workspace_bytes(n, cap)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    check(LIB.smx_voxel_downsample(dev.index, n, cap, points.data_ptr(), None if colors is None else colors.data_ptr(),
+                                   offsets.data_ptr(), float(voxel_size), int(min_points), out_points.data_ptr(),
+                                   None if out_colors is None else out_colors.data_ptr(), counts.data_ptr(),
+                                   out_offsets.data_ptr(), dropped.data_ptr(), ws.data_ptr(), ws_bytes,
+                                   _stream(dev.index)))
+    return out_points, out_colors, counts, out_offsets, dropped
+
+
+def voxel_downsample(cloud_or_list, voxel_size: float, *, min_points: int = 1):
+    """One point per occupied voxel of a PointCloud (-> PointCloud) or of each cloud of a list (-> a list), on the
+    current stream (smx_voxel_downsample; the rule is in include/stereo_mi355x.h): the centroid of the voxel's points,
+    their mean colour (when every cloud has colours) and their number (PointCloud.counts), in ascending voxel-index
+    order; the voxel index is floor(coord / voxel_size) per axis.  Voxels with fewer than min_points points are dropped,
+    as are points whose index lies outside -2^20..2^20-1.  Deterministic: the same bits on every run and for a cloud
+    alone or in a list.  SYNCHRONISES ONCE, to read the voxel counts; voxel_downsample_batched is the asynchronous form."""
+    _check_voxel_params(voxel_size, min_points)
+    single = isinstance(cloud_or_list, PointCloud)
+    clouds = [cloud_or_list] if single else list(cloud_or_list)
+    if not clouds or not all(isinstance(c, PointCloud) for c in clouds):
+        raise TypeError("voxel_downsample takes a PointCloud or a non-empty list of PointClouds")
+    dev = clouds[0].points.device
+    for c in clouds:
+        _check_input("points", c.points)
+        if c.points.dtype != torch.float32 or c.points.dim() != 2 or c.points.shape[1] != 3 or c.points.device != dev:
+            raise RuntimeError(f"every cloud's points must be float32 [N, 3] on {dev}")
+    with_colors = all(c.colors is not None for c in clouds)
+    sizes = [c.points.shape[0] for c in clouds]
+    total = sum(sizes)
+    pad = 1 if total == 0 else 0                                   # the device call needs room for one point
+    points = torch.cat([c.points for c in clouds] + [torch.zeros((pad, 3), dtype=torch.float32, device=dev)])
+    colors = None
+    if with_colors:
+        for c in clouds:
+            _check_like("colors", c.colors, torch.uint8, (c.points.shape[0], 3), dev)
+        colors = torch.cat([c.colors for c in clouds] + [torch.zeros((pad, 3), dtype=torch.uint8, device=dev)])
+    offsets = torch.tensor(np.cumsum([0] + sizes), dtype=torch.int32).to(dev)
+    out_points, out_colors, counts, out_offsets, _ = voxel_downsample_batched(points, offsets, voxel_size,
+                                                                              colors=colors, min_points=min_points)
+    off = out_offsets.cpu().tolist()                               # the one synchronisation
+    result = [PointCloud(points=out_points[a:b], colors=None if out_colors is None else out_colors[a:b],
+                         counts=counts[a:b]) for a, b in zip(off[:-1], off[1:])]
+    return result[0] if single else result

@@ -139,6 +139,21 @@ EXPORTS = {
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
+    # metric 3D points: (n, H, W) -> workspace bytes; (device_id, n, H, W, disp, Q (host float32[16]), confidence,
+    # min_confidence, z_min, z_max, invalid_disparity, image, image_channels, image_dtype, points, colors, indices,
+    # xyz_map, offsets, workspace, workspace_bytes, stream)
+    "smx_reproject_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_reproject_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float),
+                                       C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    # voxel downsampling: (n, capacity) -> workspace bytes; (device_id, n, capacity, points, colors, offsets,
+    # voxel_size, min_points, out_points, out_colors, out_counts, out_offsets, dropped, workspace, workspace_bytes,
+    # stream)
+    "smx_voxel_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "smx_voxel_downsample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

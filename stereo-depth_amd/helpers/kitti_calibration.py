@@ -136,3 +136,16 @@ def velodyne_depth_map(calib_dir: str, velo_file_name: str, im_shape: Tuple[int,
         depth[row[first], col[first]] = zmin[multi]
     depth[depth < 0] = 0
     return depth
+
+
+def reprojection_matrix(calib_dir: str, cams: Tuple[int, int] = (2, 3)) -> np.ndarray:
+    """The float32 4x4 reprojection matrix Q (cuda_depth.reprojection_matrix) of a rectified camera pair from
+    calib_cam_to_cam.txt: fx, fy, cx, cy of P_rect_0<left>, cx_right of P_rect_0<right>, and the baseline
+    t_x / -f (right) - t_x / -f (left) in metres, so that the points are in the left rectified camera's frame."""
+    cal = read_calibration(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
+    pl = np.asarray(cal[f"P_rect_0{cams[0]}"], dtype=np.float64).reshape(3, 4)
+    pr = np.asarray(cal[f"P_rect_0{cams[1]}"], dtype=np.float64).reshape(3, 4)
+    baseline = pr[0, 3] / -pr[0, 0] - pl[0, 3] / -pl[0, 0]
+    import cuda_depth
+    return cuda_depth.reprojection_matrix(float(pl[0, 0]), float(pl[0, 2]), float(pl[1, 2]), float(baseline),
+                                          fy=float(pl[1, 1]), cx_right=float(pr[0, 2]))

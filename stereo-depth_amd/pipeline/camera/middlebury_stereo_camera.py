@@ -79,6 +79,13 @@ class MiddleBuryStereoCameraCalibration:
     def get_principal_point(self) -> Tuple[float, float]:
         return self.cx, self.cy
 
+    def reprojection_matrix(self) -> np.ndarray:
+        """The float32 4x4 reprojection matrix Q (cuda_depth.reprojection_matrix) from cam0, cam1 and baseline:
+        cx_right = cam1's principal point (= cx + doffs), so Z = f baseline / (d + doffs), in the baseline's units (mm)."""
+        import cuda_depth
+        return cuda_depth.reprojection_matrix(self.fx, self.cx, self.cy, float(self.baseline), fy=self.fy,
+                                              cx_right=float(self.cam1[0, 2]))
+
 
 def _decode_png(path: str) -> torch.Tensor:
     from PIL import Image

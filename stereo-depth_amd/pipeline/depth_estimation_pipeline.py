@@ -9,6 +9,7 @@ Same public surface as /root/reference/src/python/pipeline/depth_estimation_pipe
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Any, Optional, Tuple
 
 import torch
@@ -59,6 +60,10 @@ class DepthEstimationResult:
     left_image: torch.Tensor
     right_image: torch.Tensor
     disparity_map: torch.Tensor
+    # reprojection_matrix given: the map's metric cloud (cuda_depth.PointCloud, new tensors), coloured from left_image,
+    # voxel-downsampled with point_cloud_voxel_size > 0; None otherwise.  Keyword-only, so the positional order of the
+    # earlier fields (confidence_map fourth) is unchanged.
+    point_cloud: Optional["cuda_depth.PointCloud"] = dataclasses.field(default=None, kw_only=True)
     # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
     # None otherwise
     confidence_map: Optional[torch.Tensor] = None
@@ -111,7 +116,9 @@ class DepthEstimationPipeline:
                  temporal_decay: float = 0.8, temporal_max_diff: float = 1.0, temporal_max_weight: float = 8.0,
                  temporal_min_weight: float = 0.25,
                  rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
-                 sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0):
+                 sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0, reprojection_matrix=None,
+                 point_cloud_depth_range: Tuple[float, float] = (0.0, math.inf), point_cloud_voxel_size: float = 0.0,
+                 point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -129,9 +136,22 @@ class DepthEstimationPipeline:
         before matching and the pixels outside its left_valid mask become invalid_disparity (None: frames are taken as
         rectified).  sgm_paths / sgm_p1 / sgm_p2 / sgm_uniqueness: the tuning of the 'sgm' backend (4 or 8 paths,
         0 <= P1 <= P2 <= 191, uniqueness 0..99 percent, 0 = off), which matches at image_shape over min_disparity..
-        max_disparity with the same post-processing; checked whatever the backend."""
+        max_disparity with the same post-processing; checked whatever the backend.  reprojection_matrix /
+        point_cloud_depth_range / point_cloud_voxel_size / point_cloud_min_points / point_cloud_min_confidence: with a 4x4
+        reprojection matrix Q (cuda_depth.reprojection_matrix), the final map (after the temporal filter) is reprojected
+        to metric 3D points last (cuda_depth.reproject_to_3d: depth_range, and with confidence=True the confidence map
+        and min_confidence), coloured from the left frame it was computed on (the rectified one with rectification=),
+        then voxel-downsampled when point_cloud_voxel_size > 0 (cuda_depth.voxel_downsample with min_points), and
+        returned as DepthEstimationResult.point_cloud; None (the default) changes nothing."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
+        self._reprojection_matrix = None
+        if reprojection_matrix is not None:
+            self._reprojection_matrix = cuda_depth._check_q(reprojection_matrix)
+            cuda_depth._check_reproject_params(point_cloud_min_confidence, point_cloud_depth_range,
+                                               self._config.invalid_disparity)
+            if point_cloud_voxel_size != 0:
+                cuda_depth._check_voxel_params(point_cloud_voxel_size, point_cloud_min_points)
         sgm = dict(paths=sgm_paths, P1=sgm_p1, P2=sgm_p2, uniqueness=sgm_uniqueness)
         self._stereo_matching = _make_backend(self._config, sgm, speckle_max_size=speckle_max_size,
                                               speckle_max_diff=speckle_max_diff, fill_invalid=fill_invalid,
@@ -147,6 +167,10 @@ class DepthEstimationPipeline:
                                               temporal_max_weight=temporal_max_weight,
                                               temporal_min_weight=temporal_min_weight,
                                               rectification=rectification)
+        self._point_cloud_depth_range = point_cloud_depth_range
+        self._point_cloud_voxel_size = point_cloud_voxel_size
+        self._point_cloud_min_points = point_cloud_min_points
+        self._point_cloud_min_confidence = point_cloud_min_confidence
         print(f"Using '{self._config.stereo_matching_backend}' as stereo matching backend.")
 
     def reset_temporal(self) -> None:
@@ -172,5 +196,21 @@ class DepthEstimationPipeline:
         if rectified is not None:
             left_on_device, right_image = rectified
         confidence = getattr(self._stereo_matching, "confidence_map", lambda: None)()
+        cloud = None
+        if self._reprojection_matrix is not None:
+            cloud = self._point_cloud(disparity, left_on_device, confidence)
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
-                                     confidence_map=confidence)
+                                     confidence_map=confidence, point_cloud=cloud)
+
+    def _point_cloud(self, disparity: torch.Tensor, left: torch.Tensor,
+                     confidence: Optional[torch.Tensor]) -> "cuda_depth.PointCloud":
+        """The final map's cloud, coloured from `left` ([3, H, W] or [H, W]; other dtypes than uint8 as float32)."""
+        image = left if left.dtype in (torch.uint8, torch.float32) else left.float()
+        cloud = cuda_depth.reproject_to_3d(disparity, self._reprojection_matrix, image=image.contiguous(),
+                                           confidence=confidence, min_confidence=self._point_cloud_min_confidence,
+                                           depth_range=self._point_cloud_depth_range,
+                                           invalid_disparity=self._config.invalid_disparity)
+        if self._point_cloud_voxel_size > 0:
+            cloud = cuda_depth.voxel_downsample(cloud, self._point_cloud_voxel_size,
+                                                min_points=self._point_cloud_min_points)
+        return cloud

@@ -49,7 +49,8 @@ def run_depth_estimation_pipeline(camera: Camera, pipeline: DepthEstimationPipel
     for left_view, right_view in camera.stream_image_pairs():
         frame = pipeline.process(left_view, right_view)
         collected.append(DepthEstimationResult(left_image=frame.left_image, right_image=frame.right_image,
-                                               disparity_map=frame.disparity_map.clone()))
+                                               disparity_map=frame.disparity_map.clone(),
+                                               point_cloud=frame.point_cloud))
     return collected
 
 

@@ -1,7 +1,8 @@
 """Disparity -> depth -> point list on the device ("next" row f3): what the reference's
 PointCloudSaver computes before handing the points to Open3D
 (/root/reference/src/python/pipeline/depth_estimation_pipeline_hooks.py:84-92,
-helpers/point_cloud_helpers.py:5-13).  Writing .ply files (Open3D) is out of scope."""
+helpers/point_cloud_helpers.py:5-13), kept as the reference has it.  Metric, coloured clouds: cuda_depth.reproject_to_3d
+and cuda_depth.voxel_downsample; PLY files without Open3D: helpers/ply.py."""
 from __future__ import annotations
 
 import ctypes as C

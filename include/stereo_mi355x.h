@@ -30,6 +30,8 @@
  *                                                         smx_sgm_with_right_map
  *   -- (metric 3D points, coloured, compacted)            smx_reproject_points, smx_reproject_workspace_bytes
  *   -- (voxel-grid downsampling of those points)          smx_voxel_downsample, smx_voxel_workspace_bytes
+ *   -- (TSDF fusion of posed maps into a voxel volume)    smx_tsdf_integrate, smx_tsdf_integrate_workspace_bytes
+ *   -- (surface points of that volume, ordered)           smx_tsdf_extract_points, smx_tsdf_extract_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -683,6 +685,83 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
                          const int32_t *offsets, float voxel_size, int min_points, float *out_points,
                          uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- TSDF fusion ----------------------------------------------------------------------------------------------------
+ * A volume of nx * ny * nz voxels with edge s = voxel_size and origin o (host float[3]); voxel (i, j, k) has the linear
+ * index (k*ny + j)*nx + i and the centre g = (o_x + ((float)i + 0.5f)*s, o_y + ((float)j + 0.5f)*s,
+ * o_z + ((float)k + 0.5f)*s).  Its state is caller-owned device memory: tsdf [nz][ny][nx] f32, weight [nz][ny][nx] f32
+ * and, optionally, color [nz][ny][nx][4] u8 (R, G, B, 0: one aligned 32-bit word per voxel).  The empty state is all
+ * zero.  The camera frame is smx_reproject_points': x right, y down, z forward; the world frame is the caller's.
+ * Every step below is ONE float32 operation (no fused multiply-add, correctly rounded division and sqrtf), in the stated
+ * order, on every implementation.
+ *
+ * smx_tsdf_integrate: n maps disp [n][H][W] f32 with their poses world_to_camera [n][3][4] f32 (device, row-major),
+ * applied in order.  Q: host 4x4, as for smx_reproject_points; P: host 4x4, the projection [u' v' d' w'] = P [X Y Z 1]
+ * (the Python layer sets P = inv(Q), computed in float64 and rounded once to float32).
+ *   Pixel (px, py) of map f, u = (float)px, v = (float)py, d = disp[f][py][px], is accepted iff d is finite and
+ *   d != invalid_disparity; W' = ((Q30*u + Q31*v) + Q32*d) + Q33 > 0; Zm = Z'/W' is finite, with
+ *   Z' = ((Q20*u + Q21*v) + Q22*d) + Q23; z_min <= Zm <= z_max; and, with a confidence map, c >= min_confidence and
+ *   c > 0 (a NaN c excludes the pixel).  Its weight w is c, or 1.0f without a confidence map; its colour I is the
+ *   image's (gray [n][H][W] copied to R, G and B, or planar RGB [n][3][H][W]; u8, or f32 v ->
+ *   (uint8)clamp(floorf(v + 0.5f), 0, 255) with NaN -> 0), as a float per channel.
+ *   For each voxel, for f = 0 .. n-1 in order, with M = world_to_camera[f]:
+ *     c_r = ((M[r][0]*g_x + M[r][1]*g_y) + M[r][2]*g_z) + M[r][3]          r = 0, 1, 2
+ *     skip unless c_2 > 0
+ *     p_r = ((P[r][0]*c_0 + P[r][1]*c_1) + P[r][2]*c_2) + P[r][3]          r = 0, 1, 3
+ *     skip unless p_3 > 0
+ *     fu = floorf(p_0/p_3 + 0.5f), fv = floorf(p_1/p_3 + 0.5f)
+ *     skip unless 0 <= fu <= W-1 and 0 <= fv <= H-1 (compared as floats; NaN fails)
+ *     skip unless pixel ((int)fu, (int)fv) of map f is accepted
+ *     sdf = Zm - c_2; skip unless sdf >= -truncation
+ *     t = fminf(sdf / truncation, 1.0f)
+ *     T = ((T0*W0) + (t*w)) / (W0 + w);  W = fminf(W0 + w, max_weight)
+ *     C = ((C0*W0) + (I*w)) / (W0 + w) per channel, stored as (uint8)floorf(C + 0.5f) (C lies in [0, 255] for a finite
+ *         w; a NaN C, from an infinite confidence, stores 0), with a zero fourth byte
+ *   where T0, W0 and C0 are the voxel's values before the frame; frame f's result is frame f+1's input.  Hence a voxel
+ *   that no frame of the call measures is not written, and one call with n maps gives the same bits as n calls with
+ *   one map each.
+ * Two launches on `stream` (a caller's stream), no atomics, no host synchronisation and no allocation:
+ * graph-capturable.  workspace: smx_tsdf_integrate_workspace_bytes(n, H, W) bytes (12 per pixel; 0 for sizes the call
+ * rejects).
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL origin, tsdf, weight, disp, Q, P, world_to_camera or
+ * workspace; nx, ny or nz outside 1..4096 or nx*ny*nz > 2^30; n < 1, H or W outside 1..32768 or n*H*W > 2^30;
+ * voxel_size not finite and > 0; truncation not finite or <= voxel_size; max_weight not finite and > 0; a non-finite Q,
+ * P or origin entry; a NaN z bound or z_min > z_max; a non-finite min_confidence or invalid_disparity; color without an
+ * image; an image whose channels are not 1 or 3 or whose dtype is unknown; workspace_bytes below the query; a state
+ * array or the workspace overlapping an input or each other; stream == SMX_STREAM_ENGINE. */
+size_t smx_tsdf_integrate_workspace_bytes(int n, int H, int W);
+int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                       float truncation, float max_weight, float *tsdf, float *weight, uint8_t *color, int n, int H,
+                       int W, const float *disp, const float Q[16], const float P[16], const float *world_to_camera,
+                       const float *confidence, float min_confidence, float z_min, float z_max,
+                       float invalid_disparity, const void *image, int image_channels, int image_dtype,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_tsdf_extract_points: the zero crossings of a volume (smx_tsdf_integrate's state) as points.  Voxels are visited in
+ * ascending linear index and each voxel's axes in the order x, y, z.  For axis a and the neighbour v' = v + e_a inside
+ * the grid, a point is emitted iff weight[v] >= min_weight and weight[v'] >= min_weight, (T0 >= 0) != (T1 >= 0), and
+ * |T0| < 1 and |T1| < 1 (T0 = tsdf[v], T1 = tsdf[v']; the last condition rejects the false crossings between truncated
+ * free space and the space behind a surface at occlusion edges).  For an emitted point:
+ *   position  t = T0 / (T0 - T1); the point is g(v) with its a coordinate replaced by g_a(v) + t*s
+ *   normal    (normals != NULL) the central differences x_b = T[v+e_b] - T[v-e_b] for b = x, y, z, with indices clamped
+ *             to the grid, each divided by len = sqrtf((x_x*x_x + x_y*x_y) + x_z*x_z); len == 0 gives (0, 0, 0).  It
+ *             points toward positive T, i.e. toward the cameras.
+ *   colour    (colors != NULL; needs color) the R, G, B of v if t <= 0.5f, else those of v'
+ * Outputs: count (device int32) = the total number of crossings (saturated at 2^31 - 1); the first min(total, capacity)
+ * points in the order above to points [capacity][3] f32, normals [capacity][3] f32 and colors [capacity][3] u8; nothing
+ * past them is written.  Three steps on `stream` (a caller's stream): count per (k, j) row, an exclusive scan of the
+ * row counts, ordered scatter per row; no atomics, no host synchronisation, no allocation: graph-capturable.
+ * workspace: smx_tsdf_extract_workspace_bytes(nx, ny, nz) bytes (about 8 per row of x voxels; 0 for sizes the call
+ * rejects).
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL origin, tsdf, weight, points, count or workspace;
+ * the volume's dimension, voxel_size and origin checks of smx_tsdf_integrate; min_weight not finite and > 0; capacity
+ * outside 1..2^30; colors without color; workspace_bytes below the query; an output or the workspace overlapping an
+ * input or another output; stream == SMX_STREAM_ENGINE. */
+size_t smx_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                            const float *tsdf, const float *weight, const uint8_t *color, float min_weight,
+                            int capacity, float *points, float *normals, uint8_t *colors, int32_t *count,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -147,5 +147,24 @@ hipError_t launch_voxel_downsample(int n, int capacity, const float *points, con
                                    const int32_t *offsets, float voxel_size, int min_points, float *out_points,
                                    uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
                                    void *workspace, hipStream_t s);
+// exclusive scan of L ints, in -> out, in three launches; block_sums: scan_block_sums(L) ints of scratch; gate / pass:
+// a launch returns at once when gate != NULL and pass * 8 >= *gate (the radix passes of the downsampling)
+size_t scan_block_sums(long L);
+void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s);
+
+// ---- tu_tsdf.hip: TSDF fusion and surface extraction (k_tsdf.h) --------------------------------------------------------
+// q / p / origin: host values, copied into the kernel arguments; world_to_camera [n][3][4] on the device; conf / color /
+// image may be NULL (color needs image); arguments checked by smx_tsdf_integrate
+size_t tsdf_integrate_workspace_bytes(int n, int H, int W);
+void launch_tsdf_integrate(int nx, int ny, int nz, const float origin[3], float voxel_size, float truncation,
+                           float max_weight, float *tsdf, float *weight, uint8_t *color, int n, int H, int W,
+                           const float *disp, const float q[16], const float p[16], const float *world_to_camera,
+                           const float *conf, float min_conf, float zmin, float zmax, float invalid, const void *image,
+                           int channels, bool img_f32, void *workspace, hipStream_t s);
+// normals / colors NULL: not written (colors needs color); arguments checked by smx_tsdf_extract_points
+size_t tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+void launch_tsdf_extract(int nx, int ny, int nz, const float origin[3], float voxel_size, const float *tsdf,
+                         const float *weight, const uint8_t *color, float min_weight, int capacity, float *points,
+                         float *normals, uint8_t *colors, int32_t *count, void *workspace, hipStream_t s);
 
 }  // namespace smx

@@ -507,4 +507,135 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
     });
 }
 
+// ---- TSDF fusion -------------------------------------------------------------------------------------------------------
+static constexpr long SMX_TSDF_VOXELS_MAX = 1L << 30;
+
+static bool tsdf_dims_ok(int nx, int ny, int nz) {
+    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= 4096 && ny <= 4096 && nz <= 4096 &&
+           (long)nx * ny * nz <= SMX_TSDF_VOXELS_MAX;
+}
+
+// The volume's checks shared by both TSDF entries (after their NULL checks).
+static int check_tsdf_volume(const char *fn, int nx, int ny, int nz, const float origin[3], float voxel_size) {
+    if (!tsdf_dims_ok(nx, ny, nz))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= nx, ny, nz <= 4096 and nx * ny * nz <= 2^30 (got %d, %d, %d)", fn,
+                    nx, ny, nz);
+    if (!(std::isfinite(voxel_size) && voxel_size > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: voxel_size must be finite and > 0, got %g", fn, (double)voxel_size);
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(origin[k]))
+            return fail(SMX_ERR_INVALID_ARG, "%s: origin[%d] = %g is not finite", fn, k, (double)origin[k]);
+    return SMX_OK;
+}
+
+// An output (or the workspace) that overlaps an input or another output.
+static int check_disjoint(const char *fn, int NI, const void *const *ins, const size_t *in_bytes, int NO,
+                          void *const *outs, const size_t *out_bytes) {
+    for (int i = 0; i < NO; ++i) {
+        for (int j = 0; j < NI; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: an output or the workspace overlaps an input", fn);
+        for (int j = i + 1; j < NO; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
+                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs (state arrays, workspace) overlap", fn);
+    }
+    return SMX_OK;
+}
+
+size_t smx_tsdf_integrate_workspace_bytes(int n, int H, int W) {
+    if (!map_dims_ok(n, H, W) || (long)n * H * W > SMX_POINTS_MAX) return 0;
+    return smx::tsdf_integrate_workspace_bytes(n, H, W);
+}
+
+int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                       float truncation, float max_weight, float *tsdf, float *weight, uint8_t *color, int n, int H,
+                       int W, const float *disp, const float Q[16], const float P[16], const float *world_to_camera,
+                       const float *confidence, float min_confidence, float z_min, float z_max,
+                       float invalid_disparity, const void *image, int image_channels, int image_dtype,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_tsdf_integrate";
+    if (!origin || !tsdf || !weight || !disp || !Q || !P || !world_to_camera || !workspace)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: origin, tsdf, weight, disp, Q, P, world_to_camera and workspace must be non-NULL", fn);
+    if (int rc = check_tsdf_volume(fn, nx, ny, nz, origin, voxel_size)) return rc;
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    const long px = (long)n * H * W;
+    if (px > SMX_POINTS_MAX)
+        return fail(SMX_ERR_INVALID_ARG, "%s: n * H * W = %ld exceeds 2^30: split the batch", fn, px);
+    if (!(std::isfinite(truncation) && truncation > voxel_size))
+        return fail(SMX_ERR_INVALID_ARG, "%s: truncation must be finite and > voxel_size, got %g", fn, (double)truncation);
+    if (!(std::isfinite(max_weight) && max_weight > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: max_weight must be finite and > 0, got %g", fn, (double)max_weight);
+    for (int k = 0; k < 16; ++k) {
+        if (!std::isfinite(Q[k])) return fail(SMX_ERR_INVALID_ARG, "%s: Q[%d] = %g is not finite", fn, k, (double)Q[k]);
+        if (!std::isfinite(P[k])) return fail(SMX_ERR_INVALID_ARG, "%s: P[%d] = %g is not finite", fn, k, (double)P[k]);
+    }
+    if (std::isnan(z_min) || std::isnan(z_max) || z_min > z_max)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need z_min <= z_max, got %g, %g", fn, (double)z_min, (double)z_max);
+    if (!std::isfinite(min_confidence))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_confidence must be finite, got %g", fn, (double)min_confidence);
+    if (int rc = check_finite_marker(invalid_disparity)) return rc;
+    if (image) {
+        if (image_channels != 1 && image_channels != 3)
+            return fail(SMX_ERR_INVALID_ARG, "%s: image_channels must be 1 or 3 with an image, got %d", fn, image_channels);
+        if (image_dtype != SMX_DTYPE_U8 && image_dtype != SMX_DTYPE_F32)
+            return fail(SMX_ERR_INVALID_ARG, "%s: unknown image dtype %d", fn, image_dtype);
+    } else if (color) {
+        return fail(SMX_ERR_INVALID_ARG, "%s: a colour volume needs an image", fn);
+    }
+    const size_t need = smx::tsdf_integrate_workspace_bytes(n, H, W);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_tsdf_integrate_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t vox = (size_t)nx * ny * nz, map_bytes = (size_t)px * sizeof(float);
+    const size_t img_bytes = image ? (size_t)px * image_channels * (image_dtype == SMX_DTYPE_F32 ? 4 : 1) : 0;
+    const void *const ins[4] = {disp, confidence, image, world_to_camera};
+    const size_t in_bytes[4] = {map_bytes, map_bytes, img_bytes, (size_t)n * 12 * sizeof(float)};
+    void *const outs[4] = {tsdf, weight, color, workspace};
+    const size_t out_bytes[4] = {vox * sizeof(float), vox * sizeof(float), vox * 4, workspace_bytes};
+    if (int rc = check_disjoint(fn, 4, ins, in_bytes, 4, outs, out_bytes)) return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_integrate(nx, ny, nz, origin, voxel_size, truncation, max_weight, tsdf, weight, color, n, H, W,
+                                   disp, Q, P, world_to_camera, confidence, min_confidence, z_min, z_max,
+                                   invalid_disparity, image, image_channels, image_dtype == SMX_DTYPE_F32, workspace,
+                                   (hipStream_t)stream);
+    });
+}
+
+size_t smx_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {
+    return tsdf_dims_ok(nx, ny, nz) ? smx::tsdf_extract_workspace_bytes(nx, ny, nz) : 0;
+}
+
+int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                            const float *tsdf, const float *weight, const uint8_t *color, float min_weight,
+                            int capacity, float *points, float *normals, uint8_t *colors, int32_t *count,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_tsdf_extract_points";
+    if (!origin || !tsdf || !weight || !points || !count || !workspace)
+        return fail(SMX_ERR_INVALID_ARG, "%s: origin, tsdf, weight, points, count and workspace must be non-NULL", fn);
+    if (int rc = check_tsdf_volume(fn, nx, ny, nz, origin, voxel_size)) return rc;
+    if (!(std::isfinite(min_weight) && min_weight > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and > 0, got %g", fn, (double)min_weight);
+    if (capacity < 1 || capacity > SMX_POINTS_MAX)
+        return fail(SMX_ERR_INVALID_ARG, "%s: capacity must be in 1..2^30, got %d", fn, capacity);
+    if (colors && !color) return fail(SMX_ERR_INVALID_ARG, "%s: colors needs a colour volume", fn);
+    const size_t need = smx::tsdf_extract_workspace_bytes(nx, ny, nz);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_tsdf_extract_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t vox = (size_t)nx * ny * nz, cap = (size_t)capacity;
+    const void *const ins[3] = {tsdf, weight, color};
+    const size_t in_bytes[3] = {vox * sizeof(float), vox * sizeof(float), vox * 4};
+    void *const outs[5] = {points, normals, colors, count, workspace};
+    const size_t out_bytes[5] = {cap * 3 * sizeof(float), cap * 3 * sizeof(float), cap * 3, sizeof(int32_t),
+                                 workspace_bytes};
+    if (int rc = check_disjoint(fn, 3, ins, in_bytes, 5, outs, out_bytes)) return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_extract(nx, ny, nz, origin, voxel_size, tsdf, weight, color, min_weight, capacity, points,
+                                 normals, colors, count, workspace, (hipStream_t)stream);
+    });
+}
+
 }  // extern "C"

@@ -59,15 +59,16 @@ VoxLayout vox_layout(int n, int cap) {
     l.total = at;
     return l;
 }
+}  // namespace
 
-// exclusive scan of L ints, in -> out; gate / pass: see pass_skipped
+size_t scan_block_sums(long L) { return (size_t)((L + SCAN_TILE - 1) / SCAN_TILE); }
+
 void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s) {
     const int nb = (int)((L + SCAN_TILE - 1) / SCAN_TILE);
     hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(256), 0, s, in, L, block_sums, gate, pass);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, block_sums, nb, gate, pass);
     hipLaunchKernelGGL(k_scan_down, dim3(nb), dim3(256), 0, s, in, out, L, block_sums, gate, pass);
 }
-}  // namespace
 
 size_t voxel_workspace_bytes(int n, int cap) { return vox_layout(n, cap).total; }
 

@@ -1029,12 +1029,14 @@ class PointCloud:
     """One map's point cloud; a field is None where it does not apply.  points: [N, 3] float32 (X, Y, Z in the units of
     the reprojection matrix's baseline); colors: [N, 3] uint8 RGB (with an image); indices: [N] int32, the row-major pixel
     index y * W + x of each point (reproject_to_3d); counts: [N] int32, the points per voxel (voxel_downsample);
-    xyz_map: [H, W, 3] float32, the organised cloud with NaN at the excluded pixels (reproject_to_3d(organized=True))."""
+    xyz_map: [H, W, 3] float32, the organised cloud with NaN at the excluded pixels (reproject_to_3d(organized=True));
+    normals: [N, 3] float32 unit normals (TSDFVolume.extract_point_cloud(normals=True))."""
     points: torch.Tensor
     colors: Optional[torch.Tensor] = None
     indices: Optional[torch.Tensor] = None
     counts: Optional[torch.Tensor] = None
     xyz_map: Optional[torch.Tensor] = None
+    normals: Optional[torch.Tensor] = None
 
 
 def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
@@ -1260,3 +1262,207 @@ def voxel_downsample(cloud_or_list, voxel_size: float, *, min_points: int = 1):
     result = [PointCloud(points=out_points[a:b], colors=None if out_colors is None else out_colors[a:b],
                          counts=counts[a:b]) for a, b in zip(off[:-1], off[1:])]
     return result[0] if single else result
+
+
+# ---- TSDF fusion ---------------------------------------------------------------------------------------------------------
+
+def _host_matrices(name: str, a, lead_ok: bool) -> np.ndarray:
+    """A numeric [4, 4] or [n, 4, 4] array (numpy or tensor) as float64 [n, 4, 4]."""
+    m = np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a)
+    if not np.issubdtype(m.dtype, np.number):
+        raise RuntimeError(f"{name} must be numeric")
+    if m.shape == (4, 4):
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] != (4, 4) or m.shape[0] < 1 or (m.shape[0] > 1 and not lead_ok):
+        raise RuntimeError(f"{name} must be [4, 4] or [n, 4, 4], got shape {m.shape}")
+    return m.astype(np.float64)
+
+
+def projection_matrix(Q) -> np.ndarray:
+    """P = inv(Q) of a reprojection matrix, computed in float64 and rounded once to float32: [u' v' d' w'] = P [X Y Z 1]
+    projects a camera-frame point to its pixel (u'/w', v'/w') and disparity.  A singular Q raises RuntimeError."""
+    q = _check_q(Q).astype(np.float64)
+    try:
+        p = np.linalg.inv(q)
+    except np.linalg.LinAlgError:
+        raise RuntimeError("Q is singular: it has no projection") from None
+    p32 = p.astype(np.float32)
+    if not np.isfinite(p32).all() or np.linalg.matrix_rank(q) < 4:
+        raise RuntimeError("Q is singular: it has no projection")
+    return p32
+
+
+def world_to_camera_poses(camera_to_world) -> np.ndarray:
+    """[n, 3, 4] float32: the top rows of inv(pose) of camera-to-world poses [4, 4] / [n, 4, 4], inverted in float64 and
+    rounded once.  A pose that is not finite, is singular or whose last row is not [0, 0, 0, 1] raises RuntimeError."""
+    m = _host_matrices("camera_to_world", camera_to_world, True)
+    if not np.isfinite(m).all():
+        raise RuntimeError("camera_to_world must be finite")
+    if not np.array_equal(m[:, 3, :], np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (m.shape[0], 4))):
+        raise RuntimeError("camera_to_world's last row must be [0, 0, 0, 1]")
+    if (np.linalg.matrix_rank(m[:, :3, :3]) < 3).any():
+        raise RuntimeError("camera_to_world is singular")
+    inv = np.linalg.inv(m).astype(np.float32)
+    if not np.isfinite(inv).all():
+        raise RuntimeError("camera_to_world is singular")
+    return np.ascontiguousarray(inv[:, :3, :])
+
+
+def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], float, Tuple[float, float, float]]:
+    try:
+        nx, ny, nz = dims
+    except (TypeError, ValueError):
+        raise TypeError("dims must be (nx, ny, nz)") from None
+    for name, v in (("nx", nx), ("ny", ny), ("nz", nz)):
+        _int_arg(name, v)
+        if not 1 <= v <= 4096:
+            raise RuntimeError(f"{name} must be in 1..4096, got {v}")
+    if nx * ny * nz > 2 ** 30:
+        raise RuntimeError(f"at most 2^30 voxels, got {nx} * {ny} * {nz}")
+    _number_arg("voxel_size", voxel_size)
+    if not (math.isfinite(voxel_size) and voxel_size > 0):
+        raise RuntimeError(f"voxel_size must be finite and > 0, got {voxel_size}")
+    try:
+        o = tuple(origin)
+    except TypeError:
+        raise TypeError("origin must be (x, y, z)") from None
+    if len(o) != 3:
+        raise TypeError("origin must be (x, y, z)")
+    for v in o:
+        _number_arg("origin", v)
+        if not math.isfinite(v):
+            raise RuntimeError(f"origin must be finite, got {o}")
+    return (nx, ny, nz), float(voxel_size), tuple(float(v) for v in o)
+
+
+class TSDFVolume:
+    """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
+    include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points).  The volume has
+    dims = (nx, ny, nz) voxels of edge voxel_size, its corner at origin, in the caller's world frame; voxel (i, j, k) is
+    centred at origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size.  It owns the state: .tsdf and .weight float32
+    [nz, ny, nx], and with color=True .color uint8 [nz, ny, nx, 4] (R, G, B, 0).  truncation (default 3 * voxel_size,
+    must exceed voxel_size) is the band around each surface that a measurement updates; the weight of a voxel is capped at
+    max_weight, so older frames fade once it is reached.  Memory is fixed: 8 (12 with colour) bytes per voxel."""
+
+    def __init__(self, dims, voxel_size: float, origin, *, truncation: Optional[float] = None, max_weight: float = 64.0,
+                 color: bool = True, device=None):
+        self.dims, self.voxel_size, self.origin = _check_tsdf_volume(dims, voxel_size, origin)
+        truncation = 3.0 * self.voxel_size if truncation is None else truncation
+        _number_arg("truncation", truncation)
+        if not (math.isfinite(truncation) and np.float32(truncation) > np.float32(self.voxel_size)):
+            raise RuntimeError(f"truncation must be finite and > voxel_size, got {truncation}")
+        _number_arg("max_weight", max_weight)
+        if not (math.isfinite(max_weight) and max_weight > 0):
+            raise RuntimeError(f"max_weight must be finite and > 0, got {max_weight}")
+        if not isinstance(color, bool):
+            raise TypeError("color must be a bool")
+        device = torch.device("cuda") if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"TSDFVolume needs a GPU device, got {device}")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device, self.truncation, self.max_weight = device, float(truncation), float(max_weight)
+        nx, ny, nz = self.dims
+        self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.color = torch.zeros((nz, ny, nx, 4), dtype=torch.uint8, device=device) if color else None
+        self._capacity = min(3 * nx * ny * nz, 2 ** 30, max(4096, 2 * (nx * ny + ny * nz + nx * nz)))
+
+    def reset(self) -> None:
+        """Returns the volume to empty (every state value 0), on the current stream."""
+        self.tsdf.zero_()
+        self.weight.zero_()
+        if self.color is not None:
+            self.color.zero_()
+
+    def _origin(self):
+        return (C.c_float * 3)(*self.origin)
+
+    def integrate(self, disp: torch.Tensor, Q, camera_to_world, *, image: Optional[torch.Tensor] = None,
+                  confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0, depth_range=(0.0, math.inf),
+                  invalid_disparity: float = -1.0) -> None:
+        """Fuses n disparity maps float32 [H, W] or [n, H, W] (on the volume's device) taken with the cameras at
+        camera_to_world [4, 4] / [n, 4, 4] (numpy or tensor; x right, y down, z forward, as reproject_to_3d), in order, on
+        the current stream without synchronising.  Q: the maps' 4x4 reprojection matrix; its inverse, computed in float64,
+        projects voxels to pixels.  A pixel counts where reproject_to_3d would make it a point (with depth_range,
+        invalid_disparity and, given a confidence map [n, H, W], confidence >= min_confidence) and its confidence is
+        > 0; its weight is its confidence, or 1.  image: the colour source, [H, W] / [1, H, W] (gray) or [3, H, W]
+        (RGB) per map, uint8 or float32; required by a colour volume, ignored otherwise."""
+        q = _check_q(Q)
+        p = projection_matrix(q)
+        z_min, z_max = _check_reproject_params(min_confidence, depth_range, invalid_disparity)
+        w2c = world_to_camera_poses(camera_to_world)
+        _check_input("disp", disp)
+        if disp.dtype != torch.float32 or disp.dim() not in (2, 3) or disp.device != self.device:
+            raise RuntimeError(f"disp must be float32 [H, W] or [n, H, W] on {self.device}, got {disp.dtype} "
+                               f"{tuple(disp.shape)} on {disp.device}")
+        batched = disp.dim() == 3
+        n, H, W = disp.shape if batched else (1,) + tuple(disp.shape)
+        if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768 and n * H * W <= 2 ** 30):
+            raise RuntimeError(f"need n >= 1, 1 <= H, W <= 32768 and n * H * W <= 2^30, got {tuple(disp.shape)}")
+        if w2c.shape[0] != n:
+            raise RuntimeError(f"{n} map(s) need {n} pose(s), got {w2c.shape[0]}")
+        if confidence is not None:
+            _check_like("confidence", confidence, torch.float32, disp.shape, self.device)
+        channels = 0
+        if self.color is not None:
+            if image is None:
+                raise RuntimeError("a colour volume needs image= (or build the volume with color=False)")
+            channels = _check_colour_image(image, n, H, W, batched, self.device)
+        else:
+            image = None
+        poses = torch.from_numpy(w2c).pin_memory().to(self.device, non_blocking=True)
+        ws_bytes = LIB.smx_tsdf_integrate_workspace_bytes(n, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        qc = (C.c_float * 16)(*q.reshape(-1).tolist())
+        pc = (C.c_float * 16)(*p.reshape(-1).tolist())
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        dtype = _native.DTYPE_F32 if image is not None and image.dtype == torch.float32 else _native.DTYPE_U8
+        nx, ny, nz = self.dims
+        check(LIB.smx_tsdf_integrate(self.device.index, nx, ny, nz, self._origin(), self.voxel_size, self.truncation,
+                                     self.max_weight, self.tsdf.data_ptr(), self.weight.data_ptr(), ptr(self.color),
+                                     n, H, W, disp.data_ptr(), qc, pc, poses.data_ptr(), ptr(confidence),
+                                     float(min_confidence), z_min, z_max, float(invalid_disparity), ptr(image),
+                                     channels, dtype, ws.data_ptr(), ws_bytes, _stream(self.device.index)))
+
+    def extract_point_cloud_batched(self, capacity: int, *, min_weight: float = 1.0, normals: bool = True,
+                                    colors: bool = True):
+        """The surface points without synchronising (smx_tsdf_extract_points, on the current stream): returns
+        (points [capacity, 3] f32, normals [capacity, 3] f32 or None, colors [capacity, 3] u8 or None, count [1] int32),
+        fresh tensors of which the first min(count, capacity) rows are written."""
+        _int_arg("capacity", capacity)
+        if not 1 <= capacity <= 2 ** 30:
+            raise RuntimeError(f"capacity must be in 1..2^30, got {capacity}")
+        _number_arg("min_weight", min_weight)
+        if not (math.isfinite(min_weight) and min_weight > 0):
+            raise RuntimeError(f"min_weight must be finite and > 0, got {min_weight}")
+        dev = self.device
+        pts = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+        nrm = torch.empty((capacity, 3), dtype=torch.float32, device=dev) if normals else None
+        col = torch.empty((capacity, 3), dtype=torch.uint8, device=dev) if colors and self.color is not None else None
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        nx, ny, nz = self.dims
+        ws_bytes = LIB.smx_tsdf_extract_workspace_bytes(nx, ny, nz)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(LIB.smx_tsdf_extract_points(dev.index, nx, ny, nz, self._origin(), self.voxel_size, self.tsdf.data_ptr(),
+                                          self.weight.data_ptr(), ptr(self.color), float(min_weight), capacity,
+                                          pts.data_ptr(), ptr(nrm), ptr(col), count.data_ptr(), ws.data_ptr(),
+                                          ws_bytes, _stream(dev.index)))
+        return pts, nrm, col, count
+
+    def extract_point_cloud(self, min_weight: float = 1.0, normals: bool = True) -> PointCloud:
+        """The volume's surface as a PointCloud (points, unit normals toward the cameras with normals=True, colours of a
+        colour volume): one point per zero crossing of the tsdf between two neighbouring voxels that both have weight
+        >= min_weight and |tsdf| < 1, in ascending voxel order (the rule is in include/stereo_mi355x.h).  SYNCHRONISES
+        to read the count; a first capacity that was too small is retried once with the exact count."""
+        for attempt in range(2):
+            pts, nrm, col, count = self.extract_point_cloud_batched(self._capacity, min_weight=min_weight,
+                                                                    normals=normals)
+            total = int(count.item())                                   # the synchronisation
+            if total <= self._capacity or attempt == 1:
+                break
+            self._capacity = min(total, 2 ** 30)
+        total = min(total, self._capacity)
+        return PointCloud(points=pts[:total], colors=None if col is None else col[:total],
+                          normals=None if nrm is None else nrm[:total])

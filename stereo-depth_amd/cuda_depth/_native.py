@@ -154,6 +154,22 @@ EXPORTS = {
     "smx_voxel_downsample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    # TSDF fusion: (n, H, W) -> workspace bytes; (device_id, nx, ny, nz, origin (host float32[3]), voxel_size,
+    # truncation, max_weight, tsdf, weight, color, n, H, W, disp, Q, P (host float32[16]), world_to_camera, confidence,
+    # min_confidence, z_min, z_max, invalid_disparity, image, image_channels, image_dtype, workspace, workspace_bytes,
+    # stream)
+    "smx_tsdf_integrate_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_tsdf_integrate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float,
+                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    # surface extraction: (nx, ny, nz) -> workspace bytes; (device_id, nx, ny, nz, origin, voxel_size, tsdf, weight,
+    # color, min_weight, capacity, points, normals, colors, count, workspace, workspace_bytes, stream)
+    "smx_tsdf_extract_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_tsdf_extract_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

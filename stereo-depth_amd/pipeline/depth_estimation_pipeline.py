@@ -118,7 +118,8 @@ class DepthEstimationPipeline:
                  rectification: Optional["cuda_depth.StereoRectification"] = None, sgm_paths: int = 8,
                  sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0, reprojection_matrix=None,
                  point_cloud_depth_range: Tuple[float, float] = (0.0, math.inf), point_cloud_voxel_size: float = 0.0,
-                 point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0):
+                 point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0,
+                 tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -142,10 +143,23 @@ class DepthEstimationPipeline:
         to metric 3D points last (cuda_depth.reproject_to_3d: depth_range, and with confidence=True the confidence map
         and min_confidence), coloured from the left frame it was computed on (the rectified one with rectification=),
         then voxel-downsampled when point_cloud_voxel_size > 0 (cuda_depth.voxel_downsample with min_points), and
-        returned as DepthEstimationResult.point_cloud; None (the default) changes nothing."""
+        returned as DepthEstimationResult.point_cloud; None (the default) changes nothing.  tsdf_volume: a caller-owned
+        cuda_depth.TSDFVolume on the pipeline's device (needs reprojection_matrix); every process() call then takes a
+        camera_pose and integrates the final map into it, with point_cloud_depth_range, the confidence map and
+        point_cloud_min_confidence when confidence=True, and colour from the left frame the map was computed on."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
+        if tsdf_volume is not None:
+            if not isinstance(tsdf_volume, cuda_depth.TSDFVolume):
+                raise TypeError("tsdf_volume must be a cuda_depth.TSDFVolume")
+            if reprojection_matrix is None:
+                raise ValueError("tsdf_volume needs reprojection_matrix")
+            if tsdf_volume.device != torch.device("cuda", torch.cuda.current_device()):
+                raise ValueError(f"tsdf_volume must be on the pipeline's device cuda:{torch.cuda.current_device()}, "
+                                 f"got {tsdf_volume.device}")
+            cuda_depth.projection_matrix(reprojection_matrix)
+        self._tsdf_volume = tsdf_volume
         if reprojection_matrix is not None:
             self._reprojection_matrix = cuda_depth._check_q(reprojection_matrix)
             cuda_depth._check_reproject_params(point_cloud_min_confidence, point_cloud_depth_range,
@@ -180,13 +194,21 @@ class DepthEstimationPipeline:
     def get_configuration(self) -> DepthEstimationPipelineConfig:
         return self._config
 
-    def process(self, left_image: torch.Tensor, right_image: Optional[torch.Tensor] = None) -> DepthEstimationResult:
+    def process(self, left_image: torch.Tensor, right_image: Optional[torch.Tensor] = None, *,
+                camera_pose=None) -> DepthEstimationResult:
         """One frame.  The returned disparity map aliases the engine's persistent output buffer
         (stereo_matching.cc:42): clone it before processing the next frame if it must survive.  With rectification=,
         the result's left_image / right_image are the rectified frames the map was computed on (out_shape, same
         geometry as the map; persistent buffers too), not the raw frames passed in.  With confidence=True the result's
         confidence_map aliases a persistent buffer in the same way.  Frames are matched (and rectified) as uint8 when
-        both are uint8 and as float32 otherwise: a uint8 frame beside a float32 one is converted to float32 first."""
+        both are uint8 and as float32 otherwise: a uint8 frame beside a float32 one is converted to float32 first.
+        camera_pose: the left camera's camera-to-world pose [4, 4] for this frame, required with tsdf_volume and
+        refused without one; the final map is integrated into the volume on the current stream."""
+        if (camera_pose is None) != (self._tsdf_volume is None):
+            raise ValueError("camera_pose is required with tsdf_volume" if camera_pose is None
+                             else "camera_pose needs a pipeline with tsdf_volume")
+        if camera_pose is not None:
+            cuda_depth.world_to_camera_poses(camera_pose)
         if right_image is None:
             raise RuntimeError("right_image is required: right-view synthesis (Deep3D) is not part of this build.")
         left_on_device = left_image.cuda()
@@ -199,14 +221,19 @@ class DepthEstimationPipeline:
         cloud = None
         if self._reprojection_matrix is not None:
             cloud = self._point_cloud(disparity, left_on_device, confidence)
+        if self._tsdf_volume is not None:
+            self._tsdf_volume.integrate(disparity, self._reprojection_matrix, camera_pose,
+                                        image=self._colour_source(left_on_device), confidence=confidence,
+                                        min_confidence=self._point_cloud_min_confidence,
+                                        depth_range=self._point_cloud_depth_range,
+                                        invalid_disparity=self._config.invalid_disparity)
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
                                      confidence_map=confidence, point_cloud=cloud)
 
     def _point_cloud(self, disparity: torch.Tensor, left: torch.Tensor,
                      confidence: Optional[torch.Tensor]) -> "cuda_depth.PointCloud":
         """The final map's cloud, coloured from `left` ([3, H, W] or [H, W]; other dtypes than uint8 as float32)."""
-        image = left if left.dtype in (torch.uint8, torch.float32) else left.float()
-        cloud = cuda_depth.reproject_to_3d(disparity, self._reprojection_matrix, image=image.contiguous(),
+        cloud = cuda_depth.reproject_to_3d(disparity, self._reprojection_matrix, image=self._colour_source(left),
                                            confidence=confidence, min_confidence=self._point_cloud_min_confidence,
                                            depth_range=self._point_cloud_depth_range,
                                            invalid_disparity=self._config.invalid_disparity)
@@ -214,3 +241,9 @@ class DepthEstimationPipeline:
             cloud = cuda_depth.voxel_downsample(cloud, self._point_cloud_voxel_size,
                                                 min_points=self._point_cloud_min_points)
         return cloud
+
+    @staticmethod
+    def _colour_source(left: torch.Tensor) -> torch.Tensor:
+        """`left` ([3, H, W] or [H, W]) as a colour source: uint8 and float32 as they are, other dtypes as float32."""
+        image = left if left.dtype in (torch.uint8, torch.float32) else left.float()
+        return image.contiguous()

@@ -88,6 +88,16 @@ def two_level_sum(P: np.ndarray, starts: np.ndarray, cnt: np.ndarray) -> np.ndar
     return S
 
 
+def clamp_offsets(offsets, capacity):
+    """The caller's offsets as smx_voxel_downsample reads them: "clamped to a non-decreasing sequence in [0, capacity]",
+    each entry raised to the one before it (the first to 0), then lowered to the capacity."""
+    out, prev = [], 0
+    for o in offsets:
+        prev = min(max(int(o), prev), int(capacity))
+        out.append(prev)
+    return np.asarray(out, dtype=np.int64)
+
+
 def voxel_ref(points, colors, offsets, voxel_size, min_points=1):
     """points [cap, 3] f32, colors [cap, 3] u8 or None, offsets [n + 1].  Returns (points [V, 3] f32, colors [V, 3] u8 or
     None, counts [V] int32, offsets [n + 1] int64, dropped [n] int64)."""

@@ -163,6 +163,23 @@ def test_voxel_single_point_and_single_voxel():
     assert got[2].tolist() == [300] and got[3].tolist() == [0, 1]
 
 
+def test_clamp_offsets():
+    """The device's reading of the caller's offsets: non-decreasing, in [0, capacity]; valid offsets are kept as they
+    are."""
+    assert ref.clamp_offsets([0, 3, 3, 10], 10).tolist() == [0, 3, 3, 10]
+    assert ref.clamp_offsets([-5, 4, 2, 7, 6, 30], 20).tolist() == [0, 4, 4, 7, 7, 20]
+    assert ref.clamp_offsets([25, 30, 1], 20).tolist() == [20, 20, 20]             # all past the capacity: n empty maps
+    assert ref.clamp_offsets([5, 2 ** 31 - 1], 9).tolist() == [5, 9]
+    rng = np.random.default_rng(1)
+    for _ in range(50):
+        off = rng.integers(-100, 1200, rng.integers(2, 12))
+        c = ref.clamp_offsets(off, 1000)
+        assert c[0] == min(max(off[0], 0), 1000) and np.all(np.diff(c) >= 0) and 0 <= c.min() and c.max() <= 1000
+        # brute force: the smallest non-decreasing sequence in [0, cap] at or above the input, cut at the capacity
+        exp = np.minimum(np.maximum.accumulate(np.maximum(off, 0)), 1000)
+        assert np.array_equal(c, exp)
+
+
 def test_ply_round_trip(tmp_path):
     from helpers.ply import read_ply, write_ply
     rng = np.random.default_rng(2)

@@ -140,7 +140,8 @@ typedef struct smx_config {
                                    the filtered route -- a cheap pass over all disparities bounds which of them can hold the
                                    maximum, only those are evaluated in the reference's order, same bits, k_match_filter.h --
                                    while its candidate sets stay small; the dense kernel once a call reported that they cover
-                                   most of the range, as on real scenes; re-probed every 16..64 calls; smx_get_route_info),
+                                   most of the range, as on real scenes; re-probed every 16..64 calls of that kind -- RGB batches large
+                                   enough for the filtered route; other calls do not count; smx_get_route_info),
                                    1 = always filtered, -1 = always dense */
     int32_t  fp_convention;     /* smx_fp_convention, default SMX_FP_SOURCE */
     int32_t  reserved[3];       /* must be 0 */
@@ -273,13 +274,14 @@ int smx_build_features(void);
  * plan produces the same bits; the hints only pick the faster one for the content at hand.  Third hint: how many
  * disparities the sparse second pass of the fast kernel revisited per window (on-grid batches, min_disparity = 0): above
  * ~0.10 of the range the engine switches to the pass that keeps the winner's neighbours as it goes (fast_dense), probing the
- * sparse form every 16..64 calls and returning below ~0.07.  Single frames whose
+ * sparse form every 16..64 calls of that kind (calls whose launch plan has a dense form and whose sparse form reports;
+ * calls of any other kind neither count nor take a probe) and returning below ~0.07.  Single frames whose
  * launch plan is the latency shape with 12-row bands follow the same state. */
 typedef struct smx_route_info {
     int32_t filter_available;    /* the configuration admits the filtered exact-order route                   */
     int32_t route_dense;         /* 1: off-grid batches currently take the dense exact-order kernel           */
     int32_t last_call_filtered;  /* decision taken for the most recent call (1 also while probing)            */
-    int32_t probe_period;        /* calls between probes of the filtered route while route_dense              */
+    int32_t probe_period;        /* calls that can take the filtered route between its probes while route_dense */
     float   candidate_density;   /* evaluated / possible disparity slices of the last reported filtered launch, -1: none yet */
     int32_t offgrid_hint;        /* the last reported single f32 gray call was off (1) / on (0) the exact grid; -1: no report yet */
     int32_t compute_units;       /* multiProcessorCount the launch plans are sized against                    */

@@ -31,6 +31,7 @@
 #include "k_refine.h"
 #include "smx_common.h"
 #include "smx_launch.h"
+#include "smx_route.h"
 #include "smx_status.h"
 
 namespace {
@@ -68,72 +69,7 @@ int compute_dims(const smx_config *c, smx_dims *d) {
 
 }  // namespace
 
-// Pinned host words the kernels write without any synchronisation (system-scope stores): hints for the NEXT calls'
-// launch plans, never dependencies -- every plan gives the same bits, only the time differs.
-struct HostHints {
-    unsigned long long filter_density[2];   // per stream lane: (seq << 32) | float bits: candidate density of the last filtered launch
-    unsigned long long grid;                // (epoch << 1) | pair 0 of that call was off the exact grid (k_refine_auto)
-    unsigned long long fast_density[2];     // per stream lane: (seq << 32) | float bits: second-pass marches / first-pass marches of the last sparse fast launch
-};
-
-// A launch-plan choice between a default and an alternative route that follows what earlier calls' kernels reported through
-// one HostHints word per stream lane.  Above `hi` the engine takes the alternative and probes the default route every
-// `period` calls (16, doubling to 64 while the probes keep failing); below `lo` it comes back.  A forced choice is the
-// caller's business: it does not call decide(), so the countdown stands still, and reports are observed all the same.
-struct ContentSwitch {
-    static constexpr int LANES = 2;               // one report word per stream lane (smx_engine::LANES)
-    float hi, lo;
-    bool on = false;                              // the alternative is the current choice
-    int period = 16, countdown = 0;
-    bool pending = false;                         // a probe call has been issued and its report has not been evaluated yet
-    unsigned seq = 0, seen[LANES] = {0, 0};       // last sequence number handed to a launch / seen per lane
-    float last = -1.f;                            // the last observation, -1: none yet
-
-    // Takes the reports that have arrived by now (no synchronisation: whatever has arrived, has arrived).  The two halves
-    // of a split call report separately: they are ONE observation.  Returns whether anything was fresh.
-    bool observe(const unsigned long long (&words)[LANES]) {
-        float sum = 0.f;
-        int fresh = 0;
-        for (int k = 0; k < LANES; ++k) {
-            const unsigned long long w = *(const volatile unsigned long long *)&words[k];
-            const unsigned sq = (unsigned)(w >> 32);
-            if (sq == 0 || sq == seen[k]) continue;
-            seen[k] = sq;
-            const unsigned bits = (unsigned)(w & 0xffffffffull);
-            float v;
-            std::memcpy(&v, &bits, sizeof(v));
-            sum += v;
-            fresh++;
-        }
-        if (!fresh) return false;
-        last = sum / (float)fresh;
-        if (!on && last > hi) {
-            on = true;
-            period = 16;
-            countdown = period;
-        } else if (on && last < lo) {
-            on = false;
-        } else if (on && pending && period < 64) {   // a probe that failed: look again later (once per probe,
-            period *= 2;                              // however many reports its halves send, whenever they arrive)
-        }
-        pending = false;
-        return true;
-    }
-    // The route of the call being enqueued: true = the alternative.  While `on`, every period-th call is a probe: it takes
-    // the default route, which reports what it found.
-    bool decide() {
-        if (!on) return false;
-        if (--countdown > 0) return true;
-        countdown = period;
-        pending = true;
-        return false;
-    }
-    // Sequence number for the next reporting launch (0 means "nothing reported").
-    unsigned next_seq() {
-        if (++seq == 0) seq = 1;
-        return seq;
-    }
-};
+using smx::HostHints, smx::ContentSwitch, smx::LaneLedger;   // smx_route.h: the host state machines of enqueue()
 
 struct smx_engine {
     smx_config cfg;
@@ -179,24 +115,10 @@ struct smx_engine {
     int opt_fast_dense_small = -1;                // SMX_FAST_DENSE_SMALL=1 / 0: the latency shape at 12-row bands always / never takes its dense form (tests, A/B); -1: by content
     bool opt_debug_hints = false;                 // SMX_DEBUG_HINTS: print every report of the sparse fast kernel to stderr
     HostHints *hints = nullptr, *hints_dev = nullptr;     // pinned host memory / its device address
-    // Content-aware route of off-grid (RGB) batches.  The filtered route pays a fixed filter pass to evaluate fewer
-    // disparities in exact order; on real scenes (flat cost curves in untextured and occluded regions) the candidate
-    // sets cover most of the range and the dense kernel alone is faster.  The sparse kernel reports the density of
-    // every filtered launch (hints->filter_density); filt.on: the dense route.
-    // Break-even density, measured (profiles/r03_rgb_routes.txt, 32 pairs per call): the filter's two passes cost 0.89-0.93 ms,
-    // the sparse kernel 0.19 ms + 1.1 x density x the dense kernel's 2.24-2.7 ms: the routes tie at a density of 0.45 (C5,
-    // 96 disparities) to 0.56 (the reference's pair at its calibrated range, which reports 0.65 and loses 12 % filtered).
-    ContentSwitch filt{0.50f, 0.40f};             // hi, lo
+    smx::RouteState route;                        // the content switches (route.filt: filtered / dense exact-order route of RGB batches; route.fast:
+                                                  // sparse / dense form of the fast kernel) and the grid hint, with their per-call decision step
     unsigned *stats_dev = nullptr;                // [LANES][2] counters of the sparse kernel
     bool call_use_filter = true;                  // decision for the call being enqueued (both halves alike)
-    // Form of the fast kernel by content: the sparse form reports which share of the disparities its second pass revisited
-    // (hints->fast_density; banded surfaces 0.05, scene-like 0.17, real texture / noise ~1); fast.on: the dense form.
-    // Measured per 64 C2 pairs (tools/content_breakdown.py, SMX_DEBUG_HINTS=1): the sparse form takes 0.68 ms at a ratio of 0.047
-    // (banded surfaces), 0.85 at 0.166 (scene-like ramp) and 1.20 at 0.97 (noise) -- the first marches of the second pass are the
-    // expensive ones, they deliver to many rows -- the dense form 0.80 ms whatever the content: the curves cross near 0.13.
-    // (The latency shape's curves cross lower -- its dense form costs a banded C2 frame 0.3 us and saves a scene-like one 8 -- and
-    // its windows are 12 rows, not 27: the same ramp reports 0.133 there.  One pair of thresholds a little below the crossing.)
-    ContentSwitch fast{0.10f, 0.07f};             // hi, lo
     unsigned long long *fast_stats_dev = nullptr; // [LANES] device counters of the sparse form's report
     bool call_fast_dense = false;                 // decision for the call being enqueued
     bool fast_stats_pending = false;              // the aggregation launch of the half being enqueued reports: its fill launch publishes
@@ -223,13 +145,7 @@ struct smx_engine {
     bool caller_tail_live = false;                // ... recorded and not yet waited for by the lanes
     bool caller_calls_unrecorded = false;         // calls on caller streams made before the lanes (and ev_caller) existed
     hipStream_t last_caller_stream = nullptr;     // ... the stream of the last of them
-    int hull_lo[LANES] = {}, hull_hi[LANES] = {}; // pairs [lo, hi) lane k has worked on since the other lane last waited for it
-    // ... and the caller's output bytes lane k has written since then: two calls whose `out` ranges overlap are ordered
-    // (the later call wins, as on one stream), everything else runs side by side.  Disjoint ranges are kept apart (a
-    // hull would make a ring of output buffers look like one range); more than OUT_RANGES_MAX of them synchronise the lanes.
-    struct OutRange { uintptr_t lo, hi; };
-    static constexpr size_t OUT_RANGES_MAX = 32;
-    std::vector<OutRange> out_live[LANES];
+    LaneLedger ledger;                            // what each lane has in flight that the other has not been ordered behind
     bool detached_pending = false;                // SMX_STREAM_ENGINE calls not yet joined into a caller stream
     int overlap_min = 0;
     // Left-right check (smx_compute_lr_*): the packed inputs of the 2n internal pairs, in the entry's own format, and
@@ -239,7 +155,7 @@ struct smx_engine {
     size_t lr_pair_bytes = 0;
     float *lr_raw = nullptr;                      // [B][H][W]
 };
-static_assert(ContentSwitch::LANES == smx_engine::LANES, "one report word per stream lane");
+static_assert(ContentSwitch::LANES == smx_engine::LANES && LaneLedger::LANES == smx_engine::LANES, "one report word and one ledger entry per stream lane");
 
 namespace {
 
@@ -307,25 +223,41 @@ bool env_is(const char *name, char c) {
 // fetching them in a sparse second pass; min_disparity = 0 only), and -- for the sparse form -- where its second pass reports
 // how much it revisited.  Both shapes that have a dense form follow the same per-call decision (call_fast_dense): the
 // throughput shape (batches) and the latency shape at 12-row bands (single frames).
+struct FastForm {
+    bool has_dense;     // the launch plan of these n pairs has a dense form at all
+    bool tall12;        // ... it is the latency shape at 12-row bands
+    bool reports;       // its sparse form would sample the launch and publish hints->fast_density
+    int stride;         // ... of every stride-th pair
+};
+FastForm fast_form_of(const smx_engine *e, const smx::MatchParams &mp, int n) {
+    FastForm f{};
+    if (mp.pass1_only || mp.Dd > smx::FA_BITWORDS * 32) return f;
+    const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
+    f.tall12 = pl.small && pl.th == smx::FA_TH_SMALL_TALL;
+    if (pl.small && !f.tall12) return f;                    // 8- / 10-row bands: no dense form
+    f.has_dense = true;
+    if (f.tall12 && e->opt_fast_dense_small == 1) return f; // (always dense: never reports)
+    if (!e->fast_stats_dev || !e->hints_dev || e->opt_fast_dense >= 0) return f;
+    // a sample of the launch reports: at most four pairs, and only if their waves fit the counter's 16-bit fields
+    f.stride = n > 4 ? (n + 3) / 4 : 1;
+    const long wgs_pair = f.tall12 ? (long)((mp.w + smx::FA_VALID - 1) / smx::FA_VALID) * ((mp.h + pl.th - 1) / pl.th)      // (an upper bound of the reports per pair)
+                                   : (long)((mp.w + smx::FA_VALID * smx::FA_WAVES - 1) / (smx::FA_VALID * smx::FA_WAVES)) * ((mp.h + 23) / 24) * smx::FA_WAVES;
+    if (((n + f.stride - 1) / f.stride) * wgs_pair >= (1L << 23)) return f;   // (the counter's 24-bit window field)
+    f.reports = true;
+    return f;
+}
 void plan_fast_form(smx_engine *e, smx::MatchParams &mp, int n) {
     mp.dense = mp.dense_small = 0;
-    if (mp.pass1_only || mp.Dd > smx::FA_BITWORDS * 32) return;
-    const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
-    const bool tall12 = pl.small && pl.th == smx::FA_TH_SMALL_TALL;
-    if (pl.small && !tall12) return;                        // 8- / 10-row bands: no dense form
-    const bool dense = tall12 && e->opt_fast_dense_small >= 0 ? e->opt_fast_dense_small == 1 : e->call_fast_dense;
+    const FastForm f = fast_form_of(e, mp, n);
+    if (!f.has_dense) return;
+    const bool dense = f.tall12 && e->opt_fast_dense_small >= 0 ? e->opt_fast_dense_small == 1 : e->call_fast_dense;
     if (dense) {
-        (tall12 ? mp.dense_small : mp.dense) = 1;
+        (f.tall12 ? mp.dense_small : mp.dense) = 1;
         return;
     }
-    if (!e->fast_stats_dev || !e->hints_dev || e->opt_fast_dense >= 0) return;
-    // a sample of the launch reports: at most four pairs, and only if their waves fit the counter's 16-bit fields
-    const int stride = n > 4 ? (n + 3) / 4 : 1;
-    const long wgs_pair = tall12 ? (long)((mp.w + smx::FA_VALID - 1) / smx::FA_VALID) * ((mp.h + pl.th - 1) / pl.th)      // (an upper bound of the reports per pair)
-                                 : (long)((mp.w + smx::FA_VALID * smx::FA_WAVES - 1) / (smx::FA_VALID * smx::FA_WAVES)) * ((mp.h + 23) / 24) * smx::FA_WAVES;
-    if (((n + stride - 1) / stride) * wgs_pair >= (1L << 23)) return;       // (the counter's 24-bit window field)
+    if (!f.reports) return;
     mp.fast_stats = e->fast_stats_dev + e->cur_lane;
-    mp.fast_stride = stride;
+    mp.fast_stride = f.stride;
     e->fast_stats_pending = true;            // ... published by this call's fill launch (enqueue_range)
 }
 
@@ -402,12 +334,60 @@ bool stream_capturing(hipStream_t s) {
 // call follow: the two content switches and the grid hint.
 void read_hints(smx_engine *e) {
     if (!e->hints) return;
-    e->filt.observe(e->hints->filter_density);
-    const bool was_dense = e->fast.on;
-    if (e->fast.observe(e->hints->fast_density) && e->opt_debug_hints)
-        std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", e->fast.last, was_dense ? 1 : 0);
-    const unsigned long long g = *(volatile unsigned long long *)&e->hints->grid;
-    e->call_grid_hint = g == 0ull ? -1 : (int)(g & 1ull);      // (the word carries the call counter, which starts at 1: 0 = nothing reported)
+    const bool was_dense = e->route.fast.on;
+    if (e->route.read_hints(*e->hints) && e->opt_debug_hints)
+        std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", e->route.fast.last, was_dense ? 1 : 0);
+    e->call_grid_hint = e->route.grid_hint;
+}
+
+// The aggregation kernel(s) a call of this entry enqueues: SMX_MATCH_EXACT_ORDER, SMX_MATCH_FAST_GRID, or SMX_MATCH_AUTO
+// when both are enqueued and the device-side grid flag selects.
+int call_match_mode(const smx_engine *e, int in_mode) {
+    int mode = e->cfg.match_mode;
+    if (e->vol) mode = SMX_MATCH_EXACT_ORDER;
+    if (mode == SMX_MATCH_AUTO) {
+        if (!e->fast_ok_host) mode = SMX_MATCH_EXACT_ORDER;
+        else if (in_mode == smx::IN_GRAY_U8) mode = SMX_MATCH_FAST_GRID;   // u8 is on the grid
+        // gray computed from RGB (0.2989 R + 0.5870 G + 0.1140 B in float32) is practically never on the
+        // grid, not even for R = G = B: do not enqueue the fast kernel as a gated alternative at all (the
+        // exact-order kernel is correct for any input, so this is a launch saved, never a different result)
+        else if (in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8) mode = SMX_MATCH_EXACT_ORDER;
+    }
+    return mode;
+}
+
+// The plan-relevant fields of a call's aggregation launches (enqueue_range fills in the buffers).
+smx::MatchParams plan_params(const smx_engine *e) {
+    const smx_dims &d = e->dm;
+    smx::MatchParams mp{};
+    mp.B = e->B; mp.h = d.h; mp.w = d.w; mp.dmin = d.dmin; mp.Dd = d.Dd;
+    mp.on_lanes = e->call_on_lanes ? 1 : 0;
+    mp.pass1_only = e->capture ? 1 : 0;
+    return mp;
+}
+// The filtered exact-order route serves a range of n pairs of this call (when the call's decision is "filtered").
+bool filter_serves(const smx_engine *e, int mode, bool rgb_in, bool small) {
+    return mode == SMX_MATCH_EXACT_ORDER && e->filter_ok && rgb_in && !small && e->default_radii;
+}
+
+// Which of the two content switches a call can report to on its default route, from the launch plans of its range(s)
+// (n1 = 0: an unsplit call).  A switch follows, and is probed by, calls of its own kind only.
+smx::CallKind call_kind(const smx_engine *e, int in_mode, int n0, int n1) {
+    smx::CallKind k{};
+    if (e->cfg.match_mode == SMX_MATCH_FAST_GRID && (!e->fast_ok_host || e->vol)) return k;     // (refused by enqueue_range)
+    const int mode = call_match_mode(e, in_mode);
+    const bool rgb_in = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
+    const smx::MatchParams mp = plan_params(e);
+    for (int n : {n0, n1}) {
+        if (n < 1) continue;
+        if (mode == SMX_MATCH_EXACT_ORDER) {
+            const bool small = smx::match_fast_plan(mp, n, e->cus).small;
+            if (filter_serves(e, mode, rgb_in, small) && e->stats_dev && e->hints_dev) k.filter_reports = true;
+        } else if (fast_form_of(e, mp, n).reports) {
+            k.fast_reports = true;
+        }
+    }
+    return k;
 }
 
 // The 9 steps of stereo_matching.cc:22-43 as 4 (AUTO: 5) launches on stream `s`, for the n pairs that start
@@ -461,15 +441,7 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     if (v.vol && mode == SMX_MATCH_FAST_GRID)
         return fail(SMX_ERR_UNSUPPORTED, "SMX_MATCH_FAST_GRID cannot serve min_disparity/K > disparity count or "
                                          "non-default radii with min_disparity > 0 (aggregated volume needed)");
-    if (v.vol) mode = SMX_MATCH_EXACT_ORDER;
-    if (mode == SMX_MATCH_AUTO) {
-        if (!e->fast_ok_host) mode = SMX_MATCH_EXACT_ORDER;
-        else if (in_mode == smx::IN_GRAY_U8) mode = SMX_MATCH_FAST_GRID;   // u8 is on the grid
-        // gray computed from RGB (0.2989 R + 0.5870 G + 0.1140 B in float32) is practically never on the
-        // grid, not even for R = G = B: do not enqueue the fast kernel as a gated alternative at all (the
-        // exact-order kernel is correct for any input, so this is a launch saved, never a different result)
-        else if (in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8) mode = SMX_MATCH_EXACT_ORDER;
-    }
+    mode = call_match_mode(e, in_mode);
     // dmin > 0 (capture route): the match kernels stop after the arg-max; a sparse second kernel looks up the
     // three aggregated costs step 6 reads (k_match_capture.h; the workgroup that owns pixel 0 of a pair evaluates that pixel's
     // out-of-range lookups directly, k_capture_pixel0.h)
@@ -484,7 +456,7 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     };
     const bool rgb_in = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
     const bool small = smx::match_fast_plan(mp, n, e->cus).small;
-    if (mode == SMX_MATCH_EXACT_ORDER && e->filter_ok && rgb_in && !small && e->default_radii && e->call_use_filter) {
+    if (filter_serves(e, mode, rgb_in, small) && e->call_use_filter) {
         // the filtered route (k_match_filter.h): a cheap pass over all disparities on the inputs rounded to the grid marks,
         // per exact-order tile, the disparities that can still hold the maximum; only those are evaluated in the
         // reference's order.  Pairs whose gray leaves [0, 255] (f32 RGB only; flag from the prologue) take the dense kernel.
@@ -507,7 +479,7 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
         const int lane = e->cur_lane;
         smx::launch_exact2_sparse(e->xp, mp, n, v.cand, e->cand_cw, (const int *)v.flags2,
                                   e->stats_dev ? e->stats_dev + 2 * lane : nullptr,
-                                  e->hints_dev ? &e->hints_dev->filter_density[lane] : nullptr, e->filt.next_seq(), s);
+                                  e->hints_dev ? &e->hints_dev->filter_density[lane] : nullptr, e->route.filt.next_seq(), s);
         if (e->capture) smx::launch_exact2_capture(e->xp, mp, n, false, e->cus, s);   // dmin > 0: the lookups of step 6
     } else if (mode == SMX_MATCH_EXACT_ORDER) {
         SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
@@ -590,7 +562,7 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     if (e->fast_stats_pending && e->hints_dev) {
         fp.fast_stats = e->fast_stats_dev + e->cur_lane;
         fp.fast_stats_host = &e->hints_dev->fast_density[e->cur_lane];
-        fp.fast_seq = e->fast.next_seq();
+        fp.fast_seq = e->route.fast.next_seq();
         fp.fast_pass1 = (d.Dd + 1) / 2;
     }
     e->fast_stats_pending = false;
@@ -736,55 +708,27 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     e->call_on_lanes = detached;
     // launch plans that depend on what earlier calls saw (hints only: every plan gives the same bits)
     read_hints(e);
-    // (a forced choice -- SMX_FAST_DENSE, exact_filter = 1 / -1 -- leaves its switch's countdown alone)
-    e->call_fast_dense = e->opt_fast_dense >= 0 ? e->opt_fast_dense == 1 : e->fast.decide();
-    e->call_use_filter = e->cfg.exact_filter == 0 ? !e->filt.decide() : e->cfg.exact_filter > 0;
+    const bool split = detached && e->overlap_min > 0 && n >= e->overlap_min;
+    const int n_first = split ? (n + 1) / 2 : n;
+    const smx::CallRoute route = e->route.decide_call(call_kind(e, in_mode, n_first, n - n_first), e->opt_fast_dense, e->cfg.exact_filter);
+    e->call_fast_dense = route.fast_dense;
+    e->call_use_filter = route.use_filter;
     // The two lanes run unordered against each other, which is safe only while they work on disjoint pairs of the engine's
     // buffers (steady state: lane 0 always [0, n/2), lane 1 always [n/2, n)).  When a call's split differs from what the
     // other lane has in flight, that lane's tail is waited for first.
     const size_t out_pair_bytes = (size_t)d.H * d.W * sizeof(float);
     auto lane_enter = [&](int k, int lo, int hi, const float *out_first, int pairs) -> int {
-        const int o = 1 - k;
         const uintptr_t olo = (uintptr_t)out_first, ohi = olo + (size_t)pairs * out_pair_bytes;
-        bool clash = e->hull_hi[o] > e->hull_lo[o] && lo < e->hull_hi[o] && e->hull_lo[o] < hi;
-        for (const smx_engine::OutRange &r : e->out_live[o]) clash = clash || (olo < r.hi && r.lo < ohi);
-        if (clash) {
+        if (e->ledger.enter(k, lo, hi, olo, ohi)) {
+            const int o = 1 - k;
             SMX_HIP(hipEventRecord(e->ev_cross[o], e->lane_stream[o]));
             SMX_HIP(hipStreamWaitEvent(e->lane_stream[k], e->ev_cross[o], 0));
-            e->hull_lo[o] = e->hull_hi[o] = 0;          // all of lane o's work so far is now ordered before lane k's next
-            e->out_live[o].clear();
         }
-        if (e->hull_hi[k] > e->hull_lo[k]) { lo = lo < e->hull_lo[k] ? lo : e->hull_lo[k]; hi = hi > e->hull_hi[k] ? hi : e->hull_hi[k]; }
-        e->hull_lo[k] = lo;
-        e->hull_hi[k] = hi;
-        // remember the output range (merged with the ranges of this lane it touches)
-        smx_engine::OutRange mine{olo, ohi};
-        std::vector<smx_engine::OutRange> &live = e->out_live[k];
-        for (size_t i = 0; i < live.size();) {
-            if (mine.lo <= live[i].hi && live[i].lo <= mine.hi) {
-                mine.lo = mine.lo < live[i].lo ? mine.lo : live[i].lo;
-                mine.hi = mine.hi > live[i].hi ? mine.hi : live[i].hi;
-                live[i] = live.back();
-                live.pop_back();
-                i = 0;                                   // the grown range may now touch an earlier one
-            } else {
-                ++i;
-            }
-        }
-        if (live.size() >= smx_engine::OUT_RANGES_MAX) {
-            // too many disjoint outputs to keep apart: fall back to their hull (a superset: at worst a wait too many)
-            for (const smx_engine::OutRange &r : live) {
-                mine.lo = mine.lo < r.lo ? mine.lo : r.lo;
-                mine.hi = mine.hi > r.hi ? mine.hi : r.hi;
-            }
-            live.clear();
-        }
-        live.push_back(mine);
         return SMX_OK;
     };
     int rc;
-    if (detached && e->overlap_min > 0 && n >= e->overlap_min) {
-        const int n0 = (n + 1) / 2;
+    if (split) {
+        const int n0 = n_first;
         const bool rgb = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
         const bool u8 = in_mode == smx::IN_GRAY_U8 || in_mode == smx::IN_RGB_U8;
         const size_t in_pair = (size_t)d.H * d.W * (rgb ? 3 : 1) * (u8 ? 1 : sizeof(float));
@@ -1295,13 +1239,13 @@ int smx_get_route_info(smx_engine *e, smx_route_info *info) {
     read_hints(e);
     std::memset(info, 0, sizeof(*info));
     info->filter_available = e->filter_ok ? 1 : 0;
-    info->route_dense = e->filt.on ? 1 : 0;
+    info->route_dense = e->route.filt.on ? 1 : 0;
     info->last_call_filtered = e->call_use_filter ? 1 : 0;
-    info->probe_period = e->filt.period;
-    info->candidate_density = e->filt.last;
+    info->probe_period = e->route.filt.period;
+    info->candidate_density = e->route.filt.last;
     info->offgrid_hint = e->call_grid_hint;
     info->compute_units = e->cus;
-    info->fast_dense = e->fast.on ? 1 : 0;
+    info->fast_dense = e->route.fast.on ? 1 : 0;
     return SMX_OK;
 }
 

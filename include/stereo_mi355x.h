@@ -32,6 +32,8 @@
  *   -- (voxel-grid downsampling of those points)          smx_voxel_downsample, smx_voxel_workspace_bytes
  *   -- (TSDF fusion of posed maps into a voxel volume)    smx_tsdf_integrate, smx_tsdf_integrate_workspace_bytes
  *   -- (surface points of that volume, ordered)           smx_tsdf_extract_points, smx_tsdf_extract_workspace_bytes
+ *   -- (triangles over those points: marching cubes)      smx_tsdf_extract_triangles,
+ *                                                         smx_tsdf_extract_triangles_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -764,6 +766,42 @@ int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float o
                             const float *tsdf, const float *weight, const uint8_t *color, float min_weight,
                             int capacity, float *points, float *normals, uint8_t *colors, int32_t *count,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_tsdf_extract_triangles: the surface of a volume as an indexed triangle mesh whose vertices are, by index, the
+ * points smx_tsdf_extract_points emits for the same min_weight (marching cubes; this call writes the connectivity only).
+ * A cell (i, j, k) exists for 0 <= i < nx-1, 0 <= j < ny-1, 0 <= k < nz-1; its corner c = cx + 2*cy + 4*cz is the voxel
+ * (i+cx, j+cy, k+cz).  A cell is VALID iff all eight corners have weight >= min_weight and |T| < 1; a corner is inside
+ * iff T < 0, and the cell's case is the sum of 2^c over its inside corners.  Cells are visited in ascending linear index
+ * (k*ny + j)*nx + i; a valid cell emits the triangles of its case in table order, three int32 vertex indices each; other
+ * cells emit nothing.
+ *   edges     e = 4*a + r runs along axis a (x 0, y 1, z 2) from a base corner b whose offset along a is 0, with r
+ *             x: cy + 2*cz, y: cx + 2*cz, z: cx + 2*cy of b.  The vertex of edge e of cell (i, j, k) is the crossing of
+ *             voxel (i, j, k) + b along a; every crossed edge of a valid cell satisfies smx_tsdf_extract_points' emission
+ *             rule, and the vertex index is the rank of that (voxel, axis) crossing in that call's output order.
+ *   table     per face of the cell: with 0 or 4 inside corners nothing; otherwise one segment joins the face's two
+ *             crossed edges; with two diagonally opposite inside corners two segments, each joining the two edges that
+ *             meet at an inside corner.  A face's segments depend on its four signs only, so neighbouring cells agree and
+ *             the mesh is closed wherever the cells around it are valid.  The segments of a case form closed loops; each
+ *             loop starts at its lowest edge id and is fanned from there, (l0, l_m, l_m+1), loops in the order of their
+ *             lowest edge id; at most 5 triangles.  For every triangle (a, b, c), (b - a) x (c - a) points from inside
+ *             (T < 0) to outside (T >= 0, where the cameras are): the side the vertex normals point to.
+ *             cuda_depth/mc_table.py generates the table from this rule.
+ * Crossings that no valid cell touches stay in the vertex list as unreferenced vertices: indices are not compacted.
+ * Outputs: count (device int32) = the total number of triangles (saturated at 2^31 - 1); the first min(total, capacity)
+ * triangles to triangles [capacity][3] int32; nothing past them is written.  A volume with more than 2^31 - 1 crossings
+ * has vertices that an int32 cannot index: count = -1 and nothing is written (decided on the device).  On `stream` (a
+ * caller's stream): one pass over the volume, counts per (k, j) row, one exclusive scan, ordered scatter per row; no
+ * atomics, no host synchronisation, no allocation: graph-capturable and deterministic.
+ * workspace: smx_tsdf_extract_triangles_workspace_bytes(nx, ny, nz) bytes (one per voxel, 4 per 64 voxels of a row and
+ * about 24 per row; 0 for sizes the call rejects).
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL tsdf, weight, triangles, count or workspace; the
+ * volume's dimension checks of smx_tsdf_integrate; min_weight not finite and > 0; capacity outside 1..2^30;
+ * workspace_bytes below the query; an output or the workspace overlapping an input or another output;
+ * stream == SMX_STREAM_ENGINE. */
+size_t smx_tsdf_extract_triangles_workspace_bytes(int nx, int ny, int nz);
+int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight,
+                               float min_weight, int capacity, int32_t *triangles, int32_t *count, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

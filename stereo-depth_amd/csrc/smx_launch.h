@@ -152,7 +152,7 @@ hipError_t launch_voxel_downsample(int n, int capacity, const float *points, con
 size_t scan_block_sums(long L);
 void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s);
 
-// ---- tu_tsdf.hip: TSDF fusion and surface extraction (k_tsdf.h) --------------------------------------------------------
+// ---- tu_tsdf.hip: TSDF fusion and surface extraction (k_tsdf.h, k_mesh.h) --------------------------------------------------------
 // q / p / origin: host values, copied into the kernel arguments; world_to_camera [n][3][4] on the device; conf / color /
 // image may be NULL (color needs image); arguments checked by smx_tsdf_integrate
 size_t tsdf_integrate_workspace_bytes(int n, int H, int W);
@@ -166,5 +166,9 @@ size_t tsdf_extract_workspace_bytes(int nx, int ny, int nz);
 void launch_tsdf_extract(int nx, int ny, int nz, const float origin[3], float voxel_size, const float *tsdf,
                          const float *weight, const uint8_t *color, float min_weight, int capacity, float *points,
                          float *normals, uint8_t *colors, int32_t *count, void *workspace, hipStream_t s);
+// the triangles over those points (k_mesh.h); arguments checked by smx_tsdf_extract_triangles
+size_t tsdf_triangles_workspace_bytes(int nx, int ny, int nz);
+void launch_tsdf_triangles(int nx, int ny, int nz, const float *tsdf, const float *weight, float min_weight,
+                           int capacity, int32_t *triangles, int32_t *count, void *workspace, hipStream_t s);
 
 }  // namespace smx

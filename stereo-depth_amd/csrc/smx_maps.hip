@@ -638,4 +638,39 @@ int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float o
     });
 }
 
+size_t smx_tsdf_extract_triangles_workspace_bytes(int nx, int ny, int nz) {
+    return tsdf_dims_ok(nx, ny, nz) ? smx::tsdf_triangles_workspace_bytes(nx, ny, nz) : 0;
+}
+
+int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight,
+                               float min_weight, int capacity, int32_t *triangles, int32_t *count, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_tsdf_extract_triangles";
+    if (!tsdf || !weight || !triangles || !count || !workspace)
+        return fail(SMX_ERR_INVALID_ARG, "%s: tsdf, weight, triangles, count and workspace must be non-NULL", fn);
+    if (!tsdf_dims_ok(nx, ny, nz))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= nx, ny, nz <= 4096 and nx * ny * nz <= 2^30 (got %d, %d, %d)", fn,
+                    nx, ny, nz);
+    if (!(std::isfinite(min_weight) && min_weight > 0.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and > 0, got %g", fn, (double)min_weight);
+    if (capacity < 1 || capacity > SMX_POINTS_MAX)
+        return fail(SMX_ERR_INVALID_ARG, "%s: capacity must be in 1..2^30, got %d", fn, capacity);
+    const size_t need = smx::tsdf_triangles_workspace_bytes(nx, ny, nz);
+    if (workspace_bytes < need)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: workspace_bytes %zu is below smx_tsdf_extract_triangles_workspace_bytes = %zu", fn,
+                    workspace_bytes, need);
+    const size_t vox = (size_t)nx * ny * nz;
+    const void *const ins[2] = {tsdf, weight};
+    const size_t in_bytes[2] = {vox * sizeof(float), vox * sizeof(float)};
+    void *const outs[3] = {triangles, count, workspace};
+    const size_t out_bytes[3] = {(size_t)capacity * 3 * sizeof(int32_t), sizeof(int32_t), workspace_bytes};
+    if (int rc = check_disjoint(fn, 2, ins, in_bytes, 3, outs, out_bytes)) return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_triangles(nx, ny, nz, tsdf, weight, min_weight, capacity, triangles, count, workspace,
+                                   (hipStream_t)stream);
+    });
+}
+
 }  // extern "C"

@@ -1,6 +1,8 @@
-// tu_tsdf.hip -- TSDF fusion of posed disparity maps and the extraction of the volume's surface points (k_tsdf.h).
+// tu_tsdf.hip -- TSDF fusion of posed disparity maps and the extraction of the volume's surface as points (k_tsdf.h)
+// and as triangles over those points (k_mesh.h).
 #include <cstring>
 
+#include "k_mesh.h"
 #include "k_tsdf.h"
 #include "smx_launch.h"
 
@@ -63,6 +65,55 @@ void launch_tsdf_extract(int nx, int ny, int nz, const float origin[3], float vo
     hipLaunchKernelGGL(k_tsdf_count, dim3((unsigned)rows), dim3(256), 0, s, a);
     launch_scan(a.row_count, a.row_offset, rows, block_sums, nullptr, 0, s);
     hipLaunchKernelGGL(k_tsdf_scatter, dim3((unsigned)rows), dim3(256), 0, s, a);
+}
+
+namespace {
+struct MeshLayout {
+    size_t flags, chunk_first, counts, offsets, block_sums, total;
+    int nch;
+};
+
+// one byte per voxel, one word per 64-voxel chunk of a row, three counts and three offsets per row, the scan's block sums
+MeshLayout mesh_layout(int nx, int ny, int nz) {
+    MeshLayout l;
+    const size_t rows = (size_t)ny * nz;
+    l.nch = (nx + 63) / 64;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    l.flags = take(rows * nx);
+    l.chunk_first = take(rows * l.nch * sizeof(unsigned));
+    l.counts = take(3 * rows * sizeof(int));
+    l.offsets = take(3 * rows * sizeof(int));
+    l.block_sums = take(scan_block_sums(3 * (long)rows) * sizeof(int));
+    l.total = at;
+    return l;
+}
+}  // namespace
+
+size_t tsdf_triangles_workspace_bytes(int nx, int ny, int nz) { return mesh_layout(nx, ny, nz).total; }
+
+void launch_tsdf_triangles(int nx, int ny, int nz, const float *tsdf, const float *weight, float min_weight,
+                           int capacity, int32_t *triangles, int32_t *count, void *workspace, hipStream_t s) {
+    const MeshLayout l = mesh_layout(nx, ny, nz);
+    char *ws = (char *)workspace;
+    MeshArgs a;
+    a.v = TsdfExtractArgs{};
+    a.v.nx = nx, a.v.ny = ny, a.v.nz = nz, a.v.min_weight = min_weight;
+    a.v.tsdf = tsdf, a.v.weight = weight;
+    const long rows = (long)ny * nz;
+    int *counts = (int *)(ws + l.counts), *offsets = (int *)(ws + l.offsets);
+    a.v.row_count = counts, a.v.row_offset = offsets;
+    a.tri_hi = counts + rows, a.tri_hi_offset = offsets + rows;
+    a.tri_count = counts + 2 * rows, a.tri_offset = offsets + 2 * rows;
+    a.nch = l.nch;
+    a.flags = (uint8_t *)(ws + l.flags), a.chunk_first = (unsigned *)(ws + l.chunk_first);
+    a.capacity = (unsigned)capacity, a.triangles = triangles, a.count = count;
+    int *block_sums = (int *)(ws + l.block_sums);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipLaunchKernelGGL(k_mesh_flags, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_mesh_count, grid, dim3(256), 0, s, a);
+    launch_scan(counts, offsets, 3 * rows, block_sums, nullptr, 0, s);
+    hipLaunchKernelGGL(k_mesh_scatter, grid, dim3(256), 0, s, a);
 }
 
 }  // namespace smx

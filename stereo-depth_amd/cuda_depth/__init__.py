@@ -1039,6 +1039,17 @@ class PointCloud:
     normals: Optional[torch.Tensor] = None
 
 
+@dataclasses.dataclass
+class TriangleMesh:
+    """An indexed triangle mesh (TSDFVolume.extract_triangle_mesh).  vertices: [N, 3] float32; triangles: [M, 3] int32
+    indices into the vertices, counter-clockwise seen from outside (from the cameras' side); normals: [N, 3] float32 unit
+    vertex normals or None; colors: [N, 3] uint8 RGB or None.  Vertices that no triangle refers to are kept."""
+    vertices: torch.Tensor
+    triangles: torch.Tensor
+    normals: Optional[torch.Tensor] = None
+    colors: Optional[torch.Tensor] = None
+
+
 def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
                         cx_right: Optional[float] = None) -> np.ndarray:
     """The float32 4x4 Q of a rectified pair in OpenCV's reprojectImageTo3D convention, [X' Y' Z' W'] = Q [u v d 1]:
@@ -1337,7 +1348,8 @@ def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], 
 
 class TSDFVolume:
     """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
-    include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points).  The volume has
+    include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points) or as a triangle mesh over
+    those points (smx_tsdf_extract_triangles).  The volume has
     dims = (nx, ny, nz) voxels of edge voxel_size, its corner at origin, in the caller's world frame; voxel (i, j, k) is
     centred at origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size.  It owns the state: .tsdf and .weight float32
     [nz, ny, nx], and with color=True .color uint8 [nz, ny, nx, 4] (R, G, B, 0).  truncation (default 3 * voxel_size,
@@ -1466,3 +1478,48 @@ class TSDFVolume:
         total = min(total, self._capacity)
         return PointCloud(points=pts[:total], colors=None if col is None else col[:total],
                           normals=None if nrm is None else nrm[:total])
+
+    def extract_triangle_mesh_batched(self, vertex_capacity: int, triangle_capacity: int, *, min_weight: float = 1.0,
+                                      normals: bool = True, colors: bool = True):
+        """The surface as an indexed mesh without synchronising (smx_tsdf_extract_points, then
+        smx_tsdf_extract_triangles, on the current stream): returns extract_point_cloud_batched(vertex_capacity)'s
+        (points, normals, colors, count) followed by triangles [triangle_capacity, 3] int32, of which the first
+        min(triangle_count, triangle_capacity) rows are written, and triangle_count [1] int32 (-1: the volume has more
+        crossings than an int32 can index).  The indices refer to the complete vertex list, whatever vertex_capacity."""
+        _int_arg("triangle_capacity", triangle_capacity)
+        if not 1 <= triangle_capacity <= 2 ** 30:
+            raise RuntimeError(f"triangle_capacity must be in 1..2^30, got {triangle_capacity}")
+        pts, nrm, col, count = self.extract_point_cloud_batched(vertex_capacity, min_weight=min_weight, normals=normals,
+                                                                colors=colors)
+        dev = self.device
+        tris = torch.empty((triangle_capacity, 3), dtype=torch.int32, device=dev)
+        tcount = torch.empty(1, dtype=torch.int32, device=dev)
+        nx, ny, nz = self.dims
+        ws_bytes = LIB.smx_tsdf_extract_triangles_workspace_bytes(nx, ny, nz)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(LIB.smx_tsdf_extract_triangles(dev.index, nx, ny, nz, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                             float(min_weight), triangle_capacity, tris.data_ptr(), tcount.data_ptr(),
+                                             ws.data_ptr(), ws_bytes, _stream(dev.index)))
+        return pts, nrm, col, count, tris, tcount
+
+    def extract_triangle_mesh(self, min_weight: float = 1.0, normals: bool = True) -> TriangleMesh:
+        """The volume's surface as a TriangleMesh: the vertices (normals, colours) are extract_point_cloud's points,
+        unchanged and in the same order, and the triangles are marching cubes over the cells whose eight voxels all have
+        weight >= min_weight and |tsdf| < 1 (the rule is in include/stereo_mi355x.h); a crossing next to a cell that is
+        not valid stays as a vertex without a triangle.  SYNCHRONISES to read the counts; capacities that were too small
+        are retried once with the exact counts."""
+        tcap = min(2 * self._capacity, 2 ** 30)
+        for attempt in range(2):
+            pts, nrm, col, count, tris, tcount = self.extract_triangle_mesh_batched(
+                self._capacity, tcap, min_weight=min_weight, normals=normals)
+            total, ttotal = int(count.item()), int(tcount.item())          # the synchronisation
+            if ttotal < 0:
+                raise RuntimeError("the volume has more than 2^31 - 1 crossings: its vertices cannot be indexed")
+            if (total <= self._capacity and ttotal <= tcap) or attempt == 1:
+                break
+            self._capacity = min(max(total, self._capacity), 2 ** 30)
+            tcap = min(max(ttotal, 1), 2 ** 30)
+        if total > self._capacity or ttotal > tcap:
+            raise RuntimeError(f"the mesh has {total} vertices and {ttotal} triangles: more than 2^30")
+        return TriangleMesh(vertices=pts[:total], triangles=tris[:ttotal], normals=None if nrm is None else nrm[:total],
+                            colors=None if col is None else col[:total])

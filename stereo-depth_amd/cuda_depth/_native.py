@@ -170,6 +170,11 @@ EXPORTS = {
     "smx_tsdf_extract_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # triangles over those points: (nx, ny, nz) -> workspace bytes; (device_id, nx, ny, nz, tsdf, weight, min_weight,
+    # capacity, triangles, count, workspace, workspace_bytes, stream)
+    "smx_tsdf_extract_triangles_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_tsdf_extract_triangles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

@@ -41,6 +41,16 @@
  *   - All image pointers are DEVICE pointers on the engine's device (cfg.device_id),
  *     row-major float32 (or uint8 for *_u8), contiguous.  `stream` is a hipStream_t
  *     (NULL = the legacy default stream, which is what the reference launches on).
+ *   - Alignment.  Image, map, table and output operands need only the alignment of their
+ *     element type (1 byte for uint8, 4 for float32 and int32 operands, 8 for double): a
+ *     contiguous view that starts anywhere inside a larger buffer is a valid operand.
+ *     A caller-supplied workspace must be 256-byte aligned: that is what hipMalloc (and
+ *     torch's allocator) return and the rounding of the layouts inside it, which hold
+ *     8-byte values and atomics.  Every entry that takes a workspace (smx_filter_speckles,
+ *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
+ *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample,
+ *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles) returns
+ *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
  *   - Calls enqueue work and return without synchronising (like the reference).
  *   - One engine = one device + one set of intermediate buffers: calls on the same
  *     engine must be serialised by the caller (the reference object is not thread-safe

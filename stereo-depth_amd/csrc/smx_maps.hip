@@ -18,6 +18,19 @@ static int check_caller_stream(const char *fn, void *stream) {
     return stream == SMX_STREAM_ENGINE ? fail(SMX_ERR_INVALID_ARG, "%s needs a caller stream", fn) : SMX_OK;
 }
 
+// A caller-supplied workspace must be 256-byte aligned (include/stereo_mi355x.h: conventions): the layouts inside it are
+// rounded to 256 bytes and hold 8-byte values and atomics.  NULL passes: each entry has its own rule for it.
+static int check_workspace_alignment(const char *fn, const void *workspace) {
+    if (((uintptr_t)workspace & 255u) == 0) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must be 256-byte aligned (got %p)", fn, workspace);
+}
+
+// The last two host checks of every entry that takes a workspace.
+static int check_workspace_and_stream(const char *fn, const void *workspace, void *stream) {
+    if (int rc = check_workspace_alignment(fn, workspace)) return rc;
+    return check_caller_stream(fn, stream);
+}
+
 // Selects the device, runs `launch` (which returns a status if it makes a HIP call of its own) and checks the launch.
 template <class F> static int launch_on(int device_id, F &&launch) {
     DeviceGuard guard(device_id);
@@ -42,7 +55,7 @@ static int check_post_args(const char *fn, int n, int H, int W, const float *in,
         return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in other than as the same buffer", fn);
     if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes))
         return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in or out", fn);
-    return check_caller_stream(fn, stream);
+    return check_workspace_and_stream(fn, workspace, stream);
 }
 
 extern "C" {
@@ -121,7 +134,7 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
         (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
          ranges_overlap(workspace, workspace_bytes, guide, bytes) || ranges_overlap(workspace, workspace_bytes, holes, bytes)))
         return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, holes, guide or out", fn);
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_weighted_median(n, H, W, in, holes, guide, out, radius, range_weight, spatial_weight, invalid,
                                     (hipStream_t)stream);
@@ -164,7 +177,7 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
         ranges_overlap(workspace, workspace_bytes, guide, bytes) ||
         ranges_overlap(workspace, workspace_bytes, confidence, bytes))
         return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, confidence, guide or out", fn);
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_wls(n, H, W, in, confidence, guide, out, num_iterations, lambdas, range_weight, min_weight, invalid,
                         workspace, (hipStream_t)stream);
@@ -345,7 +358,7 @@ static int sgm_entry(const char *fn, int device_id, int n, int channels, int dty
         return fail(SMX_ERR_INVALID_ARG, "%s: right_out overlaps out or gray_left_out", fn);
     if (ranges_overlap(workspace, workspace_bytes, left, in_bytes) || ranges_overlap(workspace, workspace_bytes, right, in_bytes))
         return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap left or right", fn);
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_sgm(n, channels, dtype == SMX_DTYPE_F32, H, W, left, right, min_disparity, num_disparities, paths, P1,
                         P2, uniqueness, lr_max_diff, subpixel != 0, invalid_disparity, out, gray_left_out, right_out,
@@ -451,7 +464,7 @@ int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, 
             if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
                 return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
     }
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_reproject(n, H, W, disp, Q, confidence, min_confidence, z_min, z_max, invalid_disparity, image,
                               image_channels, image_dtype == SMX_DTYPE_F32, points, colors, indices, xyz_map, offsets,
@@ -498,7 +511,7 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
             if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
                 return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
     }
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&]() -> int {
         SMX_HIP(smx::launch_voxel_downsample(n, capacity, points, colors, offsets, voxel_size, min_points, out_points,
                                              out_colors, out_counts, out_offsets, dropped, workspace,
@@ -594,7 +607,7 @@ int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin
     void *const outs[4] = {tsdf, weight, color, workspace};
     const size_t out_bytes[4] = {vox * sizeof(float), vox * sizeof(float), vox * 4, workspace_bytes};
     if (int rc = check_disjoint(fn, 4, ins, in_bytes, 4, outs, out_bytes)) return rc;
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_integrate(nx, ny, nz, origin, voxel_size, truncation, max_weight, tsdf, weight, color, n, H, W,
                                    disp, Q, P, world_to_camera, confidence, min_confidence, z_min, z_max,
@@ -631,7 +644,7 @@ int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float o
     const size_t out_bytes[5] = {cap * 3 * sizeof(float), cap * 3 * sizeof(float), cap * 3, sizeof(int32_t),
                                  workspace_bytes};
     if (int rc = check_disjoint(fn, 3, ins, in_bytes, 5, outs, out_bytes)) return rc;
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_extract(nx, ny, nz, origin, voxel_size, tsdf, weight, color, min_weight, capacity, points,
                                  normals, colors, count, workspace, (hipStream_t)stream);
@@ -666,7 +679,7 @@ int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const floa
     void *const outs[3] = {triangles, count, workspace};
     const size_t out_bytes[3] = {(size_t)capacity * 3 * sizeof(int32_t), sizeof(int32_t), workspace_bytes};
     if (int rc = check_disjoint(fn, 2, ins, in_bytes, 3, outs, out_bytes)) return rc;
-    if (int rc = check_caller_stream(fn, stream)) return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_triangles(nx, ny, nz, tsdf, weight, min_weight, capacity, triangles, count, workspace,
                                    (hipStream_t)stream);

@@ -270,6 +270,7 @@ SGM_REJECTIONS = [
     (dict(right_out=0x40000 + 4), "right_out overlaps out or gray_left_out"),
     (dict(right_out=0x60000, gray_left_out=0x60000 + 8), "right_out overlaps out or gray_left_out"),
     (dict(out=0x80000 + 4), "right_out overlaps out or gray_left_out"),
+    (dict(workspace=0x100000 + 8), "workspace must be 256-byte aligned"),
 ]
 
 

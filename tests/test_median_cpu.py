@@ -92,6 +92,8 @@ def test_weighted_median_rejects_bad_arguments_without_a_device(native):
         (dict(ws=HOLES + 16, wsb=64), "the workspace must not overlap"),
         (dict(ws=GUIDE + 16, wsb=64), "the workspace must not overlap"),
         (dict(ws=OUT - 16, wsb=64), "the workspace must not overlap"),
+        (dict(ws=WS + 8, wsb=64), "workspace must be 256-byte aligned"),
+        (dict(ws=WS + 128, wsb=0), "workspace must be 256-byte aligned"),
         (dict(s=native.STREAM_ENGINE), "needs a caller stream"),
     ]
     for change, msg in cases:

@@ -335,6 +335,7 @@ def test_c_abi_rejects_bad_arguments_without_a_device():
         assert tt(**kw) == bad, kw
         assert "smx_tsdf_extract_triangles" in native.last_error()
     assert tt(cap=2 ** 30 + 1) == bad and "capacity" in native.last_error()
+    assert tt(ws=C.c_void_p(0x100000000 + 8)) == bad and "workspace must be 256-byte aligned" in native.last_error()
     assert tt(minw=nan) == bad and "min_weight" in native.last_error()
     assert tt(stream=native.STREAM_ENGINE) == bad and "stream" in native.last_error().lower()
 

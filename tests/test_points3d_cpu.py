@@ -272,6 +272,7 @@ def test_c_abi_rejects_bad_arguments_without_a_device():
     assert rp(wsb=wsb - 1) == bad
     assert rp(pts=fake) == bad                                    # points overlap disp
     assert rp(stream=native.STREAM_ENGINE) == bad
+    assert rp(ws=C.c_void_p(0x100000000 + 8)) == bad and "workspace must be 256-byte aligned" in native.last_error()
     q2 = (C.c_float * 16)(*([math.inf] + [0.0] * 15))
     assert rp(Q=q2) == bad
     assert "Q[0]" in native.last_error()
@@ -296,6 +297,7 @@ def test_c_abi_rejects_bad_arguments_without_a_device():
     assert vd(wsb=vwb - 1) == bad
     assert vd(op=fake) == bad                                     # output overlaps points
     assert vd(stream=native.STREAM_ENGINE) == bad
+    assert vd(ws=C.c_void_p(0x100000000 + 128)) == bad and "workspace must be 256-byte aligned" in native.last_error()
 
 
 def test_python_validation_before_the_device(cd):

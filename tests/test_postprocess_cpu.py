@@ -69,6 +69,8 @@ def _speckle_cases(native):
         (dict(o=IN + 8), "other than as the same buffer"),
         (dict(ws=IN + 16), "workspace must not overlap"),
         (dict(ws=OUT - 16), "workspace must not overlap"),
+        (dict(ws=WS + 4), "workspace must be 256-byte aligned"),
+        (dict(ws=WS + 128, s=S), "workspace must be 256-byte aligned"),
         (dict(s=S), "needs a caller stream"),
     ]
     return good, cases

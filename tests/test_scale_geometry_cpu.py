@@ -1,7 +1,8 @@
-"""The geometry guard of tests/test_scale_gpu.py: reads the launch constants of the point-cloud, TSDF, speckle and metrics
-kernels from their defining lines in the sources and asserts that every case of tests/scale_cases.py still crosses the
-size at which its kernel takes the path it is there to test.  A retuned constant that leaves a case below its threshold
-fails here, by name, instead of silently shrinking what the GPU file checks."""
+"""The geometry guard of tests/test_scale_gpu.py and tests/test_launch_caps_gpu.py: reads the launch constants of the
+point-cloud, TSDF, speckle and metrics kernels, and the grid caps of the map entries' launchers, from their defining lines
+in the sources and asserts that every case of tests/scale_cases.py still crosses the size at which its kernel takes the
+path it is there to test.  A retuned constant that leaves a case below its threshold fails here, by name, instead of
+silently shrinking what the GPU files check."""
 import os
 import re
 
@@ -129,3 +130,126 @@ def test_metrics_batch_passes_the_block_cap(k):
     n, H, W = sc.METRICS_SHAPE
     blocks = sc.capped_blocks(H * W, k["MET_PER_BLOCK"], k["MET_CAP"])
     assert n > 1 and blocks == k["MET_CAP"] and sc.grid_stride_trips(H * W, blocks, 256) > k["MET_PER_BLOCK"] // 256
+
+
+# ---- the map entries past their grid caps (tests/test_launch_caps_gpu.py) ----------------------------------------------
+
+@pytest.fixture(scope="module")
+def m():
+    """The grid caps of the map entries' launchers and the kernel constants their loops stride by."""
+    c = {}
+    c["CONF_MAPS"] = one(r"const unsigned maps = \(unsigned\)\(n < (\d+) \? n : \1\);", "tu_confidence.hip")
+    c["TEMP_MAPS"] = one(r"const unsigned maps = \(unsigned\)\(n < (\d+) \? n : \1\);", "tu_temporal.hip")
+    c["SGM_IMAGES"] = one(r"const unsigned images = \(unsigned\)\(2 \* n < (\d+) \? 2 \* n : \1\);", "tu_sgm.hip")
+    c["SGM_GROUPS"] = 1 << one(r"groups < \(\(size_t\)1 << (\d+)\) \? groups : \(\(size_t\)1 << \1\)", "tu_sgm.hip")
+    c["SGM_THREADS"] = one(r"^constexpr int SGM_THREADS = (\d+);", "k_sgm.h")
+    c["MED_TILES"] = 1 << one(r"tiles < \(\(size_t\)1 << (\d+)\) \? tiles : \(\(size_t\)1 << \1\)", "tu_median.hip")
+    c["MED_TH"] = one(r"^constexpr int MED_TH = (\d+), MED_TW = \d+;", "k_median.h")
+    c["MED_TW"] = one(r"^constexpr int MED_TH = \d+, MED_TW = (\d+);", "k_median.h")
+    c["WLS_BLOCKS"] = 1 << one(r"blocks < \(\(size_t\)1 << (\d+)\) \? blocks : \(\(size_t\)1 << \1\)", "tu_wls.hip")
+    c["WLS_LINES"] = one(r"^constexpr int WLS_LINES = (\d+);", "k_wls.h")
+    c["WLS_COL_THREADS"] = one(r"^constexpr int WLS_COL_THREADS = (\d+);", "k_wls.h")
+    c["WLS_PB"] = one(r"^constexpr int WLS_PB = (\d+);", "k_wls.h")
+    c["REMAP_CHUNKS"] = one(r"if \(chunks > (\d+)\) chunks = \1;", "tu_remap.hip")
+    c["REMAP_IPT"] = one(r"^constexpr int REMAP_IPT = (\d+);", "k_remap.h")
+    c["LR_BLOCKS"] = one(r"if \(blocks > (\d+)\) blocks = \1;", "tu_lr.hip")
+    c["LR_THREADS"] = one(r"^constexpr int LR_THREADS = (\d+);", "k_lr.h")
+    c["LR_PACK_ITEMS"] = one(r"^constexpr int LR_PACK_ITEMS = (\d+);", "k_lr.h")
+    c["LR_LDS_W"] = one(r"^constexpr int LR_LDS_W = (\d+);", "k_lr.h")
+    # the loops the cases are there to send on a second trip, and what the launchers divide by
+    for name, text in (("k_confidence.h", "m += gridDim.y"), ("k_temporal.h", "m += gridDim.y"),
+                       ("k_sgm.h", "z += gridDim.y"), ("k_sgm.h", "p += waves"), ("k_median.h", "tile += gridDim.x"),
+                       ("k_wls.h", "line0 += (size_t)gridDim.x * WLS_LINES"),
+                       ("k_wls.h", "line += (size_t)gridDim.x * WLS_COL_THREADS"), ("k_lr.h", "c += stride"),
+                       ("k_lr.h", "i += stride"), ("k_lr.h", "it += stride"),
+                       ("k_remap.h", "min((long long)p.n, (long long)(chunk + 1) * p.ipt)"),
+                       ("tu_wls.hip", "grid_of((size_t)n * H, WLS_LINES)"),
+                       ("tu_wls.hip", "grid_of((size_t)n * W, WLS_COL_THREADS)"),
+                       ("tu_sgm.hip", "(pixels + SGM_THREADS / 64 - 1) / (SGM_THREADS / 64)"),
+                       ("tu_lr.hip", "const bool lds = W <= LR_LDS_W;")):
+        assert text in source(name), f"{name} no longer holds {text!r}: restate the case's geometry in scale_cases.py"
+    return c
+
+
+def test_confidence_and_temporal_maps_take_a_second_trip(m):
+    strides = []
+    for shape, cap in ((sc.CONF_CAP_SHAPE, m["CONF_MAPS"]), (sc.TEMPORAL_CAP_SHAPE, m["TEMP_MAPS"])):
+        n, H, W = shape
+        grid, stride, trips = sc.map_grid_y(n, cap)
+        assert grid == cap and trips >= 2, f"{shape}: n no longer passes the cap of {cap} maps"
+        assert n - cap >= 2, "more than one workgroup row must take the second trip"
+        strides.append(stride)
+    assert sc.TEMPORAL_FRAMES >= 3 and 1 <= sc.MAP_RADIUS <= 7
+    assert sc.tile_period_ok(strides), strides
+
+
+def test_sgm_images_and_pixels_take_a_second_trip(m):
+    n, H, W, dmin, D = sc.SGM_CAP_CASE
+    grid, stride, trips, left2, right2 = sc.sgm_census_grid(n, m["SGM_IMAGES"])
+    assert grid == m["SGM_IMAGES"] and trips >= 2 and left2 >= 1 and right2 >= 1, (grid, trips, left2, right2)
+    sgrid, sstride, strips = sc.sgm_select_grid(n, H, W, m["SGM_THREADS"], m["SGM_GROUPS"])
+    assert sgrid == m["SGM_GROUPS"] and strips >= 2, "the pixels no longer pass the cap of the selection kernels"
+    assert D <= 64, "the main case runs one disparity per lane"
+    wn, wH, wW, wdmin, wD = sc.SGM_CAP_WIDE_CASE
+    wgrid, wstride, wtrips, _, wright2 = sc.sgm_census_grid(wn, m["SGM_IMAGES"])
+    assert wgrid == m["SGM_IMAGES"] and wtrips >= 2 and wright2 >= 1
+    assert wD > 128 and wdmin + wD - 1 < wW + wD, "the wide case runs four disparities per lane"
+    assert sc.tile_period_ok([stride, sstride, wstride]), (stride, sstride, wstride)
+
+
+def test_median_tiles_take_a_second_trip(m):
+    n, H, W = sc.MEDIAN_CAP_SHAPE
+    per_map, grid, stride, trips = sc.median_grid(n, H, W, m["MED_TH"], m["MED_TW"], m["MED_TILES"])
+    assert per_map == 1, "one tile per map: the tile index is the map index"
+    assert grid == m["MED_TILES"] and trips >= 2 and n - grid >= 2
+    assert sc.tile_period_ok([stride]), stride
+
+
+def test_wls_lines_take_a_second_trip(m):
+    strides = []
+    (n, H, W), (n2, H2, W2), (n3, H3, W3) = sc.WLS_CAP_SHAPES
+    (rg, rs, rt), (cg, cs, ct) = sc.wls_grids(n, H, W, m["WLS_LINES"], m["WLS_COL_THREADS"], m["WLS_BLOCKS"])
+    assert rg == m["WLS_BLOCKS"] and rt >= 2, "rows of the first shape no longer pass the rows cap"
+    assert cg == m["WLS_BLOCKS"] and ct >= 2, "columns of the first shape no longer pass the columns cap"
+    assert W >= 2, "the first shape couples pixels along its rows"
+    strides += [rs, cs]
+    (rg, rs, rt), (cg, cs, ct) = sc.wls_grids(n2, H2, W2, m["WLS_LINES"], m["WLS_COL_THREADS"], m["WLS_BLOCKS"])
+    assert rg == m["WLS_BLOCKS"] and rt >= 2 and cg == m["WLS_BLOCKS"] and ct >= 2
+    assert H2 >= 2, "the second shape couples pixels along its columns"
+    strides += [rs, cs]
+    (rg, rs, rt), _ = sc.wls_grids(n3, H3, W3, m["WLS_LINES"], m["WLS_COL_THREADS"], m["WLS_BLOCKS"])
+    assert rg == m["WLS_BLOCKS"] and rt >= 2, "rows of the third shape no longer pass the rows cap"
+    assert H3 > 2 * m["WLS_PB"], "the third shape's columns take several groups of loads"
+    strides.append(rs)
+    assert sc.WLS_CAP_ITERATIONS >= 2, "a second iteration reads what the first one's strided trips wrote"
+    assert sc.tile_period_ok(strides), strides
+
+
+def test_remap_takes_more_images_per_thread_and_a_partial_last_chunk(m):
+    n, Hi, Wi, Ho, Wo = sc.REMAP_CAP_CASE
+    ipt, chunks, last = sc.remap_chunks(n, m["REMAP_IPT"], m["REMAP_CHUNKS"])
+    assert ipt > m["REMAP_IPT"], f"n = {n} no longer passes {m['REMAP_CHUNKS']} chunks of {m['REMAP_IPT']} images"
+    assert 1 <= last < ipt, "the last chunk must be partial"
+    assert chunks <= m["REMAP_CHUNKS"] and 2 * chunks <= 65535
+    assert sc.tile_period_ok([ipt, chunks, m["REMAP_CHUNKS"]]), (ipt, chunks)
+    runs = sc.REMAP_CAP_RUNS
+    assert {(d, c) for d, c, _, _ in runs} >= {("u8", 1), ("f32", 3)}
+    assert {b for _, _, b, _ in runs} == {"constant", "replicate"} and any(not both for _, _, _, both in runs)
+
+
+def test_lr_pack_halves_stride_and_wide_rows_leave_lds(m):
+    seen_chunk_stride = False
+    for n, dtype in sc.LR_PACK_CASES:
+        eb = 4 if dtype == "f32" else 1
+        g = sc.lr_pack_geometry(n * sc.C2_H, sc.C2_W, eb, m["LR_THREADS"], m["LR_PACK_ITEMS"], m["LR_BLOCKS"])
+        assert g["blocks"] == m["LR_BLOCKS"], f"{n} {dtype}: the pack grid is below its cap"
+        assert g["mirrored_trips"] >= 2, f"{n} {dtype}: the mirrored half does not stride"
+        if dtype == "f32":
+            assert g["chunk_trips"] >= 2 or g["element_trips"] >= 2, f"{n} {dtype}: the straight half does not stride"
+        seen_chunk_stride |= g["chunk_trips"] >= 2
+    assert seen_chunk_stride, "no case strides the straight half in 16-byte chunks"
+    assert any(not sc.lr_pack_geometry(n * sc.C2_H, sc.C2_W, 4 if d == "f32" else 1, m["LR_THREADS"],
+                                       m["LR_PACK_ITEMS"], m["LR_BLOCKS"])["vec"] for n, d in sc.LR_PACK_CASES)
+    widths = [W for _, _, W, _, _ in sc.LR_WIDE_CASES]
+    assert all(W > m["LR_LDS_W"] for W in widths), "a wide case fits the LDS row again"
+    assert any(W % 4 == 0 for W in widths) and any(W % 4 != 0 for W in widths), "float4 rows and scalar rows"

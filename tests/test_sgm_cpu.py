@@ -250,6 +250,8 @@ REJECTIONS = [
     (dict(gray_left_out=0x20000 + 4), "must not overlap left, right or the workspace"),
     (dict(gray_left_out=0x40000 + 4), "out and gray_left_out overlap"),
     (dict(workspace=0x10000 - 256, workspace_bytes=1 << 20, out=0x10000000), "workspace must not overlap left or right"),
+    (dict(workspace=0x100000 + 8), "workspace must be 256-byte aligned"),
+    (dict(workspace=0x100000 + 128), "workspace must be 256-byte aligned"),
 ]
 
 

@@ -341,6 +341,7 @@ def test_c_abi_rejects_bad_arguments_without_a_device():
                dict(stream=native.STREAM_ENGINE)):
         assert ti(**kw) == bad, kw
     assert ti(P=q_inf) == bad and "P[0]" in native.last_error()
+    assert ti(ws=C.c_void_p(0x100000000 + 8)) == bad and "workspace must be 256-byte aligned" in native.last_error()
 
     ewb = lib.smx_tsdf_extract_workspace_bytes(8, 8, 8)
     assert ewb >= 2 * 64 * 4 and lib.smx_tsdf_extract_workspace_bytes(0, 8, 8) == 0
@@ -358,6 +359,7 @@ def test_c_abi_rejects_bad_arguments_without_a_device():
                dict(wsb=ewb - 1), dict(pts=C.c_void_p(0x2000000 + 8)), dict(count=C.c_void_p(0x4000000 + 4)),
                dict(stream=native.STREAM_ENGINE)):
         assert te(**kw) == bad, kw
+    assert te(ws=C.c_void_p(0x100000000 + 128)) == bad and "workspace must be 256-byte aligned" in native.last_error()
 
 
 def test_python_validation_before_the_device(cd):

@@ -285,6 +285,8 @@ def test_wls_filter_rejects_bad_arguments_without_a_device(native):
         (dict(ws=CONF - 16), "the workspace must not overlap"),
         (dict(ws=GUIDE + 16), "the workspace must not overlap"),
         (dict(ws=OUT - 16), "the workspace must not overlap"),
+        (dict(ws=WS + 4), "workspace must be 256-byte aligned"),
+        (dict(ws=WS + 128, s=native.STREAM_ENGINE), "workspace must be 256-byte aligned"),
         (dict(s=native.STREAM_ENGINE), "needs a caller stream"),
     ]
     for change, msg in cases:

@@ -114,7 +114,14 @@ typedef enum smx_match_mode {
  *   FMA_SECOND_IN fma(a2,b2, rn(p1)) + rn(p3)
  * Integer-valued gray inputs with min_disparity = 0 (the BASELINE configurations) give the same bits under all six;
  * RGB input and min_disparity > 0 (the reference's defaults) do not (sensitivity table).  A holder of
- * outputs of a CUDA build picks the convention that reproduces them (tests/test_from_reference.py does it by itself). */
+ * outputs of a CUDA build picks the convention that reproduces them (tests/test_from_reference.py does it by itself).
+ * A compiler chooses per expression: gcc 11 -O2 -mfma -ffp-contract=fast compiles the reference's text to FMA_OUTER in
+ * step 1 and FMA_SECOND in the parabola.  SMX_FP_MIXED(step1, parabola) names the two sites separately; a plain value
+ * means the same evaluation at both.  (`a` and `b` of the parabola always share one.) */
+#define SMX_FP_MIXED(step1, parabola) ((step1) | (((parabola) + 1) << 3))
+#define SMX_FP_STEP1(c)    ((c) & 7)
+#define SMX_FP_PARABOLA(c) (((c) >> 3) ? ((c) >> 3) - 1 : ((c) & 7))
+#define SMX_FP_VALID(c)    ((c) >= 0 && ((c) & 7) < SMX_FP_CONVENTIONS && ((c) >> 3) <= SMX_FP_CONVENTIONS)
 typedef enum smx_fp_convention {
     SMX_FP_SOURCE = 0,
     SMX_FP_FMA_FIRST = 1,
@@ -155,7 +162,7 @@ typedef struct smx_config {
                                    most of the range, as on real scenes; re-probed every 16..64 calls of that kind -- RGB batches large
                                    enough for the filtered route; other calls do not count; smx_get_route_info),
                                    1 = always filtered, -1 = always dense */
-    int32_t  fp_convention;     /* smx_fp_convention, default SMX_FP_SOURCE */
+    int32_t  fp_convention;     /* smx_fp_convention or SMX_FP_MIXED(step1, parabola), default SMX_FP_SOURCE */
     int32_t  reserved[3];       /* must be 0 */
 } smx_config;
 

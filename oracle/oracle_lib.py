@@ -55,7 +55,7 @@ class OracleConfig:
     small_mbm_radius: int = 1
     mid_mbm_radius: int = 4
     large_mbm_radius: int = 10
-    fp_convention: int = 0      # SO_FP_* (stereo_oracle.h): 0 = no contraction
+    fp_convention: int = 0      # SO_FP_* or SO_FP_MIXED(step1, parabola) (stereo_oracle.h): 0 = no contraction
 
     def c(self) -> SoConfig:
         return SoConfig(**asdict(self))
@@ -170,6 +170,23 @@ class Oracle:
 
 # SO_FP_* of stereo_oracle.h: how the three sums of products of the path (step 1, the parabola's `a` and `b`) are contracted
 FP_CONVENTIONS = {0: "source", 1: "fma_first", 2: "fma_second", 3: "fma_outer", 4: "fma_first_in", 5: "fma_second_in"}
+
+
+
+def fp_mixed(step1: int, parabola: int) -> int:
+    """SO_FP_MIXED of stereo_oracle.h (= SMX_FP_MIXED): step 1 and the parabola contracted differently, as a compiler may."""
+    return step1 | ((parabola + 1) << 3)
+
+
+def fp_name(conv: int) -> str:
+    if conv >> 3:
+        return FP_CONVENTIONS[conv & 7] + "+" + FP_CONVENTIONS[(conv >> 3) - 1]
+    return FP_CONVENTIONS[conv]
+
+
+# every convention that names two different patterns (the 6 plain ones name the same pattern twice)
+FP_MIXED_CONVENTIONS = {fp_mixed(s, p): FP_CONVENTIONS[s] + "+" + FP_CONVENTIONS[p]
+                        for s in FP_CONVENTIONS for p in FP_CONVENTIONS if s != p}
 
 _CACHE: Dict[tuple, Oracle] = {}
 

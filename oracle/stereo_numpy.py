@@ -42,8 +42,18 @@ def fma32(a, b, c):
     return bits.view(np.float64).astype(F)
 
 
+def fp_step1(conv):
+    """SO_FP_STEP1 of stereo_oracle.h: the pattern of step 1 in a plain or SO_FP_MIXED convention."""
+    return conv & 7
+
+
+def fp_parabola(conv):
+    """SO_FP_PARABOLA of stereo_oracle.h: the pattern of the parabola's sums `a` and `b`."""
+    return (conv >> 3) - 1 if conv >> 3 else conv & 7
+
+
 def sum3(a1, b1, a2, b2, a3, b3, conv=0):
-    """`(a1*b1 + a2*b2) + a3*b3` under floating-point convention `conv` (stereo_oracle.h, SO_FP_*)."""
+    """`(a1*b1 + a2*b2) + a3*b3` under the plain pattern `conv` in 0..5 (stereo_oracle.h, SO_FP_*)."""
     if conv in (1, 4):
         inner = fma32(a1, b1, a2 * b2)
     elif conv in (2, 5):
@@ -58,6 +68,7 @@ def sum3(a1, b1, a2, b2, a3, b3, conv=0):
 def rgb_to_gray(rgb, conv=0):
     """imageops/kernels/rgb_to_grayscale.cu:24-28."""
     rgb = rgb.astype(F, copy=False)
+    conv = fp_step1(conv)
     if conv == 0:
         return (F(0.2989) * rgb[0] + F(0.5870) * rgb[1]) + F(0.1140) * rgb[2]
     return sum3(F(0.2989), rgb[0], F(0.5870), rgb[1], F(0.1140), rgb[2], conv)
@@ -120,6 +131,7 @@ def wta(agg, dmin):
 
 def quadratic_peak(x1, y1, x2, y2, x3, y3, conv=0):
     """device_functions.cuh:22-46 (arrays, float32; conv: how the sums `a` and `b` are contracted)."""
+    conv = fp_parabola(conv)
     den = ((x1 - x2) * (x2 - x3)) * (x1 - x3)
     mv = np.where(y1 > y2, np.where(y1 > y3, x1, x3), np.where(y2 > y3, x2, x3))
     with np.errstate(invalid="ignore", over="ignore"):

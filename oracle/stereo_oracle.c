@@ -67,7 +67,7 @@ int so_get_dims(const so_config *cfg, so_dims *d) {
      * around a halo of large_radius, i.e. it requires small, mid <= large. */
     if (cfg->small_mbm_radius > cfg->large_mbm_radius || cfg->mid_mbm_radius > cfg->large_mbm_radius)
         return -4;
-    if (cfg->fp_convention < 0 || cfg->fp_convention >= SO_FP_CONVENTIONS) return -5;
+    if (!SO_FP_VALID(cfg->fp_convention)) return -5;
     d->H = cfg->height;
     d->W = cfg->width;
     d->K = cfg->downscale_factor;
@@ -115,8 +115,9 @@ float so_sum3_products(float a1, float b1, float a2, float b2, float a3, float b
 /* step 1: imageops/kernels/rgb_to_grayscale.cu:24-28                                    */
 /*   R = 0.2989f * in[0]; G = 0.5870f * in[1]; B = 0.1140f * in[2]; out = R + G + B       */
 /* ------------------------------------------------------------------------------------ */
-void so_rgb_to_gray_conv(const float *rgb, int H, int W, float *gray, int conv) {
+void so_rgb_to_gray_conv(const float *rgb, int H, int W, float *gray, int fp_convention) {
     const size_t plane = (size_t)H * W;
+    const int conv = SO_FP_STEP1(fp_convention);
 #pragma omp parallel for schedule(static)
     for (int x = 0; x < H; x++) {
         for (int y = 0; y < W; y++) {
@@ -258,7 +259,8 @@ void so_wta(const float *agg, int h, int w, int Dd, int dmin, float *down, int32
 /* ------------------------------------------------------------------------------------ */
 /* depth/kernels/device_functions.cuh:22-46 (quadratic_function_peak)                    */
 /* ------------------------------------------------------------------------------------ */
-float so_quadratic_peak_conv(float x1, float y1, float x2, float y2, float x3, float y3, int conv) {
+float so_quadratic_peak_conv(float x1, float y1, float x2, float y2, float x3, float y3, int fp_convention) {
+    const int conv = SO_FP_PARABOLA(fp_convention);
     float denominator = (x1 - x2) * (x2 - x3) * (x1 - x3);
     float min_value;
     if (y1 > y2) {
@@ -506,16 +508,26 @@ void so_validity_masks(const so_config *cfg, uint8_t *mask_down, uint8_t *mask_f
                 for (int i = -(L + r); i <= L + r; i++)
                     if (wrap(x + i, h) == h - 1) row_taint[x] = 1;
         }
+        /* S7: with dmin > 0 the Q5 lookups of a pixel reach up to dmin floats before its own costs, i.e. into the
+         * costs of the `back` pixels that precede it in row-major order; those must be defined themselves. */
+        const int back = dm.dmin > 0 ? (dm.dmin + dm.Dd - 1) / dm.Dd : 0;
+        uint8_t *agg_ok = (uint8_t *)malloc(hw);
+        for (int x = 0; x < h; x++)
+            for (int y = 0; y < w; y++)
+                agg_ok[(size_t)x * w + y] = (uint8_t)(!row_taint[x] && (x + L <= h) && (y + L <= w));   /* A.4 (Q1, Q2) */
         for (int x = 0; x < h; x++) {
             for (int y = 0; y < w; y++) {
-                int ok = !row_taint[x];
-                ok = ok && (x + L <= h) && (y + L <= w);               /* A.4 (Q1, Q2) */
+                const long long pix = (long long)x * w + y;
+                int ok = agg_ok[pix];
                 ok = ok && (x * K + R <= H) && (y * K + R + K <= W);   /* A.6 (Q1)     */
                 if (dm.dmin > 0)                                       /* S6 (Q5)      */
-                    ok = ok && (((long long)x * w + y) * dm.Dd - dm.dmin >= 0);
-                md[(size_t)x * w + y] = (uint8_t)ok;
+                    ok = ok && (pix * dm.Dd - dm.dmin >= 0);
+                for (int b = 1; ok && b <= back; b++)                  /* S7 (Q5)      */
+                    ok = agg_ok[pix - b];
+                md[pix] = (uint8_t)ok;
             }
         }
+        free(agg_ok);
         free(row_taint);
     }
     if (mask_full) {

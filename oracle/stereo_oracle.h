@@ -6,8 +6,10 @@
  * cpu_baseline leg of bench.py, and only as the checker / reported baseline.
  *
  * PARITY PINNING: the reference ships no tests, golden vectors or fixtures for this
- * path and its CUDA sources cannot be built or run here (no nvcc / NVIDIA GPU), so
- * this oracle is "parity unpinned" by the reference itself.  What pins it instead:
+ * path.  Its own sources, compiled for the host (oracle/build_ref.py, oracle/ref_host/),
+ * pin this oracle bit for bit inside the validity masks on the cases of
+ * tests/golden/from_reference/ (tests/test_reference_host_cpu.py); outside the masks and
+ * on every other input it is "parity unpinned" by the reference.  What else pins it:
  *   (1) line-by-line conformance to the cited .cu/.cc sources (every function below
  *       cites the reference file:line it restates),
  *   (2) an independent NumPy restatement (oracle/stereo_numpy.py) that must agree
@@ -46,6 +48,13 @@
  *       (secondary_matching.cu:28-31), which is deterministic inside the volume; only
  *       when the flat index falls before the start of the volume is the cyclic wrap
  *       used instead.
+ *   S7  (masks only) with dmin > 0 those lookups reach up to dmin floats before a
+ *       pixel's own costs, i.e. into the costs of the ceil(dmin / Dd) pixels that precede
+ *       it in row-major order.  The oracle's value is deterministic (S1 costs), but the
+ *       reference's is defined only if those pixels lie where its aggregated costs are;
+ *       so_validity_masks leaves out every pixel for which one of them does not (the first
+ *       ceil(dmin / Dd) pooled columns: their predecessors are the previous row's tail).
+ *       Found by running the reference's own text on the host.
  */
 #ifndef STEREO_ORACLE_H
 #define STEREO_ORACLE_H
@@ -82,9 +91,18 @@ typedef struct so_config {
  *   FMA_OUTER     fma(a3,b3, rn(p1) + rn(p2))
  *   FMA_FIRST_IN  fma(a1,b1, rn(p2)) + rn(p3)
  *   FMA_SECOND_IN fma(a2,b2, rn(p1)) + rn(p3)
- * In `b` the factors a_k are themselves products x_k * x_k; those are exact (small integers) in any convention. */
+ * In `b` the factors a_k are themselves products x_k * x_k; those are exact (small integers) in any convention.
+ *
+ * A compiler chooses per expression, not per program: gcc 11 -O2 -mfma -ffp-contract=fast compiles the reference's own
+ * text (oracle/build_ref.py, libref_host_fma.so) to FMA_OUTER in step 1 and FMA_SECOND in the parabola.  So a
+ * convention may name the two sites separately: SO_FP_MIXED(step1, parabola).  The plain values 0..5 mean the same
+ * pattern at both sites.  (`a` and `b` of the parabola always share one pattern.) */
 enum { SO_FP_SOURCE = 0, SO_FP_FMA_FIRST = 1, SO_FP_FMA_SECOND = 2, SO_FP_FMA_OUTER = 3, SO_FP_FMA_FIRST_IN = 4,
        SO_FP_FMA_SECOND_IN = 5, SO_FP_CONVENTIONS = 6 };
+#define SO_FP_MIXED(step1, parabola) ((step1) | (((parabola) + 1) << 3))
+#define SO_FP_STEP1(c)    ((c) & 7)
+#define SO_FP_PARABOLA(c) (((c) >> 3) ? ((c) >> 3) - 1 : ((c) & 7))
+#define SO_FP_VALID(c)    ((c) >= 0 && ((c) & 7) < SO_FP_CONVENTIONS && ((c) >> 3) <= SO_FP_CONVENTIONS)
 
 /* Derived sizes: reference device_buffer.cc:3-12, stereo_matching.cc:61-62. */
 typedef struct so_dims {
@@ -112,6 +130,7 @@ int  so_get_max_threads(void);
 
 /* Individual stages (row-major, float32). */
 void so_rgb_to_gray(const float *rgb_chw, int H, int W, float *gray);                       /* SO_FP_SOURCE */
+/* the *_conv stages take a whole convention (plain or SO_FP_MIXED) and use their own site's pattern */
 void so_rgb_to_gray_conv(const float *rgb_chw, int H, int W, float *gray, int fp_convention);
 void so_mean_pool(const float *in, int H, int W, int K, float *out);
 void so_cost_volume(const float *Ld, const float *Rd, int h, int w,
@@ -129,7 +148,7 @@ void so_upscale_vfill(const float *Lg, int H, int W, const float *down, int h, i
 void so_hfill(const float *Lg, int H, int W, int K, int threshold, float *up /* in place */);
 float so_quadratic_peak(float x1, float y1, float x2, float y2, float x3, float y3);     /* SO_FP_SOURCE */
 float so_quadratic_peak_conv(float x1, float y1, float x2, float y2, float x3, float y3, int fp_convention);
-float so_sum3_products(float a1, float b1, float a2, float b2, float a3, float b3, int fp_convention);
+float so_sum3_products(float a1, float b1, float a2, float b2, float a3, float b3, int pattern /* plain 0..5 */);
 
 /* Whole path.  left/right: [3][H][W] (rgb) or [H][W] (gray).  out: [H][W]. */
 int so_run_rgb(const so_config *cfg, const float *left_chw, const float *right_chw,

@@ -792,7 +792,7 @@ class StereoMatching:
             raise RuntimeError(f"match_mode must be one of {sorted(_native.MATCH_MODES)}")
         if isinstance(fp_convention, str):
             if fp_convention not in _native.FP_CONVENTIONS:
-                raise RuntimeError(f"fp_convention must be one of {sorted(_native.FP_CONVENTIONS)} (or 0..5)")
+                raise RuntimeError(f"fp_convention must be one of {sorted(_native.FP_CONVENTIONS)} (or 0..5, or _native.fp_mixed)")
             fp_convention = _native.FP_CONVENTIONS[fp_convention]
         if not torch.cuda.is_available():
             raise RuntimeError("cuda_depth.StereoMatching needs a HIP device (no CPU fallback)")

@@ -14,6 +14,12 @@ MATCH_MODES = {"auto": 0, "exact_order": 1, "fast_grid": 2}
 # smx_fp_convention (include/stereo_mi355x.h): how step 1 and the parabola's two sums of products are contracted
 FP_CONVENTIONS = {"source": 0, "fma_first": 1, "fma_second": 2, "fma_outer": 3, "fma_first_in": 4, "fma_second_in": 5}
 
+
+def fp_mixed(step1, parabola) -> int:
+    """SMX_FP_MIXED: step 1 and the parabola contracted differently (names or 0..5)."""
+    s, p = (FP_CONVENTIONS[v] if isinstance(v, str) else int(v) for v in (step1, parabola))
+    return s | ((p + 1) << 3)
+
 STAGE_GRAY_LEFT, STAGE_GRAY_RIGHT, STAGE_DOWN_LEFT, STAGE_DOWN_RIGHT = 0, 1, 2, 3
 STAGE_WTA, STAGE_MBM_COSTS, STAGE_REFINED, STAGE_AGG_VOLUME, STAGE_GRID_FLAG = 4, 5, 6, 7, 8
 

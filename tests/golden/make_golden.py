@@ -2,8 +2,8 @@
 
     python tests/golden/make_golden.py
 
-The reference ships no golden vectors and cannot be run here (CUDA), so these are
-OUTPUTS OF THE ORACLE, not of the reference ("parity unpinned"; see oracle/stereo_oracle.h).
+These are OUTPUTS OF THE ORACLE, not of the reference (see oracle/stereo_oracle.h); outputs of
+the reference's own text, built for the host, are under from_reference/ (README.md there).
 They freeze the oracle's behaviour so that later edits to it, or to the HIP kernels,
 are checked against fixed data on both the CPU and the GPU box.
 """

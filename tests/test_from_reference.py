@@ -1,8 +1,9 @@
-"""Pin-ready hook: consumes outputs of the REFERENCE ITSELF if somebody drops them into tests/golden/from_reference/
-(schema: that directory's README.md), finds the floating-point convention the binary that produced them follows, and
-pins the HIP path to them BITWISE under that convention.
+"""The pin: consumes the outputs of the REFERENCE ITSELF under tests/golden/from_reference/ (schema and provenance:
+that directory's README.md -- the reference's own sources, built for the host), finds the floating-point convention the
+binary that produced them follows, and pins the HIP path to them BITWISE under that convention.
 
-Nothing from /root/reference is imported, copied or run here; without such files the GPU test skips.  The reference is
+Nothing of the reference is imported, copied or run here, and nothing under oracle/_ref/ is loaded: the committed
+files are enough (tests/test_reference_host_cpu.py is where the host build itself runs).  The reference is
 built by nvcc with its default --fmad=true (depth/setup.py:4-23 passes no flags), so its binary contracts the three sums
 of products of the path (rgb_to_grayscale.cu:24-28, device_functions.cuh:39-40) and WHICH products it fuses is the
 compiler's choice: the oracle and the engine both implement every possible choice (stereo_oracle.h SO_FP_* =
@@ -16,7 +17,7 @@ import pytest
 
 import oracle_lib
 import stereo_synthetic as syn
-from oracle_lib import OracleConfig, FP_CONVENTIONS
+from oracle_lib import OracleConfig, FP_CONVENTIONS, FP_MIXED_CONVENTIONS, fp_name
 
 DIR = os.path.join(os.path.dirname(__file__), "golden", "from_reference")
 FILES = sorted(glob.glob(os.path.join(DIR, "*.npz")))
@@ -27,12 +28,16 @@ def classify(z, orc):
     """Compares a reference-produced case with the oracle under every floating-point convention, inside the validity
     masks.  Returns (matching, report, cfg, masks): `matching` lists the conventions that reproduce every stored array
     bit for bit (several when the case is insensitive, e.g. integer gray with min_disparity = 0; none if the file agrees
-    with no convention), report[name] the max |difference| per stage."""
+    with no convention), report[name] the max |difference| per stage.  The six plain conventions (one pattern for step 1
+    and the parabola alike) are tried first; only a file that none of them reproduces is tried against the mixed ones
+    (a compiler chooses per expression: oracle_lib.FP_MIXED_CONVENTIONS)."""
     H, W, K, dmin, dmax = (int(v) for v in z["config"])
     cfg = OracleConfig(height=H, width=W, downscale_factor=K, min_disparity=dmin, max_disparity=dmax)
     md, mf = orc.masks(cfg)
     report, matching = {}, []
-    for conv, name in FP_CONVENTIONS.items():
+    for conv, name in list(FP_CONVENTIONS.items()) + list(FP_MIXED_CONVENTIONS.items()):
+        if conv not in FP_CONVENTIONS and matching:
+            break
         cfg.fp_convention = conv
         out, im = orc.run(cfg, z["left"], z["right"], intermediates=True)
         diffs = {"out": float(np.max(np.abs(out - z["out"])[mf])) if mf.any() else 0.0}
@@ -140,6 +145,27 @@ def test_the_pin_works_end_to_end_on_a_stand_in(oracle, conv):
 
 
 @pytest.mark.gpu
+def test_the_pin_works_end_to_end_on_a_mixed_convention(oracle):
+    """Step 1 and the parabola contracted differently (SMX_FP_MIXED; what gcc does to the reference's text): no plain
+    convention reproduces such a file, the hook names a mixed one, and the engine created with it is bitwise equal."""
+    conv = oracle_lib.fp_mixed(3, 2)
+    z = _fake_reference_case(oracle, conv, dmin=20, H=64, W=96, D=32)
+    matching, report, cfg, (md, mf) = classify(z, oracle)
+    assert conv in matching and not any(c in FP_CONVENTIONS for c in matching), report
+    from cuda_depth import _native as N
+    assert N.fp_mixed("fma_outer", "fma_second") == conv
+    cfg.fp_convention = conv
+    got = _hip_run(cfg, z["left"], z["right"], STAGES)
+    for st in got:
+        want = z["out"] if st == "out" else z[st]
+        m = mf if want.shape == mf.shape else md
+        assert np.array_equal(got[st][m], want[m]), st
+    with pytest.raises(RuntimeError):                           # pattern 6 does not exist, alone or as a site
+        cfg.fp_convention = 6 | (1 << 3)
+        _hip_run(cfg, z["left"], z["right"])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("path", FILES or [None], ids=[os.path.basename(p) for p in FILES] or ["none"])
 def test_hip_path_against_outputs_of_the_reference(path, oracle):
     """The pin: HIP path vs what the reference's own binary produced, BITWISE inside the validity mask, with the engine
@@ -156,4 +182,4 @@ def test_hip_path_against_outputs_of_the_reference(path, oracle):
         want = z["out"] if st == "out" else z[st]
         m = mf if want.shape == mf.shape else md
         bad = int(np.count_nonzero(got[st][m] != want[m]))
-        assert bad == 0, f"{path}: stage {st} differs from the reference in {bad} masked pixels under convention {FP_CONVENTIONS[cfg.fp_convention]}"
+        assert bad == 0, f"{path}: stage {st} differs from the reference in {bad} masked pixels under convention {fp_name(cfg.fp_convention)}"

@@ -23,6 +23,10 @@ int main(void) {
         if (so_run_gray(&cfg, l, r, o, NULL) || so_run_rgb(&cfg, l, r, o, NULL)) { printf("case %u failed\n", c); return 1; }
         unsigned char *md = malloc(HW), *mf = malloc(HW);
         so_validity_masks(&cfg, md, mf);
+        for (int ncc = 0; ncc <= 4; ncc += 2) {   /* S8: the cost rows and columns pad_index sends out of the image */
+            cfg.ncc_patch_radius = ncc; cfg.large_mbm_radius = 1 + ncc; cfg.mid_mbm_radius = 1;
+            so_validity_masks(&cfg, md, mf);
+        }
         free(md); free(mf); free(l); free(r); free(o);
     }
     printf("asan driver ok\n");

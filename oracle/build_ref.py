@@ -177,11 +177,27 @@ class RefHost:
     def built(fma: bool = False) -> bool:
         return os.path.exists(LIB_FMA if fma else LIB)
 
+    # the reference's defaults of the six fields after max_disparity (stereo_matching_configuration.hh:11-16)
+    DEFAULTS = (1, 5, 5, 1, 4, 10)
+
     def run(self, config, left, right, poison: float = 0.0, reverse: bool = False):
-        """config = [H, W, K, min_disparity, max_disparity]; left/right float32 [3,H,W] or [H,W].
+        """config = [H, W, K, min_disparity, max_disparity] (the reference's defaults for the rest) or all eleven fields
+        in the order of stereo_matching_configuration.hh: ... ncc_patch_radius, sad_patch_radius, threshold,
+        small_mbm_radius, mid_mbm_radius, large_mbm_radius.  left/right float32 [3,H,W] or [H,W].
         Returns a dict of the arrays named in STAGES."""
         import numpy as np
         C = self.C
+        config = [int(v) for v in config]
+        if len(config) == 5:
+            config += self.DEFAULTS
+        if len(config) != 11:
+            raise RuntimeError(f"ref_host: a configuration has 5 or 11 entries, not {len(config)}")
+        if min(config[5:]) < 0:
+            raise RuntimeError(f"ref_host: negative radius or threshold in {config[5:]}")
+        if config[8] > config[10] or config[9] > config[10]:
+            # the aggregation tile is sized by the large radius: the reference's own text indexes past it (and crashes)
+            raise RuntimeError(f"ref_host: small_mbm_radius {config[8]} / mid_mbm_radius {config[9]} above "
+                               f"large_mbm_radius {config[10]}")
         cfg = np.ascontiguousarray(config, np.int32)
         H, W = int(cfg[0]), int(cfg[1])
         left = np.ascontiguousarray(left, np.float32)

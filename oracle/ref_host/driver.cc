@@ -22,9 +22,11 @@ void copy_out(const torch::Tensor &t, float *dst) {
 
 }  // namespace
 
-/* cfg = [H, W, K, min_disparity, max_disparity]; left/right float32 [3,H,W] (rgb != 0) or [H,W]; every sink may be
- * NULL.  Sizes: out, gray_left [H,W]; down_left, wta, refined [h,w]; agg [h,w,Dd] (h, w, Dd as the reference's
- * device_buffer derives them).  Returns 0. */
+/* cfg = the eleven fields in the order of stereo_matching_configuration.hh: [H, W, K, min_disparity, max_disparity,
+ * ncc_patch_radius, sad_patch_radius, threshold, small_mbm_radius, mid_mbm_radius, large_mbm_radius].  The caller keeps
+ * small, mid <= large: the aggregation kernel's tile is sized by the large radius and the reference indexes past it
+ * otherwise.  left/right float32 [3,H,W] (rgb != 0) or [H,W]; every sink may be NULL.  Sizes: out, gray_left [H,W];
+ * down_left, wta, refined [h,w]; agg [h,w,Dd] (h, w, Dd as the reference's device_buffer derives them).  Returns 0. */
 extern "C" int ref_host_run(const int32_t *cfg, const float *left, const float *right, int rgb, float poison, int reverse,
                             float *out, float *gray_left, float *down_left, float *wta, float *refined, float *agg) {
     refhost::set_poison(poison);
@@ -36,6 +38,12 @@ extern "C" int ref_host_run(const int32_t *cfg, const float *left, const float *
     c.downscale_factor = static_cast<uint32_t>(cfg[2]);
     c.min_disparity = cfg[3];
     c.max_disparity = cfg[4];
+    c.ncc_patch_radius = static_cast<uint32_t>(cfg[5]);
+    c.sad_patch_radius = static_cast<uint32_t>(cfg[6]);
+    c.threshold = static_cast<uint32_t>(cfg[7]);
+    c.small_mbm_radius = cfg[8];
+    c.mid_mbm_radius = cfg[9];
+    c.large_mbm_radius = cfg[10];
     stereo_matching sm(c);
 
     const size_t plane = static_cast<size_t>(cfg[0]) * static_cast<size_t>(cfg[1]);

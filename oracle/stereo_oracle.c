@@ -511,10 +511,23 @@ void so_validity_masks(const so_config *cfg, uint8_t *mask_down, uint8_t *mask_f
         /* S7: with dmin > 0 the Q5 lookups of a pixel reach up to dmin floats before its own costs, i.e. into the
          * costs of the `back` pixels that precede it in row-major order; those must be defined themselves. */
         const int back = dm.dmin > 0 ? (dm.dmin + dm.Dd - 1) / dm.Dd : 0;
+        /* S8: pad_index(g, n) is negative for g > n.  The cost kernel pads x + i and y + j with |i|, |j| <= r, so the
+         * costs of the pooled rows x > h - r read rows before the image (undefined) and those of the columns y > w - r
+         * read [.][-1], [.][-2], ... (the previous row's tail: defined, but not what S1 computes).  Nothing for r <= 1.
+         * The aggregation windows span +-L rows at the centre columns and +-L columns at the centre rows, padded by
+         * the same function, so a pixel is out as soon as one of x - L .. x + L, wrapped, is such a row or one of
+         * y - L .. y + L such a column: x >= L, y >= L, x + L + r <= h, y + L + r <= w when r >= 2. */
+        uint8_t *col_taint = (uint8_t *)calloc((size_t)w, 1);
+        for (int x = 0; x < h; x++)
+            for (int i = -L; i <= L && !row_taint[x]; i++)
+                if (wrap(x + i, h) + r > h) row_taint[x] = 1;
+        for (int y = 0; y < w; y++)
+            for (int j = -L; j <= L && !col_taint[y]; j++)
+                if (wrap(y + j, w) + r > w) col_taint[y] = 1;
         uint8_t *agg_ok = (uint8_t *)malloc(hw);
         for (int x = 0; x < h; x++)
             for (int y = 0; y < w; y++)
-                agg_ok[(size_t)x * w + y] = (uint8_t)(!row_taint[x] && (x + L <= h) && (y + L <= w));   /* A.4 (Q1, Q2) */
+                agg_ok[(size_t)x * w + y] = (uint8_t)(!row_taint[x] && !col_taint[y] && (x + L <= h) && (y + L <= w));   /* A.4 (Q1, Q2), S8 */
         for (int x = 0; x < h; x++) {
             for (int y = 0; y < w; y++) {
                 const long long pix = (long long)x * w + y;
@@ -528,6 +541,7 @@ void so_validity_masks(const so_config *cfg, uint8_t *mask_down, uint8_t *mask_f
             }
         }
         free(agg_ok);
+        free(col_taint);
         free(row_taint);
     }
     if (mask_full) {

@@ -55,6 +55,20 @@
  *       so_validity_masks leaves out every pixel for which one of them does not (the first
  *       ceil(dmin / Dd) pooled columns: their predecessors are the previous row's tail).
  *       Found by running the reference's own text on the host.
+ *   S8  (masks only) ncc_patch_radius r >= 2.  pad_index(g, n) is n - g < 0 for g > n, and the cost kernel
+ *       (ncc_matching_cost_volume_construction.cu:67-76 via device_functions.cuh:64-69) pads x + i and y + j with
+ *       |i|, |j| <= r over the pooled image.  With r <= 1 no g exceeds n.  From r = 2 on, the costs of the pooled rows
+ *       x > h - r read rows -1, -2, ... (before the buffer: undefined), and the costs of the pooled columns y > w - r
+ *       read [x][-1], [x][-2], ..., i.e. the tail of row x - 1: defined and stable, but not the cyclic wrap of S1.
+ *       The oracle keeps S1 there (it does not reproduce the tail reads), so these r - 1 cost rows and r - 1 cost
+ *       columns are outside what the reference pins.  The aggregation
+ *       (multi_block_matching_cost_aggregation.cu:42-48, :58-85) reads rows x - L .. x + L at the centre columns and
+ *       columns y - L .. y + L at the centre rows (L = large_mbm_radius), padded by the same function, so a whole
+ *       tainted row or column enters every window that reaches it, also through the wrap at the top and the left
+ *       (x - L < 0 reaches row h - 1).  so_validity_masks therefore keeps, when r >= 2, only
+ *           L <= x,  x + L + r <= h,  L <= y,  y + L + r <= w
+ *       on top of the terms above (x + L <= h and y + L <= w are implied).  S7 looks `back` pixels behind through the
+ *       same table, so it follows.  For r <= 1 the term is empty and the masks are those of S1-S7.
  */
 #ifndef STEREO_ORACLE_H
 #define STEREO_ORACLE_H

@@ -22,6 +22,24 @@ from oracle_lib import OracleConfig, FP_CONVENTIONS, FP_MIXED_CONVENTIONS, fp_na
 DIR = os.path.join(os.path.dirname(__file__), "golden", "from_reference")
 FILES = sorted(glob.glob(os.path.join(DIR, "*.npz")))
 STAGES = ("gray_left", "down_left", "wta", "refined")
+# a file's `config`: the first five fields (the rest at the reference's defaults, which are OracleConfig's) or all eleven,
+# in the order of the reference's stereo_matching_configuration.hh
+CONFIG_FIELDS = ("height", "width", "downscale_factor", "min_disparity", "max_disparity", "ncc_patch_radius",
+                 "sad_patch_radius", "threshold", "small_mbm_radius", "mid_mbm_radius", "large_mbm_radius")
+
+
+def oracle_config(config, conv=0):
+    values = [int(v) for v in config]
+    assert len(values) in (5, len(CONFIG_FIELDS)), f"a config of {len(values)} entries"
+    return OracleConfig(fp_convention=conv, **dict(zip(CONFIG_FIELDS, values)))
+
+
+def _all_fields(path):
+    with np.load(path) as z:
+        return z["config"].size == len(CONFIG_FIELDS)
+
+
+ALL_FIELD_FILES = [p for p in FILES if _all_fields(p)]      # produced under non-default radii and threshold
 
 
 def classify(z, orc):
@@ -31,8 +49,7 @@ def classify(z, orc):
     with no convention), report[name] the max |difference| per stage.  The six plain conventions (one pattern for step 1
     and the parabola alike) are tried first; only a file that none of them reproduces is tried against the mixed ones
     (a compiler chooses per expression: oracle_lib.FP_MIXED_CONVENTIONS)."""
-    H, W, K, dmin, dmax = (int(v) for v in z["config"])
-    cfg = OracleConfig(height=H, width=W, downscale_factor=K, min_disparity=dmin, max_disparity=dmax)
+    cfg = oracle_config(z["config"])
     md, mf = orc.masks(cfg)
     report, matching = {}, []
     for conv, name in list(FP_CONVENTIONS.items()) + list(FP_MIXED_CONVENTIONS.items()):
@@ -111,13 +128,17 @@ def test_reference_files_follow_the_schema():
         assert z["out"].shape == (H, W) and z["left"].shape in ((3, H, W), (H, W)), f
 
 
+def _engine(cfg, **kwargs):
+    """An engine with all eleven fields of cfg and its floating-point convention."""
+    import cuda_depth
+    return cuda_depth.StereoMatching(cuda_depth.StereoMatchingConfiguration(**{f: getattr(cfg, f) for f in CONFIG_FIELDS}),
+                                     fp_convention=cfg.fp_convention, **kwargs)
+
+
 def _hip_run(cfg, left, right, stages=()):
     import torch
-    import cuda_depth
     from cuda_depth import _native as N
-    sm = cuda_depth.StereoMatching(cuda_depth.StereoMatchingConfiguration(
-        height=cfg.height, width=cfg.width, downscale_factor=cfg.downscale_factor,
-        min_disparity=cfg.min_disparity, max_disparity=cfg.max_disparity), fp_convention=cfg.fp_convention)
+    sm = _engine(cfg)
     l, r = torch.from_numpy(left).cuda(), torch.from_numpy(right).cuda()
     got = {"out": (sm.compute_disparity_map(l, r) if l.dim() == 3 else sm.compute_disparity_map_gray(l, r)).cpu().numpy()}
     ids = {"gray_left": N.STAGE_GRAY_LEFT, "down_left": N.STAGE_DOWN_LEFT, "wta": N.STAGE_WTA, "refined": N.STAGE_REFINED}
@@ -183,3 +204,93 @@ def test_hip_path_against_outputs_of_the_reference(path, oracle):
         m = mf if want.shape == mf.shape else md
         bad = int(np.count_nonzero(got[st][m] != want[m]))
         assert bad == 0, f"{path}: stage {st} differs from the reference in {bad} masked pixels under convention {fp_name(cfg.fp_convention)}"
+
+
+# ---- files produced under non-default ncc / sad radii, threshold and aggregation radii --------------------------------
+_CLASSIFIED = {}
+
+
+def _classified(path, oracle):
+    """(arrays of the file, cfg under the convention it follows, (mask_down, mask_full)), computed once per file."""
+    if path not in _CLASSIFIED:
+        with np.load(path) as f:
+            z = _Case({k: f[k] for k in f.files})
+        matching, report, cfg, masks = classify(z, oracle)
+        assert matching, f"{path}: the reference's output matches no floating-point convention of the oracle: {report}"
+        _CLASSIFIED[path] = (z, cfg, masks)
+    return _CLASSIFIED[path]
+
+
+_IDS = [os.path.basename(p)[:-4] for p in ALL_FIELD_FILES]
+
+
+def test_the_files_under_non_default_fields_are_there():
+    """Six of them, every one of the six fields away from its default somewhere, ncc_patch_radius on both sides of 2
+    (stereo_oracle.h, safe rule S8), one integer-valued (the uint8 entry needs it)."""
+    configs = [np.load(p)["config"] for p in ALL_FIELD_FILES]
+    assert len(configs) == 6
+    default = OracleConfig()
+    for i, f in enumerate(CONFIG_FIELDS[5:], 5):
+        assert any(int(c[i]) != getattr(default, f) for c in configs), f
+    assert {int(c[5]) for c in configs} >= {0, 1, 2, 3}
+    assert sum(_integer_valued(np.load(p)) for p in ALL_FIELD_FILES) == 1
+
+
+def _integer_valued(z):
+    return bool(np.all(z["left"] == np.rint(z["left"])) and np.all(z["right"] == np.rint(z["right"])))
+
+
+def _other_pair(z, cfg, index):
+    """A seeded float32 pair of the file's shape and kind (its neighbours in a batch)."""
+    D = cfg.max_disparity + 1
+    if z["left"].ndim == 3:
+        l, r = syn.random_rgb_pair(cfg.height, cfg.width, D, cfg.downscale_factor, index, dmin=cfg.min_disparity)
+    else:
+        l, r = syn.make_pair(cfg.height, cfg.width, D, cfg.downscale_factor, index, dmin=cfg.min_disparity)[:2]
+    return np.ascontiguousarray(l, np.float32), np.ascontiguousarray(r, np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ALL_FIELD_FILES, ids=_IDS)
+def test_batch_entry_against_outputs_of_the_reference(path, oracle):
+    """The file's pair as the middle of a batch of three: its map equals the file bit for bit inside the mask, and the
+    two seeded pairs around it come out as from single-pair calls, everywhere.  Non-default radii lie outside the fast
+    kernel's envelope: every call reports exact_order."""
+    torch = pytest.importorskip("torch")
+    z, cfg, (_, mf) = _classified(path, oracle)
+    pairs = [_other_pair(z, cfg, 401), (z["left"], z["right"]), _other_pair(z, cfg, 402)]
+    sm = _engine(cfg, max_batch=3)
+    left = torch.from_numpy(np.stack([p[0] for p in pairs])).cuda()
+    right = torch.from_numpy(np.stack([p[1] for p in pairs])).cuda()
+    got = sm.compute_disparity_map_batch(left, right).cpu().numpy()
+    assert sm.last_match_mode() == "exact_order"
+    bad = int(np.count_nonzero(got[1][mf] != z["out"][mf]))
+    assert bad == 0, f"{path}: the middle pair of the batch differs from the reference in {bad} of {int(mf.sum())} masked pixels"
+    single = sm.compute_disparity_map if left.dim() == 4 else sm.compute_disparity_map_gray
+    for i in (0, 1, 2):
+        alone = single(left[i], right[i]).cpu().numpy()
+        assert sm.last_match_mode() == "exact_order"
+        assert np.array_equal(got[i].view(np.uint32), alone.view(np.uint32)), f"{path}: pair {i} of the batch"
+
+
+_INTEGER_FILES = [p for p in ALL_FIELD_FILES if _integer_valued(np.load(p))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", _INTEGER_FILES, ids=[os.path.basename(p)[:-4] for p in _INTEGER_FILES])
+def test_uint8_entry_against_outputs_of_the_reference(path, oracle):
+    """The integer-valued file through the uint8 entries (single pair, and a batch of one): equal to the file bit for
+    bit inside the mask."""
+    torch = pytest.importorskip("torch")
+    z, cfg, (_, mf) = _classified(path, oracle)
+    sm = _engine(cfg)
+    l, r = torch.from_numpy(z["left"]).to(torch.uint8).cuda(), torch.from_numpy(z["right"]).to(torch.uint8).cuda()
+    assert np.array_equal(l.cpu().numpy().astype(np.float32), z["left"])
+    single = sm.compute_disparity_map if l.dim() == 3 else sm.compute_disparity_map_gray
+    got = single(l, r).cpu().numpy()
+    assert sm.last_match_mode() == "exact_order"
+    bad = int(np.count_nonzero(got[mf] != z["out"][mf]))
+    assert bad == 0, f"{path}: the uint8 entry differs from the reference in {bad} of {int(mf.sum())} masked pixels"
+    got = sm.compute_disparity_map_batch(l[None], r[None]).cpu().numpy()[0]
+    assert sm.last_match_mode() == "exact_order"
+    assert np.array_equal(got[mf], z["out"][mf])

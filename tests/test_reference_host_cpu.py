@@ -9,7 +9,9 @@ oracle/_ref/libref_host.so; tests/golden/from_reference/*.npz are its outputs on
   against the live library (skipped, with the reason, where oracle/_ref/libref_host.so has not been built -- it needs
   the reference tree): the files are current; the masks lie inside the set of pixels that does not depend on what
   uninitialised and out-of-bounds memory holds or on the order in which threads run; a real compiler's own contractions
-  are among the conventions; the stand-in runtime's barrier and accessor behave.
+  are among the conventions; the stand-in runtime's barrier and accessor behave; for the cases under non-default radii
+  and threshold the oracle's aggregated cost volume equals the library's inside the pooled mask, and a seeded sweep of
+  configurations over all six of those fields finds no masked value unstable or different.
 
 Figures of the run that produced the committed files (share of pixels; "stable" = bit-identical in all 8 runs of poison
 {0, NaN, +1e30, -1e30} x order {forward, reverse}; mask and stable are those of `out`):
@@ -23,6 +25,19 @@ Figures of the run that produced the committed files (share of pixels; "stable" 
     k3_72x96_d6_41_rgb_float           0.392  0.557   0.166
     k4_96x128_d8_71_rgb_int            0.390  0.565   0.175
     k2_65x96_d0_31_gray_int            0.231  0.318   0.087
+
+The six cases under non-default ncc / sad radii, threshold and aggregation radii (name suffix
+_r<ncc>_<sad>_<threshold>_<small>_<mid>_<large>); "before S8" is what the masks without safe rule S8 (stereo_oracle.h)
+gave on the same runs: their share, the masked values of `out` that are unstable, and the stable masked values of
+`refined` / `out` where the oracle differs from the reference:
+
+    case                                         mask   stable  stable but unmasked   before S8
+    k2_64x96_d0_31_rgb_float_r0_3_0_0_2_4        0.716  0.871   0.155                 the same mask
+    k1_64x96_d4_27_gray_float_r1_8_11_3_8_12     0.716  0.814   0.098                 the same mask
+    k3_72x108_d6_41_rgb_float_r1_5_5_6_6_6       0.593  0.704   0.111                 the same mask
+    k2_96x160_d0_31_gray_float_r2_3_2_2_3_5      0.558  0.761   0.203                 0.732, 1722 unstable, 1 / 3 differ
+    k1_64x96_d5_36_gray_float_r2_6_3_3_3_8       0.589  0.729   0.140                 0.807, 878 unstable, 311 / 271 differ
+    k4_128x192_d8_71_gray_int_r3_4_8_0_1_4       0.498  0.672   0.174                 0.728, 3257 unstable, 103 / 1618 differ
 """
 import functools
 import importlib.util
@@ -34,6 +49,7 @@ import pytest
 import build_ref
 import oracle_lib
 import stereo_numpy
+import stereo_synthetic as syn
 import test_from_reference as tfr
 from oracle_lib import OracleConfig, fp_mixed
 
@@ -45,7 +61,8 @@ _spec.loader.exec_module(mfr)
 CASES = list(mfr.CASES)
 ALL_STAGES = ("out",) + mfr.STAGES
 POISONS = (0.0, float("nan"), 1e30, -1e30)
-FLOAT_RGB = [n for n in CASES if mfr.CASES[n][5] in ("rgb_float", "rgb_noise_float")]
+NEW_CASES = list(mfr.ALL_FIELDS)          # produced under non-default values of the six fields after max_disparity
+FLOAT_RGB = [n for n in mfr.DEFAULT_FIELDS if mfr.CASES[n][5] in ("rgb_float", "rgb_noise_float")]
 
 live = pytest.mark.skipif(not build_ref.RefHost.built(),
                           reason="oracle/_ref/libref_host.so is not built (build() makes it where the reference tree exists)")
@@ -70,8 +87,7 @@ def _eight_runs(name):
 
 
 def _cfg(name, conv=0):
-    H, W, K, dmin, dmax = mfr.CASES[name][:5]
-    return OracleConfig(height=H, width=W, downscale_factor=K, min_disparity=dmin, max_disparity=dmax, fp_convention=conv)
+    return tfr.oracle_config(mfr.config_of(name), conv)
 
 
 def _bits(a):
@@ -94,12 +110,15 @@ def _assert_bitwise(name, who, got, want, md, mf):
 
 # ---- against the committed files -------------------------------------------------------------------------------------
 def test_the_committed_files_are_the_eight_cases():
+    """... and the six produced under non-default fields, whose `config` has all eleven entries."""
+    assert len(mfr.DEFAULT_FIELDS) == 8 and len(NEW_CASES) == 6
     have = sorted(os.path.basename(f)[:-4] for f in tfr.FILES)
     assert have == sorted(CASES)
     for name in CASES:
         z = _file(name)
         assert {"left", "right", "config", "out"} | set(mfr.STAGES) <= set(z)
         assert np.array_equal(z["config"], mfr.config_of(name))
+        assert z["config"].size == (11 if name in NEW_CASES else 5)
         assert z["left"].ndim == (3 if mfr.CASES[name][5].startswith("rgb") else 2)
         integer = bool(np.all(z["left"] == np.rint(z["left"])) and np.all(z["right"] == np.rint(z["right"])))
         assert integer == mfr.CASES[name][5].endswith("int"), name
@@ -138,9 +157,10 @@ def test_rule_s7_takes_the_pixels_whose_lookups_reach_undefined_costs(oracle):
     """dmin > 0: a pixel's Q5 lookups reach ceil(dmin / Dd) pixels back in row-major order, so a pixel is in the mask
     only if those lie where the aggregated costs are defined (S7).  A pixel's predecessors in its own row are defined
     when it is; those of the first columns are the previous row's tail, which never is (y + L > w).  So the mask is that
-    of the same range starting at 0, without its first ceil(dmin / Dd) columns -- and dmin = 0 loses nothing."""
+    of the same range starting at 0, without its first ceil(dmin / Dd) columns -- and dmin = 0 loses nothing.  (The
+    cases at the reference's default radii; test_masks_for_ncc_radius_of_2_and_more_only_shrink has S7 under S8.)"""
     seen = set()
-    for name in CASES:
+    for name in mfr.DEFAULT_FIELDS:
         cfg = _cfg(name)
         md, _ = oracle.masks(cfg)
         d = oracle.dims(cfg)
@@ -171,6 +191,98 @@ def test_a_mixed_convention_is_two_plain_ones(oracle):
     bad = _cfg(name, 6 | (1 << 3))
     with pytest.raises(RuntimeError):
         oracle.dims(bad)
+
+
+# ---- the masks under ncc_patch_radius (safe rule S8) -----------------------------------------------------------------
+def _masks_restated(cfg, d, s8):
+    """so_validity_masks restated in NumPy: the formula of S1-S7 as it stood before S8 (s8=False), and with S8 in its
+    closed form (s8=True: for r >= 2 the aggregated costs are defined only for L <= x, x + L + r <= h, L <= y,
+    y + L + r <= w).  The C function derives S8 another way (it marks the cost rows and columns that pad_index sends
+    out of the image and every window that reaches one), so the two check each other."""
+    H, W, K, h, w = d.H, d.W, d.K, d.h, d.w
+    r, R, L = cfg.ncc_patch_radius, cfg.sad_patch_radius, cfg.large_mbm_radius
+    md = np.zeros((h, w), bool)
+    if W % K == 0 and d.dmax + r <= w and L + r < h and L + r < w:
+        x, y = np.arange(h)[:, None], np.arange(w)[None, :]
+        row_taint = np.zeros(h, bool)
+        if H % K:
+            for i in range(-(L + r), L + r + 1):
+                row_taint |= (np.arange(h) + i) % h == h - 1
+        agg_ok = ~row_taint[:, None] & (x + L <= h) & (y + L <= w)
+        if s8 and r >= 2:
+            agg_ok &= (x >= L) & (x + L + r <= h) & (y >= L) & (y + L + r <= w)
+        md = agg_ok & (x * K + R <= H) & (y * K + R + K <= W)
+        pix = x * w + y
+        if d.dmin > 0:
+            md &= pix * d.Dd - d.dmin >= 0
+            for b in range(1, -(-d.dmin // d.Dd) + 1):
+                md &= agg_ok.ravel()[np.maximum(pix - b, 0)]       # pix - b >= 0 wherever md still holds
+    mf = np.zeros((H, W), bool)
+    c0 = np.arange(W) // K
+    live = c0 * K + K < W
+    c0, c1 = np.where(live, c0, 0), np.where(live, c0 + 1, 0)
+    for X in range(H):
+        x, i = divmod(X, K)
+        if (x == 0 and i > 0) or (i > 0 and (K + 1) * x >= H):
+            continue
+        mf[X] = live & md[x, c0] & md[x, c1]
+        if i > 0:
+            mf[X] &= md[x - 1, c0] & md[x - 1, c1]
+    return md, mf
+
+
+def _mask_configs(n, ncc_values, seed):
+    """Seeded configurations over all eleven fields, small enough that most masks are not empty and some are."""
+    rng = np.random.default_rng(seed)
+    for _ in range(n):
+        K = int(rng.integers(1, 5))
+        r = int(rng.choice(ncc_values))
+        L = int(rng.integers(0, 13))
+        h = int(rng.integers(max(8, L + r + 1), 2 * (L + r) + 30))
+        w = int(rng.integers(max(8, L + r + 1), 2 * (L + r) + 40))
+        H = h * K - (int(rng.integers(0, K)) if rng.random() < 0.3 else 0)
+        W = w * K - (int(rng.integers(0, K)) if rng.random() < 0.1 else 0)
+        dmin = int(rng.integers(0, 3 * K * 8)) if rng.random() < 0.5 else 0
+        dmax = dmin + int(rng.integers(0, K * 16))
+        yield OracleConfig(height=H, width=W, downscale_factor=K, min_disparity=dmin, max_disparity=dmax,
+                           ncc_patch_radius=r, sad_patch_radius=int(rng.integers(0, 9)), threshold=int(rng.integers(0, 12)),
+                           small_mbm_radius=int(rng.integers(0, L + 1)), mid_mbm_radius=int(rng.integers(0, L + 1)),
+                           large_mbm_radius=L)
+
+
+def test_masks_for_ncc_radius_up_to_1_are_what_they_were(oracle):
+    """S8 is empty for ncc_patch_radius <= 1: over 120 seeded configurations the masks equal, pixel for pixel, the
+    formula of S1-S7 restated in NumPy."""
+    kept = empty = 0
+    for cfg in _mask_configs(120, (0, 1), 8801):
+        md, mf = oracle.masks(cfg)
+        want_md, want_mf = _masks_restated(cfg, oracle.dims(cfg), s8=False)
+        assert np.array_equal(md, want_md) and np.array_equal(mf, want_mf), cfg
+        kept += bool(mf.any())
+        empty += not md.any()
+    assert kept >= 50 and empty >= 5, (kept, empty)
+
+
+def test_masks_for_ncc_radius_of_2_and_more_only_shrink(oracle):
+    """ncc_patch_radius >= 2: the masks equal the formula of S1-S7 with S8's closed form on the aggregated costs, lie
+    inside the masks of S1-S7 alone, and lose something nearly wherever those kept anything (not always: the SAD radius
+    or the S7 columns may have taken the same pixels already).  S7 under S8: with dmin > 0 the
+    first ceil(dmin / Dd) kept columns go as well (their predecessors are columns < L, which S8 takes)."""
+    kept = lost = with_back = 0
+    for cfg in _mask_configs(120, (2, 3, 4, 5, 8), 8802):
+        md, mf = oracle.masks(cfg)
+        d = oracle.dims(cfg)
+        want_md, want_mf = _masks_restated(cfg, d, s8=True)
+        assert np.array_equal(md, want_md) and np.array_equal(mf, want_mf), cfg
+        old_md, old_mf = _masks_restated(cfg, d, s8=False)
+        assert not (md & ~old_md).any() and not (mf & ~old_mf).any(), cfg
+        lost += bool((old_md & ~md).any())
+        kept += bool(mf.any())
+        if md.any() and d.dmin > 0:
+            back = -(-d.dmin // d.Dd)
+            assert int(np.flatnonzero(md.any(axis=0))[0]) == cfg.large_mbm_radius + back, cfg
+            with_back += 1
+    assert kept >= 50 and lost >= kept and with_back >= 10, (kept, lost, with_back)
 
 
 # ---- against the live library ----------------------------------------------------------------------------------------
@@ -204,6 +316,90 @@ def test_the_masks_lie_inside_the_stable_set(oracle, name):
                                    f"thread order, first at {tuple(int(v) for v in np.argwhere(escaped)[0])}")
     if mfr.CASES[name][5].startswith("gray"):
         assert np.array_equal(_bits(runs[0]["gray_left"]), _bits(runs[0]["left"]))
+
+
+@live
+@pytest.mark.parametrize("name", NEW_CASES)
+def test_aggregated_costs_equal_the_reference_inside_the_pooled_mask(oracle, name):
+    """The files hold no agg_volume (too large); live, the oracle's equals the reference's at every disparity of every
+    pooled pixel of the pooled mask.  This is the buffer S8 is about: wta and refined can agree where costs differ."""
+    fresh = mfr.generate(name, _ref(), volumes=True)
+    cfg = _cfg(name)
+    md, _ = oracle.masks(cfg)
+    _, im = oracle.run(cfg, fresh["left"], fresh["right"], intermediates=True, volumes=True)
+    bad = (_bits(im["agg_volume"]) != _bits(fresh["agg_volume"])).any(axis=2) & md
+    assert md.any()
+    assert not bad.any(), (f"{name}: the aggregated costs of {int(bad.sum())} of {int(md.sum())} masked pooled pixels differ, "
+                           f"first at {tuple(int(v) for v in np.argwhere(bad)[0])}")
+
+
+def _sweep_configs(n=18, seed=8803):
+    """Seeded configurations over all six fields after max_disparity: ncc 0..4, sad 1..8, threshold 0..11, small and
+    mid <= large in 2..12; K in 1..4, H % K != 0 and dmin > 0 sometimes; large + ncc below both pooled dimensions and
+    dmax / K + ncc at most the pooled width; images of 40-130 pixels a side."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        K = int(rng.integers(1, 5))
+        r = int(rng.integers(0, 5))
+        side = 130 // K                                            # largest pooled side
+        L = int(rng.integers(2, min(12, (side - 6) // 2 - r) + 1))
+        ragged = K > 1 and rng.random() < 0.35                     # H % K != 0 taints the L + r rows around the last one
+        dmin_p = int(rng.integers(1, 7)) if i % 2 else 0            # dmin > 0 in every other one
+        dd_p = int(rng.integers(6, 17))
+        h = int(rng.integers(max(2 * (L + r) + 6, -(-40 // K)), side + 1))
+        w_low = max(2 * L + r + 8, dmin_p + dd_p + r, -(-40 // K))
+        w = int(rng.integers(w_low, max(w_low, side) + 1))
+        H = h * K - (int(rng.integers(1, K)) if ragged else 0)
+        dmin = dmin_p * K + (int(rng.integers(0, K)) if dmin_p else 0)
+        dmax = (dmin_p + dd_p - 1) * K + int(rng.integers(0, K))
+        out.append((H, w * K, K, dmin, dmax, r, int(rng.integers(1, 9)), int(rng.integers(0, 12)),
+                    int(rng.integers(0, L + 1)), int(rng.integers(0, L + 1)), L))
+    return out
+
+
+SWEEP = _sweep_configs()
+
+
+def test_the_sweep_covers_what_it_says():
+    assert len(SWEEP) >= 16
+    assert {c[5] for c in SWEEP} == {0, 1, 2, 3, 4} and sum(c[5] >= 2 for c in SWEEP) >= 6
+    assert {c[2] for c in SWEEP} == {1, 2, 3, 4}
+    assert any(c[0] % c[2] for c in SWEEP) and sum(c[3] > 0 for c in SWEEP) == len(SWEEP) // 2
+    for H, W, K, dmin, dmax, r, R, thr, small, mid, L in SWEEP:
+        h, w = -(-H // K), W // K
+        assert 37 <= H <= 130 and 40 <= W <= 136 and W % K == 0, (H, W)
+        assert L + r < h and L + r < w and dmax // K + r <= w and small <= L and mid <= L and 2 <= L <= 12
+
+
+@live
+@pytest.mark.parametrize("config", SWEEP, ids=["-".join(str(v) for v in c) for c in SWEEP])
+def test_sweep_of_all_six_fields_against_the_live_reference(oracle, config):
+    """Four runs of the reference (poison 0, NaN, +1e30, -1e30; order forward, reverse, forward, reverse) on a seeded
+    gray pair with fractional samples: inside the masks no value may move between the runs, and the oracle equals them
+    bit for bit in out, down_left, wta, refined and, at the pooled mask, the whole aggregated cost volume."""
+    cfg = tfr.oracle_config(config)
+    H, W, K = config[:3]
+    seed = SWEEP.index(config)
+    l, r = syn.make_pair(H, W, config[4] + 1, K, 500 + seed, dmin=config[3])[:2]
+    l, r = mfr._fraction(l, 1000 + seed), mfr._fraction(r, 2000 + seed)
+    runs = [_ref().run(config, l, r, poison=p, reverse=rev) for p, rev in zip(POISONS, (False, True, False, True))]
+    md, mf = oracle.masks(cfg)
+    assert md.any() and mf.any(), "empty mask"
+    out, im = oracle.run(cfg, l, r, intermediates=True, volumes=True)
+    got = dict(im, out=out)
+    for st in ("out", "down_left", "wta", "refined", "agg_volume"):
+        first = _bits(runs[0][st])
+        moved = np.zeros(first.shape, bool)
+        for run in runs[1:]:
+            moved |= _bits(run[st]) != first
+        differs = _bits(got[st]) != first
+        if st == "agg_volume":
+            moved, differs = moved.any(axis=2), differs.any(axis=2)
+        m = mf if st == "out" else md
+        print(f"{config} {st}: mask {m.mean():.3f} stable {1 - moved.mean():.3f}")
+        assert not (moved & m).any(), f"stage {st}: {int((moved & m).sum())} of {int(m.sum())} masked values depend on poison or order"
+        assert not (differs & m).any(), f"stage {st}: {int((differs & m).sum())} of {int(m.sum())} masked values differ from the reference"
 
 
 @live_fma

@@ -98,12 +98,13 @@ constexpr int MATCH_AUTO_LDS_CAP = 128 * 1024;
 // the raised limit (more than ~780 disparities) take the two gated launches instead
 // th: the band height match_fast_plan chose for this call of n pairs; slices_floats: the floats of this lane's region of
 // the slice buffer (the records of the off-grid branch must fit it)
+// (whether the engine has the buffers at all -- no capture route, no volume, tickets and slices allocated -- is the
+// planner's part of the gate: smx_plan.h)
 inline bool match_auto_small_applicable(const MatchParams &p, int th, int n, size_t slices_floats) {
     const long fast_wgs = (long)((p.w + FA_VALID - 1) / FA_VALID) * ((p.h + th - 1) / th);
     const long tiles = (long)((p.w + E2_TW - 1) / E2_TW) * ((p.h + E2_TH - 1) / E2_TH);
     const size_t lds = p.Dd <= 256 - 64 + 1 ? fast_lds_bytes<256>(th, p.Dd, true) : fast_lds_bytes<320>(th, p.Dd, true);
-    return fast_wgs >= tiles && !p.pass1_only && !p.vol && lds <= (size_t)MATCH_AUTO_LDS_CAP && p.tickets != nullptr && p.slices != nullptr &&
-           match_auto_slice_floats(p, n, th) <= slices_floats;
+    return fast_wgs >= tiles && lds <= (size_t)MATCH_AUTO_LDS_CAP && match_auto_slice_floats(p, n, th) <= slices_floats;
 }
 
 template <int TH, int PR>

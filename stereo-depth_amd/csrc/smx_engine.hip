@@ -31,6 +31,7 @@
 #include "k_refine.h"
 #include "smx_common.h"
 #include "smx_launch.h"
+#include "smx_plan.h"
 #include "smx_route.h"
 #include "smx_status.h"
 
@@ -75,7 +76,7 @@ struct smx_engine {
     smx_config cfg;
     smx_dims dm;
     int B;
-    int cus = 256;                                // multiProcessorCount of the device: launch plans are sized against it
+    smx::EngineFacts facts;                       // what the launch plans depend on (smx_plan.h: derive_facts), fixed after smx_create
     // device buffers (reference device_buffer.hh:12-19, minus the two cost volumes)
     float *gray_l = nullptr, *gray_r = nullptr;   // [B][H][W]  (RGB / u8 entries)
     float *down_l = nullptr, *down_r = nullptr;   // [B][h][w]
@@ -84,26 +85,17 @@ struct smx_engine {
     float *vol = nullptr;                         // [B][h][w][Dd] only when dmin > 0
     float *slices = nullptr;                      // partial arg-max states of the disparity-split exact kernel
     unsigned *tickets = nullptr;                  // [B][exact-order tiles] arrival counters (one-launch AUTO kernel, off-grid branch)
-    int e2_tiles = 0;
-    size_t slices_floats = 0;
     int *flags = nullptr;                         // [2][B]: exact-grid flag, integer-gray flag (== epoch: set)
     int epoch = 0;                                // call counter: flags are stamped, never cleared per call
     uint8_t *gray8_l = nullptr, *gray8_r = nullptr;   // [B][H][pitch8] u8 copies with cyclic aprons
-    int pitch8 = 0, padl = 0, padr = 0;               // 0: integer step-6 kernel not applicable
-    int gpitch = 0, gpadl = 0;                        // row pitch / left-apron width (floats) of gray_l, gray_r
-    bool capture = false;                         // dmin > 0 served by the sparse capture kernels (no aggregated volume)
     unsigned *cand = nullptr;                     // [B][tiles][cw] candidate bits of the filtered exact-order route (all zero between calls)
-    int cand_tiles_x = 0, cand_tiles_y = 0, cand_cw = 0;
-    float filter_two_e = 0.f;                     // twice the filter's error bound, in aggregation units
-    int filter_unit = 0;                          // grid units per gray level of the filter's rounded inputs (>= K^2)
-    bool filter_ok = false;                       // the configuration admits the filtered route (k_match_filter.h)
-    bool fast_ok_host = false;                    // K and radii admit the FAST_GRID kernel
-    bool grid_capable = false;                    // K in {1,2,4,8}: 1/K^2 grid sums are exact
-    bool default_radii = false;                   // ncc 1, block-matching radii 1 / 4 / 10
     smx::ExactPlan xp{};                          // tile chunks, LDS sizes and the slice buffer of the exact-order kernels
-    int last_mode = SMX_MATCH_EXACT_ORDER;
-    int last_n = 0;
-    int last_first = 0;                           // first pair slot of the engine's buffers the last call used
+    // The last call, as smx_get_route_info, smx_get_match_geometry, smx_last_match_mode and smx_get_intermediate see it.
+    struct LastCall {
+        smx::CallFacts call;                      // entry, lanes or caller's stream, the switches' decision
+        smx::RangePlan plan;                      // of the range enqueued last
+        int first = 0;                            // first pair slot of the engine's buffers the call used
+    } last_call;
     int next_small_lane = 0;                      // unsplit engine-stream calls alternate between the lanes
     const float *last_gray_l = nullptr, *last_gray_r = nullptr;   // what steps 6-9 read
     int last_gpitch = 0;
@@ -111,25 +103,17 @@ struct smx_engine {
     size_t last_gplane = 0;
     // environment switches, read once in smx_create
     int opt_lane_priority = 1;                    // SMX_LANE_PRIORITY=0: lane streams at default priority (A/B runs)
-    int opt_fast_dense = -1;                      // SMX_FAST_DENSE=1 / 0: always / never the dense form of the fast kernel (tests, A/B); -1: by content
-    int opt_fast_dense_small = -1;                // SMX_FAST_DENSE_SMALL=1 / 0: the latency shape at 12-row bands always / never takes its dense form (tests, A/B); -1: by content
     bool opt_debug_hints = false;                 // SMX_DEBUG_HINTS: print every report of the sparse fast kernel to stderr
     HostHints *hints = nullptr, *hints_dev = nullptr;     // pinned host memory / its device address
     smx::RouteState route;                        // the content switches (route.filt: filtered / dense exact-order route of RGB batches; route.fast:
                                                   // sparse / dense form of the fast kernel) and the grid hint, with their per-call decision step
     unsigned *stats_dev = nullptr;                // [LANES][2] counters of the sparse kernel
-    bool call_use_filter = true;                  // decision for the call being enqueued (both halves alike)
     unsigned long long *fast_stats_dev = nullptr; // [LANES] device counters of the sparse form's report
-    bool call_fast_dense = false;                 // decision for the call being enqueued
-    bool fast_stats_pending = false;              // the aggregation launch of the half being enqueued reports: its fill launch publishes
-    bool call_on_lanes = false;                   // the call being enqueued runs on the stream lanes
-    int call_grid_hint = -1;                      // f32 gray, few pairs: the last reported call was on (0) / off (1) the exact grid; -1: no report yet
     // opt-in event profiling (smx_profile_begin / _end)
     std::vector<hipEvent_t> prof_events;      // [call][lane][slot][2]
     std::vector<unsigned char> prof_used;     // [call][lane][slot]
     int prof_calls = 0, prof_max = 0;
     bool prof_on = false;
-    int cur_lane = 0;                             // which half of a split call is being enqueued (profile slots)
     // Stream lanes.  With stream = SMX_STREAM_ENGINE a call runs on the engine's own streams, with no
     // ordering against any caller stream until smx_join, so consecutive calls pipeline; a call of at
     // least `overlap_min` pairs is enqueued as two halves (pairs [0, n0) and [n0, n): disjoint slices of
@@ -181,13 +165,13 @@ void free_buffers(smx_engine *e) {
 struct SlotTimer {
     smx_engine *e;
     hipStream_t s;
-    int slot;
+    int lane, slot;
     bool on;
-    SlotTimer(smx_engine *e_, hipStream_t s_, int slot_) : e(e_), s(s_), slot(slot_) {
+    SlotTimer(smx_engine *e_, hipStream_t s_, int lane_, int slot_) : e(e_), s(s_), lane(lane_), slot(slot_) {
         on = e->prof_on && e->prof_calls < e->prof_max;
         if (on) (void)hipEventRecord(e->prof_events[index() * 2], s);
     }
-    size_t index() const { return ((size_t)e->prof_calls * smx_engine::LANES + e->cur_lane) * SMX_KERNEL_SLOTS + slot; }
+    size_t index() const { return ((size_t)e->prof_calls * smx_engine::LANES + lane) * SMX_KERNEL_SLOTS + slot; }
     ~SlotTimer() {
         if (on) {
             (void)hipEventRecord(e->prof_events[index() * 2 + 1], s);
@@ -200,7 +184,7 @@ struct SlotTimer {
 // setting shared by every engine of the process, so it is raised ONCE per device to the fixed cap the
 // engines size their tiles against (never to one engine's own requirement, which a later, smaller
 // engine would lower again).
-constexpr int SMX_EXACT2_LDS_CAP = 80 * 1024;
+using smx::SMX_EXACT2_LDS_CAP;
 hipError_t raise_lds_caps(int device) {
     static std::mutex mu;
     static std::vector<int> done;            // devices already configured
@@ -219,56 +203,6 @@ bool env_is(const char *name, char c) {
     return v && v[0] == c;
 }
 
-// Which form of the fast kernel a call takes (k_match_fast.h DENSE: the pass that keeps the winner's neighbours instead of
-// fetching them in a sparse second pass; min_disparity = 0 only), and -- for the sparse form -- where its second pass reports
-// how much it revisited.  Both shapes that have a dense form follow the same per-call decision (call_fast_dense): the
-// throughput shape (batches) and the latency shape at 12-row bands (single frames).
-struct FastForm {
-    bool has_dense;     // the launch plan of these n pairs has a dense form at all
-    bool tall12;        // ... it is the latency shape at 12-row bands
-    bool reports;       // its sparse form would sample the launch and publish hints->fast_density
-    int stride;         // ... of every stride-th pair
-};
-FastForm fast_form_of(const smx_engine *e, const smx::MatchParams &mp, int n) {
-    FastForm f{};
-    if (mp.pass1_only || mp.Dd > smx::FA_BITWORDS * 32) return f;
-    const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
-    f.tall12 = pl.small && pl.th == smx::FA_TH_SMALL_TALL;
-    if (pl.small && !f.tall12) return f;                    // 8- / 10-row bands: no dense form
-    f.has_dense = true;
-    if (f.tall12 && e->opt_fast_dense_small == 1) return f; // (always dense: never reports)
-    if (!e->fast_stats_dev || !e->hints_dev || e->opt_fast_dense >= 0) return f;
-    // a sample of the launch reports: at most four pairs, and only if their waves fit the counter's 16-bit fields
-    f.stride = n > 4 ? (n + 3) / 4 : 1;
-    const long wgs_pair = f.tall12 ? (long)((mp.w + smx::FA_VALID - 1) / smx::FA_VALID) * ((mp.h + pl.th - 1) / pl.th)      // (an upper bound of the reports per pair)
-                                   : (long)((mp.w + smx::FA_VALID * smx::FA_WAVES - 1) / (smx::FA_VALID * smx::FA_WAVES)) * ((mp.h + 23) / 24) * smx::FA_WAVES;
-    if (((n + f.stride - 1) / f.stride) * wgs_pair >= (1L << 23)) return f;   // (the counter's 24-bit window field)
-    f.reports = true;
-    return f;
-}
-void plan_fast_form(smx_engine *e, smx::MatchParams &mp, int n) {
-    mp.dense = mp.dense_small = 0;
-    const FastForm f = fast_form_of(e, mp, n);
-    if (!f.has_dense) return;
-    const bool dense = f.tall12 && e->opt_fast_dense_small >= 0 ? e->opt_fast_dense_small == 1 : e->call_fast_dense;
-    if (dense) {
-        (f.tall12 ? mp.dense_small : mp.dense) = 1;
-        return;
-    }
-    if (!f.reports) return;
-    mp.fast_stats = e->fast_stats_dev + e->cur_lane;
-    mp.fast_stride = f.stride;
-    e->fast_stats_pending = true;            // ... published by this call's fill launch (enqueue_range)
-}
-
-// FAST_GRID aggregation: the wave-per-window kernel (short bands / disparity split for few pairs in flight,
-// right-tile chunks for wide ranges).
-void launch_fast(smx_engine *e, const smx::MatchParams &mp_in, int n, hipStream_t s) {
-    smx::MatchParams mp = mp_in;
-    plan_fast_form(e, mp, n);
-    smx::launch_match_fast(mp, n, e->cus, s);
-}
-
 // The engine's per-pair buffers as seen from pair `first`: a half of a split call works on a disjoint slice
 // of every buffer (plane strides stay those of the whole engine: `B` pairs).
 struct PairView {
@@ -279,10 +213,11 @@ struct PairView {
 };
 PairView view_from(const smx_engine *e, int first) {
     const smx_dims &d = e->dm;
+    const smx::EngineFacts &ef = e->facts;
     const size_t f = (size_t)first, hw = (size_t)d.h * d.w;
     PairView v{};
-    v.gray_l = e->gray_l + f * d.H * e->gpitch;
-    v.gray_r = e->gray_r + f * d.H * e->gpitch;
+    v.gray_l = e->gray_l + f * d.H * ef.gpitch;
+    v.gray_r = e->gray_r + f * d.H * ef.gpitch;
     v.down_l = e->down_l + f * hw;
     v.down_r = e->down_r + f * hw;
     v.wta = e->wta + f * hw;
@@ -291,22 +226,10 @@ PairView view_from(const smx_engine *e, int first) {
     v.vol = e->vol ? e->vol + f * hw * d.Dd : nullptr;
     v.flags = e->flags + first;
     v.flags2 = e->flags + e->B + first;
-    v.gray8_l = e->gray8_l ? e->gray8_l + f * d.H * e->pitch8 : nullptr;
-    v.gray8_r = e->gray8_r ? e->gray8_r + f * d.H * e->pitch8 : nullptr;
-    v.cand = e->cand ? e->cand + f * e->cand_tiles_x * e->cand_tiles_y * e->cand_cw : nullptr;
+    v.gray8_l = e->gray8_l ? e->gray8_l + f * d.H * ef.pitch8 : nullptr;
+    v.gray8_r = e->gray8_r ? e->gray8_r + f * d.H * ef.pitch8 : nullptr;
+    v.cand = e->cand ? e->cand + f * ef.cand_tiles_x * ef.cand_tiles_y * ef.cand_cw : nullptr;
     return v;
-}
-
-void launch_prologue(const smx_engine *e, int in_mode, const PairView &v, const void *l, const void *r, float *gl, float *gr,
-                     int n, hipStream_t s) {
-    const smx_dims &d = e->dm;
-    smx::PrologueArgs a{};
-    a.left = l; a.right = r; a.gray_l = gl; a.gray_r = gr; a.down_l = v.down_l; a.down_r = v.down_r;
-    a.flags = v.flags; a.flags2 = v.flags2; a.g8_l = v.gray8_l; a.g8_r = v.gray8_r;
-    a.H = d.H; a.W = d.W; a.K = d.K; a.h = d.h; a.w = d.w; a.grid_capable = e->grid_capable ? 1 : 0;
-    a.pitch8 = e->pitch8; a.padl = e->padl; a.padr = e->padr; a.epoch = e->epoch; a.gpitch = e->gpitch; a.gpadl = e->gpadl;
-    a.fp_conv = SMX_FP_STEP1(e->cfg.fp_convention);
-    smx::launch_prologue(in_mode, a, n, s);
 }
 
 // Orders `s` behind everything the engine has enqueued on its own streams (SMX_STREAM_ENGINE calls).
@@ -337,90 +260,38 @@ void read_hints(smx_engine *e) {
     const bool was_dense = e->route.fast.on;
     if (e->route.read_hints(*e->hints) && e->opt_debug_hints)
         std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", e->route.fast.last, was_dense ? 1 : 0);
-    e->call_grid_hint = e->route.grid_hint;
-}
-
-// The aggregation kernel(s) a call of this entry enqueues: SMX_MATCH_EXACT_ORDER, SMX_MATCH_FAST_GRID, or SMX_MATCH_AUTO
-// when both are enqueued and the device-side grid flag selects.
-int call_match_mode(const smx_engine *e, int in_mode) {
-    int mode = e->cfg.match_mode;
-    if (e->vol) mode = SMX_MATCH_EXACT_ORDER;
-    if (mode == SMX_MATCH_AUTO) {
-        if (!e->fast_ok_host) mode = SMX_MATCH_EXACT_ORDER;
-        else if (in_mode == smx::IN_GRAY_U8) mode = SMX_MATCH_FAST_GRID;   // u8 is on the grid
-        // gray computed from RGB (0.2989 R + 0.5870 G + 0.1140 B in float32) is practically never on the
-        // grid, not even for R = G = B: do not enqueue the fast kernel as a gated alternative at all (the
-        // exact-order kernel is correct for any input, so this is a launch saved, never a different result)
-        else if (in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8) mode = SMX_MATCH_EXACT_ORDER;
-    }
-    return mode;
-}
-
-// The plan-relevant fields of a call's aggregation launches (enqueue_range fills in the buffers).
-smx::MatchParams plan_params(const smx_engine *e) {
-    const smx_dims &d = e->dm;
-    smx::MatchParams mp{};
-    mp.B = e->B; mp.h = d.h; mp.w = d.w; mp.dmin = d.dmin; mp.Dd = d.Dd;
-    mp.on_lanes = e->call_on_lanes ? 1 : 0;
-    mp.pass1_only = e->capture ? 1 : 0;
-    return mp;
-}
-// The filtered exact-order route serves a range of n pairs of this call (when the call's decision is "filtered").
-bool filter_serves(const smx_engine *e, int mode, bool rgb_in, bool small) {
-    return mode == SMX_MATCH_EXACT_ORDER && e->filter_ok && rgb_in && !small && e->default_radii;
-}
-
-// Which of the two content switches a call can report to on its default route, from the launch plans of its range(s)
-// (n1 = 0: an unsplit call).  A switch follows, and is probed by, calls of its own kind only.
-smx::CallKind call_kind(const smx_engine *e, int in_mode, int n0, int n1) {
-    smx::CallKind k{};
-    if (e->cfg.match_mode == SMX_MATCH_FAST_GRID && (!e->fast_ok_host || e->vol)) return k;     // (refused by enqueue_range)
-    const int mode = call_match_mode(e, in_mode);
-    const bool rgb_in = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
-    const smx::MatchParams mp = plan_params(e);
-    for (int n : {n0, n1}) {
-        if (n < 1) continue;
-        if (mode == SMX_MATCH_EXACT_ORDER) {
-            const bool small = smx::match_fast_plan(mp, n, e->cus).small;
-            if (filter_serves(e, mode, rgb_in, small) && e->stats_dev && e->hints_dev) k.filter_reports = true;
-        } else if (fast_form_of(e, mp, n).reports) {
-            k.fast_reports = true;
-        }
-    }
-    return k;
 }
 
 // The 9 steps of stereo_matching.cc:22-43 as 4 (AUTO: 5) launches on stream `s`, for the n pairs that start
-// at pair `first` of the engine's buffers (left / right / out already point at that pair).
-int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call, const void *left, const void *right,
-                  float *out, hipStream_t s) {
+// at pair `first` of the engine's buffers (left / right / out already point at that pair), as plan `pl` says
+// (smx_plan.h: plan_range); `lane`: the stream lane's report words, slice region and profile slots.
+int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePlan &pl, int lane, int first, int n,
+                  const void *left, const void *right, float *out, hipStream_t s) {
     const smx_dims &d = e->dm;
+    const smx::EngineFacts &f = e->facts;
     const PairView v = view_from(e, first);
     // full-resolution gray as steps 6-9 see it: column 0 of row 0 of pair 0, row pitch, pair stride
-    const float *gl, *gr;
-    int gpitch = d.W;
-    size_t gplane = (size_t)d.H * d.W;
-    bool apron = false;
+    const float *gl = pl.owns_gray ? v.gray_l + f.gpadl : (const float *)left;
+    const float *gr = pl.owns_gray ? v.gray_r + f.gpadl : (const float *)right;
+    const int gpitch = pl.owns_gray ? f.gpitch : d.W;
+    const size_t gplane = (size_t)d.H * gpitch;
     {
-    SlotTimer tm(e, s, SMX_KERNEL_PROLOGUE);
-    if (in_mode == smx::IN_GRAY_F32) {
-        gl = (const float *)left;
-        gr = (const float *)right;
-        launch_prologue(e, in_mode, v, left, right, nullptr, nullptr, n, s);
-    } else {
-        gl = v.gray_l + e->gpadl;
-        gr = v.gray_r + e->gpadl;
-        gpitch = e->gpitch;
-        gplane = (size_t)d.H * e->gpitch;
-        apron = e->gpadl > 0 && in_mode != smx::IN_GRAY_U8;   // the u8 gray prologue writes no float aprons
-        launch_prologue(e, in_mode, v, left, right, v.gray_l, v.gray_r, n, s);
-    }
+        SlotTimer tm(e, s, lane, SMX_KERNEL_PROLOGUE);
+        smx::PrologueArgs a{};
+        a.left = left; a.right = right; a.gray_l = pl.owns_gray ? v.gray_l : nullptr; a.gray_r = pl.owns_gray ? v.gray_r : nullptr;
+        a.down_l = v.down_l; a.down_r = v.down_r;
+        a.flags = v.flags; a.flags2 = v.flags2; a.g8_l = v.gray8_l; a.g8_r = v.gray8_r;
+        a.H = d.H; a.W = d.W; a.K = d.K; a.h = d.h; a.w = d.w; a.grid_capable = f.grid_capable ? 1 : 0;
+        a.pitch8 = f.pitch8; a.padl = f.padl; a.padr = f.padr; a.epoch = e->epoch; a.gpitch = f.gpitch; a.gpadl = f.gpadl;
+        a.fp_conv = SMX_FP_STEP1(e->cfg.fp_convention);
+        smx::launch_prologue(call.in_mode, a, n, s);
     }
     e->last_gray_l = gl - (size_t)first * gplane;         // of pair 0 of the call
     e->last_gray_r = gr - (size_t)first * gplane;
-    e->last_gray_owned = in_mode != smx::IN_GRAY_F32;
+    e->last_gray_owned = pl.owns_gray;
     e->last_gpitch = gpitch;
     e->last_gplane = gplane;
+    if (pl.status != SMX_OK) return fail(pl.status, "%s", pl.refusal);
 
     smx::MatchParams mp{};
     mp.Ld = v.down_l; mp.Rd = v.down_r; mp.wta = v.wta; mp.costs = v.costs; mp.vol = v.vol;
@@ -428,100 +299,90 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     mp.rn = (int)e->cfg.ncc_patch_radius; mp.rs = e->cfg.small_mbm_radius;
     mp.rm = e->cfg.mid_mbm_radius; mp.rl = e->cfg.large_mbm_radius;
     mp.unit = (float)(d.K * d.K);
-    mp.on_lanes = e->call_on_lanes ? 1 : 0;
-    mp.tickets = e->tickets ? e->tickets + (size_t)first * e->e2_tiles : nullptr;
-
-    int mode = e->cfg.match_mode;
-    if (mode == SMX_MATCH_FAST_GRID && !e->fast_ok_host)
-        return fail(SMX_ERR_UNSUPPORTED,
-                    "SMX_MATCH_FAST_GRID needs downscale_factor in {1,2,4,8}, ncc radius 1 and "
-                    "block-matching radii 1/4/10");
-    // min_disparity > 0 outside the capture route (dmin > Dd, or other radii): only the generic exact-order
-    // kernel still materialises the aggregated volume step 6 then gathers from (rule S6)
-    if (v.vol && mode == SMX_MATCH_FAST_GRID)
-        return fail(SMX_ERR_UNSUPPORTED, "SMX_MATCH_FAST_GRID cannot serve min_disparity/K > disparity count or "
-                                         "non-default radii with min_disparity > 0 (aggregated volume needed)");
-    mode = call_match_mode(e, in_mode);
-    // dmin > 0 (capture route): the match kernels stop after the arg-max; a sparse second kernel looks up the
-    // three aggregated costs step 6 reads (k_match_capture.h; the workgroup that owns pixel 0 of a pair evaluates that pixel's
-    // out-of-range lookups directly, k_capture_pixel0.h)
-    mp.pass1_only = e->capture ? 1 : 0;
+    mp.on_lanes = call.on_lanes ? 1 : 0;
+    mp.tickets = e->tickets ? e->tickets + (size_t)first * f.e2_tiles : nullptr;
+    mp.pass1_only = pl.capture_follows ? 1 : 0;
     smx::ExactPlan xp = e->xp;                     // this lane's region of the slice buffer
-    if (xp.slices) xp.slices += (size_t)e->cur_lane * xp.slices_floats;
+    if (xp.slices) xp.slices += (size_t)lane * xp.slices_floats;
     mp.slices = xp.slices;                         // (the one-launch AUTO kernel's off-grid branch; launch_exact sets its own)
-    auto exact = [&](smx::MatchParams p, bool allow_split) -> int {
-        if (smx::launch_exact(xp, p, n, allow_split, e->cus, s))
+    auto exact = [&](const smx::MatchParams &p, bool allow_split) -> int {
+        if (smx::launch_exact(xp, p, n, allow_split, f.cus, s))
             return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
+        if (pl.capture_follows) smx::launch_exact2_capture(e->xp, p, n, allow_split, f.cus, s);   // dmin > 0: the lookups of step 6
         return SMX_OK;
     };
-    const bool rgb_in = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
-    const bool small = smx::match_fast_plan(mp, n, e->cus).small;
-    if (filter_serves(e, mode, rgb_in, small) && e->call_use_filter) {
-        // the filtered route (k_match_filter.h): a cheap pass over all disparities on the inputs rounded to the grid marks,
-        // per exact-order tile, the disparities that can still hold the maximum; only those are evaluated in the
-        // reference's order.  Pairs whose gray leaves [0, 255] (f32 RGB only; flag from the prologue) take the dense kernel.
+    // the fast kernel in the plan's form; the sparse form's report is published by this range's fill launch
+    auto fast = [&](smx::MatchParams p, int gate) -> smx::MatchParams {
+        p.gate = gate;
+        p.dense = pl.dense ? 1 : 0;
+        p.dense_small = pl.dense_small ? 1 : 0;
+        if (pl.fill_publishes) {
+            p.fast_stats = e->fast_stats_dev + lane;
+            p.fast_stride = pl.stride;
+        }
+        return p;
+    };
+    switch (pl.route) {
+    case smx::AGG_FILTERED: {
         smx::FilterParams fp{};
-        fp.cand = v.cand; fp.tiles_x = e->cand_tiles_x; fp.tiles_y = e->cand_tiles_y; fp.cw = e->cand_cw;
-        fp.two_e = e->filter_two_e; fp.range_flags = v.flags2;
+        fp.cand = v.cand; fp.tiles_x = f.cand_tiles_x; fp.tiles_y = f.cand_tiles_y; fp.cw = f.cand_cw;
+        fp.two_e = f.filter_two_e; fp.range_flags = v.flags2;
         {
-            SlotTimer tm(e, s, SMX_KERNEL_MATCH_FAST);
-            if (in_mode == smx::IN_RGB_F32) {  // the gated alternative first (see the AUTO branch below)
+            SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
+            if (pl.gated_dense_first) {        // the gated alternative first (see AGG_AUTO_GATED below)
                 smx::MatchParams dp = mp;
                 dp.flags = v.flags2;
                 dp.gate = 2;
-                if (int rc = exact(dp, false)) return rc;
+                if (smx::launch_exact(xp, dp, n, false, f.cus, s))
+                    return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
             }
             smx::MatchParams fmp = mp;
-            fmp.unit = (float)e->filter_unit;
-            smx::launch_match_filter_tu(fmp, fp, n, e->cus, s);
+            fmp.unit = (float)f.filter_unit;
+            smx::launch_match_filter_tu(fmp, fp, n, f.cus, s);
         }
-        SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
-        const int lane = e->cur_lane;
-        smx::launch_exact2_sparse(e->xp, mp, n, v.cand, e->cand_cw, (const int *)v.flags2,
-                                  e->stats_dev ? e->stats_dev + 2 * lane : nullptr,
-                                  e->hints_dev ? &e->hints_dev->filter_density[lane] : nullptr, e->route.filt.next_seq(), s);
-        if (e->capture) smx::launch_exact2_capture(e->xp, mp, n, false, e->cus, s);   // dmin > 0: the lookups of step 6
-    } else if (mode == SMX_MATCH_EXACT_ORDER) {
-        SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
-        mp.gate = 0;
-        // (the disparity split is for calls of a few pairs; its slice buffer is not divided between halves)
-        if (int rc = exact(mp, whole_call)) return rc;
-        if (e->capture) smx::launch_exact2_capture(e->xp, mp, n, whole_call, e->cus, s);
-    } else if (mode == SMX_MATCH_FAST_GRID) {
-        SlotTimer tm(e, s, SMX_KERNEL_MATCH_FAST);
-        mp.gate = 0;
-        launch_fast(e, mp, n, s);
-        if (e->capture) smx::launch_match_capture_tu(mp, n, e->cus, s);
-    } else if (e->default_radii && small && e->call_grid_hint == 0 && smx::match_auto_small_ok(mp, n, e->cus, xp.slices_floats)) {
-        // AUTO, few pairs in flight, the last reported call on the grid: one launch that branches on the device-side
-        // flag (k_match_auto.h).  Its exact-order branch (the disparity-split register-tiled kernel on the fast kernel's
-        // grid, merged by the last workgroup of a tile) is ~1.4 x slower than the two gated launches below, so those serve
-        // once a call has reported off-grid input -- and as long as nothing has been reported at all: an engine's first calls.
-        SlotTimer tm(e, s, SMX_KERNEL_MATCH_FAST);
-        mp.gate = 0;
-        mp.nd_chunk = e->xp.exact2_nd;
-        plan_fast_form(e, mp, n);
-        smx::launch_match_auto_small_tu(mp, n, e->cus, s);
-    } else {   // AUTO: both enqueued, the device-side grid flag lets exactly one do the work
+        SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
+        smx::launch_exact2_sparse(e->xp, mp, n, v.cand, f.cand_cw, (const int *)v.flags2, e->stats_dev + 2 * lane,
+                                  &e->hints_dev->filter_density[lane], e->route.filt.next_seq(), s);
+        if (pl.capture_follows) smx::launch_exact2_capture(e->xp, mp, n, false, f.cus, s);   // dmin > 0: the lookups of step 6
+        break;
+    }
+    case smx::AGG_EXACT: {
+        SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
+        if (int rc = exact(mp, pl.exact_split)) return rc;
+        break;
+    }
+    case smx::AGG_FAST: {
+        SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
+        const smx::MatchParams p = fast(mp, 0);
+        smx::launch_match_fast(p, n, f.cus, s);
+        if (pl.capture_follows) smx::launch_match_capture_tu(p, n, f.cus, s);
+        break;
+    }
+    case smx::AGG_AUTO_ONE_LAUNCH: {
+        SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
+        smx::MatchParams p = fast(mp, 0);
+        p.nd_chunk = e->xp.exact2_nd;
+        smx::launch_match_auto_small_tu(p, n, f.cus, s);
+        break;
+    }
+    default: {   // AGG_AUTO_GATED: both enqueued, the device-side grid flag lets exactly one do the work
         // The gated exact-order launch goes first.  Its workgroups ask for 72-80 KB of LDS each even when they only read
         // the flag and leave, so on a chip that another lane's aggregation kernel fills they wait for a CU to drain;
         // behind the fast kernel that wait held back this lane's refine / fill (the launches that fit into the other
         // lane's tail), in front of it it overlaps the wait the fast kernel has anyway (NOTES.md: lanes).
         {
-            SlotTimer tm(e, s, SMX_KERNEL_MATCH_EXACT);
+            SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
             mp.gate = 2;
-            // the disparity split (and its merge launch) only for few pairs that are known to be off the grid; for the
-            // gated alternative of on-grid batches it would be pure overhead
-            const bool split = whole_call && small && e->call_grid_hint != 0;
-            if (int rc = exact(mp, split)) return rc;
-            if (e->capture) smx::launch_exact2_capture(e->xp, mp, n, split, e->cus, s);
+            if (int rc = exact(mp, pl.exact_split)) return rc;
         }
-        SlotTimer tm(e, s, SMX_KERNEL_MATCH_FAST);
-        mp.gate = 1;
-        launch_fast(e, mp, n, s);
-        if (e->capture) smx::launch_match_capture_tu(mp, n, e->cus, s);
+        SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
+        const smx::MatchParams p = fast(mp, 1);
+        smx::launch_match_fast(p, n, f.cus, s);
+        if (pl.capture_follows) smx::launch_match_capture_tu(p, n, f.cus, s);
+        break;
     }
-    e->last_mode = mode;
+    }
+    e->last_call.plan = pl;
 
     smx::RefineParams rp{};
     rp.Lg = gl; rp.Rg = gr; rp.gpitch = gpitch; rp.gplane = gplane; rp.wta = v.wta; rp.costs = v.costs; rp.vol = v.vol;
@@ -529,46 +390,31 @@ int enqueue_range(smx_engine *e, int in_mode, int first, int n, bool whole_call,
     rp.w = d.w; rp.Dd = d.Dd; rp.R = (int)e->cfg.sad_patch_radius;
     rp.flags2 = v.flags2;
     rp.epoch = e->epoch;
-    rp.L8 = v.gray8_l; rp.R8 = v.gray8_r; rp.pitch8 = e->pitch8; rp.padl = e->padl;
+    rp.L8 = v.gray8_l; rp.R8 = v.gray8_r; rp.pitch8 = f.pitch8; rp.padl = f.padl;
     rp.gate = 0;
     rp.fp_conv = SMX_FP_PARABOLA(e->cfg.fp_convention);
     // largest |abscissa| of the SAD parabola: d_hi = K * (dmin / K + Dd) (k_refine.h refine_finish_int: exact up to 271)
     rp.sad_exact = (long long)d.K * ((long long)e->cfg.min_disparity / d.K + d.Dd) <= 271 ? 1 : 0;
+    if (pl.refine_kind == smx::REFINE_AUTO) rp.grid_flags = v.flags;
+    if (pl.refine_reports_grid) rp.grid_hint = &e->hints_dev->grid;
     smx::FillParams fp{};
     fp.Lg = gl; fp.lpitch = gpitch; fp.lplane = gplane; fp.refined = v.refined; fp.out = out; fp.B = e->B; fp.H = d.H; fp.W = d.W;
     fp.K = d.K; fp.h = d.h; fp.w = d.w; fp.thr = (float)e->cfg.threshold;
     fp.log2k = 0;
     while ((1 << fp.log2k) < d.K) fp.log2k++;
-    {
-        SlotTimer tm(e, s, SMX_KERNEL_REFINE);
-        const int kt = (rp.R == 5 && (d.K == 1 || d.K == 2 || d.K == 4)) ? d.K : 0;
-        // integer-valued gray -> v_sad_u8 kernel; otherwise the float kernel (same results)
-        if (kt == 0 || e->pitch8 == 0 || rgb_in) {
-            smx::launch_refine(smx::REFINE_FLOAT, kt, apron, rp, n, s);
-        } else if (in_mode == smx::IN_GRAY_U8) {
-            // u8 is integer-valued by construction; the prologue wrote the padded copy.  Batches: four pooled rows per
-            // thread share their row SADs (k_refine_int_v)
-            smx::launch_refine(n > 4 ? smx::REFINE_INT_V : smx::REFINE_INT, kt, false, rp, n, s);
-        } else if (n <= 4) {   // f32 gray, few pairs: one launch picks per pair (k_refine_auto) and reports the grid flag
-            rp.grid_flags = v.flags;
-            rp.grid_hint = (whole_call && e->hints_dev) ? &e->hints_dev->grid : nullptr;
-            smx::launch_refine(smx::REFINE_AUTO, kt, false, rp, n, s);
-        } else {   // f32 gray batches: the prologue wrote u8 copies and the per-pair integrality flag; one launch
-            // branches on it per pair (k_refine_auto_v: a gated-out launch of the float kernel still has to be placed on
-            // a chip the other lane fills, and the lane's chain waits for it)
-            smx::launch_refine(smx::REFINE_AUTO_V, kt, false, rp, n, s);
-        }
-    }
-    if (e->fast_stats_pending && e->hints_dev) {
-        fp.fast_stats = e->fast_stats_dev + e->cur_lane;
-        fp.fast_stats_host = &e->hints_dev->fast_density[e->cur_lane];
+    if (pl.fill_publishes) {
+        fp.fast_stats = e->fast_stats_dev + lane;
+        fp.fast_stats_host = &e->hints_dev->fast_density[lane];
         fp.fast_seq = e->route.fast.next_seq();
         fp.fast_pass1 = (d.Dd + 1) / 2;
     }
-    e->fast_stats_pending = false;
     {
-        SlotTimer tm(e, s, SMX_KERNEL_FILL);
-        smx::launch_fill(fp, n, e->call_on_lanes && n > 4 ? 4 : 8, s);
+        SlotTimer tm(e, s, lane, SMX_KERNEL_REFINE);
+        smx::launch_refine(pl.refine_kind, pl.kt, pl.refine_apron, rp, n, s);
+    }
+    {
+        SlotTimer tm(e, s, lane, SMX_KERNEL_FILL);
+        smx::launch_fill(fp, n, pl.fill_px, s);
     }
     SMX_HIP(hipGetLastError());
     return SMX_OK;
@@ -703,16 +549,17 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
         SMX_HIP(hipStreamSynchronize(nullptr));       // the lanes are non-blocking streams: not ordered behind the null stream
     }
     e->epoch++;
-    e->last_n = n;
-    e->last_first = 0;
-    e->call_on_lanes = detached;
     // launch plans that depend on what earlier calls saw (hints only: every plan gives the same bits)
     read_hints(e);
+    const smx::EngineFacts &f = e->facts;
     const bool split = detached && e->overlap_min > 0 && n >= e->overlap_min;
-    const int n_first = split ? (n + 1) / 2 : n;
-    const smx::CallRoute route = e->route.decide_call(call_kind(e, in_mode, n_first, n - n_first), e->opt_fast_dense, e->cfg.exact_filter);
-    e->call_fast_dense = route.fast_dense;
-    e->call_use_filter = route.use_filter;
+    const int n0 = split ? (n + 1) / 2 : n;
+    smx::CallFacts call;
+    call.in_mode = in_mode;
+    call.on_lanes = detached;
+    call.route = e->route.decide_call(smx::call_kind(f, in_mode, detached, n0, n - n0), f.opt.fast_dense, f.exact_filter);
+    e->last_call.call = call;
+    e->last_call.first = 0;
     // The two lanes run unordered against each other, which is safe only while they work on disjoint pairs of the engine's
     // buffers (steady state: lane 0 always [0, n/2), lane 1 always [n/2, n)).  When a call's split differs from what the
     // other lane has in flight, that lane's tail is waited for first.
@@ -728,17 +575,15 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     };
     int rc;
     if (split) {
-        const int n0 = n_first;
         const bool rgb = in_mode == smx::IN_RGB_F32 || in_mode == smx::IN_RGB_U8;
         const bool u8 = in_mode == smx::IN_GRAY_U8 || in_mode == smx::IN_RGB_U8;
         const size_t in_pair = (size_t)d.H * d.W * (rgb ? 3 : 1) * (u8 ? 1 : sizeof(float));
         if (int lrc = lane_enter(1, n0, n, out + (size_t)n0 * d.H * d.W, n - n0)) return lrc;
-        e->cur_lane = 1;                       // second half first: the profile's and last_gray's "current" ends on lane 0
-        rc = enqueue_range(e, in_mode, n0, n - n0, false, (const char *)left + n0 * in_pair, (const char *)right + n0 * in_pair,
-                           out + (size_t)n0 * d.H * d.W, e->lane_stream[1]);
-        e->cur_lane = 0;
+        // second half first: last_call's plan and last_gray end on lane 0
+        rc = enqueue_range(e, call, smx::plan_range(f, call, n - n0, false), 1, n0, n - n0, (const char *)left + n0 * in_pair,
+                           (const char *)right + n0 * in_pair, out + (size_t)n0 * d.H * d.W, e->lane_stream[1]);
         if (rc == SMX_OK) rc = lane_enter(0, 0, n0, out, n0);
-        if (rc == SMX_OK) rc = enqueue_range(e, in_mode, 0, n0, false, left, right, out, e->lane_stream[0]);
+        if (rc == SMX_OK) rc = enqueue_range(e, call, smx::plan_range(f, call, n0, false), 0, 0, n0, left, right, out, e->lane_stream[0]);
     } else {
         // An unsplit engine-stream call that needs at most half of the engine's pair slots alternates between the two
         // lanes AND between the two halves of the buffers: consecutive small calls (single frames, as the reference's runner
@@ -749,12 +594,11 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
             e->next_small_lane ^= 1;
             first = lane * (e->B / 2);
         }
-        e->cur_lane = lane;
-        e->last_first = first;
+        e->last_call.first = first;
         if (detached)
             if (int lrc = lane_enter(lane, first, first + n, out, n)) return lrc;
-        rc = enqueue_range(e, in_mode, first, n, true, left, right, out, detached ? e->lane_stream[lane] : (hipStream_t)stream);
-        e->cur_lane = 0;
+        rc = enqueue_range(e, call, smx::plan_range(f, call, n, true), lane, first, n, left, right, out,
+                           detached ? e->lane_stream[lane] : (hipStream_t)stream);
         if (!detached && !capturing) {
             // a later engine-stream call must come after this one.  Lanes exist: record the tail.  No lanes yet: remember
             // that there is an unrecorded tail (create_lanes waits for it once).  Under capture nothing runs now: a graph
@@ -880,16 +724,14 @@ int smx_get_dims(const smx_config *cfg, smx_dims *dims) {
 // (C2: 2 x 13 = 26 pairs; measured with the shared high-priority lanes, tools/batch_sweep.py: 32 pairs 82.2 k split
 // against 63.5 k unsplit, 48 pairs 81 k against 67 k, while 24 pairs -- halves in the latency shape -- lose: 52.5 k against
 // 62.5 k).  SMX_OVERLAP_MIN_PAIRS overrides it for every engine (0: never split); read once, in smx_create.
-static int overlap_min_pairs_default(const smx_dims &d, int cus) {
+static int overlap_min_pairs_default(const smx::EngineFacts &f) {
     const char *v = std::getenv("SMX_OVERLAP_MIN_PAIRS");
     if (v && *v) {
         const int k = std::atoi(v);
         return k < 0 ? 0 : (k == 1 ? 2 : k);
     }
-    smx::MatchParams mp{};
-    mp.h = d.h; mp.w = d.w; mp.Dd = d.Dd;
     int n_tall = 1;
-    while (n_tall < 4096 && smx::match_fast_plan(mp, n_tall, cus).small) ++n_tall;
+    while (n_tall < 4096 && smx::range_fast_plan(f, false, n_tall).small) ++n_tall;
     return 2 * n_tall;
 }
 
@@ -929,31 +771,16 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     e->cfg = *cfg;
     e->dm = d;
     e->B = cfg->max_batch > 0 ? cfg->max_batch : 1;
-    const int K = d.K;
-    e->grid_capable = (K == 1 || K == 2 || K == 4 || K == 8);
-    e->fast_ok_host = e->grid_capable && cfg->ncc_patch_radius == 1 &&
-                      cfg->small_mbm_radius == 1 && cfg->mid_mbm_radius == 4 &&
-                      cfg->large_mbm_radius == 10 && smx::match_fast_supported(d.h, d.w, d.Dd);
-    // largest right-tile chunk that keeps the exact kernel within 64 KB of LDS
-    int nd = d.Dd;
-    while (nd > 1 && smx::exact_lds_floats((int)cfg->ncc_patch_radius, cfg->large_mbm_radius, nd) *
-                             sizeof(float) > 64 * 1024)
-        nd = (nd + 1) / 2;
-    e->xp.exact_nd = nd;
-    e->xp.exact_lds = smx::exact_lds_floats((int)cfg->ncc_patch_radius, cfg->large_mbm_radius, nd) * sizeof(float);
-    {   // register-tiled exact kernel: up to 80 KB of LDS (two workgroups per CU), opt-in above 64 KB
-        int nd2 = d.Dd;
-        while (nd2 > 1 && smx::exact2_lds_floats(nd2) * sizeof(float) > (size_t)SMX_EXACT2_LDS_CAP) nd2 = (nd2 + 1) / 2;
-        e->xp.exact2_nd = nd2;
-        e->xp.exact2_lds = smx::exact2_lds_floats(nd2) * sizeof(float);
-    }
-    if (e->xp.exact_lds > 64 * 1024) {
-        const size_t need = e->xp.exact_lds;
-        delete e;
-        return fail(SMX_ERR_UNSUPPORTED,
-                    "radii too large for the LDS tile: ncc_patch_radius %u + large_mbm_radius %d need %zu bytes "
-                    "of the 65536 available to the exact-order kernel",
-                    cfg->ncc_patch_radius, cfg->large_mbm_radius, need);
+    {
+        int nd = 0;
+        const size_t need = smx::exact_tile_lds(*cfg, d.Dd, &nd);
+        if (need > 64 * 1024) {
+            delete e;
+            return fail(SMX_ERR_UNSUPPORTED,
+                        "radii too large for the LDS tile: ncc_patch_radius %u + large_mbm_radius %d need %zu bytes "
+                        "of the 65536 available to the exact-order kernel",
+                        cfg->ncc_patch_radius, cfg->large_mbm_radius, need);
+        }
     }
 
     DeviceGuard guard(cfg->device_id);
@@ -961,44 +788,34 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
         delete e;
         return fail(SMX_ERR_HIP, "cannot select HIP device %d", cfg->device_id);
     }
-    {   // launch plans are sized against the device's CU count (256 on MI355X)
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device_id) == hipSuccess && cus > 0) e->cus = cus;
-    }
-    e->default_radii = cfg->ncc_patch_radius == 1 && cfg->small_mbm_radius == 1 && cfg->mid_mbm_radius == 4 &&
-                       cfg->large_mbm_radius == 10;
+    int cus = 0;       // launch plans are sized against the device's CU count (256 on MI355X)
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device_id) != hipSuccess || cus <= 0) cus = 256;
     // environment switches are read here, once (never per call)
-    e->overlap_min = cfg->overlap_min_pairs < 0 ? 0
-                     : (cfg->overlap_min_pairs > 0 ? (cfg->overlap_min_pairs < 2 ? 2 : cfg->overlap_min_pairs) : overlap_min_pairs_default(d, e->cus));
+    smx::PlanOptions opt;
+    opt.fast_dense = env_is("SMX_FAST_DENSE", '1') ? 1 : (env_is("SMX_FAST_DENSE", '0') ? 0 : -1);
+    opt.fast_dense_small = env_is("SMX_FAST_DENSE_SMALL", '1') ? 1 : (env_is("SMX_FAST_DENSE_SMALL", '0') ? 0 : -1);
     e->opt_lane_priority = env_is("SMX_LANE_PRIORITY", '0') ? 0 : 1;
-    e->opt_fast_dense = env_is("SMX_FAST_DENSE", '1') ? 1 : (env_is("SMX_FAST_DENSE", '0') ? 0 : -1);
-    e->opt_fast_dense_small = env_is("SMX_FAST_DENSE_SMALL", '1') ? 1 : (env_is("SMX_FAST_DENSE_SMALL", '0') ? 0 : -1);
     e->opt_debug_hints = std::getenv("SMX_DEBUG_HINTS") != nullptr;
     if (const char *v = std::getenv("SMX_TEST_EPOCH_START")) {      // tests only: start the call counter near its wrap
         const long k = std::atol(v);
         if (k > 0 && k < 0x7fffffffL) e->epoch = (int)k;
     }
+    // everything the launch plans depend on, decided once (smx_plan.h); the rest of this function allocates what it names
+    e->facts = smx::derive_facts(*cfg, d, cus, opt);
+    const smx::EngineFacts &f = e->facts;
+    e->xp.exact_nd = f.exact_nd; e->xp.exact_lds = f.exact_lds;
+    e->xp.exact2_nd = f.exact2_nd; e->xp.exact2_lds = f.exact2_lds;
+    e->xp.slices_floats = f.slices_floats;
+    e->overlap_min = cfg->overlap_min_pairs < 0 ? 0
+                     : (cfg->overlap_min_pairs > 0 ? (cfg->overlap_min_pairs < 2 ? 2 : cfg->overlap_min_pairs) : overlap_min_pairs_default(f));
     const size_t B = (size_t)e->B, hw = (size_t)d.h * d.w;
     hipError_t err = hipSuccess;
     auto alloc = [&](void **p, size_t bytes) {
         if (err == hipSuccess) err = hipMalloc(p, bytes);
         if (err == hipSuccess) err = hipMemset(*p, 0, bytes);
     };
-    {   // cyclic column aprons wide enough for every shifted step-6 window (u8 planes and float gray alike)
-        const int padl = (8 + K * (d.dmax + 2) + 3) & ~3, padr = (32 + K + 3) & ~3;
-        const bool kt_ok = cfg->sad_patch_radius == 5 && (K == 1 || K == 2 || K == 4);
-        if (kt_ok && padl <= d.W && padr <= d.W) {
-            e->padl = padl; e->padr = padr;
-            e->pitch8 = (padl + d.W + padr + 3) & ~3;
-            e->gpitch = e->pitch8;
-            e->gpadl = padl;
-        } else {
-            e->gpitch = d.W;
-            e->gpadl = 0;
-        }
-    }
-    alloc((void **)&e->gray_l, B * (size_t)d.H * e->gpitch * sizeof(float));
-    alloc((void **)&e->gray_r, B * (size_t)d.H * e->gpitch * sizeof(float));
+    alloc((void **)&e->gray_l, B * (size_t)d.H * f.gpitch * sizeof(float));
+    alloc((void **)&e->gray_r, B * (size_t)d.H * f.gpitch * sizeof(float));
     alloc((void **)&e->down_l, B * hw * sizeof(float));
     alloc((void **)&e->down_r, B * hw * sizeof(float));
     alloc((void **)&e->wta, B * hw * sizeof(float));
@@ -1006,51 +823,21 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     alloc((void **)&e->costs, 3 * B * hw * sizeof(float));
     alloc((void **)&e->flags, 2 * B * sizeof(int));
     alloc((void **)&e->fast_stats_dev, smx_engine::LANES * sizeof(unsigned long long));
-    if (e->pitch8 > 0) {   // u8 planes for the integer step-6 kernel
-        alloc((void **)&e->gray8_l, B * (size_t)d.H * e->pitch8);
-        alloc((void **)&e->gray8_r, B * (size_t)d.H * e->pitch8);
+    if (f.has_u8_planes()) {   // u8 planes for the integer step-6 kernel
+        alloc((void **)&e->gray8_l, B * (size_t)d.H * f.pitch8);
+        alloc((void **)&e->gray8_r, B * (size_t)d.H * f.pitch8);
     }
-    if (e->default_radii) {
-        // slice records of the disparity-split exact kernel and of the one-launch AUTO kernel's off-grid branch (few pairs
-        // in flight): one region per stream lane, sized by the rule the launches check against (k_match_auto.h)
-        smx::MatchParams sp{};
-        sp.h = d.h; sp.w = d.w; sp.Dd = d.Dd;
-        const size_t floats = smx::slice_region_floats(sp, e->B, e->cus, e->fast_ok_host);
-        const int tiles = ((d.w + smx::E2_TW - 1) / smx::E2_TW) * ((d.h + smx::E2_TH - 1) / smx::E2_TH);
-        // arrival tickets per (pair slot, tile): the last slice of a tile merges it inside the split launch
-        e->e2_tiles = tiles;
-        alloc((void **)&e->tickets, B * (size_t)tiles * sizeof(unsigned));
-        if (floats) {
-            e->xp.slices_floats = floats;
-            // one region per stream lane: two small calls may be in flight at once (alternating lanes, see enqueue)
-            alloc((void **)&e->slices, smx_engine::LANES * e->xp.slices_floats * sizeof(float));
-            e->xp.slices = e->slices;
-        }
+    if (f.has_tickets()) alloc((void **)&e->tickets, B * (size_t)f.e2_tiles * sizeof(unsigned));
+    if (f.has_slices()) {
+        // one region per stream lane: two small calls may be in flight at once (alternating lanes, see enqueue)
+        alloc((void **)&e->slices, smx_engine::LANES * f.slices_floats * sizeof(float));
+        e->xp.slices = e->slices;
     }
-    // filtered exact-order route for off-grid input (gray from RGB): dmin == 0 or the capture route.  Its error bound
-    // (k_match_filter.h: filter_error_bound_units) is derived for exactly these radii -- 63 / 63 / 81 taps of a 3x3
-    // cost -- and for grid units up to 64 (exact integer sums below 2^24): anything else takes the dense kernel.
-    static_assert(smx::FILTER_TILE_H == smx::E2_TH && smx::FILTER_TILE_W == smx::E2_TW, "the filter marks exact-order tiles");
-    e->filter_ok = cfg->exact_filter >= 0 && e->fast_ok_host && e->default_radii && K * K <= 64 &&
-                   smx::filter_cand_words(d.Dd) <= smx::E2_SPARSE_WORDS;       // (&& no aggregated volume: checked below)
-    if (e->filter_ok) {
-        e->cand_tiles_x = (d.w + smx::E2_TW - 1) / smx::E2_TW;
-        e->cand_tiles_y = (d.h + smx::E2_TH - 1) / smx::E2_TH;
-        e->cand_cw = smx::filter_cand_words(d.Dd);
-        // grid unit of the filter's rounded inputs: K^2, the pooled grid.  (Measured: a finer grid -- 16 or 64 units at
-        // K = 2, i.e. an error bound 3.5x / 8x smaller -- takes the candidate density of the reference's real pair from
-        // 0.65 to 0.57 / 0.55 only: the flat cost curves of a real scene are genuinely ambiguous, and the filter
-        // loses the packed u16 stages; profiles/r03_filter_unit.txt.)
-        e->filter_unit = K * K;
-        e->filter_two_e = (float)(2.0 * smx::filter_error_bound_units((double)e->filter_unit) * (1.0 + 1e-6));
-        alloc((void **)&e->cand, B * (size_t)e->cand_tiles_x * e->cand_tiles_y * e->cand_cw * sizeof(unsigned));
+    if (f.filter_ok) {
+        alloc((void **)&e->cand, B * (size_t)f.cand_tiles_x * f.cand_tiles_y * f.cand_cw * sizeof(unsigned));
         alloc((void **)&e->stats_dev, 2 * smx_engine::LANES * sizeof(unsigned));
     }
-    // dmin > 0: step 6 indexes the aggregated volume by absolute disparity (Q5 / rule S6).  With the default
-    // radii the sparse capture kernels deliver exactly those entries; only other radii still materialise it.
-    e->capture = smx::capture_applicable(d.dmin, d.Dd) && e->default_radii;
-    if (d.dmin > 0 && !e->capture) alloc((void **)&e->vol, B * hw * (size_t)d.Dd * sizeof(float));
-    if (d.dmin > 0 && !e->capture) e->filter_ok = false;      // the volume route needs every disparity anyway
+    if (f.has_volume) alloc((void **)&e->vol, B * hw * (size_t)d.Dd * sizeof(float));
     if (err == hipSuccess) {   // hint words the kernels publish for later calls' launch plans (pinned, device-visible)
         err = hipHostMalloc((void **)&e->hints, sizeof(HostHints), hipHostMallocDefault);
         if (err == hipSuccess) {
@@ -1162,8 +949,8 @@ int smx_get_intermediate(smx_engine *e, int stage, int pair, void *dst, size_t b
     if (!guard.ok) return fail(SMX_ERR_HIP, "cannot select HIP device %d", e->cfg.device_id);
     hipStream_t s = (hipStream_t)stream;
     const smx_dims &d = e->dm;
-    if (pair + e->last_first >= e->B) return fail(SMX_ERR_INVALID_ARG, "pair_index out of range");
-    const size_t hw = (size_t)d.h * d.w, p = (size_t)(pair + e->last_first);       // slot of the last call's pair `pair`
+    if (pair + e->last_call.first >= e->B) return fail(SMX_ERR_INVALID_ARG, "pair_index out of range");
+    const size_t hw = (size_t)d.h * d.w, p = (size_t)(pair + e->last_call.first);       // slot of the last call's pair `pair`
     const void *src = nullptr;
     switch (stage) {
         case SMX_STAGE_GRAY_LEFT:
@@ -1206,29 +993,9 @@ int smx_get_intermediate(smx_engine *e, int stage, int pair, void *dst, size_t b
 int smx_get_match_geometry(const smx_engine *e, int n, smx_match_geometry *g) {
     if (!e || !g || n < 1) return fail(SMX_ERR_INVALID_ARG, "smx_get_match_geometry: NULL argument or n < 1");
     std::memset(g, 0, sizeof(*g));
-    const smx_dims &d = e->dm;
-    if (!e->fast_ok_host) {
-        g->kernel = SMX_KERNEL_EXACT_ONLY;
-        return SMX_OK;
-    }
-    smx::MatchParams mp{};
-    mp.h = d.h; mp.w = d.w; mp.Dd = d.Dd; mp.dmin = d.dmin; mp.vol = e->vol; mp.pass1_only = e->capture ? 1 : 0;
-    mp.on_lanes = e->call_on_lanes ? 1 : 0;        // the shape the engine's LAST call ran with (lanes or a caller's stream)
-    if (mp.on_lanes && smx_overlap_lanes(e, n) == 2) n = (n + 1) / 2;      // ... a split call launches its halves
-    const smx::FastPlan pl = smx::match_fast_plan(mp, n, e->cus);
-    g->kernel = pl.small ? SMX_KERNEL_FAST_SPLIT : SMX_KERNEL_FAST_WINDOW;
-    g->band_rows = pl.th;
-    g->waves_per_workgroup = pl.small ? smx::FA_DS_WAVES : smx::FA_WAVES;
-    const int cols_per_wg = smx::FA_VALID * (pl.small ? 1 : smx::FA_WAVES);
-    const long wgs = (long)((d.w + cols_per_wg - 1) / cols_per_wg) * ((d.h + pl.th - 1) / pl.th);
-    g->rows_marched = g->band_rows + 22;
-    g->workgroups = (int)(wgs * n);
-    const long waves = wgs * g->waves_per_workgroup;
-    // the disparity-split kernel spends its 4 waves on one window: a quarter of the range each
-    const double lane_rows = (double)waves * 64.0 * g->rows_marched / (g->kernel == SMX_KERNEL_FAST_SPLIT ? (double)smx::FA_DS_WAVES : 1.0);
-    g->useful_fraction = (double)d.h * d.w / lane_rows;
-    g->columns_per_wave = (double)d.w * ((d.h + g->band_rows - 1) / g->band_rows) /
-                          ((double)waves / (g->kernel == SMX_KERNEL_FAST_SPLIT ? (double)smx::FA_DS_WAVES : 1.0));
+    const bool on_lanes = e->last_call.call.on_lanes;     // the shape the engine's LAST call ran with (lanes or a caller's stream)
+    if (on_lanes && smx_overlap_lanes(e, n) == 2) n = (n + 1) / 2;      // ... a split call launches its halves
+    smx::match_geometry(e->facts, on_lanes, n, g);
     return SMX_OK;
 }
 
@@ -1238,19 +1005,19 @@ int smx_get_route_info(smx_engine *e, smx_route_info *info) {
     if (!e || !info) return fail(SMX_ERR_INVALID_ARG, "smx_get_route_info: NULL argument");
     read_hints(e);
     std::memset(info, 0, sizeof(*info));
-    info->filter_available = e->filter_ok ? 1 : 0;
+    info->filter_available = e->facts.filter_ok ? 1 : 0;
     info->route_dense = e->route.filt.on ? 1 : 0;
-    info->last_call_filtered = e->call_use_filter ? 1 : 0;
+    info->last_call_filtered = e->last_call.call.route.use_filter ? 1 : 0;
     info->probe_period = e->route.filt.period;
     info->candidate_density = e->route.filt.last;
-    info->offgrid_hint = e->call_grid_hint;
-    info->compute_units = e->cus;
+    info->offgrid_hint = e->route.grid_hint;
+    info->compute_units = e->facts.cus;
     info->fast_dense = e->route.fast.on ? 1 : 0;
     return SMX_OK;
 }
 
 int smx_last_match_mode(const smx_engine *e) {
-    return e ? e->last_mode : SMX_ERR_INVALID_ARG;
+    return e ? e->last_call.plan.mode : SMX_ERR_INVALID_ARG;
 }
 
 int smx_join(smx_engine *e, void *stream) {

@@ -64,8 +64,6 @@ void launch_match_fast(const MatchParams &p, int n, int cus, hipStream_t s);
 void launch_match_fast_tall_24(const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_27(const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_32(const MatchParams &p, int n, hipStream_t s);
-// slices_floats: this lane's region of the slice buffer (k_match_auto.h: slice_region_floats)
-bool match_auto_small_ok(const MatchParams &p, int n, int cus, size_t slices_floats);
 void launch_match_auto_small_tu(const MatchParams &p, int n, int cus, hipStream_t s);
 hipError_t match_auto_raise_caps();       // k_match_auto.h: MATCH_AUTO_LDS_CAP
 

@@ -28,10 +28,6 @@ void launch_match_fast(const MatchParams &p, int n, int cus, hipStream_t s) {
     else launch_match_fast_tall_24(p, n, s);
 }
 
-bool match_auto_small_ok(const MatchParams &p, int n, int cus, size_t slices_floats) {
-    return match_auto_small_applicable(p, match_fast_plan(p, n, cus).th, n, slices_floats);
-}
-
 void launch_match_auto_small_tu(const MatchParams &p, int n, int cus, hipStream_t s) {
     launch_match_auto_small(p, n, match_fast_plan(p, n, cus).th, 0, s);
 }

@@ -1,7 +1,8 @@
 // Host-only harness of tests/test_auto_slice_plan_cpu.py: sweeps the engine's launch plans over frame shapes, disparity
 // counts, batch limits, stream-lane modes and CU counts, and checks that every slice record a launch would write fits the
-// per-lane region of the slice buffer smx_create allocates (k_match_auto.h: slice_region_floats).  It uses the library's
-// own host plan functions and never calls the HIP runtime.
+// per-lane region of the slice buffer smx_create allocates (k_match_auto.h: slice_region_floats).  The region and the
+// engine's choice of the one-launch AUTO kernel come from the engine's own planner (smx_plan.h: derive_facts, plan_range);
+// the HIP runtime is never called.
 //
 // Output: a line per violation ("overflow <kind> h w Dd B n on_lanes cus nsplit th need region": the first 50, and every
 // one at the pooled shapes of the GPU tests for an MI355X (256 CUs) with max_batch = 64), then a summary line
@@ -9,7 +10,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "k_match_auto.h"
+#include "smx_plan.h"
 
 using namespace smx;
 
@@ -45,29 +46,35 @@ int main() {
     const int bs[] = {1, 2, 4, 8, 16, 17, 32, 64, 128};
     const int cuss[] = {1, 80, 256, 304};
     long configs = 0, accepted = 0, split = 0, violations = 0;
-    float slice_word = 0.f;
-    unsigned ticket = 0;
+    smx_config cfg{};
+    cfg.downscale_factor = 2; cfg.ncc_patch_radius = 1; cfg.sad_patch_radius = 5; cfg.threshold = 5;
+    cfg.small_mbm_radius = 1; cfg.mid_mbm_radius = 4; cfg.large_mbm_radius = 10; cfg.match_mode = SMX_MATCH_AUTO;
+    CallFacts gray;
+    gray.in_mode = IN_GRAY_F32;
+    gray.route.grid_hint = 0;
     for (int cus : cuss)
         for (int h : hs)
             for (int w : ws)
                 for (int Dd : dds)
                     for (int B : bs) {
+                        // an AUTO engine of the default configuration at this pooled shape: the region of one lane
+                        smx_dims d{};
+                        d.K = 2; d.H = 2 * h; d.W = 2 * w; d.h = h; d.w = w; d.dmin = 0; d.dmax = Dd - 1; d.Dd = Dd;
+                        cfg.max_batch = B;
+                        const EngineFacts f = derive_facts(cfg, d, cus, PlanOptions{});
+                        const size_t region = f.slices_floats;
+                        const int tiles = f.e2_tiles;
                         MatchParams p{};
                         p.h = h; p.w = w; p.Dd = Dd;
-                        // smx_create, default radii: the region of one lane, and the buffers the calls then see
-                        const bool one_launch = match_fast_supported(h, w, Dd);
-                        const size_t region = slice_region_floats(p, B, cus, one_launch);
-                        p.slices = region ? &slice_word : nullptr;
-                        p.tickets = &ticket;
-                        const int tiles = ((w + E2_TW - 1) / E2_TW) * ((h + E2_TH - 1) / E2_TH);
                         const size_t hw = (size_t)h * w;
                         ++configs;
                         for (int on_lanes = 0; on_lanes < 2; ++on_lanes)
                             for (int n = 1; n <= B; ++n) {
-                                p.on_lanes = on_lanes;
-                                const FastPlan pl = match_fast_plan(p, n, cus);
-                                // the engine's AUTO gate (smx_engine.hip: small, then match_auto_small_ok)
-                                if (one_launch && pl.small && match_auto_small_applicable(p, pl.th, n, region)) {
+                                // a whole f32 gray call after an on-grid report: the one call that can take the one-launch kernel
+                                gray.on_lanes = on_lanes != 0;
+                                const RangePlan plan = plan_range(f, gray, n, true);
+                                const FastPlan &pl = plan.fast;
+                                if (plan.route == AGG_AUTO_ONE_LAUNCH) {
                                     ++accepted;
                                     // launch_match_auto_small_t: nsplit slices, records at [sp][word][n][h][w]
                                     const int ns = match_auto_nsplit(p, pl.th);

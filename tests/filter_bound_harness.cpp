@@ -7,13 +7,14 @@
 // Output:
 //   "E <u> <filter_error_bound_units(u)>"                                      for u = 1, 4, 16, 64
 //   "plan <cus> <name> <h> <w> <Dd> <n> <small at n-1> <small at n> <th> <wide> <chunks> <words>"   per CU count and shape
-// where small is match_fast_plan(...).small (the engine's gate of the filtered route), th / wide are filter_plan's band
-// height and right-tile pitch choice at n pairs, chunks the right-tile stagings per pass that choice needs, and words
-// filter_cand_words(Dd).
+// where small is 0 when the engine's planner (smx_plan.h: plan_range) gives an RGB call of that many pairs the filtered
+// route and 1 when the call is too small for it, th / wide are filter_plan's band height and right-tile pitch choice at n
+// pairs, chunks the right-tile stagings per pass that choice needs, and words filter_cand_words(Dd).
 #include <cstdio>
 #include <cstdlib>
 
 #include "k_match_filter.h"
+#include "smx_plan.h"
 
 using namespace smx;
 
@@ -31,8 +32,18 @@ int main(int argc, char **argv) {
             const Row &r = rows[i];
             MatchParams p{};
             p.h = r.h; p.w = r.w; p.Dd = r.Dd;
-            const bool small_below = r.n > 1 ? match_fast_plan(p, r.n - 1, cus).small : true;
-            const bool small = match_fast_plan(p, r.n, cus).small;
+            // an engine of the default configuration at this pooled shape, an RGB call on a caller's stream, filter allowed
+            smx_config cfg{};
+            cfg.downscale_factor = 2; cfg.ncc_patch_radius = 1; cfg.sad_patch_radius = 5; cfg.threshold = 5;
+            cfg.small_mbm_radius = 1; cfg.mid_mbm_radius = 4; cfg.large_mbm_radius = 10; cfg.match_mode = SMX_MATCH_AUTO;
+            cfg.max_batch = r.n;
+            smx_dims d{};
+            d.K = 2; d.H = 2 * r.h; d.W = 2 * r.w; d.h = r.h; d.w = r.w; d.dmin = 0; d.dmax = r.Dd - 1; d.Dd = r.Dd;
+            const EngineFacts f = derive_facts(cfg, d, cus, PlanOptions{});
+            CallFacts rgb;
+            rgb.in_mode = IN_RGB_U8;
+            const bool small_below = r.n > 1 ? plan_range(f, rgb, r.n - 1, true).route != AGG_FILTERED : true;
+            const bool small = plan_range(f, rgb, r.n, true).route != AGG_FILTERED;
             const FilterPlan pl = filter_plan(p, r.n, cus);
             const int nd = (pl.wide ? 320 : 256) - FA_WGCOLS + 1;
             printf("plan %d %s %d %d %d %d %d %d %d %d %d %d\n", cus, r.name, r.h, r.w, r.Dd, r.n, small_below ? 1 : 0, small ? 1 : 0,

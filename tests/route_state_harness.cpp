@@ -358,7 +358,7 @@ static void switch_rules_sweep(SwitchTotals &t) {
             if (sim.rng() % 89 == 0) content[1] = (float)(sim.rng() % 1000) / 1000.f;
             const int k = (int)(sim.rng() % 4);
             CallKind kind{};
-            kind.fast_reports = k == 0 && forced_fast < 0;           // (a forced form never reports: plan_fast_form)
+            kind.fast_reports = k == 0 && forced_fast < 0;           // (a forced form never reports: smx_plan.h plan_range)
             kind.filter_reports = k == 1;
             const int halves = sim.rng() % 3 == 0 ? 2 : 1;
             const int mask = halves == 2 ? 1 + (int)(sim.rng() % 3) : 1;

@@ -1,0 +1,76 @@
+"""The engine's launch planner (stereo-depth_amd/csrc/smx_plan.h) against its prediction, its invariants and a hand-written table.
+
+One call's launches are decided in one place: derive_facts() fixes what a configuration admits, plan_range() turns those
+facts, the call and the content switches' decision into a RangePlan that enqueue_range executes, and call_kind() predicts
+from the same plans which switch a call can report to.  The header is host-only code, so tests/launch_plan_harness.cpp runs
+the engine's own lines over configurations (radii, K, min_disparity on the capture and the volume route, pooled shapes, disparity
+counts, step-6 radius), match modes, entries, lanes, 1 .. max_batch pairs, whole calls and halves, every decision, the forced
+forms and three CU counts, and checks
+
+  1. prediction equals execution: call_kind()'s two flags against what an executor of the plans would hand to the kernels;
+  2. the plan invariants (which route may appear when, splits only for whole calls, capture launches, what the fill
+     launch publishes, the forms of the fast kernel);
+  3. a table of cases written by hand from the rules.  Among them: before any grid report (hint -1) the gated
+     exact-order launch of a whole small AUTO call may split the disparity range, exactly as after an off-grid report --
+     the rule is `grid_hint != 0`, not `grid_hint == 1`.
+
+Built like the slice-plan harness (host code only, no HIP runtime linked), with the address and undefined-behaviour
+sanitizers when their runtimes link that way and without them otherwise.  No GPU."""
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HARNESS = os.path.join(ROOT, "tests", "launch_plan_harness.cpp")
+SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+ROUTES = ("FILTERED", "EXACT", "FAST", "AUTO_ONE_LAUNCH", "AUTO_GATED")
+REFINES = ("FLOAT", "INT", "INT_V", "AUTO", "AUTO_V")
+
+
+def _build_module():
+    spec = importlib.util.spec_from_file_location("smx_build", os.path.join(ROOT, "stereo-depth_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not found")
+    b = _build_module()
+    exe = str(tmp_path_factory.mktemp("launch_plan") / "launch_plan")
+    log = ""
+    for extra in (SANITIZE, []):               # with the sanitizers if their runtimes link without the HIP runtime
+        cmd = [b.hipcc(), "-x", "hip", "--cuda-host-only", "-no-hip-rt"] + b.FLAGS + extra + ["-I", b.INCLUDE, "-I", b.CSRC,
+                                                                                                "-o", exe, HARNESS]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        if r.returncode == 0:
+            print("launch-plan harness built", "with -fsanitize=address,undefined" if extra else "WITHOUT the sanitizers (their runtimes did not link)")
+            return exe
+        log += " ".join(cmd) + "\n" + r.stdout + r.stderr + "\n"
+    raise AssertionError("harness did not compile:\n" + log[-6000:])
+
+
+def test_prediction_invariants_and_directed_table(harness):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([harness], capture_output=True, text=True, timeout=600, env=env)
+    summary = re.search(r"^launch-plan plans (\d+) kinds (\d+) directed (\d+) routes (\d+) (\d+) (\d+) (\d+) (\d+) refused (\d+) "
+                        r"refine (\d+) (\d+) (\d+) (\d+) (\d+) hash ([0-9a-f]{16}) violations (\d+)$", r.stdout, re.M)
+    assert summary, r.stdout[-3000:] + r.stderr[-3000:]
+    print(summary.group(0))
+    plans, kinds, directed = (int(v) for v in summary.groups()[:3])
+    routes = dict(zip(ROUTES, map(int, summary.groups()[3:8])))
+    refused = int(summary.group(9))
+    refines = dict(zip(REFINES, map(int, summary.groups()[9:14])))
+    violations = int(summary.group(16))
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("violation")]
+    assert violations == 0 and r.returncode == 0, f"{violations} violations:\n" + "\n".join(lines[:60]) + "\n" + r.stderr[-3000:]
+    # the sweep was not vacuous: every route and every step-6 kernel many times over, refusals, predictions, the table
+    assert all(v >= 1000 for v in routes.values()), routes
+    assert all(v >= 1000 for v in refines.values()), refines
+    assert plans > 10_000_000 and kinds > 500_000 and refused >= 1000 and directed >= 30, summary.group(0)

@@ -15,6 +15,7 @@
 #include <climits>
 
 #include "smx_common.h"
+#include "smx_workspace.h"        // SCAN_ITEMS, SCAN_TILE, VOX_TILE, VM_COUNT: shared with the workspace layout
 
 namespace smx {
 
@@ -150,9 +151,6 @@ __global__ __launch_bounds__(256) void k_reproj_scatter(const ReprojArgs a) {
 }
 
 // ---- shared: exclusive scan of an int array (three launches) --------------------------------------------------------
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
-
 // A launch of a skipped radix pass returns at once: gate = the key width in bits (device), pass = the pass's index.
 __device__ __forceinline__ bool pass_skipped(const int *gate, int pass) { return gate && pass * 8 >= *gate; }
 
@@ -224,10 +222,9 @@ __global__ __launch_bounds__(256) void k_scan_down(const int *in, int *out, long
 }
 
 // ---- voxel downsampling ----------------------------------------------------------------------------------------------
-constexpr int VOX_TILE = 4096;            // points per radix tile (one workgroup of 256 threads)
 constexpr float VOX_LIMIT = 1048576.0f;   // kept iff -2^20 <= index < 2^20 on every axis
-// meta[]: the device-side state of one call
-enum { VM_MINX = 0, VM_MINY, VM_MINZ, VM_MAXX, VM_MAXY, VM_MAXZ, VM_KEY_BITS, VM_FLAG_SHIFT, VM_TILES, VM_COUNT = 16 };
+// meta[VM_COUNT]: the device-side state of one call
+enum { VM_MINX = 0, VM_MINY, VM_MINZ, VM_MAXX, VM_MAXY, VM_MAXZ, VM_KEY_BITS, VM_FLAG_SHIFT, VM_TILES };
 
 struct VoxArgs {
     const float *points;            // [cap][3]

@@ -84,8 +84,7 @@ void launch_lr_check(bool mirrored, const float *left, const float *right, float
                      float max_diff, float invalid, hipStream_t s);
 
 // ---- tu_post.hip: speckle filter and hole fill (k_post.h) --------------------------------------------------------
-// workspace: post_workspace_bytes(n, H, W) bytes, layout private to tu_post.hip; nothing in it survives a call
-size_t post_workspace_bytes(int n, int H, int W);
+// workspace: smx_workspace.h: post_layout(n, H, W)
 void launch_filter_speckles(int n, int H, int W, const float *in, float *out, int max_size, float max_diff, float invalid,
                             void *workspace, hipStream_t s);
 void launch_fill_invalid(int n, int H, int W, const float *in, float *out, float invalid, void *workspace, hipStream_t s);
@@ -97,9 +96,8 @@ void launch_weighted_median(int n, int H, int W, const float *in, const float *h
                             int radius, const uint16_t *range, const uint16_t *spatial, float invalid, hipStream_t s);
 
 // ---- tu_wls.hip: image-guided weighted least squares filter (k_wls.h) ----------------------------------------------
-// workspace: wls_workspace_bytes(n, H, W) bytes; lambdas[iterations] and range[256]: the host tables, copied into the
+// workspace: smx_workspace.h: wls_layout(n, H, W); lambdas[iterations] and range[256]: the host tables, copied into the
 // kernel arguments; arguments checked by smx_wls_filter
-size_t wls_workspace_bytes(int n, int H, int W);
 void launch_wls(int n, int H, int W, const float *in, const float *conf, const float *guide, float *out, int iterations,
                 const float *lambdas, const float *range, float min_weight, float invalid, void *workspace,
                 hipStream_t s);
@@ -124,48 +122,41 @@ void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, 
                         float border_value, hipStream_t s);
 
 // ---- tu_sgm.hip: semi-global matching (k_sgm.h) ----------------------------------------------------------------------
-// workspace: sgm_workspace_bytes(n, H, W, D) bytes (smx_sgm_workspace_bytes); right_out NULL: not written (the
+// workspace: smx_workspace.h: sgm_layout(n, H, W, D); right_out NULL: not written (the
 // right-view WTA runs only for the LR check); arguments checked by smx_sgm / smx_sgm_with_right_map
-size_t sgm_workspace_bytes(int n, int H, int W, int D);
 void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const void *right, int dmin, int D, int paths,
                 int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
                 float *gray_out, float *right_out, void *workspace, hipStream_t s);
 
 // ---- tu_reproject.hip: metric 3D points and voxel-grid downsampling (k_reproject.h) ------------------------------------
 // q: the host's 4x4 matrix, copied into the kernel arguments; conf / image / colors / indices / xyz_map may be NULL;
-// arguments checked by smx_reproject_points
-size_t reproject_workspace_bytes(int n, int H);
+// workspace: reproject_layout(n, H); arguments checked by smx_reproject_points
 void launch_reproject(int n, int H, int W, const float *disp, const float q[16], const float *conf, float min_conf,
                       float zmin, float zmax, float invalid, const void *image, int channels, bool img_f32,
                       float *points, uint8_t *colors, int32_t *indices, float *xyz_map, int32_t *offsets,
                       void *workspace, hipStream_t s);
-// colors / out_colors NULL: no colour; arguments checked by smx_voxel_downsample
-size_t voxel_workspace_bytes(int n, int capacity);
+// colors / out_colors NULL: no colour; workspace: vox_layout(n, capacity); arguments checked by smx_voxel_downsample
 hipError_t launch_voxel_downsample(int n, int capacity, const float *points, const uint8_t *colors,
                                    const int32_t *offsets, float voxel_size, int min_points, float *out_points,
                                    uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
                                    void *workspace, hipStream_t s);
-// exclusive scan of L ints, in -> out, in three launches; block_sums: scan_block_sums(L) ints of scratch; gate / pass:
+// exclusive scan of L ints, in -> out, in three launches; block_sums: scan_block_sums(L) ints (smx_workspace.h); gate / pass:
 // a launch returns at once when gate != NULL and pass * 8 >= *gate (the radix passes of the downsampling)
-size_t scan_block_sums(long L);
 void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s);
 
 // ---- tu_tsdf.hip: TSDF fusion and surface extraction (k_tsdf.h, k_mesh.h) --------------------------------------------------------
 // q / p / origin: host values, copied into the kernel arguments; world_to_camera [n][3][4] on the device; conf / color /
-// image may be NULL (color needs image); arguments checked by smx_tsdf_integrate
-size_t tsdf_integrate_workspace_bytes(int n, int H, int W);
+// image may be NULL (color needs image); workspace: tsdf_integrate_layout(n, H, W); arguments checked by smx_tsdf_integrate
 void launch_tsdf_integrate(int nx, int ny, int nz, const float origin[3], float voxel_size, float truncation,
                            float max_weight, float *tsdf, float *weight, uint8_t *color, int n, int H, int W,
                            const float *disp, const float q[16], const float p[16], const float *world_to_camera,
                            const float *conf, float min_conf, float zmin, float zmax, float invalid, const void *image,
                            int channels, bool img_f32, void *workspace, hipStream_t s);
-// normals / colors NULL: not written (colors needs color); arguments checked by smx_tsdf_extract_points
-size_t tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+// normals / colors NULL: not written (colors needs color); workspace: tsdf_extract_layout(ny, nz); checked by smx_tsdf_extract_points
 void launch_tsdf_extract(int nx, int ny, int nz, const float origin[3], float voxel_size, const float *tsdf,
                          const float *weight, const uint8_t *color, float min_weight, int capacity, float *points,
                          float *normals, uint8_t *colors, int32_t *count, void *workspace, hipStream_t s);
-// the triangles over those points (k_mesh.h); arguments checked by smx_tsdf_extract_triangles
-size_t tsdf_triangles_workspace_bytes(int nx, int ny, int nz);
+// the triangles over those points (k_mesh.h); workspace: mesh_layout(nx, ny, nz); checked by smx_tsdf_extract_triangles
 void launch_tsdf_triangles(int nx, int ny, int nz, const float *tsdf, const float *weight, float min_weight,
                            int capacity, int32_t *triangles, int32_t *count, void *workspace, hipStream_t s);
 

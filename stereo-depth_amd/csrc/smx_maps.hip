@@ -1,9 +1,11 @@
 // smx_maps.hip -- the engine-free entries of the C ABI of include/stereo_mi355x.h: operations on maps and frames the
 // caller already has, checked here and enqueued on the caller's stream through the launchers of smx_launch.h.
+#include <initializer_list>
 #include <type_traits>
 
 #include "smx_launch.h"
 #include "smx_status.h"
+#include "smx_workspace.h"
 
 using namespace smx;
 
@@ -31,6 +33,97 @@ static int check_workspace_and_stream(const char *fn, const void *workspace, voi
     return check_caller_stream(fn, stream);
 }
 
+// ---- one spelling per kind of rule ---------------------------------------------------------------------------------
+static int check_positive(const char *fn, const char *name, float v) {
+    if (std::isfinite(v) && v > 0.0f) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: %s must be finite and > 0, got %g", fn, name, (double)v);
+}
+
+static int check_non_negative(const char *fn, const char *name, float v) {
+    if (std::isfinite(v) && v >= 0.0f) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: %s must be finite and >= 0, got %g", fn, name, (double)v);
+}
+
+static int check_int_range(const char *fn, const char *name, int v, int lo, int hi) {
+    if (v >= lo && v <= hi) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: %s must be in %d..%d, got %d", fn, name, lo, hi, v);
+}
+
+static int check_finite_at(const char *fn, const char *name, const float *v, int k) {
+    if (std::isfinite(v[k])) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: %s[%d] = %g is not finite", fn, name, k, (double)v[k]);
+}
+
+static int check_finite_array(const char *fn, const char *name, const float *v, int count) {
+    for (int k = 0; k < count; ++k)
+        if (int rc = check_finite_at(fn, name, v, k)) return rc;
+    return SMX_OK;
+}
+
+// `query`: the name of the entry's size query, whose value for these arguments is `need`.
+static int check_workspace_bytes(const char *fn, const char *query, size_t workspace_bytes, size_t need) {
+    if (workspace_bytes >= need) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below %s = %zu", fn, workspace_bytes, query, need);
+}
+
+// what: "" or "image "
+static int check_dtype(const char *fn, const char *what, int dtype) {
+    if (dtype == SMX_DTYPE_U8 || dtype == SMX_DTYPE_F32) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: unknown %sdtype %d", fn, what, dtype);
+}
+
+static constexpr long SMX_POINTS_MAX = 1L << 30;     // n*H*W (reprojection, TSDF integration) and every capacity
+
+static int check_capacity(const char *fn, int capacity) {
+    if (capacity >= 1 && capacity <= SMX_POINTS_MAX) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: capacity must be in 1..2^30, got %d", fn, capacity);
+}
+
+static bool points_dims_ok(int n, int H, int W) { return map_dims_ok(n, H, W) && (long)n * H * W <= SMX_POINTS_MAX; }
+
+// After check_map_dims.
+static int check_pixel_count(const char *fn, int n, int H, int W) {
+    if ((long)n * H * W <= SMX_POINTS_MAX) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: n * H * W = %ld exceeds 2^30: split the batch", fn, (long)n * H * W);
+}
+
+// An operand's bytes; a NULL operand overlaps nothing.
+struct Span {
+    const void *p;
+    size_t bytes;
+};
+
+// Each of `outs` in turn: it must overlap none of `ins` (else in_text) and, where out_text is given, none of the outs
+// after it (else out_text).  The texts are the entry's own.
+static int check_disjoint(const char *fn, std::initializer_list<Span> ins, std::initializer_list<Span> outs,
+                          const char *in_text, const char *out_text = nullptr) {
+    for (const Span *o = outs.begin(); o != outs.end(); ++o) {
+        for (const Span &i : ins)
+            if (ranges_overlap(o->p, o->bytes, i.p, i.bytes)) return fail(SMX_ERR_INVALID_ARG, "%s: %s", fn, in_text);
+        for (const Span *q = o + 1; out_text && q != outs.end(); ++q)
+            if (ranges_overlap(o->p, o->bytes, q->p, q->bytes)) return fail(SMX_ERR_INVALID_ARG, "%s: %s", fn, out_text);
+    }
+    return SMX_OK;
+}
+
+// The rules smx_reproject_points and smx_tsdf_integrate share, in their order; colour_out: the output that needs an
+// image, colour_text: what the entry says when it has none.
+static int check_reprojection_args(const char *fn, float z_min, float z_max, float min_confidence, float invalid_disparity,
+                                   const void *image, int image_channels, int image_dtype, const void *colour_out,
+                                   const char *colour_text) {
+    if (std::isnan(z_min) || std::isnan(z_max) || z_min > z_max)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need z_min <= z_max, got %g, %g", fn, (double)z_min, (double)z_max);
+    if (!std::isfinite(min_confidence))
+        return fail(SMX_ERR_INVALID_ARG, "%s: min_confidence must be finite, got %g", fn, (double)min_confidence);
+    if (int rc = check_finite_marker(invalid_disparity)) return rc;
+    if (image) {
+        if (image_channels != 1 && image_channels != 3)
+            return fail(SMX_ERR_INVALID_ARG, "%s: image_channels must be 1 or 3 with an image, got %d", fn, image_channels);
+        return check_dtype(fn, "image ", image_dtype);
+    }
+    return colour_out ? fail(SMX_ERR_INVALID_ARG, "%s: %s", fn, colour_text) : SMX_OK;
+}
+
 // Selects the device, runs `launch` (which returns a status if it makes a HIP call of its own) and checks the launch.
 template <class F> static int launch_on(int device_id, F &&launch) {
     DeviceGuard guard(device_id);
@@ -46,15 +139,15 @@ static int check_post_args(const char *fn, int n, int H, int W, const float *in,
                            size_t workspace_bytes, void *stream) {
     if (!in || !out || !workspace) return fail(SMX_ERR_INVALID_ARG, "%s: in, out and workspace must be non-NULL", fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    const size_t need = smx::post_workspace_bytes(n, H, W);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_postprocess_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, "smx_postprocess_workspace_bytes", workspace_bytes, post_layout(n, H, W).total))
+        return rc;
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (out != in && ranges_overlap(in, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in other than as the same buffer", fn);
-    if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in or out", fn);
+    if (int rc = check_disjoint(fn, {{out != in ? in : nullptr, bytes}}, {{out, bytes}},
+                                "out must not overlap in other than as the same buffer"))
+        return rc;
+    if (int rc = check_disjoint(fn, {{in, bytes}, {out, bytes}}, {{workspace, workspace_bytes}},
+                                "the workspace must not overlap in or out"))
+        return rc;
     return check_workspace_and_stream(fn, workspace, stream);
 }
 
@@ -67,15 +160,16 @@ int smx_lr_check(int device_id, int n, int H, int W, const float *left, const fl
     if (int rc = check_map_dims("smx_lr_check", n, H, W)) return rc;
     if (int rc = check_caller_stream("smx_lr_check", stream)) return rc;
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (ranges_overlap(right, bytes, out, bytes) || (out != left && ranges_overlap(left, bytes, out, bytes)))
-        return fail(SMX_ERR_INVALID_ARG, "smx_lr_check: out must not overlap right_disp, and overlap left_disp only as the same buffer");
+    if (int rc = check_disjoint("smx_lr_check", {{right, bytes}, {out != left ? left : nullptr, bytes}}, {{out, bytes}},
+                                "out must not overlap right_disp, and overlap left_disp only as the same buffer"))
+        return rc;
     return launch_on(device_id, [&] {
         smx::launch_lr_check(false, left, right, out, nullptr, n, H, W, max_diff, invalid, (hipStream_t)stream);
     });
 }
 
 size_t smx_postprocess_workspace_bytes(int n, int H, int W) {
-    return map_dims_ok(n, H, W) ? smx::post_workspace_bytes(n, H, W) : 0;
+    return map_dims_ok(n, H, W) ? post_layout(n, H, W).total : 0;
 }
 
 int smx_filter_speckles(int device_id, int n, int H, int W, const float *in, float *out, int max_speckle_size,
@@ -111,7 +205,7 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
     if (!range_weight || !spatial_weight)
         return fail(SMX_ERR_INVALID_ARG, "%s: range_weight and spatial_weight must be non-NULL", fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    if (radius < 1 || radius > 15) return fail(SMX_ERR_INVALID_ARG, "%s: radius must be in 1..15, got %d", fn, radius);
+    if (int rc = check_int_range(fn, "radius", radius, 1, 15)) return rc;
     for (int k = 0; k < 256; ++k)
         if (range_weight[k] > 1023)
             return fail(SMX_ERR_INVALID_ARG, "%s: range_weight[%d] = %d is above 1023", fn, k, (int)range_weight[k]);
@@ -119,21 +213,19 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
         if (spatial_weight[k] > 1023)
             return fail(SMX_ERR_INVALID_ARG, "%s: spatial_weight[%d] = %d is above 1023", fn, k, (int)spatial_weight[k]);
     if (int rc = check_finite_marker(invalid)) return rc;
-    const size_t need = smx::median_workspace_bytes(n, H, W);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_median_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, "smx_median_workspace_bytes", workspace_bytes, smx::median_workspace_bytes(n, H, W)))
+        return rc;
     if (!workspace && workspace_bytes > 0)
         return fail(SMX_ERR_INVALID_ARG, "%s: workspace is NULL but workspace_bytes is %zu", fn, workspace_bytes);
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(guide, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap in or guide", fn);
-    if (holes && out != holes && ranges_overlap(holes, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap holes other than as the same buffer", fn);
-    if (workspace_bytes > 0 &&
-        (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
-         ranges_overlap(workspace, workspace_bytes, guide, bytes) || ranges_overlap(workspace, workspace_bytes, holes, bytes)))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, holes, guide or out", fn);
+    if (int rc = check_disjoint(fn, {{in, bytes}, {guide, bytes}}, {{out, bytes}}, "out must not overlap in or guide")) return rc;
+    if (int rc = check_disjoint(fn, {{out != holes ? holes : nullptr, bytes}}, {{out, bytes}},
+                                "out must not overlap holes other than as the same buffer"))
+        return rc;
+    if (workspace_bytes > 0)
+        if (int rc = check_disjoint(fn, {{in, bytes}, {out, bytes}, {guide, bytes}, {holes, bytes}},
+                                    {{workspace, workspace_bytes}}, "the workspace must not overlap in, holes, guide or out"))
+            return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_weighted_median(n, H, W, in, holes, guide, out, radius, range_weight, spatial_weight, invalid,
@@ -142,7 +234,7 @@ int smx_weighted_median(int device_id, int n, int H, int W, const float *in, con
 }
 
 size_t smx_wls_workspace_bytes(int n, int H, int W) {
-    return map_dims_ok(n, H, W) ? smx::wls_workspace_bytes(n, H, W) : 0;
+    return map_dims_ok(n, H, W) ? wls_layout(n, H, W).total : 0;
 }
 
 int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const float *confidence, const float *guide,
@@ -152,8 +244,7 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
     if (!in || !guide || !out) return fail(SMX_ERR_INVALID_ARG, "%s: in, guide and out must be non-NULL", fn);
     if (!lambdas || !range_weight) return fail(SMX_ERR_INVALID_ARG, "%s: lambdas and range_weight must be non-NULL", fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    if (num_iterations < 1 || num_iterations > 8)
-        return fail(SMX_ERR_INVALID_ARG, "%s: num_iterations must be in 1..8, got %d", fn, num_iterations);
+    if (int rc = check_int_range(fn, "num_iterations", num_iterations, 1, 8)) return rc;
     for (int t = 0; t < num_iterations; ++t)
         if (!(std::isfinite(lambdas[t]) && lambdas[t] >= 0.0f && lambdas[t] <= 1048576.0f))
             return fail(SMX_ERR_INVALID_ARG, "%s: lambdas[%d] = %g is not finite in [0, 2^20]", fn, t, (double)lambdas[t]);
@@ -161,22 +252,19 @@ int smx_wls_filter(int device_id, int n, int H, int W, const float *in, const fl
         if (!(std::isfinite(range_weight[k]) && range_weight[k] >= 0.0f && range_weight[k] <= 1.0f))
             return fail(SMX_ERR_INVALID_ARG, "%s: range_weight[%d] = %g is not finite in [0, 1]", fn, k,
                         (double)range_weight[k]);
-    if (!(std::isfinite(min_weight) && min_weight >= 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and >= 0, got %g", fn, (double)min_weight);
+    if (int rc = check_non_negative(fn, "min_weight", min_weight)) return rc;
     if (int rc = check_finite_marker(invalid)) return rc;
-    const size_t need = smx::wls_workspace_bytes(n, H, W);
+    const size_t need = wls_layout(n, H, W).total;
     if (!workspace || workspace_bytes < need)
         return fail(SMX_ERR_INVALID_ARG, "%s: workspace is NULL or workspace_bytes %zu is below smx_wls_workspace_bytes = %zu",
                     fn, workspace_bytes, need);
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if ((out != in && ranges_overlap(in, bytes, out, bytes)) || ranges_overlap(confidence, bytes, out, bytes) ||
-        ranges_overlap(guide, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap confidence or guide, and overlap in only as the same buffer",
-                    fn);
-    if (ranges_overlap(workspace, workspace_bytes, in, bytes) || ranges_overlap(workspace, workspace_bytes, out, bytes) ||
-        ranges_overlap(workspace, workspace_bytes, guide, bytes) ||
-        ranges_overlap(workspace, workspace_bytes, confidence, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap in, confidence, guide or out", fn);
+    if (int rc = check_disjoint(fn, {{out != in ? in : nullptr, bytes}, {confidence, bytes}, {guide, bytes}}, {{out, bytes}},
+                                "out must not overlap confidence or guide, and overlap in only as the same buffer"))
+        return rc;
+    if (int rc = check_disjoint(fn, {{in, bytes}, {out, bytes}, {guide, bytes}, {confidence, bytes}},
+                                {{workspace, workspace_bytes}}, "the workspace must not overlap in, confidence, guide or out"))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_wls(n, H, W, in, confidence, guide, out, num_iterations, lambdas, range_weight, min_weight, invalid,
@@ -192,15 +280,13 @@ int smx_confidence_map(int device_id, int n, int H, int W, const float *left_dis
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
     if (guide && (radius < 1 || radius > 15))
         return fail(SMX_ERR_INVALID_ARG, "%s: radius must be in 1..15 with a guide, got %d", fn, radius);
-    if (!(std::isfinite(lr_scale) && lr_scale > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: lr_scale must be finite and > 0, got %g", fn, (double)lr_scale);
-    if (!(std::isfinite(texture_scale) && texture_scale > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: texture_scale must be finite and > 0, got %g", fn, (double)texture_scale);
+    if (int rc = check_positive(fn, "lr_scale", lr_scale)) return rc;
+    if (int rc = check_positive(fn, "texture_scale", texture_scale)) return rc;
     if (int rc = check_finite_marker(invalid)) return rc;
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    if (ranges_overlap(left_disp, bytes, out, bytes) || ranges_overlap(right_disp, bytes, out, bytes) ||
-        ranges_overlap(guide, bytes, out, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap left_disp, right_disp or guide", fn);
+    if (int rc = check_disjoint(fn, {{left_disp, bytes}, {right_disp, bytes}, {guide, bytes}}, {{out, bytes}},
+                                "out must not overlap left_disp, right_disp or guide"))
+        return rc;
     if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_confidence(n, H, W, left_disp, right_disp, guide, radius, lr_scale, texture_scale, invalid, out,
@@ -217,37 +303,22 @@ int smx_temporal_filter(int device_id, int n, int H, int W, const float *disp, c
         return fail(SMX_ERR_INVALID_ARG, "%s: disp, guide, prev_guide, state_disp, state_weight and out must be non-NULL",
                     fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    if (motion_radius < 0 || motion_radius > 7)
-        return fail(SMX_ERR_INVALID_ARG, "%s: motion_radius must be in 0..7, got %d", fn, motion_radius);
-    if (!(std::isfinite(motion_threshold) && motion_threshold >= 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: motion_threshold must be finite and >= 0, got %g", fn,
-                    (double)motion_threshold);
+    if (int rc = check_int_range(fn, "motion_radius", motion_radius, 0, 7)) return rc;
+    if (int rc = check_non_negative(fn, "motion_threshold", motion_threshold)) return rc;
     if (!(decay > 0.0f && decay <= 1.0f))
         return fail(SMX_ERR_INVALID_ARG, "%s: decay must be in (0, 1], got %g", fn, (double)decay);
-    if (!(std::isfinite(max_diff) && max_diff >= 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: max_diff must be finite and >= 0, got %g", fn, (double)max_diff);
-    if (!(std::isfinite(max_weight) && max_weight > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: max_weight must be finite and > 0, got %g", fn, (double)max_weight);
-    if (!(std::isfinite(min_weight) && min_weight >= 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and >= 0, got %g", fn, (double)min_weight);
+    if (int rc = check_non_negative(fn, "max_diff", max_diff)) return rc;
+    if (int rc = check_positive(fn, "max_weight", max_weight)) return rc;
+    if (int rc = check_non_negative(fn, "min_weight", min_weight)) return rc;
     if (int rc = check_finite_marker(invalid)) return rc;
     const size_t bytes = (size_t)n * H * W * sizeof(float);
-    const void *inputs[4] = {disp, confidence, guide, prev_guide};
-    if (out != disp && ranges_overlap(out, bytes, disp, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap disp other than as the same buffer", fn);
-    const void *others[6] = {confidence, guide, prev_guide, state_disp, state_weight, guide_out};
-    for (const void *o : others)
-        if (ranges_overlap(out, bytes, o, bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: out must not overlap an operand other than disp", fn);
-    for (const void *i : inputs)
-        if (ranges_overlap(state_disp, bytes, i, bytes) || ranges_overlap(state_weight, bytes, i, bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: the state buffers must not overlap an input", fn);
-    if (ranges_overlap(state_disp, bytes, state_weight, bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: state_disp and state_weight overlap", fn);
-    const void *not_guide_out[6] = {disp, confidence, guide, prev_guide, state_disp, state_weight};
-    for (const void *o : not_guide_out)
-        if (ranges_overlap(guide_out, bytes, o, bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: guide_out must not overlap another operand", fn);
+    const Span d{disp, bytes}, d_unless_out{out != disp ? disp : nullptr, bytes}, c{confidence, bytes}, g{guide, bytes},
+        pg{prev_guide, bytes}, sd{state_disp, bytes}, sw{state_weight, bytes}, go{guide_out, bytes}, o{out, bytes};
+    if (int rc = check_disjoint(fn, {d_unless_out}, {o}, "out must not overlap disp other than as the same buffer")) return rc;
+    if (int rc = check_disjoint(fn, {c, g, pg, sd, sw, go}, {o}, "out must not overlap an operand other than disp")) return rc;
+    if (int rc = check_disjoint(fn, {d, c, g, pg}, {sd, sw}, "the state buffers must not overlap an input")) return rc;
+    if (int rc = check_disjoint(fn, {sd}, {sw}, "state_disp and state_weight overlap")) return rc;
+    if (int rc = check_disjoint(fn, {d, c, g, pg, sd, sw}, {go}, "guide_out must not overlap another operand")) return rc;
     if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_temporal(n, H, W, disp, confidence, guide, prev_guide, state_disp, state_weight, guide_out, out,
@@ -269,8 +340,8 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
     if (H_in < 1 || W_in < 1 || H_out < 1 || W_out < 1 || H_in > 32768 || W_in > 32768 || H_out > 32768 || W_out > 32768)
         return fail(SMX_ERR_INVALID_ARG, "%s: sizes must be in 1..32768 (got in %dx%d, out %dx%d)", fn, H_in, W_in, H_out,
                     W_out);
-    if (channels < 1 || channels > 4) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be in 1..4, got %d", fn, channels);
-    if (dtype != SMX_DTYPE_U8 && dtype != SMX_DTYPE_F32) return fail(SMX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (int rc = check_int_range(fn, "channels", channels, 1, 4)) return rc;
+    if (int rc = check_dtype(fn, "", dtype)) return rc;
     if (border_mode != SMX_BORDER_CONSTANT && border_mode != SMX_BORDER_REPLICATE)
         return fail(SMX_ERR_INVALID_ARG, "%s: unknown border mode %d", fn, border_mode);
     if (!std::isfinite(border_value))
@@ -285,15 +356,10 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
     const size_t in_bytes = (size_t)n * channels * H_in * W_in * es;
     const size_t out_bytes = (size_t)n * channels * H_out * W_out * es;
     const size_t map_bytes = (size_t)H_out * W_out * 2 * sizeof(int32_t);
-    const void *outs[2] = {left_out, right_out};
-    for (const void *o : outs) {
-        if (!o) continue;
-        if (ranges_overlap(o, out_bytes, left_in, in_bytes) || ranges_overlap(o, out_bytes, right_in, in_bytes) ||
-            ranges_overlap(o, out_bytes, left_map, map_bytes) || ranges_overlap(o, out_bytes, right_map, map_bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or a map", fn);
-    }
-    if (ranges_overlap(left_out, out_bytes, right_out, out_bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: left_out and right_out overlap", fn);
+    if (int rc = check_disjoint(fn, {{left_in, in_bytes}, {right_in, in_bytes}, {left_map, map_bytes}, {right_map, map_bytes}},
+                                {{left_out, out_bytes}, {right_out, out_bytes}}, "an output overlaps an input or a map"))
+        return rc;
+    if (int rc = check_disjoint(fn, {{left_out, out_bytes}}, {{right_out, out_bytes}}, "left_out and right_out overlap")) return rc;
     if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_remap_pairs(n, channels, dtype == SMX_DTYPE_F32, H_in, W_in, H_out, W_out, left_in, right_in, left_map,
@@ -312,7 +378,7 @@ static int sgm_size_error(int n, int H, int W, int D, int paths) {
 }
 
 size_t smx_sgm_workspace_bytes(int n, int H, int W, int num_disparities, int paths) {
-    return sgm_size_error(n, H, W, num_disparities, paths) ? 0 : smx::sgm_workspace_bytes(n, H, W, num_disparities);
+    return sgm_size_error(n, H, W, num_disparities, paths) ? 0 : sgm_layout(n, H, W, num_disparities).total;
 }
 
 // smx_sgm and smx_sgm_with_right_map: right_out NULL is smx_sgm.
@@ -327,11 +393,9 @@ static int sgm_entry(const char *fn, int device_id, int n, int channels, int dty
         return fail(SMX_ERR_INVALID_ARG, "%s: n * (H + W) = %zu exceeds 2^31: split the batch", fn,
                     (size_t)n * (size_t)(H + W));
     if (channels != 1 && channels != 3) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be 1 or 3, got %d", fn, channels);
-    if (dtype != SMX_DTYPE_U8 && dtype != SMX_DTYPE_F32) return fail(SMX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
-    if (min_disparity < 0 || min_disparity > 32768)
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_disparity must be in 0..32768, got %d", fn, min_disparity);
-    if (num_disparities < 1 || num_disparities > 256)
-        return fail(SMX_ERR_INVALID_ARG, "%s: num_disparities must be in 1..256, got %d", fn, num_disparities);
+    if (int rc = check_dtype(fn, "", dtype)) return rc;
+    if (int rc = check_int_range(fn, "min_disparity", min_disparity, 0, 32768)) return rc;
+    if (int rc = check_int_range(fn, "num_disparities", num_disparities, 1, 256)) return rc;
     if (paths != 4 && paths != 8) return fail(SMX_ERR_INVALID_ARG, "%s: paths must be 4 or 8, got %d", fn, paths);
     if (!(0 <= P1 && P1 <= P2 && P2 <= 191))
         return fail(SMX_ERR_INVALID_ARG, "%s: need 0 <= P1 <= P2 <= 191, got P1 %d, P2 %d", fn, P1, P2);
@@ -341,23 +405,17 @@ static int sgm_entry(const char *fn, int device_id, int n, int channels, int dty
         return fail(SMX_ERR_INVALID_ARG, "%s: lr_max_diff must be finite (negative: no LR check), got %g", fn,
                     (double)lr_max_diff);
     if (int rc = check_finite_marker(invalid_disparity)) return rc;
-    const size_t need = smx::sgm_workspace_bytes(n, H, W, num_disparities);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_sgm_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, "smx_sgm_workspace_bytes", workspace_bytes,
+                                       sgm_layout(n, H, W, num_disparities).total))
+        return rc;
     const size_t in_bytes = (size_t)n * channels * H * W * (dtype == SMX_DTYPE_F32 ? 4 : 1);
     const size_t map_bytes = (size_t)n * H * W * sizeof(float);
-    const void *outs[3] = {out, gray_left_out, right_out};
-    for (const void *o : outs)
-        if (ranges_overlap(o, map_bytes, left, in_bytes) || ranges_overlap(o, map_bytes, right, in_bytes) ||
-            ranges_overlap(o, map_bytes, workspace, workspace_bytes))
-            return fail(SMX_ERR_INVALID_ARG, "%s: the outputs must not overlap left, right or the workspace", fn);
-    if (ranges_overlap(out, map_bytes, gray_left_out, map_bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: out and gray_left_out overlap", fn);
-    if (ranges_overlap(right_out, map_bytes, out, map_bytes) || ranges_overlap(right_out, map_bytes, gray_left_out, map_bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: right_out overlaps out or gray_left_out", fn);
-    if (ranges_overlap(workspace, workspace_bytes, left, in_bytes) || ranges_overlap(workspace, workspace_bytes, right, in_bytes))
-        return fail(SMX_ERR_INVALID_ARG, "%s: the workspace must not overlap left or right", fn);
+    const Span l{left, in_bytes}, r{right, in_bytes}, ws{workspace, workspace_bytes}, o{out, map_bytes},
+        g{gray_left_out, map_bytes}, ro{right_out, map_bytes};
+    if (int rc = check_disjoint(fn, {l, r, ws}, {o, g, ro}, "the outputs must not overlap left, right or the workspace")) return rc;
+    if (int rc = check_disjoint(fn, {g}, {o}, "out and gray_left_out overlap")) return rc;
+    if (int rc = check_disjoint(fn, {o, g}, {ro}, "right_out overlaps out or gray_left_out")) return rc;
+    if (int rc = check_disjoint(fn, {l, r}, {ws}, "the workspace must not overlap left or right")) return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_sgm(n, channels, dtype == SMX_DTYPE_F32, H, W, left, right, min_disparity, num_disparities, paths, P1,
@@ -410,11 +468,8 @@ int smx_eval_metrics(int device_id, int n, const float *est, const float *gt, co
 }
 
 // ---- metric 3D points ----------------------------------------------------------------------------------------------------
-static constexpr long SMX_POINTS_MAX = 1L << 30;     // n*H*W (reprojection) and the capacity (downsampling)
-
 size_t smx_reproject_workspace_bytes(int n, int H, int W) {
-    if (!map_dims_ok(n, H, W) || (long)n * H * W > SMX_POINTS_MAX) return 0;
-    return smx::reproject_workspace_bytes(n, H);
+    return points_dims_ok(n, H, W) ? reproject_layout(n, H).total : 0;
 }
 
 int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, const float Q[16],
@@ -426,44 +481,21 @@ int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, 
     if (!disp || !Q || !points || !offsets || !workspace)
         return fail(SMX_ERR_INVALID_ARG, "%s: disp, Q, points, offsets and workspace must be non-NULL", fn);
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    const long cap = (long)n * H * W;
-    if (cap > SMX_POINTS_MAX)
-        return fail(SMX_ERR_INVALID_ARG, "%s: n * H * W = %ld exceeds 2^30: split the batch", fn, cap);
-    for (int k = 0; k < 16; ++k)
-        if (!std::isfinite(Q[k])) return fail(SMX_ERR_INVALID_ARG, "%s: Q[%d] = %g is not finite", fn, k, (double)Q[k]);
-    if (std::isnan(z_min) || std::isnan(z_max) || z_min > z_max)
-        return fail(SMX_ERR_INVALID_ARG, "%s: need z_min <= z_max, got %g, %g", fn, (double)z_min, (double)z_max);
-    if (!std::isfinite(min_confidence))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_confidence must be finite, got %g", fn, (double)min_confidence);
-    if (int rc = check_finite_marker(invalid_disparity)) return rc;
-    if (image) {
-        if (image_channels != 1 && image_channels != 3)
-            return fail(SMX_ERR_INVALID_ARG, "%s: image_channels must be 1 or 3 with an image, got %d", fn, image_channels);
-        if (image_dtype != SMX_DTYPE_U8 && image_dtype != SMX_DTYPE_F32)
-            return fail(SMX_ERR_INVALID_ARG, "%s: unknown image dtype %d", fn, image_dtype);
-    } else if (colors) {
-        return fail(SMX_ERR_INVALID_ARG, "%s: colors needs an image", fn);
-    }
-    const size_t need = smx::reproject_workspace_bytes(n, H);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_reproject_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
-    const size_t px = (size_t)cap;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (int rc = check_finite_array(fn, "Q", Q, 16)) return rc;
+    if (int rc = check_reprojection_args(fn, z_min, z_max, min_confidence, invalid_disparity, image, image_channels,
+                                         image_dtype, colors, "colors needs an image"))
+        return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_reproject_workspace_bytes", workspace_bytes, reproject_layout(n, H).total))
+        return rc;
+    const size_t px = (size_t)n * H * W;
     const size_t map_bytes = px * sizeof(float);
     const size_t img_bytes = image ? px * image_channels * (image_dtype == SMX_DTYPE_F32 ? 4 : 1) : 0;
-    const void *ins[4] = {disp, confidence, image, workspace};
-    const size_t in_bytes[4] = {map_bytes, map_bytes, img_bytes, workspace_bytes};
-    void *outs[5] = {points, colors, indices, xyz_map, offsets};
-    const size_t out_bytes[5] = {px * 3 * sizeof(float), px * 3, px * sizeof(int32_t), px * 3 * sizeof(float),
-                                 ((size_t)n + 1) * sizeof(int32_t)};
-    for (int i = 0; i < 5; ++i) {
-        for (int j = 0; j < 4; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or the workspace", fn);
-        for (int j = i + 1; j < 5; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
-    }
+    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {image, img_bytes}, {workspace, workspace_bytes}},
+                                {{points, px * 3 * sizeof(float)}, {colors, px * 3}, {indices, px * sizeof(int32_t)},
+                                 {xyz_map, px * 3 * sizeof(float)}, {offsets, ((size_t)n + 1) * sizeof(int32_t)}},
+                                "an output overlaps an input or the workspace", "two outputs overlap"))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_reproject(n, H, W, disp, Q, confidence, min_confidence, z_min, z_max, invalid_disparity, image,
@@ -475,7 +507,7 @@ int smx_reproject_points(int device_id, int n, int H, int W, const float *disp, 
 static bool voxel_dims_ok(int n, int capacity) { return n >= 1 && n <= 65536 && capacity >= 1 && capacity <= SMX_POINTS_MAX; }
 
 size_t smx_voxel_workspace_bytes(int n, int capacity) {
-    return voxel_dims_ok(n, capacity) ? smx::voxel_workspace_bytes(n, capacity) : 0;
+    return voxel_dims_ok(n, capacity) ? vox_layout(n, capacity).total : 0;
 }
 
 int smx_voxel_downsample(int device_id, int n, int capacity, const float *points, const uint8_t *colors,
@@ -491,26 +523,17 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
     if (!voxel_dims_ok(n, capacity))
         return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= n <= 65536 and 1 <= capacity <= 2^30 (got n %d, capacity %d)", fn,
                     n, capacity);
-    if (!(std::isfinite(voxel_size) && voxel_size > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: voxel_size must be finite and > 0, got %g", fn, (double)voxel_size);
+    if (int rc = check_positive(fn, "voxel_size", voxel_size)) return rc;
     if (min_points < 1) return fail(SMX_ERR_INVALID_ARG, "%s: min_points must be >= 1, got %d", fn, min_points);
-    const size_t need = smx::voxel_workspace_bytes(n, capacity);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_voxel_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, "smx_voxel_workspace_bytes", workspace_bytes, vox_layout(n, capacity).total))
+        return rc;
     const size_t cap = (size_t)capacity, offs = ((size_t)n + 1) * sizeof(int32_t);
-    const void *ins[4] = {points, colors, offsets, workspace};
-    const size_t in_bytes[4] = {cap * 3 * sizeof(float), cap * 3, offs, workspace_bytes};
-    void *outs[5] = {out_points, out_colors, out_counts, out_offsets, dropped};
-    const size_t out_bytes[5] = {cap * 3 * sizeof(float), cap * 3, cap * sizeof(int32_t), offs, (size_t)n * sizeof(int32_t)};
-    for (int i = 0; i < 5; ++i) {
-        for (int j = 0; j < 4; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: an output overlaps an input or the workspace", fn);
-        for (int j = i + 1; j < 5; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs overlap", fn);
-    }
+    const size_t xyz = cap * 3 * sizeof(float);
+    if (int rc = check_disjoint(fn, {{points, xyz}, {colors, cap * 3}, {offsets, offs}, {workspace, workspace_bytes}},
+                                {{out_points, xyz}, {out_colors, cap * 3}, {out_counts, cap * sizeof(int32_t)},
+                                 {out_offsets, offs}, {dropped, (size_t)n * sizeof(int32_t)}},
+                                "an output overlaps an input or the workspace", "two outputs overlap"))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&]() -> int {
         SMX_HIP(smx::launch_voxel_downsample(n, capacity, points, colors, offsets, voxel_size, min_points, out_points,
@@ -528,36 +551,25 @@ static bool tsdf_dims_ok(int nx, int ny, int nz) {
            (long)nx * ny * nz <= SMX_TSDF_VOXELS_MAX;
 }
 
-// The volume's checks shared by both TSDF entries (after their NULL checks).
-static int check_tsdf_volume(const char *fn, int nx, int ny, int nz, const float origin[3], float voxel_size) {
-    if (!tsdf_dims_ok(nx, ny, nz))
-        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= nx, ny, nz <= 4096 and nx * ny * nz <= 2^30 (got %d, %d, %d)", fn,
-                    nx, ny, nz);
-    if (!(std::isfinite(voxel_size) && voxel_size > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: voxel_size must be finite and > 0, got %g", fn, (double)voxel_size);
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(origin[k]))
-            return fail(SMX_ERR_INVALID_ARG, "%s: origin[%d] = %g is not finite", fn, k, (double)origin[k]);
-    return SMX_OK;
+static int check_tsdf_dims(const char *fn, int nx, int ny, int nz) {
+    if (tsdf_dims_ok(nx, ny, nz)) return SMX_OK;
+    return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= nx, ny, nz <= 4096 and nx * ny * nz <= 2^30 (got %d, %d, %d)", fn, nx,
+                ny, nz);
 }
 
-// An output (or the workspace) that overlaps an input or another output.
-static int check_disjoint(const char *fn, int NI, const void *const *ins, const size_t *in_bytes, int NO,
-                          void *const *outs, const size_t *out_bytes) {
-    for (int i = 0; i < NO; ++i) {
-        for (int j = 0; j < NI; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: an output or the workspace overlaps an input", fn);
-        for (int j = i + 1; j < NO; ++j)
-            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j]))
-                return fail(SMX_ERR_INVALID_ARG, "%s: two outputs (state arrays, workspace) overlap", fn);
-    }
-    return SMX_OK;
+// The volume's checks shared by smx_tsdf_integrate and smx_tsdf_extract_points (after their NULL checks).
+static int check_tsdf_volume(const char *fn, int nx, int ny, int nz, const float origin[3], float voxel_size) {
+    if (int rc = check_tsdf_dims(fn, nx, ny, nz)) return rc;
+    if (int rc = check_positive(fn, "voxel_size", voxel_size)) return rc;
+    return check_finite_array(fn, "origin", origin, 3);
 }
+
+// The texts of the TSDF entries' disjointness rule.
+static const char *const TSDF_IN_TEXT = "an output or the workspace overlaps an input";
+static const char *const TSDF_OUT_TEXT = "two outputs (state arrays, workspace) overlap";
 
 size_t smx_tsdf_integrate_workspace_bytes(int n, int H, int W) {
-    if (!map_dims_ok(n, H, W) || (long)n * H * W > SMX_POINTS_MAX) return 0;
-    return smx::tsdf_integrate_workspace_bytes(n, H, W);
+    return points_dims_ok(n, H, W) ? tsdf_integrate_layout(n, H, W).total : 0;
 }
 
 int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
@@ -572,41 +584,27 @@ int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin
                     "%s: origin, tsdf, weight, disp, Q, P, world_to_camera and workspace must be non-NULL", fn);
     if (int rc = check_tsdf_volume(fn, nx, ny, nz, origin, voxel_size)) return rc;
     if (int rc = check_map_dims(fn, n, H, W)) return rc;
-    const long px = (long)n * H * W;
-    if (px > SMX_POINTS_MAX)
-        return fail(SMX_ERR_INVALID_ARG, "%s: n * H * W = %ld exceeds 2^30: split the batch", fn, px);
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
     if (!(std::isfinite(truncation) && truncation > voxel_size))
         return fail(SMX_ERR_INVALID_ARG, "%s: truncation must be finite and > voxel_size, got %g", fn, (double)truncation);
-    if (!(std::isfinite(max_weight) && max_weight > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: max_weight must be finite and > 0, got %g", fn, (double)max_weight);
-    for (int k = 0; k < 16; ++k) {
-        if (!std::isfinite(Q[k])) return fail(SMX_ERR_INVALID_ARG, "%s: Q[%d] = %g is not finite", fn, k, (double)Q[k]);
-        if (!std::isfinite(P[k])) return fail(SMX_ERR_INVALID_ARG, "%s: P[%d] = %g is not finite", fn, k, (double)P[k]);
+    if (int rc = check_positive(fn, "max_weight", max_weight)) return rc;
+    for (int k = 0; k < 16; ++k) {                            // one loop: the lower index is reported, Q before P
+        if (int rc = check_finite_at(fn, "Q", Q, k)) return rc;
+        if (int rc = check_finite_at(fn, "P", P, k)) return rc;
     }
-    if (std::isnan(z_min) || std::isnan(z_max) || z_min > z_max)
-        return fail(SMX_ERR_INVALID_ARG, "%s: need z_min <= z_max, got %g, %g", fn, (double)z_min, (double)z_max);
-    if (!std::isfinite(min_confidence))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_confidence must be finite, got %g", fn, (double)min_confidence);
-    if (int rc = check_finite_marker(invalid_disparity)) return rc;
-    if (image) {
-        if (image_channels != 1 && image_channels != 3)
-            return fail(SMX_ERR_INVALID_ARG, "%s: image_channels must be 1 or 3 with an image, got %d", fn, image_channels);
-        if (image_dtype != SMX_DTYPE_U8 && image_dtype != SMX_DTYPE_F32)
-            return fail(SMX_ERR_INVALID_ARG, "%s: unknown image dtype %d", fn, image_dtype);
-    } else if (color) {
-        return fail(SMX_ERR_INVALID_ARG, "%s: a colour volume needs an image", fn);
-    }
-    const size_t need = smx::tsdf_integrate_workspace_bytes(n, H, W);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_tsdf_integrate_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
-    const size_t vox = (size_t)nx * ny * nz, map_bytes = (size_t)px * sizeof(float);
-    const size_t img_bytes = image ? (size_t)px * image_channels * (image_dtype == SMX_DTYPE_F32 ? 4 : 1) : 0;
-    const void *const ins[4] = {disp, confidence, image, world_to_camera};
-    const size_t in_bytes[4] = {map_bytes, map_bytes, img_bytes, (size_t)n * 12 * sizeof(float)};
-    void *const outs[4] = {tsdf, weight, color, workspace};
-    const size_t out_bytes[4] = {vox * sizeof(float), vox * sizeof(float), vox * 4, workspace_bytes};
-    if (int rc = check_disjoint(fn, 4, ins, in_bytes, 4, outs, out_bytes)) return rc;
+    if (int rc = check_reprojection_args(fn, z_min, z_max, min_confidence, invalid_disparity, image, image_channels,
+                                         image_dtype, color, "a colour volume needs an image"))
+        return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_tsdf_integrate_workspace_bytes", workspace_bytes,
+                                       tsdf_integrate_layout(n, H, W).total))
+        return rc;
+    const size_t vox = (size_t)nx * ny * nz, px = (size_t)n * H * W, map_bytes = px * sizeof(float);
+    const size_t img_bytes = image ? px * image_channels * (image_dtype == SMX_DTYPE_F32 ? 4 : 1) : 0;
+    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {image, img_bytes},
+                                     {world_to_camera, (size_t)n * 12 * sizeof(float)}},
+                                {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}, {color, vox * 4},
+                                 {workspace, workspace_bytes}}, TSDF_IN_TEXT, TSDF_OUT_TEXT))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_integrate(nx, ny, nz, origin, voxel_size, truncation, max_weight, tsdf, weight, color, n, H, W,
@@ -617,7 +615,7 @@ int smx_tsdf_integrate(int device_id, int nx, int ny, int nz, const float origin
 }
 
 size_t smx_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {
-    return tsdf_dims_ok(nx, ny, nz) ? smx::tsdf_extract_workspace_bytes(nx, ny, nz) : 0;
+    return tsdf_dims_ok(nx, ny, nz) ? tsdf_extract_layout(ny, nz).total : 0;
 }
 
 int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
@@ -628,22 +626,17 @@ int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float o
     if (!origin || !tsdf || !weight || !points || !count || !workspace)
         return fail(SMX_ERR_INVALID_ARG, "%s: origin, tsdf, weight, points, count and workspace must be non-NULL", fn);
     if (int rc = check_tsdf_volume(fn, nx, ny, nz, origin, voxel_size)) return rc;
-    if (!(std::isfinite(min_weight) && min_weight > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and > 0, got %g", fn, (double)min_weight);
-    if (capacity < 1 || capacity > SMX_POINTS_MAX)
-        return fail(SMX_ERR_INVALID_ARG, "%s: capacity must be in 1..2^30, got %d", fn, capacity);
+    if (int rc = check_positive(fn, "min_weight", min_weight)) return rc;
+    if (int rc = check_capacity(fn, capacity)) return rc;
     if (colors && !color) return fail(SMX_ERR_INVALID_ARG, "%s: colors needs a colour volume", fn);
-    const size_t need = smx::tsdf_extract_workspace_bytes(nx, ny, nz);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG, "%s: workspace_bytes %zu is below smx_tsdf_extract_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, "smx_tsdf_extract_workspace_bytes", workspace_bytes,
+                                       tsdf_extract_layout(ny, nz).total))
+        return rc;
     const size_t vox = (size_t)nx * ny * nz, cap = (size_t)capacity;
-    const void *const ins[3] = {tsdf, weight, color};
-    const size_t in_bytes[3] = {vox * sizeof(float), vox * sizeof(float), vox * 4};
-    void *const outs[5] = {points, normals, colors, count, workspace};
-    const size_t out_bytes[5] = {cap * 3 * sizeof(float), cap * 3 * sizeof(float), cap * 3, sizeof(int32_t),
-                                 workspace_bytes};
-    if (int rc = check_disjoint(fn, 3, ins, in_bytes, 5, outs, out_bytes)) return rc;
+    if (int rc = check_disjoint(fn, {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}, {color, vox * 4}},
+                                {{points, cap * 3 * sizeof(float)}, {normals, cap * 3 * sizeof(float)}, {colors, cap * 3},
+                                 {count, sizeof(int32_t)}, {workspace, workspace_bytes}}, TSDF_IN_TEXT, TSDF_OUT_TEXT))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_extract(nx, ny, nz, origin, voxel_size, tsdf, weight, color, min_weight, capacity, points,
@@ -652,7 +645,7 @@ int smx_tsdf_extract_points(int device_id, int nx, int ny, int nz, const float o
 }
 
 size_t smx_tsdf_extract_triangles_workspace_bytes(int nx, int ny, int nz) {
-    return tsdf_dims_ok(nx, ny, nz) ? smx::tsdf_triangles_workspace_bytes(nx, ny, nz) : 0;
+    return tsdf_dims_ok(nx, ny, nz) ? mesh_layout(nx, ny, nz).total : 0;
 }
 
 int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight,
@@ -661,24 +654,17 @@ int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const floa
     const char *fn = "smx_tsdf_extract_triangles";
     if (!tsdf || !weight || !triangles || !count || !workspace)
         return fail(SMX_ERR_INVALID_ARG, "%s: tsdf, weight, triangles, count and workspace must be non-NULL", fn);
-    if (!tsdf_dims_ok(nx, ny, nz))
-        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= nx, ny, nz <= 4096 and nx * ny * nz <= 2^30 (got %d, %d, %d)", fn,
-                    nx, ny, nz);
-    if (!(std::isfinite(min_weight) && min_weight > 0.0f))
-        return fail(SMX_ERR_INVALID_ARG, "%s: min_weight must be finite and > 0, got %g", fn, (double)min_weight);
-    if (capacity < 1 || capacity > SMX_POINTS_MAX)
-        return fail(SMX_ERR_INVALID_ARG, "%s: capacity must be in 1..2^30, got %d", fn, capacity);
-    const size_t need = smx::tsdf_triangles_workspace_bytes(nx, ny, nz);
-    if (workspace_bytes < need)
-        return fail(SMX_ERR_INVALID_ARG,
-                    "%s: workspace_bytes %zu is below smx_tsdf_extract_triangles_workspace_bytes = %zu", fn,
-                    workspace_bytes, need);
+    if (int rc = check_tsdf_dims(fn, nx, ny, nz)) return rc;
+    if (int rc = check_positive(fn, "min_weight", min_weight)) return rc;
+    if (int rc = check_capacity(fn, capacity)) return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_tsdf_extract_triangles_workspace_bytes", workspace_bytes,
+                                       mesh_layout(nx, ny, nz).total))
+        return rc;
     const size_t vox = (size_t)nx * ny * nz;
-    const void *const ins[2] = {tsdf, weight};
-    const size_t in_bytes[2] = {vox * sizeof(float), vox * sizeof(float)};
-    void *const outs[3] = {triangles, count, workspace};
-    const size_t out_bytes[3] = {(size_t)capacity * 3 * sizeof(int32_t), sizeof(int32_t), workspace_bytes};
-    if (int rc = check_disjoint(fn, 2, ins, in_bytes, 3, outs, out_bytes)) return rc;
+    if (int rc = check_disjoint(fn, {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}},
+                                {{triangles, (size_t)capacity * 3 * sizeof(int32_t)}, {count, sizeof(int32_t)},
+                                 {workspace, workspace_bytes}}, TSDF_IN_TEXT, TSDF_OUT_TEXT))
+        return rc;
     if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_tsdf_triangles(nx, ny, nz, tsdf, weight, min_weight, capacity, triangles, count, workspace,

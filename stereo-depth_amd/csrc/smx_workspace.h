@@ -1,0 +1,153 @@
+// smx_workspace.h -- the layout of every caller-supplied workspace, written once.  A size query (smx_maps.hip) reads
+// `total`, the launcher (tu_*.hip) carves its pointers from the parts with ws_at(), and neither does arithmetic of its
+// own, so the two cannot disagree.  Host-only code without a HIP include: tests/workspace_layout_harness.cpp sweeps it
+// on the CPU.  Every part starts on a multiple of 256 bytes (include/stereo_mi355x.h: conventions); the layouts are
+// private to the library and nothing in a workspace survives a call.
+#pragma once
+#include <stddef.h>
+
+namespace smx {
+
+struct WsPart {
+    size_t offset, bytes;
+};
+
+// Hands out the parts of one workspace in order, each rounded up to 256 bytes.
+struct WsCursor {
+    size_t at = 0;
+    WsPart take(size_t bytes) {
+        const WsPart p{at, bytes};
+        at += (bytes + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+template <class T> inline T *ws_at(void *workspace, const WsPart &p) { return (T *)((char *)workspace + p.offset); }
+
+// ---- constants the layouts share with the kernels of k_reproject.h, and SGM's pitch rule for tu_sgm.hip --------------
+constexpr int SCAN_ITEMS = 16;             // exclusive scan of an int array: values per thread,
+constexpr int SCAN_TILE = 256 * SCAN_ITEMS;   // ... per workgroup
+constexpr int VOX_TILE = 4096;             // voxel downsampling: points per radix tile (one workgroup of 256 threads)
+constexpr int VM_COUNT = 16;               // ... ints of device-side state (meta[], indexed by k_reproject.h's VM_*)
+
+inline size_t scan_block_sums(long L) { return (size_t)((L + SCAN_TILE - 1) / SCAN_TILE); }   // ints of scan scratch
+
+// SGM: disparities per lane of a wave, and the disparity count rounded up to it (the pitch of S)
+inline int sgm_dpl(int D) { return D <= 64 ? 1 : D <= 128 ? 2 : 4; }
+inline int sgm_dp(int D) { const int k = sgm_dpl(D); return (D + k - 1) / k * k; }
+
+// ---- speckle filter and hole fill: labels int[P] | sizes int[P] | row flags int[n H], P = n H W ---------------------
+struct PostLayout {
+    WsPart label, size, flags;
+    size_t total;
+};
+inline PostLayout post_layout(int n, int H, int W) {
+    const size_t px = (size_t)n * H * W;
+    WsCursor c;                                            // a braced list is evaluated left to right
+    return PostLayout{c.take(px * sizeof(int)), c.take(px * sizeof(int)), c.take((size_t)n * H * sizeof(int)), c.at};
+}
+
+// ---- WLS: the planes U | V | E, each f32[n][H][W].  The forward sweeps write y_U over U, y_V over V and e to E; the
+// back sweeps read them.
+struct WlsLayout {
+    WsPart U, V, E;
+    size_t total;
+};
+inline WlsLayout wls_layout(int n, int H, int W) {
+    const size_t plane = (size_t)n * H * W * sizeof(float);
+    WsCursor c;
+    return WlsLayout{c.take(plane), c.take(plane), c.take(plane), c.at};
+}
+
+// ---- SGM: left census u64[P] | right census u64[P] | S u16[P][Dp] | iR i16[P] ---------------------------------------
+struct SgmLayout {
+    int Dp;
+    WsPart cen_l, cen_r, S, iR;
+    size_t total;
+};
+inline SgmLayout sgm_layout(int n, int H, int W, int D) {
+    const size_t P = (size_t)n * H * W;
+    const int Dp = sgm_dp(D);
+    WsCursor c;
+    return SgmLayout{Dp, c.take(P * 8), c.take(P * 8), c.take(P * Dp * 2), c.take(P * 2), c.at};
+}
+
+// ---- reprojection: one part, row counts int[n H] and row offsets int[n H] back to back ------------------------------
+struct ReprojectLayout {
+    WsPart rows;
+    size_t total;
+};
+inline ReprojectLayout reproject_layout(int n, int H) {
+    WsCursor c;
+    return ReprojectLayout{c.take(2 * (size_t)n * H * sizeof(int)), c.at};
+}
+
+// ---- voxel downsampling: two key and two value buffers of the radix sort, the tiles' histograms and their scan, the
+// voxel heads' flags / positions / counts, the scan's block sums, per-map offsets and tile bases, meta[] --------------
+struct VoxLayout {
+    WsPart keys, vals, counts, counts_scan, flag, pos, vcnt, block_sums, off, tile_base, meta;
+    size_t total;
+    long max_tiles, Lc, Lf;
+    int nb;
+};
+inline VoxLayout vox_layout(int n, int cap) {
+    VoxLayout l;
+    l.max_tiles = ((long)cap + VOX_TILE - 1) / VOX_TILE + n;
+    l.Lc = l.max_tiles * 256;
+    l.Lf = (long)cap + 1;
+    l.nb = (int)(((l.Lc > l.Lf ? l.Lc : l.Lf) + SCAN_TILE - 1) / SCAN_TILE);
+    WsCursor c;
+    l.keys = c.take(2 * (size_t)cap * sizeof(unsigned long long));
+    l.vals = c.take(2 * (size_t)cap * sizeof(int));
+    l.counts = c.take((size_t)l.Lc * sizeof(int));
+    l.counts_scan = c.take((size_t)l.Lc * sizeof(int));
+    l.flag = c.take((size_t)l.Lf * sizeof(int));
+    l.pos = c.take((size_t)l.Lf * sizeof(int));
+    l.vcnt = c.take((size_t)l.Lf * sizeof(int));
+    l.block_sums = c.take((size_t)l.nb * sizeof(int));
+    l.off = c.take(((size_t)n + 1) * sizeof(int));
+    l.tile_base = c.take(((size_t)n + 1) * sizeof(int));
+    l.meta = c.take(VM_COUNT * sizeof(int));
+    l.total = c.at;
+    return l;
+}
+
+// ---- TSDF integrate: measurements float2[P] | colour words u32[P] ---------------------------------------------------
+struct TsdfIntegrateLayout {
+    WsPart meas, pcol;
+    size_t total;
+};
+inline TsdfIntegrateLayout tsdf_integrate_layout(int n, int H, int W) {
+    const size_t px = (size_t)n * H * W;
+    WsCursor c;
+    return TsdfIntegrateLayout{c.take(px * 2 * sizeof(float)), c.take(px * sizeof(unsigned)), c.at};
+}
+
+// ---- TSDF extract points: counts int[rows] | offsets int[rows] | the scan's block sums, rows = ny nz -----------------
+struct TsdfExtractLayout {
+    WsPart row_count, row_offset, block_sums;
+    size_t total;
+};
+inline TsdfExtractLayout tsdf_extract_layout(int ny, int nz) {
+    const long rows = (long)ny * nz;
+    WsCursor c;
+    return TsdfExtractLayout{c.take((size_t)rows * sizeof(int)), c.take((size_t)rows * sizeof(int)),
+                             c.take(scan_block_sums(rows) * sizeof(int)), c.at};
+}
+
+// ---- TSDF extract triangles: one byte per voxel | one word per 64-voxel chunk of a row | three counts and three
+// offsets per row | the scan's block sums ------------------------------------------------------------------------------
+struct MeshLayout {
+    int nch;
+    WsPart flags, chunk_first, counts, offsets, block_sums;
+    size_t total;
+};
+inline MeshLayout mesh_layout(int nx, int ny, int nz) {
+    const size_t rows = (size_t)ny * nz;
+    const int nch = (nx + 63) / 64;
+    WsCursor c;
+    return MeshLayout{nch, c.take(rows * nx), c.take(rows * nch * sizeof(unsigned)), c.take(3 * rows * sizeof(int)),
+                      c.take(3 * rows * sizeof(int)), c.take(scan_block_sums(3 * (long)rows) * sizeof(int)), c.at};
+}
+
+}  // namespace smx

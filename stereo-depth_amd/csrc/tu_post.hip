@@ -1,12 +1,11 @@
 // tu_post.hip -- disparity post-processing kernels (k_post.h): speckle filter and hole fill.
 #include "k_post.h"
 #include "smx_launch.h"
+#include "smx_workspace.h"
 
 namespace smx {
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 unsigned stride_blocks(size_t items) {                     // grid-stride kernels: enough blocks, capped
     size_t blocks = (items + SPK_THREADS - 1) / SPK_THREADS;
@@ -16,17 +15,11 @@ unsigned stride_blocks(size_t items) {                     // grid-stride kernel
 
 }  // namespace
 
-// [label: n*H*W ints][size: n*H*W ints][flags: n*H ints], each part 256-byte aligned
-size_t post_workspace_bytes(int n, int H, int W) {
-    const size_t px = (size_t)n * H * W;
-    return 2 * align256(px * sizeof(int)) + align256((size_t)n * H * sizeof(int));
-}
-
 void launch_filter_speckles(int n, int H, int W, const float *in, float *out, int max_size, float max_diff, float invalid,
                             void *workspace, hipStream_t s) {
     const size_t px = (size_t)n * H * W;
-    int *label = (int *)workspace;
-    int *size = (int *)((char *)workspace + align256(px * sizeof(int)));
+    const PostLayout l = post_layout(n, H, W);
+    int *label = ws_at<int>(workspace, l.label), *size = ws_at<int>(workspace, l.size);
     const unsigned fin = stride_blocks(px);
     if (max_size == 0) {                                   // nothing is ever that small: a copy
         hipLaunchKernelGGL((k_spk_finalize<true>), dim3(fin), dim3(SPK_THREADS), 0, s, in, out, label, size, H, W, n,
@@ -43,8 +36,7 @@ void launch_filter_speckles(int n, int H, int W, const float *in, float *out, in
 }
 
 void launch_fill_invalid(int n, int H, int W, const float *in, float *out, float invalid, void *workspace, hipStream_t s) {
-    const size_t px = (size_t)n * H * W;
-    int *flags = (int *)((char *)workspace + 2 * align256(px * sizeof(int)));
+    int *flags = ws_at<int>(workspace, post_layout(n, H, W).flags);
     const dim3 rows((unsigned)((size_t)n * H));
     if (W <= FILL_LDS_W)
         hipLaunchKernelGGL((k_fill_rows<true>), rows, dim3(FILL_THREADS), 0, s, in, out, flags, W, invalid);

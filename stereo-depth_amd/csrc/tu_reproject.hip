@@ -4,12 +4,9 @@
 
 #include "k_reproject.h"
 #include "smx_launch.h"
+#include "smx_workspace.h"
 
 namespace smx {
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t reproject_workspace_bytes(int n, int H) { return align256(2 * (size_t)n * H * sizeof(int)); }
 
 void launch_reproject(int n, int H, int W, const float *disp, const float q[16], const float *conf, float min_conf,
                       float zmin, float zmax, float invalid, const void *image, int channels, bool img_f32,
@@ -21,7 +18,7 @@ void launch_reproject(int n, int H, int W, const float *disp, const float q[16],
     a.min_conf = min_conf, a.zmin = zmin, a.zmax = zmax, a.invalid = invalid;
     a.points = points, a.colors = image ? colors : nullptr, a.indices = indices, a.xyz_map = xyz_map;
     a.offsets = offsets;
-    a.row_count = (int *)workspace;
+    a.row_count = ws_at<int>(workspace, reproject_layout(n, H).rows);
     a.row_offset = a.row_count + (size_t)n * H;
     a.n = n, a.H = H, a.W = W;
     const unsigned rows = (unsigned)(n * H);
@@ -30,65 +27,30 @@ void launch_reproject(int n, int H, int W, const float *disp, const float q[16],
     hipLaunchKernelGGL(k_reproj_scatter, dim3(rows), dim3(256), 0, s, a);
 }
 
-namespace {
-struct VoxLayout {
-    size_t keys, vals, counts, counts_scan, flag, pos, vcnt, block_sums, off, tile_base, meta, total;
-    long max_tiles, Lc, Lf;
-    int nb;
-};
-
-VoxLayout vox_layout(int n, int cap) {
-    VoxLayout l;
-    l.max_tiles = ((long)cap + VOX_TILE - 1) / VOX_TILE + n;
-    l.Lc = l.max_tiles * 256;
-    l.Lf = (long)cap + 1;
-    l.nb = (int)((std::max(l.Lc, l.Lf) + SCAN_TILE - 1) / SCAN_TILE);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
-    l.keys = take(2 * (size_t)cap * sizeof(unsigned long long));
-    l.vals = take(2 * (size_t)cap * sizeof(int));
-    l.counts = take((size_t)l.Lc * sizeof(int));
-    l.counts_scan = take((size_t)l.Lc * sizeof(int));
-    l.flag = take((size_t)l.Lf * sizeof(int));
-    l.pos = take((size_t)l.Lf * sizeof(int));
-    l.vcnt = take((size_t)l.Lf * sizeof(int));
-    l.block_sums = take((size_t)l.nb * sizeof(int));
-    l.off = take(((size_t)n + 1) * sizeof(int));
-    l.tile_base = take(((size_t)n + 1) * sizeof(int));
-    l.meta = take(VM_COUNT * sizeof(int));
-    l.total = at;
-    return l;
-}
-}  // namespace
-
-size_t scan_block_sums(long L) { return (size_t)((L + SCAN_TILE - 1) / SCAN_TILE); }
-
 void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s) {
-    const int nb = (int)((L + SCAN_TILE - 1) / SCAN_TILE);
+    const int nb = (int)scan_block_sums(L);
     hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(256), 0, s, in, L, block_sums, gate, pass);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, block_sums, nb, gate, pass);
     hipLaunchKernelGGL(k_scan_down, dim3(nb), dim3(256), 0, s, in, out, L, block_sums, gate, pass);
 }
-
-size_t voxel_workspace_bytes(int n, int cap) { return vox_layout(n, cap).total; }
 
 hipError_t launch_voxel_downsample(int n, int cap, const float *points, const uint8_t *colors, const int32_t *offsets,
                                    float voxel_size, int min_points, float *out_points, uint8_t *out_colors,
                                    int32_t *out_counts, int32_t *out_offsets, int32_t *dropped, void *workspace,
                                    hipStream_t s) {
     const VoxLayout l = vox_layout(n, cap);
-    char *ws = (char *)workspace;
     VoxArgs a;
     a.points = points, a.colors = colors, a.offsets_in = offsets, a.voxel_size = voxel_size;
     a.min_points = min_points, a.n = n, a.cap = cap;
     a.out_points = out_points, a.out_colors = colors ? out_colors : nullptr, a.out_counts = out_counts;
     a.out_offsets = out_offsets, a.dropped = dropped;
-    a.keys[0] = (unsigned long long *)(ws + l.keys), a.keys[1] = a.keys[0] + cap;
-    a.vals[0] = (int *)(ws + l.vals), a.vals[1] = a.vals[0] + cap;
-    a.counts = (int *)(ws + l.counts), a.counts_scan = (int *)(ws + l.counts_scan);
-    a.flag = (int *)(ws + l.flag), a.pos = (int *)(ws + l.pos), a.vcnt = (int *)(ws + l.vcnt);
-    a.block_sums = (int *)(ws + l.block_sums);
-    a.off = (int *)(ws + l.off), a.tile_base = (int *)(ws + l.tile_base), a.meta = (int *)(ws + l.meta);
+    a.keys[0] = ws_at<unsigned long long>(workspace, l.keys), a.keys[1] = a.keys[0] + cap;
+    a.vals[0] = ws_at<int>(workspace, l.vals), a.vals[1] = a.vals[0] + cap;
+    a.counts = ws_at<int>(workspace, l.counts), a.counts_scan = ws_at<int>(workspace, l.counts_scan);
+    a.flag = ws_at<int>(workspace, l.flag), a.pos = ws_at<int>(workspace, l.pos), a.vcnt = ws_at<int>(workspace, l.vcnt);
+    a.block_sums = ws_at<int>(workspace, l.block_sums);
+    a.off = ws_at<int>(workspace, l.off), a.tile_base = ws_at<int>(workspace, l.tile_base);
+    a.meta = ws_at<int>(workspace, l.meta);
     // the tail of the histogram array past this call's tiles is scanned too: keep it zero
     hipError_t e = hipMemsetAsync(a.counts, 0, (size_t)l.Lc * sizeof(int), s);
     if (e != hipSuccess) return e;

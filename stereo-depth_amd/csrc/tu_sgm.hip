@@ -1,33 +1,11 @@
 // tu_sgm.hip -- semi-global matching (k_sgm.h).
 #include "k_sgm.h"
 #include "smx_launch.h"
+#include "smx_workspace.h"
 
 namespace smx {
 
 namespace {
-
-constexpr size_t SGM_ALIGN = 256;
-size_t align_up(size_t v) { return (v + SGM_ALIGN - 1) / SGM_ALIGN * SGM_ALIGN; }
-
-int sgm_dpl(int D) { return D <= 64 ? 1 : D <= 128 ? 2 : 4; }
-int sgm_dp(int D) { const int k = sgm_dpl(D); return (D + k - 1) / k * k; }
-
-// Workspace layout (include/stereo_mi355x.h: smx_sgm_workspace_bytes), P = n H W pixels:
-// left census u64[P] | right census u64[P] | S u16[P][Dp] | iR i16[P], each part rounded up to 256 bytes.
-struct SgmLayout {
-    size_t cen_l, cen_r, S, iR, total;
-};
-
-SgmLayout sgm_layout(int n, int H, int W, int D) {
-    const size_t P = (size_t)n * H * W;
-    SgmLayout l;
-    l.cen_l = 0;
-    l.cen_r = l.cen_l + align_up(P * 8);
-    l.S = l.cen_r + align_up(P * 8);
-    l.iR = l.S + align_up(P * sgm_dp(D) * 2);
-    l.total = l.iR + align_up(P * 2);
-    return l;
-}
 
 template <int DPL>
 void launch_dpl(const SgmPathArgs &base, int paths, const SgmSelectArgs &sel, hipStream_t s) {
@@ -50,16 +28,13 @@ void launch_dpl(const SgmPathArgs &base, int paths, const SgmSelectArgs &sel, hi
 
 }  // namespace
 
-size_t sgm_workspace_bytes(int n, int H, int W, int D) { return sgm_layout(n, H, W, D).total; }
-
 void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const void *right, int dmin, int D, int paths,
                 int P1, int P2, int uniqueness, float lr_max_diff, bool subpixel, float invalid, float *out,
                 float *gray_out, float *right_out, void *workspace, hipStream_t s) {
     const SgmLayout l = sgm_layout(n, H, W, D);
-    char *ws = (char *)workspace;
-    uint64_t *cen_l = (uint64_t *)(ws + l.cen_l), *cen_r = (uint64_t *)(ws + l.cen_r);
-    uint16_t *S = (uint16_t *)(ws + l.S);
-    int16_t *iR = (int16_t *)(ws + l.iR);
+    uint64_t *cen_l = ws_at<uint64_t>(workspace, l.cen_l), *cen_r = ws_at<uint64_t>(workspace, l.cen_r);
+    uint16_t *S = ws_at<uint16_t>(workspace, l.S);
+    int16_t *iR = ws_at<int16_t>(workspace, l.iR);
     const int tiles_x = (W + SGM_TW - 1) / SGM_TW, tiles_y = (H + SGM_TH - 1) / SGM_TH;
     const unsigned images = (unsigned)(2 * n < 65535 ? 2 * n : 65535);            // grid-stride beyond
     hipLaunchKernelGGL(k_sgm_census, dim3(tiles_x * tiles_y, images), dim3(SGM_THREADS), 0, s, left, right, C, (int)f32,
@@ -68,7 +43,7 @@ void launch_sgm(int n, int C, bool f32, int H, int W, const void *left, const vo
     a.cen_l = cen_l;
     a.cen_r = cen_r;
     a.S = S;
-    a.n = n, a.H = H, a.W = W, a.dmin = dmin, a.D = D, a.Dp = sgm_dp(D), a.P1 = P1, a.P2 = P2;
+    a.n = n, a.H = H, a.W = W, a.dmin = dmin, a.D = D, a.Dp = l.Dp, a.P1 = P1, a.P2 = P2;
     a.axis = 0, a.lines = 0, a.init = 1;
     SgmSelectArgs sel;
     sel.S = S;

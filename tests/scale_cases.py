@@ -105,7 +105,7 @@ def scan_blocks(L: int, scan_tile: int) -> int:
 
 
 def voxel_scan_lengths(n: int, cap: int, vox_tile: int):
-    """(Lc, Lf): the histogram array's and the flag array's scan lengths (vox_layout in tu_reproject.hip)."""
+    """(Lc, Lf): the histogram array's and the flag array's scan lengths (vox_layout in smx_workspace.h)."""
     max_tiles = cdiv(cap, vox_tile) + n
     return max_tiles * 256, cap + 1
 

@@ -30,10 +30,10 @@ def one(pattern: str, name: str) -> int:
 def k():
     """The constants the cases depend on, read from the kernel sources."""
     c = {}
-    c["SCAN_ITEMS"] = one(r"^constexpr int SCAN_ITEMS = (\d+);", "k_reproject.h")
-    c["SCAN_THREADS"] = one(r"^constexpr int SCAN_TILE = (\d+) \* SCAN_ITEMS;", "k_reproject.h")
+    c["SCAN_ITEMS"] = one(r"^constexpr int SCAN_ITEMS = (\d+);", "smx_workspace.h")
+    c["SCAN_THREADS"] = one(r"^constexpr int SCAN_TILE = (\d+) \* SCAN_ITEMS;", "smx_workspace.h")
     c["SCAN_TILE"] = c["SCAN_THREADS"] * c["SCAN_ITEMS"]
-    c["VOX_TILE"] = one(r"^constexpr int VOX_TILE = (\d+);", "k_reproject.h")
+    c["VOX_TILE"] = one(r"^constexpr int VOX_TILE = (\d+);", "smx_workspace.h")
     c["VOX_BBOX_BLOCKS"] = one(r"^constexpr int VOX_BBOX_BLOCKS = (\d+);", "k_reproject.h")
     c["VOX_CHUNK"] = one(r"for \(int c0 = 0; c0 < cnt; c0 \+= (\d+)\)", "k_reproject.h")
     c["DIGIT_BITS"] = one(r"pass_skipped\(const int \*gate, int pass\) \{ return gate && pass \* (\d+) >= \*gate; \}",

@@ -1,0 +1,200 @@
+"""Every entry that takes a workspace, run with exactly the bytes its size query returns.
+
+A size query and the launcher behind it read one layout (stereo-depth_amd/csrc/smx_workspace.h), and tests/test_workspace_layout_cpu.py
+checks the layouts on the CPU.  What is left is the kernels: one that writes past the part it was given writes past the
+caller's buffer.  Here each entry runs twice on the same inputs: with a roomy workspace (the queried bytes plus 4096)
+and with a 256-byte aligned view of exactly the queried bytes inside a sentinel-filled buffer, with max(4096, queried)
+bytes of guard on each side.  Every output must be the same bit for bit (the entries' own tests tie that result to the
+references; their generators make the inputs here), and both guards must still hold the sentinel.
+
+The Python entries allocate their workspace themselves, always as torch.empty(<queried bytes>, dtype=torch.uint8,
+device=...).  PlacedWorkspaces stands in for the name `torch` inside cuda_depth and answers exactly those allocations;
+each case names the queries it expects, so a case whose workspaces were not placed fails instead of passing vacuously.
+
+The shapes are the smallest at which the roundings and every part of a layout matter: odd maps whose parts end off a
+256-byte boundary, both roundings of SGM's disparity pitch, more than one 4096-point radix tile, two 64-voxel chunks per
+volume row."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import test_mesh_gpu as t_mesh                      # noqa: E402  (the generators of each entry's own tests)
+import test_operand_alignment_gpu as t_align        # noqa: E402  (SENTINEL_BYTE, the guard check, the bitwise comparison)
+import test_points3d_gpu as t_pts                   # noqa: E402
+import test_postprocess_gpu as t_post               # noqa: E402
+import test_sgm_gpu as t_sgm                        # noqa: E402
+import test_tsdf_gpu as t_tsdf                      # noqa: E402
+import test_wls_gpu as t_wls                        # noqa: E402
+
+ROOMY_BYTES = 4096
+MIN_GUARD_BYTES = 4096
+
+
+@pytest.fixture(scope="module")
+def cd():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import cuda_depth
+    return cuda_depth
+
+
+class PlacedWorkspaces:
+    """The `torch` of cuda_depth for one run: a workspace allocation (an int size, uint8) is answered with a view of that
+    many bytes, roomy or exact between guards; one view per size, so two calls of one size share their workspace."""
+
+    def __init__(self, exact):
+        self.exact = exact
+        self.placed = {}
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    def empty(self, *args, **kw):
+        if len(args) == 1 and isinstance(args[0], int) and kw.get("dtype") is torch.uint8:
+            return self.place(args[0], kw["device"])
+        return torch.empty(*args, **kw)
+
+    def place(self, nbytes, device):
+        if nbytes not in self.placed:
+            assert nbytes > 0 and nbytes % 256 == 0, f"a workspace of {nbytes} bytes"
+            if self.exact:
+                guard = max(MIN_GUARD_BYTES, nbytes)
+                buf = torch.full((guard + nbytes + guard,), t_align.SENTINEL_BYTE, dtype=torch.uint8, device=device)
+                view = buf[guard:guard + nbytes]
+            else:
+                view = torch.empty(nbytes + ROOMY_BYTES, dtype=torch.uint8, device=device)[:nbytes]
+            assert view.data_ptr() % 256 == 0 and view.numel() == nbytes
+            self.placed[nbytes] = view
+        return self.placed[nbytes]
+
+
+def check_exact_against_roomy(cd, monkeypatch, call, queried):
+    """call() -> [(name, tensor)]: the outputs of the entries under test, cut to what they wrote."""
+    outs = {}
+    for exact in (False, True):
+        placed = PlacedWorkspaces(exact)
+        with monkeypatch.context() as m:
+            m.setattr(cd, "torch", placed)
+            outs[exact] = call()
+        torch.cuda.synchronize()
+        assert sorted(placed.placed) == sorted(set(int(q) for q in queried)), "the workspaces of this case were not placed"
+    assert len(outs[True]) == len(outs[False]) > 0
+    for (name, got), (_, want) in zip(outs[True], outs[False]):
+        assert got.numel() > 0, f"{name}: nothing to compare"
+        t_align.assert_same(got.contiguous(), want.contiguous(), f"{name} with an exact workspace")
+    for nbytes, view in placed.placed.items():
+        t_align.assert_guards(view, f"the workspace of {nbytes} bytes")
+
+
+def lib():
+    from cuda_depth import _native
+    return _native.LIB
+
+
+def test_speckle_filter_and_fill_share_one_workspace(cd, monkeypatch):
+    n, H, W = 2, 5, 37
+    d = t_align.dev(t_post.random_map(np.random.default_rng(51), (n, H, W)))
+
+    def call():
+        kept = cd.filter_speckles(d, max_speckle_size=6, max_diff=1.0)
+        return [("filter_speckles", kept), ("fill_invalid", cd.fill_invalid(kept))]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_postprocess_workspace_bytes(n, H, W)])
+
+
+def test_wls_filter(cd, monkeypatch):
+    shape = n, H, W = 2, 5, 37
+    rng = np.random.default_rng(52)
+    d, g, c = (t_align.dev(x) for x in (t_wls.random_map(rng, shape), t_wls.random_guide(rng, shape, nan_frac=0.02),
+                                        t_wls.random_conf(rng, shape)))
+
+    def call():
+        return [("wls_filter", cd.wls_filter(d, g, lam=500.0, sigma_color=4.0, iterations=2, confidence=c))]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_wls_workspace_bytes(n, H, W)])
+
+
+@pytest.mark.parametrize("D", [40, 130])                 # one disparity per lane (Dp = D) and four (Dp = 132)
+def test_sgm_with_right_map_and_lr_check(cd, monkeypatch, D):
+    n, C, H, W = 2, 1, 12, 40
+    left, right = (t_align.dev(x) for x in t_sgm.frames(n, C, H, W, "u8", 53 + D))
+
+    def call():
+        sgm = cd.StereoSGM(0, D - 1, paths=8, uniqueness=10, lr_max_diff=1.0)
+        out, gray, right_out = (torch.empty((n, H, W), device="cuda") for _ in range(3))
+        sgm.compute(left, right, out=out, gray_out=gray, right_out=right_out)
+        return [("out", out), ("gray_out", gray), ("right_out", right_out)]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_sgm_workspace_bytes(n, H, W, D, 8)])
+
+
+def test_reproject_points(cd, monkeypatch):
+    n, H, W = 3, 5, 37
+    rng = np.random.default_rng(54)
+    d, img = t_pts.dev(t_pts.maps(rng, n, H, W)), t_pts.dev(t_pts.image(rng, n, H, W, (3, "u8")))
+    Q = t_pts.q_matrix(cd, H, W, doffs=3.5)
+
+    def call():
+        p, c, i, o, xyz = cd.reproject_to_3d_batched(d, Q, image=img, organized=True, depth_range=(0.5, 400.0))
+        total = int(o[-1])
+        assert 0 < total < n * H * W
+        return [("points", p[:total]), ("colors", c[:total]), ("indices", i[:total]), ("offsets", o), ("xyz_map", xyz)]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_reproject_workspace_bytes(n, H, W)])
+
+
+def test_voxel_downsample(cd, monkeypatch):
+    n, cap = 2, 5000                                     # two 4096-point radix tiles
+    rng = np.random.default_rng(55)
+    pts = t_pts.dev(rng.uniform(-2.0, 2.0, (cap, 3)).astype(np.float32))
+    cols = t_pts.dev(rng.integers(0, 256, (cap, 3)).astype(np.uint8))
+    off = t_pts.dev(np.array([0, 4500, cap], np.int32))
+
+    def call():
+        p, c, k, o, dropped = cd.voxel_downsample_batched(pts, off, 0.25, colors=cols, min_points=2)
+        total = int(o[-1])
+        assert 0 < total < cap
+        return [("points", p[:total]), ("colors", c[:total]), ("counts", k[:total]), ("offsets", o), ("dropped", dropped)]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_voxel_workspace_bytes(n, cap)])
+
+
+def test_tsdf_integrate_with_colour_then_extract_points(cd, monkeypatch):
+    dims, (n, H, W) = (16, 12, 10), (2, 12, 20)
+    rng = np.random.default_rng(56)
+    d, img = t_tsdf.dev(t_tsdf.maps(rng, n, H, W)), t_tsdf.dev(t_tsdf.image(rng, n, H, W, (3, "u8")))
+    Q, c2w = t_tsdf.q_kitti(cd, H, W), t_tsdf.poses("outside", n, rng)
+
+    def call():
+        vol = cd.TSDFVolume(dims, t_tsdf.VS, (-0.4, -0.3, 0.75), color=True)     # around the maps' surface near z = 1
+        vol.integrate(d, Q, c2w, image=img)
+        p, nrm, c, count = vol.extract_point_cloud_batched(4096)
+        total = int(count.item())
+        assert 0 < total <= 4096, f"{total} surface points"
+        return [("tsdf", vol.tsdf), ("weight", vol.weight), ("color", vol.color), ("points", p[:total]),
+                ("normals", nrm[:total]), ("colors", c[:total]), ("count", count)]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_tsdf_integrate_workspace_bytes(n, H, W),
+                                                      lib().smx_tsdf_extract_workspace_bytes(*dims)])
+
+
+def test_tsdf_extract_triangles(cd, monkeypatch):
+    dims = (70, 6, 5)                                    # two 64-voxel chunks per row
+    state = t_mesh.rough_state(dims, 57)
+    T, Wt = t_tsdf.dev(state["tsdf"]), t_tsdf.dev(state["weight"])
+
+    def call():
+        vol = cd.TSDFVolume(dims, t_tsdf.VS, t_tsdf.ORIGIN)
+        vol.tsdf.copy_(T)
+        vol.weight.copy_(Wt)
+        p, nrm, _, count, tris, tcount = vol.extract_triangle_mesh_batched(8192, 16384)
+        total, ttotal = int(count.item()), int(tcount.item())
+        assert 0 < total <= 8192 and 0 < ttotal <= 16384, f"{total} vertices, {ttotal} triangles"
+        return [("points", p[:total]), ("normals", nrm[:total]), ("count", count), ("triangles", tris[:ttotal]),
+                ("triangle count", tcount)]
+
+    check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_tsdf_extract_workspace_bytes(*dims),
+                                                      lib().smx_tsdf_extract_triangles_workspace_bytes(*dims)])

@@ -26,6 +26,9 @@
  *   -- (per-pixel confidence: LR agreement x texture)     smx_confidence_map
  *   -- (motion-gated temporal filter of map streams)      smx_temporal_filter
  *   -- (rectification of raw frames: bilinear remap)      smx_remap_pairs
+ *   Deep3D's selection layer, upsampling and rescale      smx_synthesize_right_view (the head only: the
+ *     python/pipeline/synthesis/deep3d.py:155,162-183,      network is the caller's)
+ *     synthesis/kernels/rescale_generated_view.cu
  *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes,
  *                                                         smx_sgm_with_right_map
  *   -- (metric 3D points, coloured, compacted)            smx_reproject_points, smx_reproject_workspace_bytes
@@ -595,6 +598,38 @@ int smx_temporal_filter(int device_id, int n, int H, int W, const float *disp, c
 int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int W_in, int H_out, int W_out,
                     const void *left_in, const void *right_in, const int32_t *left_map, const int32_t *right_map,
                     void *left_out, void *right_out, int border_mode, float border_value, void *stream);
+
+/* Right-view synthesis head: everything Deep3D does after the network's last layer, in one launch.  The network (the
+ * caller's) leaves a soft-maxed probability volume at low resolution; the head upsamples it bilinearly by an integer
+ * factor, weighs D shifted copies of the left frame with it, sums over the disparity axis and rescales to 0..255.
+ * Neither the upsampled volume nor the stack of shifted copies is ever stored.
+ *   - prob: [n][D][h][w] f32 (P).  left: [n][C][H][W], SMX_DTYPE_F32 or SMX_DTYPE_U8, H = h * S, W = w * S.
+ *     out: [n][C][H][W] f32.  S = scale (1..16; the reference's is 4), D in 1..256 (the reference's is 65), C 1 or 3.
+ *   - Bilinear source indices, in integers (the half-pixel rule of align_corners = False), per axis, for output index t
+ *     and input length len:  u = max(2t + 1 - S, 0);  i0 = u / 2S;  i1 = min(i0 + 1, len - 1);
+ *     l1 = (float)(u % 2S) / (float)(2S) (one correctly rounded division; exact for S a power of two);  l0 = 1.0f - l1.
+ *     The row X gives (r0, r1, a0, a1), the column Y gives (c0, c1, b0, b1).
+ *   - For d = 0, 1, ..., D-1 in this order, while Y + d < W (later terms are skipped, not added as zeros):
+ *       top = b0 * P[d][r0][c0] + b1 * P[d][r0][c1];   bot = b0 * P[d][r1][c0] + b1 * P[d][r1][c1];
+ *       q = a0 * top + a1 * bot;   for each channel c:  acc_c = acc_c + q * v_c,
+ *     with v_c = left[c][X][Y + d] for f32 and (float)byte / 255.0f (the correctly rounded division; the reference's
+ *     `/ 255.0`) for u8; acc_c starts at +0.0f.
+ *   - Rescale: out = fminf(fmaxf(acc_c * 255.0f + 0.5f, 0.0f), 255.0f).  The reference writes `x * 255 + 0.5` with a
+ *     double literal: the float32 product plus 0.5 is exact in double, so its one rounding back to float gives the bits
+ *     of the float32 addition.
+ * Every operation is one float32 round-to-nearest with no fused operation, denormals are kept, and a NaN follows
+ * fmaxf / fminf (a NaN sum is stored as 0).  The order of the sum over d is part of the rule, so every implementation
+ * gives the same bits, however it tiles the frame or splits the disparity axis.  Against the reference's torch
+ * expression (interpolate, shifted stack, mul, sum) the result differs only by that expression's own summation order:
+ * at most 255 * 2 (D + 6) 2^-24, 1.4e-4 measured at D = 65.
+ * prob and left may alias each other; out must not overlap either.  One launch on `stream` (a caller's stream), with no
+ * workspace, no host synchronisation and no allocation, so the call can be captured into a HIP graph.  Engine-free:
+ * device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL prob, left or out, n < 1 (or n frames larger than
+ * the address space), channels not 1 or 3, an unknown dtype, D outside 1..256, scale outside 1..16, h or w < 1 or
+ * h * scale or w * scale > 32768, the overlaps above, stream == SMX_STREAM_ENGINE. */
+int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                              const float *prob, const void *left, float *out, void *stream);
 
 /* Semi-global matching (Hirschmueller, TPAMI 2008) with a census cost: a second matcher beside the engine, engine-free.
  * The rule is integer up to one float32 division, so every implementation gives the same bits.

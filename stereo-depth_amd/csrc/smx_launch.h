@@ -121,6 +121,11 @@ void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, 
                         const int32_t *map_l, const int32_t *map_r, void *out_l, void *out_r, bool replicate,
                         float border_value, hipStream_t s);
 
+// ---- tu_synthesis.hip: right-view synthesis head (k_synthesis.h) ------------------------------------------------------
+// left / out: [n][C][h*S][w*S], C 1 or 3; arguments checked by smx_synthesize_right_view
+void launch_synthesis(int n, int C, bool f32, int D, int h, int w, int S, const float *prob, const void *left, float *out,
+                      hipStream_t s);
+
 // ---- tu_sgm.hip: semi-global matching (k_sgm.h) ----------------------------------------------------------------------
 // workspace: smx_workspace.h: sgm_layout(n, H, W, D); right_out NULL: not written (the
 // right-view WTA runs only for the LR check); arguments checked by smx_sgm / smx_sgm_with_right_map

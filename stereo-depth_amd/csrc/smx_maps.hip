@@ -368,6 +368,33 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
     });
 }
 
+int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                              const float *prob, const void *left, float *out, void *stream) {
+    const char *fn = "smx_synthesize_right_view";
+    if (!prob || !left || !out) return fail(SMX_ERR_INVALID_ARG, "%s: prob, left and out must be non-NULL", fn);
+    if (n < 1) return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1, got %d", fn, n);
+    if (channels != 1 && channels != 3) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be 1 or 3, got %d", fn, channels);
+    if (int rc = check_dtype(fn, "", dtype)) return rc;
+    if (int rc = check_int_range(fn, "D", D, 1, 256)) return rc;
+    if (int rc = check_int_range(fn, "scale", scale, 1, 16)) return rc;
+    if (h < 1 || w < 1 || h > 32768 / scale || w > 32768 / scale)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need h, w >= 1 and h * scale, w * scale <= 32768 (got h %d, w %d, scale %d)", fn,
+                    h, w, scale);
+    const size_t px = (size_t)h * scale * w * scale;                        // <= 2^30
+    const size_t frame = ((size_t)D * h * w > px * channels ? (size_t)D * h * w : px * channels) * sizeof(float);
+    if ((size_t)n > SIZE_MAX / frame)                                       // frame <= 2^40: the byte sizes below do not overflow
+        return fail(SMX_ERR_INVALID_ARG, "%s: n = %d frames do not fit the address space", fn, n);
+    const size_t prob_bytes = (size_t)n * D * h * w * sizeof(float);
+    const size_t left_bytes = (size_t)n * channels * px * (dtype == SMX_DTYPE_F32 ? 4 : 1);
+    if (int rc = check_disjoint(fn, {{prob, prob_bytes}, {left, left_bytes}}, {{out, (size_t)n * channels * px * sizeof(float)}},
+                                "out must not overlap prob or left"))
+        return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_synthesis(n, channels, dtype == SMX_DTYPE_F32, D, h, w, scale, prob, left, out, (hipStream_t)stream);
+    });
+}
+
 // The size rules of smx_sgm that the workspace query shares: 0 = accepted.
 static int sgm_size_error(int n, int H, int W, int D, int paths) {
     if (!map_dims_ok(n, H, W)) return 1;

@@ -684,6 +684,69 @@ class StereoRectification:
         return lo if right is None else (lo, ro)
 
 
+def _launch_synthesis(probabilities, left, out, n, channels, D, h, w, scale) -> None:
+    """smx_synthesize_right_view on the current stream."""
+    dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
+    dev = left.device.index
+    check(LIB.smx_synthesize_right_view(dev, n, channels, dt, D, h, w, int(scale), probabilities.data_ptr(),
+                                        left.data_ptr(), out.data_ptr(), _stream(dev)))
+
+
+def synthesize_right_view(probabilities: torch.Tensor, left: torch.Tensor, scale: int = 4,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The right view of `left` under a disparity probability volume (smx_synthesize_right_view; the rule is in
+    include/stereo_mi355x.h), on the current stream: everything Deep3D does after the network's softmax -- bilinear
+    upsampling by `scale`, the probability-weighted sum of the shifted left frames, `* 255 + 0.5` clamped to 0..255 --
+    in one launch that stores neither the upsampled volume nor the shifted frames.  probabilities: [n, D, h, w] or
+    [D, h, w] float32 on a GPU, D in 1..256; left: [n, C, H, W], [C, H, W] or [H, W] with C in (1, 3), H = h * scale,
+    W = w * scale, float32 (values in 0..1) or uint8 (divided by 255); scale in 1..16.  Returns float32 in 0..255 in
+    the shape of left; out: the tensor to write (it must not overlap the inputs).  TypeError for a dtype mistake,
+    ValueError for a shape or device mismatch or a non-contiguous operand, before anything is launched."""
+    for name, t in (("probabilities", probabilities), ("left", left)) + ((("out", out),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _int_arg("scale", scale)
+    if probabilities.dtype != torch.float32:
+        raise TypeError(f"probabilities must be float32, got {probabilities.dtype}")
+    if left.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"left must be uint8 or float32, got {left.dtype}")
+    if out is not None and out.dtype != torch.float32:
+        raise TypeError(f"out must be float32, got {out.dtype}")
+    if not 1 <= scale <= 16:
+        raise ValueError(f"scale must be in 1..16, got {scale}")
+    if probabilities.dim() not in (3, 4) or probabilities.numel() == 0:
+        raise ValueError(f"probabilities must be a non-empty [n, D, h, w] or [D, h, w], got {tuple(probabilities.shape)}")
+    batched = probabilities.dim() == 4
+    if left.dim() not in ((4,) if batched else (2, 3)):
+        raise ValueError(f"left must be {'[n, C, H, W]' if batched else '[C, H, W] or [H, W]'} beside probabilities "
+                         f"{tuple(probabilities.shape)}, got {tuple(left.shape)}")
+    n = int(probabilities.shape[0]) if batched else 1
+    D, h, w = (int(v) for v in probabilities.shape[-3:])
+    channels = 1 if left.dim() == 2 else int(left.shape[-3])
+    if channels not in (1, 3):
+        raise ValueError(f"left must have 1 or 3 channels, got {channels}")
+    if not 1 <= D <= 256:
+        raise ValueError(f"probabilities must hold 1..256 disparity planes, got {D}")
+    if tuple(left.shape[-2:]) != (h * scale, w * scale) or (batched and int(left.shape[0]) != n):
+        raise ValueError(f"left must be {'%d frames of ' % n if batched else ''}{h * scale} x {w * scale} "
+                         f"(probabilities {h} x {w}, scale {scale}), got {tuple(left.shape)}")
+    if h * scale > 32768 or w * scale > 32768:
+        raise ValueError(f"frames may be at most 32768 x 32768, got {h * scale} x {w * scale}")
+    if out is not None and tuple(out.shape) != tuple(left.shape):
+        raise ValueError(f"out must be {tuple(left.shape)} like left, got {tuple(out.shape)}")
+    for name, t in (("probabilities", probabilities), ("left", left)) + ((("out", out),) if out is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not probabilities.is_cuda or left.device != probabilities.device:
+        raise ValueError(f"probabilities and left must live on one GPU, got {probabilities.device} and {left.device}")
+    if out is not None and out.device != left.device:
+        raise ValueError(f"out must live on {left.device}, got {out.device}")
+    if out is None:
+        out = torch.empty(left.shape, dtype=torch.float32, device=left.device)
+    _launch_synthesis(probabilities, left, out, n, channels, D, h, w, scale)
+    return out
+
+
 class StereoSGM:
     """Semi-global matching with a census 9x7 cost (smx_sgm; the rule is in include/stereo_mi355x.h), a second matcher
     beside StereoMatching.  Candidates are min_disparity..max_disparity (at most 256); paths 4 or 8; 0 <= P1 <= P2 <= 191;

@@ -133,6 +133,9 @@ EXPORTS = {
     "smx_remap_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                   C.c_void_p]),
+    # right-view synthesis head: (device_id, n, channels, dtype, D, h, w, scale, prob, left, out, stream)
+    "smx_synthesize_right_view": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # semi-global matching: (n, H, W, num_disparities, paths) -> workspace bytes; (device_id, n, channels, dtype, H, W,
     # left, right, min_disparity, num_disparities, paths, P1, P2, uniqueness, lr_max_diff, subpixel, invalid_disparity,
     # out, gray_left_out, workspace, workspace_bytes, stream)

@@ -3,8 +3,9 @@
 Same public surface as /root/reference/src/python/pipeline/depth_estimation_pipeline.py:14-87
 (`DepthEstimationPipelineConfig` with its six fields -- plus the opt-in left-right check -- and `update`, `DepthEstimationResult`,
 `DepthEstimationPipelineContext`, `DepthEstimationPipeline.process / get_configuration`) for the
-'cuda' and 'sgm' backends.  Right-view synthesis (Deep3D) and the traced-DNN backends are out of scope
-(SURVEY.md section 2): `right_image` is mandatory here and the other backend names raise.
+'cuda' and 'sgm' backends.  The right view is synthesised when process() gets none and the pipeline was given a
+pipeline.synthesis.RightViewSynthesis (the network inside it is the caller's); without one
+`right_image` is mandatory.  The traced-DNN backends are out of scope: their names raise.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import torch
 import cuda_depth
 from helpers.torch_helpers import cuda_perf_clock
 from pipeline.depth import AVAILABLE_DNN_BACKENDS, CudaStereoMatchingBackend, SgmStereoMatchingBackend, StereoMatching
+from pipeline.synthesis import RightViewSynthesis
 
 _BACKENDS = ("cuda", "sgm") + AVAILABLE_DNN_BACKENDS
 
@@ -119,7 +121,8 @@ class DepthEstimationPipeline:
                  sgm_p1: int = 10, sgm_p2: int = 120, sgm_uniqueness: int = 0, reprojection_matrix=None,
                  point_cloud_depth_range: Tuple[float, float] = (0.0, math.inf), point_cloud_voxel_size: float = 0.0,
                  point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0,
-                 tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None):
+                 tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None,
+                 right_view_synthesis: Optional[RightViewSynthesis] = None):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -146,7 +149,10 @@ class DepthEstimationPipeline:
         returned as DepthEstimationResult.point_cloud; None (the default) changes nothing.  tsdf_volume: a caller-owned
         cuda_depth.TSDFVolume on the pipeline's device (needs reprojection_matrix); every process() call then takes a
         camera_pose and integrates the final map into it, with point_cloud_depth_range, the confidence map and
-        point_cloud_min_confidence when confidence=True, and colour from the left frame the map was computed on."""
+        point_cloud_min_confidence when confidence=True, and colour from the left frame the map was computed on.
+        right_view_synthesis: a pipeline.synthesis.RightViewSynthesis whose full_resolution is the frames' size; a
+        process() call without a right image then generates one from the left frame, as the reference's pipeline does,
+        and matches against it (None: such a call raises)."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
@@ -160,6 +166,9 @@ class DepthEstimationPipeline:
                                  f"got {tsdf_volume.device}")
             cuda_depth.projection_matrix(reprojection_matrix)
         self._tsdf_volume = tsdf_volume
+        if right_view_synthesis is not None and not isinstance(right_view_synthesis, RightViewSynthesis):
+            raise TypeError("right_view_synthesis must be a pipeline.synthesis.RightViewSynthesis")
+        self._right_view_synthesis = right_view_synthesis
         if reprojection_matrix is not None:
             self._reprojection_matrix = cuda_depth._check_q(reprojection_matrix)
             cuda_depth._check_reproject_params(point_cloud_min_confidence, point_cloud_depth_range,
@@ -202,6 +211,8 @@ class DepthEstimationPipeline:
         geometry as the map; persistent buffers too), not the raw frames passed in.  With confidence=True the result's
         confidence_map aliases a persistent buffer in the same way.  Frames are matched (and rectified) as uint8 when
         both are uint8 and as float32 otherwise: a uint8 frame beside a float32 one is converted to float32 first.
+        Without a right_image, and with right_view_synthesis, the right view is generated from the left frame first and
+        returned as the result's right_image ([3, H, W] float32 in 0..255, the synthesiser's persistent buffer).
         camera_pose: the left camera's camera-to-world pose [4, 4] for this frame, required with tsdf_volume and
         refused without one; the final map is integrated into the volume on the current stream."""
         if (camera_pose is None) != (self._tsdf_volume is None):
@@ -209,9 +220,12 @@ class DepthEstimationPipeline:
                              else "camera_pose needs a pipeline with tsdf_volume")
         if camera_pose is not None:
             cuda_depth.world_to_camera_poses(camera_pose)
-        if right_image is None:
+        if right_image is None and self._right_view_synthesis is None:
             raise RuntimeError("right_image is required: right-view synthesis (Deep3D) is not part of this build.")
         left_on_device = left_image.cuda()
+        if right_image is None:
+            with cuda_perf_clock("Right view generation", self._config.log_perf_time):
+                right_image = self._right_view_synthesis.process(left_on_device)
         with cuda_perf_clock("Stereo matching", self._config.log_perf_time):
             disparity = self._stereo_matching.process(left_on_device, right_image)
         rectified = getattr(self._stereo_matching, "rectified_frames", lambda: None)()

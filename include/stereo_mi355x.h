@@ -267,7 +267,8 @@ int smx_overlap_lanes(const smx_engine *engine, int n);
  * multi_block_matching_cost_aggregation.cu:54-88).  useful_fraction = output (pixel, disparity) cells /
  * (lane, row, disparity) cells marched by the dense first pass, over the whole launch.  The plan is the one the engine's
  * LAST call used (stream lanes or a caller's stream: the lanes take the throughput shape from fewer pairs on); for a
- * call the lanes split, `workgroups` counts one half's launch. */
+ * call the lanes split, `workgroups` counts one half's launch.  The geometry describes the plan of the kernel's SPARSE
+ * form: a batch call that takes the dense form where the sparse plan has 32-row bands launches 27-row bands. */
 typedef enum smx_match_kernel {
     SMX_KERNEL_EXACT_ONLY = 0,      /* configuration outside the FAST_GRID envelope                         */
     SMX_KERNEL_FAST_WINDOW = 1,     /* one 64-column window per wave, tall bands                             */

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(64 * FA_DS_WAVES, TH >= FA_TH_SMALL_TALL ? 2 : SMX_
         match_fast_body<TH, PR, false, true, PK16>(p, blk);
         return;
     }
-    // off the grid: p.nsplit slices per 16x128 tile (a power of two, nsplit * tiles <= workgroups per pair: launch_match_auto_small)
+    // off the grid: p.nsplit slices per 16x128 tile (a power of two, nsplit * tiles <= workgroups per pair: match_auto_nsplit)
     static_assert(64 * FA_DS_WAVES == E2K<2>::THREADS, "the off-grid branch is the 8-wave exact-order body");
     const int tiles_x = (p.w + E2_TW - 1) / E2_TW, tiles = tiles_x * ((p.h + E2_TH - 1) / E2_TH);
     const int lin = (int)(blk.x + gridDim.x * blk.y);
@@ -62,7 +62,7 @@ inline size_t match_auto_slice_floats(const MatchParams &p, int n, int th) {
 }
 
 // Floats of one stream lane's region of the slice buffer (smx_create; two small calls may be in flight at once): the
-// largest disparity split launch_exact can pick (calls of up to 4 pairs) and, if the engine can take the one-launch AUTO
+// largest disparity split exact_launch (smx_plan.h) can plan (calls of up to 4 pairs) and, if the engine can take the one-launch AUTO
 // kernel (one_launch), the records of its calls of up to 16 pairs in the latency shape, on a caller's stream or on the
 // lanes.  Larger calls that would need more room take the two gated launches, whose split is 1 beyond 4 pairs.
 // p: the engine's h, w and Dd; cus: the device's CU count.
@@ -103,39 +103,29 @@ constexpr int MATCH_AUTO_LDS_CAP = 128 * 1024;
 inline bool match_auto_small_applicable(const MatchParams &p, int th, int n, size_t slices_floats) {
     const long fast_wgs = (long)((p.w + FA_VALID - 1) / FA_VALID) * ((p.h + th - 1) / th);
     const long tiles = (long)((p.w + E2_TW - 1) / E2_TW) * ((p.h + E2_TH - 1) / E2_TH);
-    const size_t lds = p.Dd <= 256 - 64 + 1 ? fast_lds_bytes<256>(th, p.Dd, true) : fast_lds_bytes<320>(th, p.Dd, true);
+    const size_t lds = fast_small_wide(p.Dd) ? fast_lds_bytes<320>(th, p.Dd, true) : fast_lds_bytes<256>(th, p.Dd, true);
     return fast_wgs >= tiles && lds <= (size_t)MATCH_AUTO_LDS_CAP && match_auto_slice_floats(p, n, th) <= slices_floats;
 }
 
+// From launch spec (smx_plan.h: auto_launch) to instantiation; p.nsplit, p.pairs and p.nd_chunk are the spec's.
 template <int TH, int PR>
-inline void launch_match_auto_small_t(MatchParams p, int n, size_t exact_lds, hipStream_t s) {
-    dim3 grid((p.w + FA_VALID - 1) / FA_VALID, (p.h + TH - 1) / TH, n);
-    size_t lds = fast_lds_bytes<PR>(TH, p.Dd, true);
-    // the off-grid branch: slices, right-tile chunk no wider than a slice, records of n pairs
-    p.nsplit = match_auto_nsplit(p, TH);
-    p.pairs = n;
-    const int per = (p.Dd + p.nsplit - 1) / p.nsplit;
-    if (p.nd_chunk > per) p.nd_chunk = per;
-    exact_lds = exact2_lds_floats(p.nd_chunk) * sizeof(float);
-    if (exact_lds > lds) lds = exact_lds;
-    const int pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
-    const dim3 block(64 * FA_DS_WAVES);
-    if (pk == 2) hipLaunchKernelGGL((k_match_auto_small<TH, PR, 2>), grid, block, lds, s, p);
-    else if (pk == 1) hipLaunchKernelGGL((k_match_auto_small<TH, PR, 1>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((k_match_auto_small<TH, PR, 0>), grid, block, lds, s, p);
+inline void launch_match_auto_small_t(const AutoLaunch &al, const MatchParams &p, int n, hipStream_t s) {
+    const dim3 grid((p.w + FA_VALID - 1) / FA_VALID, (p.h + TH - 1) / TH, n), block(64 * FA_DS_WAVES);
+    if (al.pk == 2) hipLaunchKernelGGL((k_match_auto_small<TH, PR, 2>), grid, block, al.lds_bytes, s, p);
+    else if (al.pk == 1) hipLaunchKernelGGL((k_match_auto_small<TH, PR, 1>), grid, block, al.lds_bytes, s, p);
+    else hipLaunchKernelGGL((k_match_auto_small<TH, PR, 0>), grid, block, al.lds_bytes, s, p);
 }
 
-inline void launch_match_auto_small(const MatchParams &p, int n, int th, size_t exact_lds, hipStream_t s) {
-    const bool wide = p.Dd > 256 - 64 + 1;
-    if (th == FA_TH_SMALL_TALL) {
-        if (!wide) launch_match_auto_small_t<FA_TH_SMALL_TALL, 256>(p, n, exact_lds, s);
-        else launch_match_auto_small_t<FA_TH_SMALL_TALL, 320>(p, n, exact_lds, s);
-    } else if (th == FA_TH_SMALL_MID) {
-        if (!wide) launch_match_auto_small_t<FA_TH_SMALL_MID, 256>(p, n, exact_lds, s);
-        else launch_match_auto_small_t<FA_TH_SMALL_MID, 320>(p, n, exact_lds, s);
+inline void launch_match_auto_small(const AutoLaunch &al, const MatchParams &p, int n, hipStream_t s) {
+    if (al.th == FA_TH_SMALL_TALL) {
+        if (!al.wide) launch_match_auto_small_t<FA_TH_SMALL_TALL, 256>(al, p, n, s);
+        else launch_match_auto_small_t<FA_TH_SMALL_TALL, 320>(al, p, n, s);
+    } else if (al.th == FA_TH_SMALL_MID) {
+        if (!al.wide) launch_match_auto_small_t<FA_TH_SMALL_MID, 256>(al, p, n, s);
+        else launch_match_auto_small_t<FA_TH_SMALL_MID, 320>(al, p, n, s);
     } else {
-        if (!wide) launch_match_auto_small_t<FA_TH_SMALL, 256>(p, n, exact_lds, s);
-        else launch_match_auto_small_t<FA_TH_SMALL, 320>(p, n, exact_lds, s);
+        if (!al.wide) launch_match_auto_small_t<FA_TH_SMALL, 256>(al, p, n, s);
+        else launch_match_auto_small_t<FA_TH_SMALL, 320>(al, p, n, s);
     }
 }
 

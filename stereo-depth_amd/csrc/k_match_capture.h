@@ -149,24 +149,21 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_capture(Mat
 //  capture_applicable -- two copies of each kernel, built with different per-file flags, of which the runtime picks one.)
 #ifdef SMX_TU_CAPTURE
 template <int TH, int PR>
-inline void launch_match_capture_t(const MatchParams &p, int n, hipStream_t s) {
-    dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + TH - 1) / TH, n);
+inline void launch_match_capture_t(int pk, const MatchParams &p, int n, hipStream_t s) {
+    const dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + TH - 1) / TH, n), block(64 * FA_WAVES);
     const size_t lds = fast_lds_bytes<PR>(TH, p.Dd, false);
-    const int pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
-    const dim3 block(64 * FA_WAVES);
     if (pk == 2) hipLaunchKernelGGL((k_match_capture<TH, PR, 2>), grid, block, lds, s, p);
     else if (pk == 1) hipLaunchKernelGGL((k_match_capture<TH, PR, 1>), grid, block, lds, s, p);
     else hipLaunchKernelGGL((k_match_capture<TH, PR, 0>), grid, block, lds, s, p);
 }
 
-inline void launch_match_capture(const MatchParams &p, int n, int cus, hipStream_t s) {
-    const bool wide = p.Dd > FA_WIDE_FROM;
-    if (match_fast_plan(p, n, cus).small) {           // few pairs in flight (same rule as the arg-max kernel)
-        if (!wide) launch_match_capture_t<CAP_TH_SMALL, 256>(p, n, s);
-        else launch_match_capture_t<CAP_TH_SMALL, 320>(p, n, s);
+inline void launch_match_capture(const FastCaptureLaunch &cl, const MatchParams &p, int n, hipStream_t s) {
+    if (cl.small) {           // few pairs in flight (the arg-max kernel's rule)
+        if (!cl.wide) launch_match_capture_t<CAP_TH_SMALL, 256>(cl.pk, p, n, s);
+        else launch_match_capture_t<CAP_TH_SMALL, 320>(cl.pk, p, n, s);
     } else {
-        if (!wide) launch_match_capture_t<CAP_TH, 256>(p, n, s);
-        else launch_match_capture_t<CAP_TH, 320>(p, n, s);
+        if (!cl.wide) launch_match_capture_t<CAP_TH, 256>(cl.pk, p, n, s);
+        else launch_match_capture_t<CAP_TH, 320>(cl.pk, p, n, s);
     }
 }
 

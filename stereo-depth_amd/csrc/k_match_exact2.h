@@ -28,7 +28,7 @@ constexpr int E2_TW = 128;                // tile columns (64 lanes x 2)
 //           (384x1280, 240 workgroups: 69 -> 49 us), a launch of several rounds gains the faster staging and tail
 //           (1080p, 1,904 workgroups: 392 -> 367 us), and the capture kernel, whose workgroups mostly stage, gains 21 %
 //           (74 -> 58 us); dense batches are within 3 % either way and two single frames pipelined on the stream lanes LOSE
-//           10 % at C5 (the LDS pipe is the shared resource there).  tu_exact.hip picks per launch.
+//           10 % at C5 (the LDS pipe is the shared resource there).  smx_plan.h (exact_launch) picks per launch.
 template <int NR> struct E2K {
     static_assert(NR == 4 || NR == 2, "rows per thread");
     static constexpr int WAVES = E2_TH / NR;          // waves per workgroup: 4 or 8
@@ -54,6 +54,23 @@ inline int exact_split(int tiles, int n, int Dd, int cus) {
     for (int sp = 2; sp <= SMX_E2_MAX_SPLIT && Dd / sp >= SMX_E2_MIN_PER; ++sp) {
         const long per = (Dd + sp - 1) / sp;
         const long cost = ((wgs * sp + slots - 1) / slots) * per + 2;
+        if (cost < best_cost) { best_cost = cost; best = sp; }
+    }
+    return best;
+}
+
+// Workgroups per tile of the capture kernel (few pairs in flight): every workgroup stages the tiles (about two slices'
+// worth) and then evaluates its share of the indices the tile needs -- between ~8 (one surface) and ~Dd / 2 (real scene);
+// planned for a quarter of the range.  The 1080p default configuration: 3 workgroups per tile (816 in two rounds); seven,
+// as the dense kernel uses, cost 172 instead of ~70 us on the synthetic pair because each of them stages the tiles for
+// one slice of work.
+inline int capture_split(int tiles, int n, int Dd, int cus) {
+    if (n > 4 || Dd < 16) return 1;
+    const long slots = 2L * cus, wgs = (long)tiles * n, need = (Dd + 3) / 4;
+    int best = 1;
+    long best_cost = ((wgs + slots - 1) / slots) * (2 + need);
+    for (int sp = 2; sp <= 8; ++sp) {
+        const long cost = ((wgs * sp + slots - 1) / slots) * (2 + (need + sp - 1) / sp);
         if (cost < best_cost) { best_cost = cost; best = sp; }
     }
     return best;

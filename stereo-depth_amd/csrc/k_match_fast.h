@@ -842,18 +842,28 @@ __global__ __launch_bounds__(64 * (DSPLIT ? FA_DS_WAVES : FA_WAVES), DENSE ? 2 :
     match_fast_body<TH, PR, P1ONLY, DSPLIT, PK16, ARGB, DENSE>(p, blk);
 }
 
-inline bool match_fast_supported(int h, int w, int Dd) {
-    (void)h; (void)w; (void)Dd;
-    return true;
+// Packed-sum form PK16 of a launch: two disparities per 32-bit lane operation while the sums fit 16 bits -- up to R3 for
+// K <= 2 (2), up to CV for K = 4 (1), not at all beyond (0).  unit: grid units per gray level (K^2).
+inline int fast_pk(int unit) { return unit <= 4 ? 2 : (unit <= 16 ? 1 : 0); }
+// Latency shape: ranges above 193 disparities take the pitch-320 right tile (257 per chunk) instead of chunks at pitch 256.
+inline bool fast_small_wide(int Dd) { return Dd > 256 - 64 + 1; }
+
+template <int TH, int PR, bool P1ONLY, bool DSPLIT, bool ARGB, bool DENSE>
+inline void launch_match_fast_k(int pk, dim3 grid, dim3 block, size_t lds, const MatchParams &p, hipStream_t s) {
+    if (pk == 2) hipLaunchKernelGGL((k_match_fast<TH, PR, P1ONLY, DSPLIT, 2, ARGB, DENSE>), grid, block, lds, s, p);
+    else if (pk == 1) hipLaunchKernelGGL((k_match_fast<TH, PR, P1ONLY, DSPLIT, 1, ARGB, DENSE>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((k_match_fast<TH, PR, P1ONLY, DSPLIT, 0, ARGB, DENSE>), grid, block, lds, s, p);
 }
 
+// From launch spec (smx_plan.h: fast_launch) to instantiation.  The dense forms exist for the latency shape at 12-row bands
+// (by construction at most one workgroup per CU: up to 256 registers; no second pass at all, the whole range in one
+// right-tile chunk) and for the throughput shape with byte-packed winners up to FA_DENSE_MAX_TH rows (beyond, the four
+// extra registers per row spill); the planner names them nowhere else (tests/launch_plan_harness.cpp).
 template <int TH, int PR, bool DSPLIT, bool ARGB>
-inline void launch_match_fast_a(const MatchParams &p, int n, hipStream_t s) {
+inline void launch_match_fast_a(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s) {
     const int win_per_wg = DSPLIT ? 1 : FA_WAVES;
-    dim3 grid((p.w + FA_VALID * win_per_wg - 1) / (FA_VALID * win_per_wg), (p.h + TH - 1) / TH, n);
+    const dim3 grid((p.w + FA_VALID * win_per_wg - 1) / (FA_VALID * win_per_wg), (p.h + TH - 1) / TH, n);
     const size_t lds = fast_lds_bytes<PR>(TH, p.Dd, DSPLIT);
-    // two disparities per 32-bit lane operation while the sums fit 16 bits: up to R3 for K <= 2, up to CV for K = 4
-    const int pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
     const dim3 block(64 * (DSPLIT ? FA_DS_WAVES : FA_WAVES));
 #ifdef SMX_FA_FORCE_TH
     if (lds > 64 * 1024) {       // tuning experiments only: tall forced bands need the raised dynamic-LDS limit
@@ -861,32 +871,14 @@ inline void launch_match_fast_a(const MatchParams &p, int n, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
 #endif
-    if constexpr (DSPLIT && TH == FA_TH_SMALL_TALL) {
-        // latency shape at 12-row bands (by construction at most one workgroup per CU: up to 256 registers): the dense form
-        // has no second pass at all; it needs the whole range in one right-tile chunk
-        if (p.dense_small && !p.pass1_only && p.Dd <= PR - 64 + 1) {
-            if (pk == 2) hipLaunchKernelGGL((k_match_fast<TH, PR, false, true, 2, false, true>), grid, block, lds, s, p);
-            else if (pk == 1) hipLaunchKernelGGL((k_match_fast<TH, PR, false, true, 1, false, true>), grid, block, lds, s, p);
-            else hipLaunchKernelGGL((k_match_fast<TH, PR, false, true, 0, false, true>), grid, block, lds, s, p);
-            return;
-        }
-    }
-    if constexpr (!DSPLIT && ARGB && TH <= FA_DENSE_MAX_TH) {     // (byte-packed winners: up to 256 disparities; beyond, the four extra registers per row spill)
-        if (p.dense && !p.pass1_only) {      // content whose windows hold many winners (the engine's choice, smx_engine.hip)
-            if (pk == 2) hipLaunchKernelGGL((k_match_fast<TH, PR, false, false, 2, ARGB, true>), grid, block, lds, s, p);
-            else if (pk == 1) hipLaunchKernelGGL((k_match_fast<TH, PR, false, false, 1, ARGB, true>), grid, block, lds, s, p);
-            else hipLaunchKernelGGL((k_match_fast<TH, PR, false, false, 0, ARGB, true>), grid, block, lds, s, p);
-            return;
-        }
-    }
-    if (p.pass1_only) {        // dmin > 0: arg-max only; k_match_capture looks the step-6 costs up afterwards
-        if (pk == 2) hipLaunchKernelGGL((k_match_fast<TH, PR, true, DSPLIT, 2, ARGB>), grid, block, lds, s, p);
-        else if (pk == 1) hipLaunchKernelGGL((k_match_fast<TH, PR, true, DSPLIT, 1, ARGB>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((k_match_fast<TH, PR, true, DSPLIT, 0, ARGB>), grid, block, lds, s, p);
+    if (fl.form == FAST_DENSE_SMALL) {
+        if constexpr (DSPLIT && TH == FA_TH_SMALL_TALL) launch_match_fast_k<TH, PR, false, true, false, true>(fl.pk, grid, block, lds, p, s);
+    } else if (fl.form == FAST_DENSE) {      // content whose windows hold many winners (the engine's choice, smx_route.h)
+        if constexpr (!DSPLIT && ARGB && TH <= FA_DENSE_MAX_TH) launch_match_fast_k<TH, PR, false, false, ARGB, true>(fl.pk, grid, block, lds, p, s);
+    } else if (fl.form == FAST_PASS1_ONLY) {   // dmin > 0: arg-max only; k_match_capture looks the step-6 costs up afterwards
+        launch_match_fast_k<TH, PR, true, DSPLIT, ARGB, false>(fl.pk, grid, block, lds, p, s);
     } else {
-        if (pk == 2) hipLaunchKernelGGL((k_match_fast<TH, PR, false, DSPLIT, 2, ARGB>), grid, block, lds, s, p);
-        else if (pk == 1) hipLaunchKernelGGL((k_match_fast<TH, PR, false, DSPLIT, 1, ARGB>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((k_match_fast<TH, PR, false, DSPLIT, 0, ARGB>), grid, block, lds, s, p);
+        launch_match_fast_k<TH, PR, false, DSPLIT, ARGB, false>(fl.pk, grid, block, lds, p, s);
     }
 }
 
@@ -894,29 +886,29 @@ inline void launch_match_fast_a(const MatchParams &p, int n, hipStream_t s) {
 // tiles are only ever launched for ranges of at most 67 disparities (match_fast_plan), pitch-320 tiles take the byte
 // form up to 256 disparities.  The latency shape (DSPLIT, 8-row bands) has registers to spare: one register per row.
 template <int TH, int PR, bool DSPLIT>
-inline void launch_match_fast_t(const MatchParams &p, int n, hipStream_t s) {
+inline void launch_match_fast_t(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s) {
     if constexpr (DSPLIT) {
-        launch_match_fast_a<TH, PR, true, false>(p, n, s);
+        launch_match_fast_a<TH, PR, true, false>(fl, p, n, s);
     } else if constexpr (PR == 256 || PR == FA_MID_PITCH) {
-        launch_match_fast_a<TH, PR, false, true>(p, n, s);       // (at most 67 / 99 disparities: the byte form always applies)
+        launch_match_fast_a<TH, PR, false, true>(fl, p, n, s);       // (at most 67 / 99 disparities: the byte form always applies)
     } else {
-        if (p.Dd <= 256) launch_match_fast_a<TH, PR, false, true>(p, n, s);
-        else launch_match_fast_a<TH, PR, false, false>(p, n, s);
+        if (fl.argb) launch_match_fast_a<TH, PR, false, true>(fl, p, n, s);
+        else launch_match_fast_a<TH, PR, false, false>(fl, p, n, s);
     }
 }
 
-// right-tile pitch of the throughput shape for a range of Dd pooled disparities (one rule for launch and plan)
+// right-tile pitch of the throughput shape for a range of Dd pooled disparities
 __host__ __device__ constexpr int fast_tall_pitch(int Dd) { return Dd <= FA_WIDE_FROM ? 256 : (Dd <= FA_MID_UPTO ? FA_MID_PITCH : 320); }
 
 template <int TH>
-inline void launch_match_fast_tall(const MatchParams &p, int n, hipStream_t s) {
-    const int pr = fast_tall_pitch(p.Dd);
-    if (pr == 256) launch_match_fast_t<TH, 256, false>(p, n, s);
-    else if (pr == FA_MID_PITCH) launch_match_fast_t<TH, FA_MID_PITCH, false>(p, n, s);
-    else launch_match_fast_t<TH, 320, false>(p, n, s);
+inline void launch_match_fast_tall(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s) {
+    if (fl.pitch == 256) launch_match_fast_t<TH, 256, false>(fl, p, n, s);
+    else if (fl.pitch == FA_MID_PITCH) launch_match_fast_t<TH, FA_MID_PITCH, false>(fl, p, n, s);
+    else launch_match_fast_t<TH, 320, false>(fl, p, n, s);
 }
 
-// Which instantiation a launch of n pairs uses (also reported by smx_match_geometry).
+// Shape of a fast-kernel launch of n pairs in its sparse form (also reported by smx_match_geometry; what is launched:
+// smx_plan.h: fast_launch).
 struct FastPlan {
     bool small;      // few pairs in flight: short bands, disparity range split over the 4 waves
     int th;          // output rows per band
@@ -937,7 +929,7 @@ inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus) {
     // right-tile pitch 256 holds 67 (window-per-wave) / 193 (split) disparities per chunk, 320: 131 / 257
     if (pl.small) {
         pl.th = FA_TH_SMALL;
-        pl.wide = p.Dd > 256 - 64 + 1;
+        pl.wide = fast_small_wide(p.Dd);
         // one workgroup per window and band: more than one but fewer than two per CU -> the taller bands, if those fit one per CU
         const long windows = (long)((p.w + FA_VALID - 1) / FA_VALID) * n;
         const long wg_small = windows * ((p.h + FA_TH_SMALL - 1) / FA_TH_SMALL), wg_tall = windows * ((p.h + FA_TH_SMALL_TALL - 1) / FA_TH_SMALL_TALL);

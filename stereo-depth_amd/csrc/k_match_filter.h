@@ -170,11 +170,9 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_filter(Matc
 
 
 template <int TH, int PR>
-inline void launch_match_filter_t(const MatchParams &p, const FilterParams &f, int n, hipStream_t s) {
-    dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + TH - 1) / TH, n);
+inline void launch_match_filter_t(int pk, const MatchParams &p, const FilterParams &f, int n, hipStream_t s) {
+    const dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + TH - 1) / TH, n), block(64 * FA_WAVES);
     const size_t lds = filter_lds_bytes<PR>(TH);
-    const int pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
-    const dim3 block(64 * FA_WAVES);
     if (pk == 2) hipLaunchKernelGGL((k_match_filter<TH, PR, 2>), grid, block, lds, s, p, f);
     else if (pk == 1) hipLaunchKernelGGL((k_match_filter<TH, PR, 1>), grid, block, lds, s, p, f);
     else hipLaunchKernelGGL((k_match_filter<TH, PR, 0>), grid, block, lds, s, p, f);

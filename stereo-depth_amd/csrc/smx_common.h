@@ -197,4 +197,31 @@ struct MatchParams {
     unsigned *tickets;      // [B][exact-order tiles] arrival counters of the one-launch AUTO kernel's off-grid branch (k_match_auto.h)
 };
 
+// ---- launch specs of the aggregation family ----
+// One POD per aggregation launch a range can enqueue: plan_range() (smx_plan.h) fills them, the launchers (smx_launch.h) are tables
+// from spec to kernel instantiation and decide nothing.  What a spec says about the kernel's parameters (nsplit, pairs,
+// nd_chunk, slices, tickets) enqueue_range has already copied into the MatchParams it passes.
+enum ExactKernel { EXACT_GENERIC = 0, EXACT_GENERIC_VOLUME, EXACT_TILED };   // k_match_exact [+ volume] / k_match_exact2 (default radii)
+struct ExactLaunch {
+    int kernel = EXACT_GENERIC;
+    int split = 1;               // disparity slices per tile (TILED, calls of up to 4 pairs); > 1: a merge launch follows
+    int rows_per_thread = 4;     // TILED: 4-wave (4) or 8-wave (2) workgroups
+    int nd_chunk = 0;            // disparities per right-tile load, never more than a slice holds
+    size_t lds_bytes = 0;
+    size_t slice_floats = 0;     // slice records the split launch writes: [split][SMX_SLICE_WORDS][n][h][w] (0: unsplit)
+};
+struct ExactCaptureLaunch { int split = 1, rows_per_thread = 4, nd_chunk = 0; size_t lds_bytes = 0; };
+enum FastForm { FAST_SPARSE = 0, FAST_PASS1_ONLY, FAST_DENSE, FAST_DENSE_SMALL, FAST_FORMS };
+struct FastLaunch {
+    int th = 0;                  // band rows of the instantiation launched
+    bool small = false;          // latency shape (disparity range split over a workgroup's waves)
+    int pitch = 0;               // right-tile pitch: 256 / 320, throughput shape also 288
+    int pk = 0;                  // packed-sum form (k_match_fast.h: fast_pk)
+    bool argb = false;           // the arg-max indices are kept as bytes
+    int form = FAST_SPARSE;
+};
+struct FastCaptureLaunch { bool small = false, wide = false; int pk = 0; };
+struct AutoLaunch { int th = 0; bool wide = false; int pk = 0, nsplit = 1, nd_chunk = 0; size_t lds_bytes = 0; };
+struct FilterLaunch { int th = 0; bool wide = false; int pk = 0; };
+
 }  // namespace smx

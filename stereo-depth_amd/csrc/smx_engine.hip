@@ -83,13 +83,12 @@ struct smx_engine {
     float *wta = nullptr, *refined = nullptr;     // [B][h][w]
     float *costs = nullptr;                       // [3][B][h][w]
     float *vol = nullptr;                         // [B][h][w][Dd] only when dmin > 0
-    float *slices = nullptr;                      // partial arg-max states of the disparity-split exact kernel
+    float *slices = nullptr;                      // [LANES][facts.slices_floats] partial arg-max states of the disparity-split launches
     unsigned *tickets = nullptr;                  // [B][exact-order tiles] arrival counters (one-launch AUTO kernel, off-grid branch)
     int *flags = nullptr;                         // [2][B]: exact-grid flag, integer-gray flag (== epoch: set)
     int epoch = 0;                                // call counter: flags are stamped, never cleared per call
     uint8_t *gray8_l = nullptr, *gray8_r = nullptr;   // [B][H][pitch8] u8 copies with cyclic aprons
     unsigned *cand = nullptr;                     // [B][tiles][cw] candidate bits of the filtered exact-order route (all zero between calls)
-    smx::ExactPlan xp{};                          // tile chunks, LDS sizes and the slice buffer of the exact-order kernels
     // The last call, as smx_get_route_info, smx_get_match_geometry, smx_last_match_mode and smx_get_intermediate see it.
     struct LastCall {
         smx::CallFacts call;                      // entry, lanes or caller's stream, the switches' decision
@@ -302,17 +301,28 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
     mp.on_lanes = call.on_lanes ? 1 : 0;
     mp.tickets = e->tickets ? e->tickets + (size_t)first * f.e2_tiles : nullptr;
     mp.pass1_only = pl.capture_follows ? 1 : 0;
-    smx::ExactPlan xp = e->xp;                     // this lane's region of the slice buffer
-    if (xp.slices) xp.slices += (size_t)lane * xp.slices_floats;
-    mp.slices = xp.slices;                         // (the one-launch AUTO kernel's off-grid branch; launch_exact sets its own)
-    auto exact = [&](const smx::MatchParams &p, bool allow_split) -> int {
-        if (smx::launch_exact(xp, p, n, allow_split, f.cus, s))
-            return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
-        if (pl.capture_follows) smx::launch_exact2_capture(e->xp, p, n, allow_split, f.cus, s);   // dmin > 0: the lookups of step 6
+    mp.slices = e->slices ? e->slices + (size_t)lane * f.slices_floats : nullptr;   // this lane's region of the slice buffer
+    // The launches below are the plan's launch specs; what a spec says about the kernel's parameters is copied here.
+    auto exact_capture = [&](smx::MatchParams p) {           // dmin > 0: the lookups of step 6 behind an exact-order arg-max
+        if (!pl.capture_follows) return;
+        p.nd_chunk = pl.exact_capture.nd_chunk;
+        p.nsplit = pl.exact_capture.split;
+        smx::launch_exact2_capture(pl.exact_capture, p, n, s);
+    };
+    auto exact = [&](smx::MatchParams p) -> int {            // the dense exact-order launch
+        p.nd_chunk = pl.exact.nd_chunk;
+        if (pl.exact.split > 1) {
+            if (pl.exact.slice_floats > f.slices_floats)
+                return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
+            p.nsplit = pl.exact.split;
+            p.pairs = n;
+            p.tickets = nullptr;                             // merged by a launch of its own, not by a tile's last slice
+        }
+        smx::launch_exact(pl.exact, p, n, s);
         return SMX_OK;
     };
-    // the fast kernel in the plan's form; the sparse form's report is published by this range's fill launch
-    auto fast = [&](smx::MatchParams p, int gate) -> smx::MatchParams {
+    // the parameters of the fast kernel in the plan's form; the sparse form's report is published by this range's fill launch
+    auto fast_params = [&](smx::MatchParams p, int gate) -> smx::MatchParams {
         p.gate = gate;
         p.dense = pl.dense ? 1 : 0;
         p.dense_small = pl.dense_small ? 1 : 0;
@@ -321,6 +331,11 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
             p.fast_stride = pl.stride;
         }
         return p;
+    };
+    auto fast = [&](int gate) {                              // the fast kernel [and its lookups]
+        const smx::MatchParams p = fast_params(mp, gate);
+        smx::launch_match_fast(pl.fast_launch, p, n, s);
+        if (pl.capture_follows) smx::launch_match_capture_tu(pl.fast_capture, p, n, s);
     };
     switch (pl.route) {
     case smx::AGG_FILTERED: {
@@ -333,36 +348,38 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
                 smx::MatchParams dp = mp;
                 dp.flags = v.flags2;
                 dp.gate = 2;
-                if (smx::launch_exact(xp, dp, n, false, f.cus, s))
-                    return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
+                if (int rc = exact(dp)) return rc;
             }
             smx::MatchParams fmp = mp;
             fmp.unit = (float)f.filter_unit;
-            smx::launch_match_filter_tu(fmp, fp, n, f.cus, s);
+            smx::launch_match_filter_tu(pl.filter, fmp, fp, n, s);
         }
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
-        smx::launch_exact2_sparse(e->xp, mp, n, v.cand, f.cand_cw, (const int *)v.flags2, e->stats_dev + 2 * lane,
+        smx::MatchParams sp = mp;
+        sp.nd_chunk = f.exact2_nd;
+        smx::launch_exact2_sparse(sp, n, v.cand, f.cand_cw, (const int *)v.flags2, e->stats_dev + 2 * lane,
                                   &e->hints_dev->filter_density[lane], e->route.filt.next_seq(), s);
-        if (pl.capture_follows) smx::launch_exact2_capture(e->xp, mp, n, false, f.cus, s);   // dmin > 0: the lookups of step 6
+        exact_capture(mp);
         break;
     }
     case smx::AGG_EXACT: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
-        if (int rc = exact(mp, pl.exact_split)) return rc;
+        if (int rc = exact(mp)) return rc;
+        exact_capture(mp);
         break;
     }
     case smx::AGG_FAST: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        const smx::MatchParams p = fast(mp, 0);
-        smx::launch_match_fast(p, n, f.cus, s);
-        if (pl.capture_follows) smx::launch_match_capture_tu(p, n, f.cus, s);
+        fast(0);
         break;
     }
     case smx::AGG_AUTO_ONE_LAUNCH: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        smx::MatchParams p = fast(mp, 0);
-        p.nd_chunk = e->xp.exact2_nd;
-        smx::launch_match_auto_small_tu(p, n, f.cus, s);
+        smx::MatchParams p = fast_params(mp, 0);
+        p.nsplit = pl.auto_launch.nsplit;      // the off-grid branch: slices, right-tile chunk no wider than a slice, records of n pairs
+        p.pairs = n;
+        p.nd_chunk = pl.auto_launch.nd_chunk;
+        smx::launch_match_auto_small_tu(pl.auto_launch, p, n, s);
         break;
     }
     default: {   // AGG_AUTO_GATED: both enqueued, the device-side grid flag lets exactly one do the work
@@ -373,12 +390,11 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
         {
             SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
             mp.gate = 2;
-            if (int rc = exact(mp, pl.exact_split)) return rc;
+            if (int rc = exact(mp)) return rc;
+            exact_capture(mp);
         }
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        const smx::MatchParams p = fast(mp, 1);
-        smx::launch_match_fast(p, n, f.cus, s);
-        if (pl.capture_follows) smx::launch_match_capture_tu(p, n, f.cus, s);
+        fast(1);
         break;
     }
     }
@@ -803,9 +819,6 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     // everything the launch plans depend on, decided once (smx_plan.h); the rest of this function allocates what it names
     e->facts = smx::derive_facts(*cfg, d, cus, opt);
     const smx::EngineFacts &f = e->facts;
-    e->xp.exact_nd = f.exact_nd; e->xp.exact_lds = f.exact_lds;
-    e->xp.exact2_nd = f.exact2_nd; e->xp.exact2_lds = f.exact2_lds;
-    e->xp.slices_floats = f.slices_floats;
     e->overlap_min = cfg->overlap_min_pairs < 0 ? 0
                      : (cfg->overlap_min_pairs > 0 ? (cfg->overlap_min_pairs < 2 ? 2 : cfg->overlap_min_pairs) : overlap_min_pairs_default(f));
     const size_t B = (size_t)e->B, hw = (size_t)d.h * d.w;
@@ -831,7 +844,6 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     if (f.has_slices()) {
         // one region per stream lane: two small calls may be in flight at once (alternating lanes, see enqueue)
         alloc((void **)&e->slices, smx_engine::LANES * f.slices_floats * sizeof(float));
-        e->xp.slices = e->slices;
     }
     if (f.filter_ok) {
         alloc((void **)&e->cand, B * (size_t)f.cand_tiles_x * f.cand_tiles_y * f.cand_cw * sizeof(unsigned));

@@ -42,39 +42,33 @@ void launch_metrics(int n, const float *est, const float *gt, const uint8_t *mas
 void launch_points(const float *disp, int H, int W, float bf, float invalid, float *depth, float *points, int *count_dev,
                    int *workspace, hipStream_t s);
 
+// ---- the aggregation family: every launcher is a table from its launch spec (smx_common.h; filled by plan_range,
+// smx_plan.h) to a kernel instantiation and decides nothing itself
 // ---- tu_exact.hip: the exact-order aggregation kernels ----------------------------------------------------
-struct ExactPlan {
-    int exact_nd;            // disparities per right-tile load, generic kernel
-    size_t exact_lds;
-    int exact2_nd;           // ... register-tiled kernel (default radii)
-    size_t exact2_lds;
-    float *slices;           // partial arg-max states of the disparity-split launch
-    size_t slices_floats;
-};
-// 0 = enqueued; 1 = the slice buffer is too small for the split this launch would choose (internal error)
-int launch_exact(const ExactPlan &pl, MatchParams p, int n, bool allow_split, int cus, hipStream_t s);
-void launch_exact2_capture(const ExactPlan &pl, MatchParams p, int n, bool allow_split, int cus, hipStream_t s);
-// stats_dev / stats_host: candidate density of the launch, published to pinned host memory (k_match_exact2.h: SparseStats); may be NULL
-void launch_exact2_sparse(const ExactPlan &pl, MatchParams p, int n, unsigned *cand, int cw, const int *range_flags,
-                          unsigned *stats_dev, unsigned long long *stats_host, unsigned seq, hipStream_t s);
+void launch_exact(const ExactLaunch &x, const MatchParams &p, int n, hipStream_t s);
+void launch_exact2_capture(const ExactCaptureLaunch &x, const MatchParams &p, int n, hipStream_t s);
+// p.nd_chunk: the engine's exact2_nd; stats_dev / stats_host: candidate density of the launch, published to pinned host
+// memory (k_match_exact2.h: SparseStats); may be NULL
+void launch_exact2_sparse(const MatchParams &p, int n, unsigned *cand, int cw, const int *range_flags, unsigned *stats_dev,
+                          unsigned long long *stats_host, unsigned seq, hipStream_t s);
 hipError_t exact_raise_lds_caps(int cap_bytes);
 
 // ---- tu_fast_*.hip: the running-sum (FAST_GRID) aggregation kernels ---------------------------------------
-void launch_match_fast(const MatchParams &p, int n, int cus, hipStream_t s);
-void launch_match_fast_tall_24(const MatchParams &p, int n, hipStream_t s);
-void launch_match_fast_tall_27(const MatchParams &p, int n, hipStream_t s);
-void launch_match_fast_tall_32(const MatchParams &p, int n, hipStream_t s);
-void launch_match_auto_small_tu(const MatchParams &p, int n, int cus, hipStream_t s);
+void launch_match_fast(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
+void launch_match_fast_tall_24(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
+void launch_match_fast_tall_27(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
+void launch_match_fast_tall_32(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
+void launch_match_auto_small_tu(const AutoLaunch &al, const MatchParams &p, int n, hipStream_t s);
 hipError_t match_auto_raise_caps();       // k_match_auto.h: MATCH_AUTO_LDS_CAP
 
 // ---- tu_capture.hip: min_disparity > 0 without the volume -------------------------------------------------
-void launch_match_capture_tu(const MatchParams &p, int n, int cus, hipStream_t s);
+void launch_match_capture_tu(const FastCaptureLaunch &cl, const MatchParams &p, int n, hipStream_t s);
 
 // ---- tu_filter_*.hip: candidate marking of the filtered exact-order route ---------------------------------
-void launch_match_filter_tu(const MatchParams &p, const FilterParams &f, int n, int cus, hipStream_t s);
-void launch_match_filter_24(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s);
-void launch_match_filter_27(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s);
-void launch_match_filter_32(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s);
+void launch_match_filter_tu(const FilterLaunch &fl, const MatchParams &p, const FilterParams &f, int n, hipStream_t s);
+void launch_match_filter_24(const FilterLaunch &fl, const MatchParams &p, const FilterParams &f, int n, hipStream_t s);
+void launch_match_filter_27(const FilterLaunch &fl, const MatchParams &p, const FilterParams &f, int n, hipStream_t s);
+void launch_match_filter_32(const FilterLaunch &fl, const MatchParams &p, const FilterParams &f, int n, hipStream_t s);
 
 // ---- tu_lr.hip: left-right consistency check (k_lr.h) ----------------------------------------------------
 // rows = n * planes * H rows of W elements of elem_bytes (1 or 4) per input; pl / pr: [2n] pairs, the second n mirrored

@@ -3,11 +3,17 @@
 // derive_facts() turns a configuration into everything the plans depend on that is fixed after smx_create; plan_range()
 // turns those facts, the call (entry, stream lanes or caller's stream, the decision of the content switches) and a range
 // of n pairs into a RangePlan: which aggregation kernels run, in which form, followed by which step-6 and fill launch.
-// smx_engine.hip executes the plan (enqueue_range), predicts from it which content switch a call can report to
-// (call_kind) and answers its queries from it; the CPU harnesses under tests/ compile the same lines.
+// Every aggregation launch of the range is named by a launch spec (smx_common.h: ExactLaunch, ExactCaptureLaunch,
+// FastLaunch, FastCaptureLaunch, AutoLaunch, FilterLaunch): the kernel instantiation -- band height as launched, pitch,
+// packed-sum form, form of the fast kernel, disparity split, rows per thread -- with its right-tile chunk, dynamic LDS and
+// slice records.  The launchers behind smx_launch.h are tables from spec to instantiation; nothing below this header
+// decides anything.  smx_engine.hip executes the plan (enqueue_range), predicts from it which content switch a call can
+// report to (call_kind) and answers its queries from it; the CPU harnesses under tests/ compile the same lines, so what a
+// call launches can be read, and swept, without a GPU.
 //
 // Host-only inline functions without a HIP runtime call, like smx_route.h; the kernel headers are included for their
-// constants and plan helpers (match_fast_plan, exact_split, match_auto_small_applicable, ...).
+// constants and for the helpers that hold the tuning (match_fast_plan, exact_split, capture_split, match_auto_nsplit,
+// filter_plan, fast_tall_pitch, match_auto_small_applicable, ...).
 #pragma once
 
 #include "../../include/stereo_mi355x.h"
@@ -87,7 +93,7 @@ inline EngineFacts derive_facts(const smx_config &cfg, const smx_dims &d, int cu
     f.grid_capable = (K == 1 || K == 2 || K == 4 || K == 8);
     f.default_radii = cfg.ncc_patch_radius == 1 && cfg.small_mbm_radius == 1 && cfg.mid_mbm_radius == 4 &&
                       cfg.large_mbm_radius == 10;
-    f.fast_ok = f.grid_capable && f.default_radii && match_fast_supported(d.h, d.w, d.Dd);
+    f.fast_ok = f.grid_capable && f.default_radii;
     f.exact_lds = exact_tile_lds(cfg, d.Dd, &f.exact_nd);
     // register-tiled exact kernel: up to 80 KB of LDS (two workgroups per CU), opt-in above 64 KB
     int nd2 = d.Dd;
@@ -168,7 +174,7 @@ struct RangePlan {
     bool gated_dense_first = false; // FILTERED, f32 RGB: pairs whose gray leaves [0, 255] take the dense kernel, enqueued first
     bool exact_split = false;       // the dense exact-order launch (and its capture launch) may split the disparity range
     bool capture_follows = false;   // dmin > 0: every arg-max launch is followed by its sparse lookup launch
-    FastPlan fast{};                // shape of a fast-kernel launch of these n pairs (also what smx_get_match_geometry reports)
+    FastPlan fast{};                // shape of a sparse fast-kernel launch of these n pairs (what smx_get_match_geometry reports; launched: fast_launch)
     // form of the fast kernel, on the routes that launch it (k_match_fast.h DENSE: the pass that keeps the winner's neighbours
     // instead of fetching them in a sparse second pass; min_disparity = 0 only).  Both shapes that have a dense form follow
     // the same per-call decision: the throughput shape (batches) and the latency shape at 12-row bands (single frames).
@@ -182,6 +188,13 @@ struct RangePlan {
     bool refine_apron = false;      // the gray rows step 6 reads carry cyclic column aprons
     bool refine_reports_grid = false;   // k_refine_auto publishes the grid flag of pair 0 (hints->grid)
     int fill_px = 8;                // pixels per thread of the fill launch
+    // The aggregation launches of the route, as the launchers get them (value-initialised where the route has no such launch):
+    ExactLaunch exact{};            // FILTERED (the gated dense launch), EXACT, AUTO_GATED
+    ExactCaptureLaunch exact_capture{};   // ... followed by this when capture_follows
+    FastLaunch fast_launch{};       // FAST, AUTO_GATED
+    FastCaptureLaunch fast_capture{};     // ... followed by this when capture_follows
+    AutoLaunch auto_launch{};       // AUTO_ONE_LAUNCH
+    FilterLaunch filter{};          // FILTERED
 
     bool has_fast_launch() const { return route == AGG_FAST || route == AGG_AUTO_ONE_LAUNCH || route == AGG_AUTO_GATED; }
 };
@@ -198,6 +211,94 @@ inline MatchParams plan_params(const EngineFacts &f, bool on_lanes) {
 }
 // Shape of a fast-kernel launch of n pairs; `small` is also the engine's notion of "few pairs in flight".
 inline FastPlan range_fast_plan(const EngineFacts &f, bool on_lanes, int n) { return match_fast_plan(plan_params(f, on_lanes), n, f.cus); }
+
+// ---- the launch specs ------------------------------------------------------------------------------------------------------
+// The dense exact-order launch of n pairs.  Default radii without the volume: the register-tiled kernel, for few pairs
+// (allow_split) in slices of the disparity range that run as separate workgroups and are merged by a launch of their own.
+inline ExactLaunch exact_launch(const EngineFacts &f, bool on_lanes, int n, bool allow_split) {
+    ExactLaunch x;
+    if (!f.default_radii || f.has_volume) {
+        x.kernel = f.has_volume ? EXACT_GENERIC_VOLUME : EXACT_GENERIC;
+        x.nd_chunk = f.exact_nd;
+        x.lds_bytes = f.exact_lds;
+        return x;
+    }
+    x.kernel = EXACT_TILED;
+    x.nd_chunk = f.exact2_nd;
+    x.lds_bytes = f.exact2_lds;
+    x.split = allow_split ? exact_split(f.e2_tiles, n, f.Dd, f.cus) : 1;
+    if (x.split > 1) {
+        x.slice_floats = (size_t)x.split * SMX_SLICE_WORDS * n * f.h * f.w;
+        const int per = (f.Dd + x.split - 1) / x.split;
+        if (x.nd_chunk > per) x.nd_chunk = per;          // right tile: never wider than one slice needs
+        // 8-wave workgroups (2 rows per thread) unless the launch fills the chip about once AND shares it with the other
+        // stream lane's launches (k_match_exact2.h: E2K)
+        const long wgs = (long)f.e2_tiles * n * x.split, slots = 2L * f.cus;
+        x.rows_per_thread = on_lanes && 2 * wgs > slots && wgs < 2 * slots ? 4 : 2;
+    }
+    return x;
+}
+
+// ... and the lookups of step 6 behind it on the capture route: few pairs share a tile's needed indices between workgroups
+// (capture_split), which mostly stage their tiles -- 8 waves do that twice as fast (74 -> 58 us at 1080p)
+inline ExactCaptureLaunch exact_capture_launch(const EngineFacts &f, int n, bool allow_split) {
+    ExactCaptureLaunch x;
+    x.split = allow_split ? capture_split(f.e2_tiles, n, f.Dd, f.cus) : 1;
+    x.rows_per_thread = allow_split ? 2 : 4;
+    x.nd_chunk = f.exact2_nd;
+    x.lds_bytes = exact2_capture_lds_bytes(f.exact2_nd);
+    return x;
+}
+
+// The fast-kernel launch of a range whose sparse-form shape is pl, in the form the plan asks for (dense: the throughput
+// shape, dense_small: the latency shape at 12-row bands).  The dense forms are instantiated for up to 256 disparities at up
+// to FA_DENSE_MAX_TH rows (a call that asks for one does not take 32-row bands) and, in the latency shape, for the ranges
+// one right-tile chunk holds (257 at pitch 320); a call planned dense beyond that launches the SPARSE instantiation --
+// with MatchParams::dense / dense_small still set and without report words (NOTES.md: "Launch specs").
+inline FastLaunch fast_launch(const EngineFacts &f, const FastPlan &pl, bool dense, bool dense_small) {
+    FastLaunch x;
+    x.small = pl.small;
+    x.th = pl.th;
+    x.pk = fast_pk(f.K * f.K);
+    bool dense_here;
+    if (pl.small) {
+        x.pitch = pl.wide ? 320 : 256;
+        dense_here = dense_small && pl.th == FA_TH_SMALL_TALL && f.Dd <= x.pitch - 64 + 1;
+    } else {
+        x.pitch = fast_tall_pitch(f.Dd);
+        x.argb = x.pitch != 320 || f.Dd <= 256;
+        if (pl.th == 32 && dense && !f.capture && f.Dd <= 256) x.th = FA_DENSE_MAX_TH;
+        dense_here = dense && x.argb && x.th <= FA_DENSE_MAX_TH;
+    }
+    x.form = f.capture ? FAST_PASS1_ONLY : (!dense_here ? FAST_SPARSE : (pl.small ? FAST_DENSE_SMALL : FAST_DENSE));
+    return x;
+}
+
+inline FastCaptureLaunch fast_capture_launch(const EngineFacts &f, const FastPlan &pl) {
+    return FastCaptureLaunch{pl.small, f.Dd > FA_WIDE_FROM, fast_pk(f.K * f.K)};
+}
+
+// The one-launch AUTO kernel at band height th: the grid and tile of the latency-shape fast kernel; its off-grid branch
+// splits the range into nsplit slices, with a right-tile chunk no wider than a slice, and needs the larger of the two tiles.
+inline AutoLaunch auto_launch(const EngineFacts &f, const MatchParams &mp, int th) {
+    AutoLaunch x;
+    x.th = th;
+    x.wide = fast_small_wide(f.Dd);
+    x.pk = fast_pk(f.K * f.K);
+    x.nsplit = match_auto_nsplit(mp, th);
+    x.nd_chunk = f.exact2_nd;
+    const int per = (f.Dd + x.nsplit - 1) / x.nsplit;
+    if (x.nd_chunk > per) x.nd_chunk = per;
+    x.lds_bytes = x.wide ? fast_lds_bytes<320>(th, f.Dd, true) : fast_lds_bytes<256>(th, f.Dd, true);
+    const size_t exact_lds = exact2_lds_floats(x.nd_chunk) * sizeof(float);
+    if (exact_lds > x.lds_bytes) x.lds_bytes = exact_lds;
+    return x;
+}
+
+inline FilterLaunch filter_launch(const EngineFacts &f, const MatchParams &mp, int n) {
+    const FilterPlan pl = filter_plan(mp, n, f.cus);
+    return FilterLaunch{pl.th, pl.wide, fast_pk(f.filter_unit)};
+}
 
 inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, bool whole_call) {
     RangePlan p;
@@ -243,6 +344,7 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
         // reference's order.  Pairs whose gray leaves [0, 255] (f32 RGB only; flag from the prologue) take the dense kernel.
         p.route = AGG_FILTERED;
         p.gated_dense_first = call.in_mode == IN_RGB_F32;
+        p.filter = filter_launch(f, mp, n);
     } else if (p.mode == SMX_MATCH_EXACT_ORDER) {
         p.route = AGG_EXACT;
         // (the disparity split is for calls of a few pairs; its slice buffer is not divided between halves)
@@ -258,6 +360,7 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
                                 f.has_slices() && match_auto_small_applicable(mp, p.fast.th, n, f.slices_floats);
         if (one_launch) {
             p.route = AGG_AUTO_ONE_LAUNCH;
+            p.auto_launch = auto_launch(f, mp, p.fast.th);
         } else {
             p.route = AGG_AUTO_GATED;
             // the disparity split (and its merge launch) only for few pairs that are known to be off the grid; for the
@@ -282,6 +385,15 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
             if (dense) (tall12 ? p.dense_small : p.dense) = true;
             else p.fill_publishes = p.reports;
         }
+    }
+
+    if (p.route == AGG_FILTERED || p.route == AGG_EXACT || p.route == AGG_AUTO_GATED) {
+        p.exact = exact_launch(f, call.on_lanes, n, p.exact_split);
+        if (p.capture_follows) p.exact_capture = exact_capture_launch(f, n, p.exact_split);
+    }
+    if (p.route == AGG_FAST || p.route == AGG_AUTO_GATED) {
+        p.fast_launch = fast_launch(f, p.fast, p.dense, p.dense_small);
+        if (p.capture_follows) p.fast_capture = fast_capture_launch(f, p.fast);
     }
 
     // step 6: integer-valued gray -> v_sad_u8 kernel; otherwise the float kernel (same results)
@@ -322,7 +434,8 @@ inline CallKind call_kind(const EngineFacts &f, int in_mode, bool on_lanes, int 
     return k;
 }
 
-// What smx_get_match_geometry reports for a fast-kernel launch of n pairs.
+// What smx_get_match_geometry reports for a fast-kernel launch of n pairs: the plan of the sparse form (FastPlan), not the
+// instantiation a dense call launches (RangePlan::fast_launch).
 inline void match_geometry(const EngineFacts &f, bool on_lanes, int n, smx_match_geometry *g) {
     if (!f.fast_ok) {
         g->kernel = SMX_KERNEL_EXACT_ONLY;

@@ -4,5 +4,5 @@
 #include "smx_launch.h"
 
 namespace smx {
-void launch_match_capture_tu(const MatchParams &p, int n, int cus, hipStream_t s) { launch_match_capture(p, n, cus, s); }
+void launch_match_capture_tu(const FastCaptureLaunch &cl, const MatchParams &p, int n, hipStream_t s) { launch_match_capture(cl, p, n, s); }
 }  // namespace smx

@@ -8,7 +8,7 @@
 #define SMX_TU_CAT(a, b) SMX_TU_CAT2(a, b)
 
 namespace smx {
-void SMX_TU_CAT(launch_match_fast_tall_, SMX_TU_TH)(const MatchParams &p, int n, hipStream_t s) {
-    launch_match_fast_tall<SMX_TU_TH>(p, n, s);
+void SMX_TU_CAT(launch_match_fast_tall_, SMX_TU_TH)(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s) {
+    launch_match_fast_tall<SMX_TU_TH>(fl, p, n, s);
 }
 }  // namespace smx

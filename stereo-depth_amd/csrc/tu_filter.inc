@@ -6,8 +6,8 @@
 #define SMX_TU_CAT(a, b) SMX_TU_CAT2(a, b)
 
 namespace smx {
-void SMX_TU_CAT(launch_match_filter_, SMX_TU_TH)(const MatchParams &p, const FilterParams &f, int n, bool wide, hipStream_t s) {
-    if (!wide) launch_match_filter_t<SMX_TU_TH, 256>(p, f, n, s);
-    else launch_match_filter_t<SMX_TU_TH, 320>(p, f, n, s);
+void SMX_TU_CAT(launch_match_filter_, SMX_TU_TH)(const FilterLaunch &fl, const MatchParams &p, const FilterParams &f, int n, hipStream_t s) {
+    if (!fl.wide) launch_match_filter_t<SMX_TU_TH, 256>(fl.pk, p, f, n, s);
+    else launch_match_filter_t<SMX_TU_TH, 320>(fl.pk, p, f, n, s);
 }
 }  // namespace smx

@@ -76,7 +76,7 @@ int main() {
                                 const FastPlan &pl = plan.fast;
                                 if (plan.route == AGG_AUTO_ONE_LAUNCH) {
                                     ++accepted;
-                                    // launch_match_auto_small_t: nsplit slices, records at [sp][word][n][h][w]
+                                    // auto_launch (smx_plan.h): nsplit slices, records at [sp][word][n][h][w]
                                     const int ns = match_auto_nsplit(p, pl.th);
                                     const size_t need = (size_t)ns * SMX_SLICE_WORDS * n * hw;
                                     if (need > region) {
@@ -85,7 +85,7 @@ int main() {
                                                    pl.th, need, region);
                                     }
                                 }
-                                // launch_exact with the split allowed: records at [sp][word][n][h][w]
+                                // exact_launch (smx_plan.h) with the split allowed: records at [sp][word][n][h][w]
                                 const int sp = exact_split(tiles, n, Dd, cus);
                                 if (sp > 1 && on_lanes == 0) {
                                     ++split;

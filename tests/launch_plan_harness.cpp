@@ -7,13 +7,30 @@
 //   2. Plan invariants, over the sweep (configurations x match modes x entries x lanes x pairs x halves x decisions x
 //      forced options x CU counts).
 //   3. The directed table: the plans of today's rules for the cases a reader would ask about first.
+//   4. The launch specs.  Every aggregation launch a plan names (ExactLaunch, ExactCaptureLaunch, FastLaunch,
+//      FastCaptureLaunch, AutoLaunch, FilterLaunch) against the launcher glue as it was while the launchers still decided
+//      for themselves, restated here by hand (old_*), field by field over the whole sweep; and the specs' own invariants:
+//      a split fits the lane's slice region and belongs to a whole call of at most 4 pairs, a dense form is planned only
+//      where its instantiation exists, the dynamic LDS stays within what the engine raises the kernel to.  A call planned
+//      dense that launches the sparse instantiation (no dense one exists for it) is counted: "dense-fallback".
 //
 // Output: a line per violation ("violation <what>: <inputs>", the first 60), then
 //   "launch-plan plans <n> kinds <n> directed <n> routes <FILTERED> <EXACT> <FAST> <AUTO_ONE_LAUNCH> <AUTO_GATED> refused <n>
-//    refine <FLOAT> <INT> <INT_V> <AUTO> <AUTO_V> hash <fnv-1a of every (inputs -> plan) of the sweep> violations <n>".
+//    refine <FLOAT> <INT> <INT_V> <AUTO> <AUTO_V> hash <fnv-1a of every (inputs -> plan) of the sweep> violations <n>
+//    specs <launch specs compared> exact <GENERIC> <GENERIC_VOLUME> <TILED> split <exact launches split> form <SPARSE>
+//    <PASS1_ONLY> <DENSE> <DENSE_SMALL> dense-fallback <n>".
+//
+// Other uses (tests/test_launch_spec_gpu.py), on the CU count given:
+//   launch_plan_harness spec <cus> <radii> <K> <h> <w> <Dd> <dmin> <B> <mode> <opt dense> <opt dense small> <in_mode> <lanes>
+//                       <dense> <filter> <hint> <n> <whole>     one line "keys ..." : the spec keys of that plan
+//   launch_plan_harness reach <cus>                              "reach-small ..." / "reach-large-only ...": the keys the
+//                       sweep's configurations reach at its two smallest shapes, and those only its larger shapes reach
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <set>
+#include <string>
 
 #include "smx_plan.h"
 
@@ -58,6 +75,146 @@ static const char *describe(const Config &c, const CallFacts &call, int n, bool 
     return buf;
 }
 
+// ---- the launcher glue of the parent, restated ---------------------------------------------------------------------------
+// Written by hand from tu_exact.hip, tu_fast_small.hip and the launcher tails of k_match_fast.h, k_match_auto.h,
+// k_match_capture.h and k_match_filter.h as they were when each launcher took (params, n, cus) and chose its instantiation
+// itself; not built by calling the spec functions of smx_plan.h.  `p` is the MatchParams enqueue_range handed them.
+static MatchParams engine_params(const Config &c, const EngineFacts &f, const RangePlan &pl, bool on_lanes) {
+    MatchParams p{};
+    p.B = f.B; p.h = f.h; p.w = f.w; p.dmin = f.dmin; p.Dd = f.Dd;
+    p.rn = 1; p.rs = c.default_radii ? 1 : 2; p.rm = c.default_radii ? 4 : 3; p.rl = c.default_radii ? 10 : 8;
+    p.unit = (float)(c.K * c.K);
+    p.on_lanes = on_lanes ? 1 : 0;
+    p.pass1_only = pl.capture_follows ? 1 : 0;
+    return p;
+}
+struct OldExact { int kernel, split, rows, nd_chunk; size_t lds, need; };
+static OldExact old_launch_exact(const EngineFacts &f, MatchParams p, bool vol, int n, bool allow_split, int cus) {
+    if (!vol && p.rn == 1 && p.rs == 1 && p.rm == 4 && p.rl == 10) {
+        const int gx = (p.w + E2_TW - 1) / E2_TW, gy = (p.h + E2_TH - 1) / E2_TH;
+        p.nd_chunk = f.exact2_nd;
+        const int sp = allow_split ? exact_split(gx * gy, n, p.Dd, cus) : 1;
+        if (sp > 1) {
+            const size_t need = (size_t)sp * SMX_SLICE_WORDS * n * p.h * p.w;
+            const int gz = n * sp;
+            const int per = (p.Dd + sp - 1) / sp;
+            if (p.nd_chunk > per) p.nd_chunk = per;
+            const long wgs = (long)gx * gy * gz, slots = 2L * cus;
+            const int rows = (p.on_lanes && 2 * wgs > slots && wgs < 2 * slots) ? 4 : 2;
+            return OldExact{EXACT_TILED, sp, rows, p.nd_chunk, f.exact2_lds, need};
+        }
+        return OldExact{EXACT_TILED, 1, 4, p.nd_chunk, f.exact2_lds, 0};
+    }
+    return OldExact{vol ? EXACT_GENERIC_VOLUME : EXACT_GENERIC, 1, 4, f.exact_nd, f.exact_lds, 0};
+}
+// (capture_split was a static function of tu_exact.hip: its body is the one now in k_match_exact2.h, restated too)
+static int old_capture_split(int tiles, int n, int Dd, int cus) {
+    if (n > 4 || Dd < 16) return 1;
+    const long slots = 2L * cus, wgs = (long)tiles * n, need = (Dd + 3) / 4;
+    int best = 1;
+    long best_cost = ((wgs + slots - 1) / slots) * (2 + need);
+    for (int sp = 2; sp <= 8; ++sp) {
+        const long cost = ((wgs * sp + slots - 1) / slots) * (2 + (need + sp - 1) / sp);
+        if (cost < best_cost) { best_cost = cost; best = sp; }
+    }
+    return best;
+}
+static ExactCaptureLaunch old_launch_exact2_capture(const EngineFacts &f, const MatchParams &cp, int n, bool allow_split, int cus) {
+    const int gx = (cp.w + E2_TW - 1) / E2_TW, gy = (cp.h + E2_TH - 1) / E2_TH;
+    ExactCaptureLaunch x;
+    x.nd_chunk = f.exact2_nd;
+    x.split = allow_split ? old_capture_split(gx * gy, n, cp.Dd, cus) : 1;
+    x.rows_per_thread = allow_split ? 2 : 4;
+    x.lds_bytes = f.exact2_lds + E2_CAPBITS * sizeof(unsigned);
+    return x;
+}
+static FastLaunch old_launch_match_fast(const MatchParams &p, int n, int cus) {
+    const FastPlan pl = match_fast_plan(p, n, cus);
+    FastLaunch x;
+    bool dsplit;
+    if (pl.small) {                                              // launch_match_fast_t<TH, 256 / 320, true>
+        x.th = pl.th == FA_TH_SMALL_TALL ? FA_TH_SMALL_TALL : (pl.th == FA_TH_SMALL_MID ? FA_TH_SMALL_MID : FA_TH_SMALL);
+        x.pitch = !pl.wide ? 256 : 320;
+        dsplit = true;
+        x.argb = false;                                          // launch_match_fast_a<TH, PR, true, false>
+    } else {
+        if (pl.th == 27 || (pl.th == 32 && p.dense && !p.pass1_only && p.Dd <= 256)) x.th = 27;
+        else if (pl.th == 32) x.th = 32;
+        else x.th = 24;
+        x.pitch = fast_tall_pitch(p.Dd);                         // launch_match_fast_tall<TH>
+        dsplit = false;
+        x.argb = (x.pitch == 256 || x.pitch == FA_MID_PITCH) ? true : p.Dd <= 256;
+    }
+    x.small = dsplit;
+    x.pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);       // launch_match_fast_a
+    if (dsplit && x.th == FA_TH_SMALL_TALL && p.dense_small && !p.pass1_only && p.Dd <= x.pitch - 64 + 1) x.form = FAST_DENSE_SMALL;
+    else if (!dsplit && x.argb && x.th <= FA_DENSE_MAX_TH && p.dense && !p.pass1_only) x.form = FAST_DENSE;
+    else if (p.pass1_only) x.form = FAST_PASS1_ONLY;
+    else x.form = FAST_SPARSE;
+    return x;
+}
+static FastCaptureLaunch old_launch_match_capture(const MatchParams &p, int n, int cus) {
+    FastCaptureLaunch x;
+    x.wide = p.Dd > FA_WIDE_FROM;
+    x.small = match_fast_plan(p, n, cus).small;
+    x.pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
+    return x;
+}
+static AutoLaunch old_launch_match_auto_small(const EngineFacts &f, MatchParams p, int n, int cus) {
+    AutoLaunch x;
+    x.th = match_fast_plan(p, n, cus).th;                        // launch_match_auto_small_tu
+    p.nd_chunk = f.exact2_nd;                                    // (enqueue_range)
+    x.wide = p.Dd > 256 - 64 + 1;
+    size_t lds = x.wide ? fast_lds_bytes<320>(x.th, p.Dd, true) : fast_lds_bytes<256>(x.th, p.Dd, true);
+    p.nsplit = match_auto_nsplit(p, x.th);
+    const int per = (p.Dd + p.nsplit - 1) / p.nsplit;
+    if (p.nd_chunk > per) p.nd_chunk = per;
+    const size_t exact_lds = exact2_lds_floats(p.nd_chunk) * sizeof(float);
+    if (exact_lds > lds) lds = exact_lds;
+    x.nsplit = p.nsplit; x.nd_chunk = p.nd_chunk; x.lds_bytes = lds;
+    x.pk = p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0);
+    return x;
+}
+static FilterLaunch old_launch_match_filter(const EngineFacts &f, MatchParams p, int n, int cus) {
+    p.unit = (float)f.filter_unit;                               // (enqueue_range: fmp)
+    const FilterPlan pl = filter_plan(p, n, cus);
+    return FilterLaunch{pl.th, pl.wide, p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0)};
+}
+
+static const char *const EXACT_NAMES[] = {"GENERIC", "GENERIC_VOLUME", "TILED"};
+static const char *const FORM_NAMES[] = {"SPARSE", "PASS1_ONLY", "DENSE", "DENSE_SMALL"};
+static bool has_exact(const RangePlan &p) { return (p.route == AGG_FILTERED && p.gated_dense_first) || p.route == AGG_EXACT || p.route == AGG_AUTO_GATED; }
+static bool has_exact_capture(const RangePlan &p) { return p.capture_follows && (p.route == AGG_FILTERED || p.route == AGG_EXACT || p.route == AGG_AUTO_GATED); }
+static bool has_fast(const RangePlan &p) { return p.route == AGG_FAST || p.route == AGG_AUTO_GATED; }
+
+// The spec keys of a plan: one "<spec>.<field>=<value>" per field that selects an instantiation, of the launches it enqueues.
+static void keys_of(const RangePlan &p, std::set<std::string> &keys) {
+    char b[64];
+    auto key = [&](const char *fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(b, sizeof(b), fmt, ap);
+        va_end(ap);
+        keys.insert(b);
+    };
+    if (has_exact(p)) {
+        key("exact.kernel=%s", EXACT_NAMES[p.exact.kernel]);
+        if (p.exact.kernel == EXACT_TILED) key(p.exact.split > 1 ? "exact.split=yes.rows=%d" : "exact.split=no", p.exact.rows_per_thread);
+    }
+    if (has_exact_capture(p)) key("exact_capture.rows=%d", p.exact_capture.rows_per_thread);
+    if (has_fast(p)) {
+        key("fast.form=%s", FORM_NAMES[p.fast_launch.form]);
+        key("fast.small=%d.th=%d", p.fast_launch.small ? 1 : 0, p.fast_launch.th);
+        key("fast.small=%d.pitch=%d", p.fast_launch.small ? 1 : 0, p.fast_launch.pitch);
+        key("fast.pk=%d", p.fast_launch.pk);
+        if (!p.fast_launch.small) key("fast.argb=%d", p.fast_launch.argb ? 1 : 0);
+        if (p.capture_follows) key("fast_capture.small=%d.wide=%d", p.fast_capture.small ? 1 : 0, p.fast_capture.wide ? 1 : 0);
+    }
+    if (p.route == AGG_AUTO_ONE_LAUNCH) key("auto.th=%d.wide=%d", p.auto_launch.th, p.auto_launch.wide ? 1 : 0);
+    if (p.route == AGG_FILTERED) key("filter.th=%d.wide=%d", p.filter.th, p.filter.wide ? 1 : 0);
+}
+static std::set<std::string> *reach_keys = nullptr;                 // `reach`: collect instead of checking
+
 // ---- the sweep -----------------------------------------------------------------------------------------------------------
 static unsigned long long plan_hash = 1469598103934665603ull;
 static void mix(long long v) {
@@ -67,9 +224,102 @@ static void mix(long long v) {
     }
 }
 static long plans = 0, kinds = 0, refused = 0, routes[AGG_ROUTES] = {}, refines[5] = {};
+static long specs = 0, exact_kernels[3] = {}, exact_splits = 0, forms[FAST_FORMS] = {}, dense_fallbacks = 0;
+
+// item 4 of the head comment
+static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &call, const RangePlan &p, int n, bool whole) {
+#define SPEC_EQ(what, a, b) do { if ((long long)(a) != (long long)(b)) violation("spec %s: %lld, the parent's launcher %lld: %s", what, (long long)(a), (long long)(b), describe(c, call, n, whole)); } while (0)
+    MatchParams mp = engine_params(c, f, p, call.on_lanes);
+    const size_t tiled_cap = (size_t)SMX_EXACT2_LDS_CAP + (E2_CAPBITS + 2 * E2_SPARSE_WORDS) * sizeof(unsigned);    // smx_engine.hip: raise_lds_caps
+    if (has_exact(p)) {
+        // (the gated dense launch of the filtered route never splits; the others as the plan allows)
+        const OldExact o = old_launch_exact(f, mp, f.has_volume, n, p.route == AGG_FILTERED ? false : p.exact_split, f.cus);
+        ++specs;
+        exact_kernels[p.exact.kernel]++;
+        if (p.exact.split > 1) ++exact_splits;
+        SPEC_EQ("exact.kernel", p.exact.kernel, o.kernel);
+        SPEC_EQ("exact.split", p.exact.split, o.split);
+        SPEC_EQ("exact.rows_per_thread", p.exact.rows_per_thread, o.rows);
+        SPEC_EQ("exact.nd_chunk", p.exact.nd_chunk, o.nd_chunk);
+        SPEC_EQ("exact.lds_bytes", p.exact.lds_bytes, o.lds);
+        SPEC_EQ("exact.slice_floats", p.exact.slice_floats, o.need);
+        if (p.exact.split < 1 || p.exact.split > 8 || (p.exact.rows_per_thread != 2 && p.exact.rows_per_thread != 4) || p.exact.nd_chunk < 1)
+            violation("exact spec out of range: %s", describe(c, call, n, whole));
+        if (p.exact.split > 1 && p.exact.slice_floats > f.slices_floats) violation("split does not fit the lane's slice region: %s", describe(c, call, n, whole));
+        if ((p.exact.split > 1) != (p.exact.slice_floats != 0)) violation("slice floats without a split: %s", describe(c, call, n, whole));
+        if (p.exact.split > 1 && (!whole || n > 4)) violation("split outside whole calls of at most 4 pairs: %s", describe(c, call, n, whole));
+        if (p.exact.lds_bytes > (p.exact.kernel == EXACT_TILED ? tiled_cap : (size_t)64 * 1024)) violation("exact LDS beyond the cap: %s", describe(c, call, n, whole));
+    }
+    if (has_exact_capture(p)) {
+        const ExactCaptureLaunch o = old_launch_exact2_capture(f, mp, n, p.route == AGG_FILTERED ? false : p.exact_split, f.cus);
+        ++specs;
+        SPEC_EQ("exact_capture.split", p.exact_capture.split, o.split);
+        SPEC_EQ("exact_capture.rows_per_thread", p.exact_capture.rows_per_thread, o.rows_per_thread);
+        SPEC_EQ("exact_capture.nd_chunk", p.exact_capture.nd_chunk, o.nd_chunk);
+        SPEC_EQ("exact_capture.lds_bytes", p.exact_capture.lds_bytes, o.lds_bytes);
+        if (p.exact_capture.split > 1 && (!whole || n > 4)) violation("capture split outside whole calls of at most 4 pairs: %s", describe(c, call, n, whole));
+        if (p.exact_capture.split < 1 || p.exact_capture.split > 8 || p.exact_capture.lds_bytes > tiled_cap) violation("exact capture spec: %s", describe(c, call, n, whole));
+    }
+    if (has_fast(p)) {
+        mp.dense = p.dense ? 1 : 0;                               // (enqueue_range: fast())
+        mp.dense_small = p.dense_small ? 1 : 0;
+        const FastLaunch o = old_launch_match_fast(mp, n, f.cus), &x = p.fast_launch;
+        ++specs;
+        forms[x.form]++;
+        SPEC_EQ("fast.th", x.th, o.th);
+        SPEC_EQ("fast.small", x.small, o.small);
+        SPEC_EQ("fast.pitch", x.pitch, o.pitch);
+        SPEC_EQ("fast.pk", x.pk, o.pk);
+        SPEC_EQ("fast.argb", x.argb, o.argb);
+        SPEC_EQ("fast.form", x.form, o.form);
+        // the instantiations that exist (k_match_fast.h: launch_match_fast_a / _t, the three tall translation units)
+        const bool shape_ok = x.small ? ((x.th == 8 || x.th == 10 || x.th == 12) && (x.pitch == 256 || x.pitch == 320) && !x.argb)
+                                      : ((x.th == 24 || x.th == 27 || x.th == 32) && (x.pitch == 256 || x.pitch == FA_MID_PITCH || x.pitch == 320) &&
+                                         (x.argb || x.pitch == 320));
+        if (!shape_ok || x.pk < 0 || x.pk > 2) violation("fast spec names no instantiation: %s", describe(c, call, n, whole));
+        if (x.form == FAST_DENSE && (x.small || !x.argb || x.th > FA_DENSE_MAX_TH || f.Dd > 256)) violation("DENSE without an instantiation: %s", describe(c, call, n, whole));
+        if (x.form == FAST_DENSE_SMALL && (!x.small || x.th != FA_TH_SMALL_TALL || f.Dd > x.pitch - 64 + 1)) violation("DENSE_SMALL without an instantiation: %s", describe(c, call, n, whole));
+        if ((x.form == FAST_PASS1_ONLY) != f.capture) violation("PASS1_ONLY: %s", describe(c, call, n, whole));
+        if ((x.form == FAST_DENSE && !p.dense) || (x.form == FAST_DENSE_SMALL && !p.dense_small)) violation("dense form not planned: %s", describe(c, call, n, whole));
+        if ((p.dense || p.dense_small) && x.form == FAST_SPARSE) ++dense_fallbacks;
+        if (p.capture_follows) {
+            const FastCaptureLaunch oc = old_launch_match_capture(mp, n, f.cus);
+            ++specs;
+            SPEC_EQ("fast_capture.small", p.fast_capture.small, oc.small);
+            SPEC_EQ("fast_capture.wide", p.fast_capture.wide, oc.wide);
+            SPEC_EQ("fast_capture.pk", p.fast_capture.pk, oc.pk);
+        }
+    }
+    if (p.route == AGG_AUTO_ONE_LAUNCH) {
+        const AutoLaunch o = old_launch_match_auto_small(f, mp, n, f.cus), &x = p.auto_launch;
+        ++specs;
+        SPEC_EQ("auto.th", x.th, o.th);
+        SPEC_EQ("auto.wide", x.wide, o.wide);
+        SPEC_EQ("auto.pk", x.pk, o.pk);
+        SPEC_EQ("auto.nsplit", x.nsplit, o.nsplit);
+        SPEC_EQ("auto.nd_chunk", x.nd_chunk, o.nd_chunk);
+        SPEC_EQ("auto.lds_bytes", x.lds_bytes, o.lds_bytes);
+        if (x.lds_bytes > (size_t)MATCH_AUTO_LDS_CAP) violation("one-launch LDS beyond the cap: %s", describe(c, call, n, whole));
+        if ((size_t)x.nsplit * n * SMX_SLICE_WORDS * f.h * f.w > f.slices_floats) violation("one-launch records do not fit the lane's slice region: %s", describe(c, call, n, whole));
+        if (x.th != 8 && x.th != 10 && x.th != 12) violation("one-launch band height: %s", describe(c, call, n, whole));
+    }
+    if (p.route == AGG_FILTERED) {
+        const FilterLaunch o = old_launch_match_filter(f, mp, n, f.cus);
+        ++specs;
+        SPEC_EQ("filter.th", p.filter.th, o.th);
+        SPEC_EQ("filter.wide", p.filter.wide, o.wide);
+        SPEC_EQ("filter.pk", p.filter.pk, o.pk);
+        if (p.filter.th != 24 && p.filter.th != 27 && p.filter.th != 32) violation("filter band height: %s", describe(c, call, n, whole));
+    }
+#undef SPEC_EQ
+}
 
 static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &call, int n, bool whole) {
     const RangePlan p = plan_range(f, call, n, whole);
+    if (reach_keys) {
+        if (p.status == SMX_OK) keys_of(p, *reach_keys);
+        return;
+    }
     ++plans;
     const bool refuse = c.match_mode == SMX_MATCH_FAST_GRID && (!f.fast_ok || f.has_volume);
     if ((p.status != SMX_OK) != refuse || (p.status != SMX_OK && (p.status != SMX_ERR_UNSUPPORTED || !p.refusal)))
@@ -89,6 +339,19 @@ static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &c
                        (unsigned)p.kt, (unsigned)p.refine_apron, (unsigned)p.refine_reports_grid, (unsigned)p.fill_px})
         word = word * 67 + v;
     mix((long long)word);
+    // ... and every field of the launch specs (value-initialised where the route has no such launch)
+    unsigned long long sw = 0;
+    for (long long v : {(long long)p.exact.kernel, (long long)p.exact.split, (long long)p.exact.rows_per_thread, (long long)p.exact.nd_chunk,
+                        (long long)p.exact.lds_bytes, (long long)p.exact.slice_floats, (long long)p.exact_capture.split,
+                        (long long)p.exact_capture.rows_per_thread, (long long)p.exact_capture.nd_chunk, (long long)p.exact_capture.lds_bytes,
+                        (long long)p.fast_launch.th, (long long)p.fast_launch.small, (long long)p.fast_launch.pitch, (long long)p.fast_launch.pk,
+                        (long long)p.fast_launch.argb, (long long)p.fast_launch.form, (long long)p.fast_capture.small, (long long)p.fast_capture.wide,
+                        (long long)p.fast_capture.pk, (long long)p.auto_launch.th, (long long)p.auto_launch.wide, (long long)p.auto_launch.pk,
+                        (long long)p.auto_launch.nsplit, (long long)p.auto_launch.nd_chunk, (long long)p.auto_launch.lds_bytes,
+                        (long long)p.filter.th, (long long)p.filter.wide, (long long)p.filter.pk})
+        sw = sw * 1000003ull + (unsigned long long)v;
+    mix((long long)sw);
+    check_specs(c, f, call, p, n, whole);
     const bool rgb = call.in_mode == IN_RGB_F32 || call.in_mode == IN_RGB_U8;
     if (p.route == AGG_AUTO_ONE_LAUNCH) {
         MatchParams mp{};
@@ -147,13 +410,13 @@ static void check_kind(const Config &c, const EngineFacts &f, int in_mode, bool 
 
 static void sweep_facts(const Config &c) {
     const EngineFacts f = facts_of(c);
-    if (f.capture != (c.default_radii && c.dmin > 0 && c.dmin <= c.Dd) || f.has_volume != (c.dmin > 0 && !f.capture) || (f.filter_ok && f.has_volume))
+    if (!reach_keys && (f.capture != (c.default_radii && c.dmin > 0 && c.dmin <= c.Dd) || f.has_volume != (c.dmin > 0 && !f.capture) || (f.filter_ok && f.has_volume)))
         violation("facts: %s", describe(c, CallFacts{}, 0, false));
     for (int in_mode : {IN_GRAY_F32, IN_RGB_F32, IN_GRAY_U8, IN_RGB_U8})
         for (int on_lanes = 0; on_lanes < 2; ++on_lanes)
             for (int n = 1; n <= c.B; ++n) {
-                check_kind(c, f, in_mode, on_lanes != 0, n, 0);
-                if (on_lanes && n >= 2) check_kind(c, f, in_mode, true, (n + 1) / 2, n - (n + 1) / 2);
+                if (!reach_keys) check_kind(c, f, in_mode, on_lanes != 0, n, 0);
+                if (!reach_keys && on_lanes && n >= 2) check_kind(c, f, in_mode, true, (n + 1) / 2, n - (n + 1) / 2);
                 CallFacts call;
                 call.in_mode = in_mode;
                 call.on_lanes = on_lanes != 0;
@@ -161,6 +424,8 @@ static void sweep_facts(const Config &c) {
                     for (int dense = 0; dense < 2; ++dense)
                         for (int filt = 0; filt < 2; ++filt)
                             for (int hint = -1; hint <= 1; ++hint) {
+                                // (`reach`: only k_refine_auto reports the grid flag; an engine without the u8 planes never holds a hint)
+                                if (reach_keys && hint != -1 && (f.kt == 0 || !f.has_u8_planes())) continue;
                                 call.route.fast_dense = dense != 0;
                                 call.route.use_filter = filt != 0;
                                 call.route.grid_hint = hint;
@@ -169,7 +434,8 @@ static void sweep_facts(const Config &c) {
             }
 }
 
-static void sweep() {
+// only_cus > 0 (`reach`): the same configurations on that CU count alone, at the two smallest shapes (large: the other two)
+static void sweep(int only_cus = 0, bool large = false) {
     const int shapes[4][2] = {{48, 80}, {64, 128}, {187, 621}, {540, 960}};
     const int forced[9][2] = {{-1, -1}, {0, -1}, {1, -1}, {-1, 0}, {-1, 1}, {0, 0}, {0, 1}, {1, 0}, {1, 1}};
     for (int radii = 0; radii < 2; ++radii)
@@ -195,9 +461,10 @@ static void sweep() {
                                             if (cus != 256 && (mode != SMX_MATCH_AUTO || !defaults || sad != 5)) continue;
                                             if (!defaults && (sad != 5 || radii != 0 || K != 2 || mode == SMX_MATCH_EXACT_ORDER)) continue;
                                             if (sad != 5 && Dd != 64) continue;
+                                            if (only_cus > 0 && (cus != 256 || (shape[0] > 64) != large)) continue;
                                             Config c;
                                             c.default_radii = radii == 0; c.K = K; c.dmin = dmin; c.h = shape[0]; c.w = shape[1]; c.Dd = Dd;
-                                            c.B = B; c.match_mode = mode; c.cus = cus; c.sad = sad;
+                                            c.B = B; c.match_mode = mode; c.cus = only_cus > 0 ? only_cus : cus; c.sad = sad;
                                             c.opt.fast_dense = opt[0]; c.opt.fast_dense_small = opt[1];
                                             c.exact_filter = cus == 80 ? 1 : (defaults && sad == 5 ? 0 : -1);     // all three values
                                             sweep_facts(c);
@@ -369,6 +636,32 @@ static void directed_table() {
             expect(p.refine_kind == REFINE_FLOAT && p.kt == 0 && !p.refine_apron && !p.refine_reports_grid, "sad_patch_radius 4: float, kt 0");
         }
     }
+    {   // the launch specs of the examples the source comments give (k_match_exact2.h: exact_split, capture_split; tu_fast_small.hip)
+        RangePlan p = plan_range(f, call_of(IN_RGB_U8, false, false, true, -1), 1, true);
+        expect(f.e2_tiles == 60 && p.route == AGG_EXACT && p.exact.kernel == EXACT_TILED && p.exact.split == 8 && p.exact.nd_chunk == 8 &&
+               p.exact.rows_per_thread == 2 && p.exact.slice_floats == (size_t)8 * SMX_SLICE_WORDS * 188 * 621, "C2 pair: 60 tiles, 8 slices of 8");
+        p = plan_range(f, call_of(IN_RGB_U8, false, false, true, -1), 1, false);
+        expect(p.exact.split == 1 && p.exact.rows_per_thread == 4 && p.exact.nd_chunk == f.exact2_nd && p.exact.slice_floats == 0, "C2 pair as a half: unsplit");
+        Config c = c2;                                          // the reference's default configuration: 1080p, K 2, disparities 75 .. 262
+        c.h = 540; c.w = 960; c.dmin = 37; c.Dd = 95; c.B = 1;
+        const EngineFacts fd = facts_of(c);
+        p = plan_range(fd, call_of(IN_RGB_U8, false, false, true, -1), 1, true);
+        expect(fd.e2_tiles == 272 && fd.capture && p.route == AGG_EXACT && p.exact.split == 7 && p.exact.nd_chunk == 14 && p.capture_follows &&
+               p.exact_capture.split == 3 && p.exact_capture.rows_per_thread == 2, "1080p default: 272 tiles x 95 disparities, 7 slices of 14, capture split 3");
+        c = c2;                                                  // 64 pooled rows: the sparse plan's bands are 32 rows high
+        c.h = 64; c.w = 128; c.B = 256; c.Dd = 256;
+        EngineFacts fb = facts_of(c);
+        p = plan_range(fb, call_of(IN_GRAY_U8, false, true, true, -1), 200, true);
+        expect(p.route == AGG_FAST && !p.fast.small && p.fast.th == 32 && p.dense && p.fast_launch.th == 27 && p.fast_launch.form == FAST_DENSE &&
+               p.fast_launch.argb && p.fast_launch.pitch == 320, "32-row plan, dense form, Dd 256: launches 27 rows");
+        p = plan_range(fb, call_of(IN_GRAY_U8, false, false, true, -1), 200, true);
+        expect(p.fast.th == 32 && p.fast_launch.th == 32 && p.fast_launch.form == FAST_SPARSE, "32-row plan, sparse form: launches 32 rows");
+        c.Dd = 257;
+        fb = facts_of(c);
+        p = plan_range(fb, call_of(IN_GRAY_U8, false, true, true, -1), 200, true);
+        expect(p.fast.th == 32 && p.dense && p.fast_launch.th == 32 && p.fast_launch.form == FAST_SPARSE && !p.fast_launch.argb,
+               "32-row plan, dense form, Dd 257: launches 32 rows sparse (no dense instantiation)");
+    }
     {   // the prediction on the table's shape
         CallKind k = call_kind(f, IN_RGB_U8, false, 32, 0);
         expect(k.filter_reports && !k.fast_reports, "kind: RGB n=32 reports to the filter switch");
@@ -381,11 +674,44 @@ static void directed_table() {
     }
 }
 
-int main() {
+static void print_keys(const char *head, const std::set<std::string> &keys) {
+    printf("%s", head);
+    for (const std::string &k : keys) printf(" %s", k.c_str());
+    printf("\n");
+}
+
+int main(int argc, char **argv) {
+    if (argc == 3 && !strcmp(argv[1], "reach")) {
+        std::set<std::string> small, large, only;
+        reach_keys = &small;
+        sweep(atoi(argv[2]), false);
+        reach_keys = &large;
+        sweep(atoi(argv[2]), true);
+        for (const std::string &k : large)
+            if (!small.count(k)) only.insert(k);
+        print_keys("reach-small", small);
+        print_keys("reach-large-only", only);
+        return 0;
+    }
+    if (argc == 20 && !strcmp(argv[1], "spec")) {
+        int a[18];
+        for (int i = 0; i < 18; ++i) a[i] = atoi(argv[2 + i]);
+        Config c;
+        c.cus = a[0]; c.default_radii = a[1] != 0; c.K = a[2]; c.h = a[3]; c.w = a[4]; c.Dd = a[5]; c.dmin = a[6]; c.B = a[7]; c.match_mode = a[8];
+        c.opt.fast_dense = a[9]; c.opt.fast_dense_small = a[10];
+        const RangePlan p = plan_range(facts_of(c), call_of(a[11], a[12] != 0, a[13] != 0, a[14] != 0, a[15]), a[16], a[17] != 0);
+        std::set<std::string> keys;
+        if (p.status == SMX_OK) keys_of(p, keys);
+        print_keys("keys", keys);
+        return p.status == SMX_OK ? 0 : 2;
+    }
     directed_table();
     sweep();
-    printf("launch-plan plans %ld kinds %ld directed %ld routes %ld %ld %ld %ld %ld refused %ld refine %ld %ld %ld %ld %ld hash %016llx violations %ld\n",
+    printf("launch-plan plans %ld kinds %ld directed %ld routes %ld %ld %ld %ld %ld refused %ld refine %ld %ld %ld %ld %ld hash %016llx violations %ld "
+           "specs %ld exact %ld %ld %ld split %ld form %ld %ld %ld %ld dense-fallback %ld\n",
            plans, kinds, directed, routes[AGG_FILTERED], routes[AGG_EXACT], routes[AGG_FAST], routes[AGG_AUTO_ONE_LAUNCH], routes[AGG_AUTO_GATED],
-           refused, refines[REFINE_FLOAT], refines[REFINE_INT], refines[REFINE_INT_V], refines[REFINE_AUTO], refines[REFINE_AUTO_V], plan_hash, violations);
+           refused, refines[REFINE_FLOAT], refines[REFINE_INT], refines[REFINE_INT_V], refines[REFINE_AUTO], refines[REFINE_AUTO_V], plan_hash, violations,
+           specs, exact_kernels[EXACT_GENERIC], exact_kernels[EXACT_GENERIC_VOLUME], exact_kernels[EXACT_TILED], exact_splits, forms[FAST_SPARSE],
+           forms[FAST_PASS1_ONLY], forms[FAST_DENSE], forms[FAST_DENSE_SMALL], dense_fallbacks);
     return violations == 0 ? 0 : 1;
 }

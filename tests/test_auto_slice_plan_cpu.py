@@ -2,7 +2,7 @@
 
 The one-launch AUTO kernel (k_match_auto.h) turns the workgroups of off-grid pairs into disparity slices that write
 partial arg-max records at [slice][word][pair][h][w] into the calling stream lane's region of the engine's slice buffer;
-the split exact-order launch (launch_exact) does the same for calls of up to 4 pairs.  A record written past the region
+the split exact-order launch (smx_plan.h: exact_launch) does the same for calls of up to 4 pairs.  A record written past the region
 lands in the other lane's region or past the allocation.  tests/auto_slice_plan_harness.cpp compiles the library's own
 plan functions (match_fast_plan, match_auto_nsplit, the launch gate, exact_split and slice_region_floats, which sizes the
 region in smx_create) for the host and sweeps them over frame shapes up to C4's, disparity counts, batch limits, stream-lane

@@ -12,7 +12,12 @@ forms and three CU counts, and checks
      launch publishes, the forms of the fast kernel);
   3. a table of cases written by hand from the rules.  Among them: before any grid report (hint -1) the gated
      exact-order launch of a whole small AUTO call may split the disparity range, exactly as after an off-grid report --
-     the rule is `grid_hint != 0`, not `grid_hint == 1`.
+     the rule is `grid_hint != 0`, not `grid_hint == 1`;
+  4. the launch specs every plan names for its aggregation launches (kernel instantiation, band height as launched, pitch,
+     disparity split, LDS bytes, slice records) against the launcher glue of the time when the launchers still decided
+     for themselves, restated by hand in the harness: no difference over the whole sweep; a split fits the lane's slice
+     region and belongs to a whole call of at most 4 pairs; a dense form is planned only where its instantiation exists
+     (calls planned dense that launch the sparse instantiation are counted); the LDS stays within the raised caps.
 
 Built like the slice-plan harness (host code only, no HIP runtime linked), with the address and undefined-behaviour
 sanitizers when their runtimes link that way and without them otherwise.  No GPU."""
@@ -29,6 +34,8 @@ HARNESS = os.path.join(ROOT, "tests", "launch_plan_harness.cpp")
 SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
 ROUTES = ("FILTERED", "EXACT", "FAST", "AUTO_ONE_LAUNCH", "AUTO_GATED")
 REFINES = ("FLOAT", "INT", "INT_V", "AUTO", "AUTO_V")
+EXACT_KERNELS = ("GENERIC", "GENERIC_VOLUME", "TILED")
+FAST_FORMS = ("SPARSE", "PASS1_ONLY", "DENSE", "DENSE_SMALL")
 
 
 def _build_module():
@@ -60,7 +67,8 @@ def test_prediction_invariants_and_directed_table(harness):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([harness], capture_output=True, text=True, timeout=600, env=env)
     summary = re.search(r"^launch-plan plans (\d+) kinds (\d+) directed (\d+) routes (\d+) (\d+) (\d+) (\d+) (\d+) refused (\d+) "
-                        r"refine (\d+) (\d+) (\d+) (\d+) (\d+) hash ([0-9a-f]{16}) violations (\d+)$", r.stdout, re.M)
+                        r"refine (\d+) (\d+) (\d+) (\d+) (\d+) hash ([0-9a-f]{16}) violations (\d+) "
+                        r"specs (\d+) exact (\d+) (\d+) (\d+) split (\d+) form (\d+) (\d+) (\d+) (\d+) dense-fallback (\d+)$", r.stdout, re.M)
     assert summary, r.stdout[-3000:] + r.stderr[-3000:]
     print(summary.group(0))
     plans, kinds, directed = (int(v) for v in summary.groups()[:3])
@@ -74,3 +82,12 @@ def test_prediction_invariants_and_directed_table(harness):
     assert all(v >= 1000 for v in routes.values()), routes
     assert all(v >= 1000 for v in refines.values()), refines
     assert plans > 10_000_000 and kinds > 500_000 and refused >= 1000 and directed >= 30, summary.group(0)
+    # the launch specs: more specs than plans compared with the restated launchers, every kernel and form, splits, and
+    # the dense calls without a dense instantiation (Dd = 257) -- a finding, NOTES.md "Launch specs"
+    specs, split, fallback = int(summary.group(17)), int(summary.group(21)), int(summary.group(26))
+    exact = dict(zip(EXACT_KERNELS, map(int, summary.groups()[17:20])))
+    forms = dict(zip(FAST_FORMS, map(int, summary.groups()[21:25])))
+    assert specs > plans and split >= 1000 and fallback >= 1000, summary.group(0)
+    assert all(v >= 1000 for v in exact.values()), exact
+    assert all(v >= 1000 for v in forms.values()), forms
+    assert directed >= 37, summary.group(0)

@@ -175,8 +175,8 @@ __device__ __forceinline__ float refine_finish(const RefineParams &p, int b, int
 // 2*y1 - y2 - y3, y1 the FIRST maximum of the candidates, so y3 < y1, y2 <= y1 and a >= 1 -- the reference's `a < 0` never
 // holds and the peak is the comparison chain's pick (:28-34): x1, or x2 on a tie y2 == y1.  That needs `a` to be computed
 // without rounding, under any fp_convention: integers y <= 30,855 and |x| <= X give products and partial sums below
-// 2*X*30,855, exact in fp32 up to X = 271 (SX: the launcher picks the instantiation from RefineParams.sad_exact, which
-// the engine derives from its largest candidate disparity).  Maximum,
+// 2*X*30,855, exact in fp32 up to X = 271 (SX: the instantiation is named by RefineLaunch::sad_exact, which derive_facts,
+// smx_plan.h, derives from the engine's largest candidate disparity; RefineParams.sad_exact is its copy).  Maximum,
 // tie and interior tests are then integer compares on the SADs (first minimum, strict <; cost > FLT_MIN is sd < 121*255).
 template <int N, bool SX>
 __device__ __forceinline__ float refine_finish_int(const RefineParams &p, int b, int x, int y, size_t rowpix,

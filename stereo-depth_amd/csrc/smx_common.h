@@ -197,10 +197,12 @@ struct MatchParams {
     unsigned *tickets;      // [B][exact-order tiles] arrival counters of the one-launch AUTO kernel's off-grid branch (k_match_auto.h)
 };
 
-// ---- launch specs of the aggregation family ----
-// One POD per aggregation launch a range can enqueue: plan_range() (smx_plan.h) fills them, the launchers (smx_launch.h) are tables
-// from spec to kernel instantiation and decide nothing.  What a spec says about the kernel's parameters (nsplit, pairs,
-// nd_chunk, slices, tickets) enqueue_range has already copied into the MatchParams it passes.
+// ---- launch specs ----
+// One POD per launch a range can enqueue: plan_range() (smx_plan.h) fills them, the launchers (smx_launch.h) are tables from
+// spec to kernel instantiation and decide nothing.  A spec of the aggregation family that can be gated carries its gate
+// (MatchParams::gate) and the flag word the gate reads; what a spec says about the kernel's parameters (gate, nsplit, pairs,
+// nd_chunk, tickets) the parameter functions of smx_plan.h (exact_params, ...) have copied into the MatchParams passed with it.
+enum GateFlag { GATE_GRID_FLAG = 0, GATE_RANGE_FLAG };   // [B] pooled inputs off the exact grid / full-resolution gray outside [0, 255]
 enum ExactKernel { EXACT_GENERIC = 0, EXACT_GENERIC_VOLUME, EXACT_TILED };   // k_match_exact [+ volume] / k_match_exact2 (default radii)
 struct ExactLaunch {
     int kernel = EXACT_GENERIC;
@@ -209,8 +211,9 @@ struct ExactLaunch {
     int nd_chunk = 0;            // disparities per right-tile load, never more than a slice holds
     size_t lds_bytes = 0;
     size_t slice_floats = 0;     // slice records the split launch writes: [split][SMX_SLICE_WORDS][n][h][w] (0: unsplit)
+    int gate = 0, gate_flag = GATE_GRID_FLAG;
 };
-struct ExactCaptureLaunch { int split = 1, rows_per_thread = 4, nd_chunk = 0; size_t lds_bytes = 0; };
+struct ExactCaptureLaunch { int split = 1, rows_per_thread = 4, nd_chunk = 0; size_t lds_bytes = 0; int gate = 0; };
 enum FastForm { FAST_SPARSE = 0, FAST_PASS1_ONLY, FAST_DENSE, FAST_DENSE_SMALL, FAST_FORMS };
 struct FastLaunch {
     int th = 0;                  // band rows of the instantiation launched
@@ -219,9 +222,32 @@ struct FastLaunch {
     int pk = 0;                  // packed-sum form (k_match_fast.h: fast_pk)
     bool argb = false;           // the arg-max indices are kept as bytes
     int form = FAST_SPARSE;
+    int gate = 0;                // (on the grid flag, like the two capture launches)
 };
-struct FastCaptureLaunch { bool small = false, wide = false; int pk = 0; };
+struct FastCaptureLaunch { bool small = false, wide = false; int pk = 0, gate = 0; };
 struct AutoLaunch { int th = 0; bool wide = false; int pk = 0, nsplit = 1, nd_chunk = 0; size_t lds_bytes = 0; };
 struct FilterLaunch { int th = 0; bool wide = false; int pk = 0; };
+// ... and of the launches around them: steps 1-2, 6 and 7-9
+enum PrologueKernel { PROLOGUE_GENERIC = 0, PROLOGUE_K2, PROLOGUE_K4 };   // k_prologue / _k2 (two pooled pixels per thread) / _k4 (4 x 4 blocks)
+struct PrologueLaunch { int in_mode = 0, kernel = PROLOGUE_GENERIC; };     // in_mode: the entry (k_prologue.h: IN_*)
+enum RefineKind {
+    REFINE_FLOAT = 0,     // k_refine: any float input, reference summation order
+    REFINE_INT = 1,       // k_refine_int: integer-valued gray on the u8 planes
+    REFINE_INT_V = 2,     // k_refine_int_v: batches, four vertically adjacent pooled pixels per thread
+    REFINE_AUTO = 3,      // k_refine_auto: one launch, per pair INT or FLOAT by the device flag (few pairs)
+    REFINE_AUTO_V = 4     // k_refine_auto_v: ... batches
+};
+struct RefineLaunch {
+    int kind = REFINE_FLOAT;
+    int kt = 0;                  // compile-time K of the specialised kernels (1, 2, 4) or 0: the generic float kernel
+    bool apron = false;          // the gray rows step 6 reads carry cyclic column aprons (engine-owned planes)
+    bool sad_exact = true;       // integer kernels: the SAD parabola is exact for this engine's disparities (RefineParams::sad_exact)
+};
+enum FillKernel { FILL_4 = 0, FILL_POW2, FILL_GENERIC };   // k_fill4<K, px> (K = 1, 2, 4) / k_fill<true> / k_fill<false>
+struct FillLaunch {
+    int kernel = FILL_GENERIC, K = 1;
+    int px = 8;                  // output pixels per thread and row of k_fill4 at K = 2 / 4: 4 or 8 (the other kernels have one form)
+    int log2k = 0;               // FillParams::log2k
+};
 
 }  // namespace smx

@@ -261,38 +261,25 @@ void read_hints(smx_engine *e) {
         std::fprintf(stderr, "[smx] fast kernel: second pass / first pass = %.3f (dense %d)\n", e->route.fast.last, was_dense ? 1 : 0);
 }
 
-// The 9 steps of stereo_matching.cc:22-43 as 4 (AUTO: 5) launches on stream `s`, for the n pairs that start
-// at pair `first` of the engine's buffers (left / right / out already point at that pair), as plan `pl` says
-// (smx_plan.h: plan_range); `lane`: the stream lane's report words, slice region and profile slots.
-int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePlan &pl, int lane, int first, int n,
-                  const void *left, const void *right, float *out, hipStream_t s) {
+// What the launches of a range read and write, bound once per range (pair `first` onwards: view_from): the prologue's arguments, ...
+smx::PrologueArgs prologue_args(const smx_engine *e, const PairView &v, bool owns_gray, const void *left, const void *right) {
     const smx_dims &d = e->dm;
     const smx::EngineFacts &f = e->facts;
-    const PairView v = view_from(e, first);
-    // full-resolution gray as steps 6-9 see it: column 0 of row 0 of pair 0, row pitch, pair stride
-    const float *gl = pl.owns_gray ? v.gray_l + f.gpadl : (const float *)left;
-    const float *gr = pl.owns_gray ? v.gray_r + f.gpadl : (const float *)right;
-    const int gpitch = pl.owns_gray ? f.gpitch : d.W;
-    const size_t gplane = (size_t)d.H * gpitch;
-    {
-        SlotTimer tm(e, s, lane, SMX_KERNEL_PROLOGUE);
-        smx::PrologueArgs a{};
-        a.left = left; a.right = right; a.gray_l = pl.owns_gray ? v.gray_l : nullptr; a.gray_r = pl.owns_gray ? v.gray_r : nullptr;
-        a.down_l = v.down_l; a.down_r = v.down_r;
-        a.flags = v.flags; a.flags2 = v.flags2; a.g8_l = v.gray8_l; a.g8_r = v.gray8_r;
-        a.H = d.H; a.W = d.W; a.K = d.K; a.h = d.h; a.w = d.w; a.grid_capable = f.grid_capable ? 1 : 0;
-        a.pitch8 = f.pitch8; a.padl = f.padl; a.padr = f.padr; a.epoch = e->epoch; a.gpitch = f.gpitch; a.gpadl = f.gpadl;
-        a.fp_conv = SMX_FP_STEP1(e->cfg.fp_convention);
-        smx::launch_prologue(call.in_mode, a, n, s);
-    }
-    e->last_gray_l = gl - (size_t)first * gplane;         // of pair 0 of the call
-    e->last_gray_r = gr - (size_t)first * gplane;
-    e->last_gray_owned = pl.owns_gray;
-    e->last_gpitch = gpitch;
-    e->last_gplane = gplane;
-    if (pl.status != SMX_OK) return fail(pl.status, "%s", pl.refusal);
-
-    smx::MatchParams mp{};
+    smx::PrologueArgs a{};
+    a.left = left; a.right = right; a.gray_l = owns_gray ? v.gray_l : nullptr; a.gray_r = owns_gray ? v.gray_r : nullptr;
+    a.down_l = v.down_l; a.down_r = v.down_r;
+    a.flags = v.flags; a.flags2 = v.flags2; a.g8_l = v.gray8_l; a.g8_r = v.gray8_r;
+    a.H = d.H; a.W = d.W; a.K = d.K; a.h = d.h; a.w = d.w; a.grid_capable = f.grid_capable ? 1 : 0;
+    a.pitch8 = f.pitch8; a.padl = f.padl; a.padr = f.padr; a.epoch = e->epoch; a.gpitch = f.gpitch; a.gpadl = f.gpadl;
+    a.fp_conv = SMX_FP_STEP1(e->cfg.fp_convention);
+    return a;
+}
+// ... what the aggregation launches share (smx_plan.h: RangeParams; `lane`: the stream lane's slice region and counter), ...
+smx::RangeParams range_params(const smx_engine *e, const PairView &v, const smx::CallFacts &call, const smx::RangePlan &pl, int lane, int first) {
+    const smx_dims &d = e->dm;
+    const smx::EngineFacts &f = e->facts;
+    smx::RangeParams b;
+    smx::MatchParams &mp = b.mp;
     mp.Ld = v.down_l; mp.Rd = v.down_r; mp.wta = v.wta; mp.costs = v.costs; mp.vol = v.vol;
     mp.flags = v.flags; mp.epoch = e->epoch; mp.B = e->B; mp.h = d.h; mp.w = d.w; mp.dmin = d.dmin; mp.Dd = d.Dd;
     mp.rn = (int)e->cfg.ncc_patch_radius; mp.rs = e->cfg.small_mbm_radius;
@@ -302,41 +289,85 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
     mp.tickets = e->tickets ? e->tickets + (size_t)first * f.e2_tiles : nullptr;
     mp.pass1_only = pl.capture_follows ? 1 : 0;
     mp.slices = e->slices ? e->slices + (size_t)lane * f.slices_floats : nullptr;   // this lane's region of the slice buffer
-    // The launches below are the plan's launch specs; what a spec says about the kernel's parameters is copied here.
-    auto exact_capture = [&](smx::MatchParams p) {           // dmin > 0: the lookups of step 6 behind an exact-order arg-max
-        if (!pl.capture_follows) return;
-        p.nd_chunk = pl.exact_capture.nd_chunk;
-        p.nsplit = pl.exact_capture.split;
-        smx::launch_exact2_capture(pl.exact_capture, p, n, s);
-    };
-    auto exact = [&](smx::MatchParams p) -> int {            // the dense exact-order launch
-        p.nd_chunk = pl.exact.nd_chunk;
-        if (pl.exact.split > 1) {
-            if (pl.exact.slice_floats > f.slices_floats)
-                return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
-            p.nsplit = pl.exact.split;
-            p.pairs = n;
-            p.tickets = nullptr;                             // merged by a launch of its own, not by a tile's last slice
-        }
-        smx::launch_exact(pl.exact, p, n, s);
-        return SMX_OK;
-    };
-    // the parameters of the fast kernel in the plan's form; the sparse form's report is published by this range's fill launch
-    auto fast_params = [&](smx::MatchParams p, int gate) -> smx::MatchParams {
-        p.gate = gate;
-        p.dense = pl.dense ? 1 : 0;
-        p.dense_small = pl.dense_small ? 1 : 0;
-        if (pl.fill_publishes) {
-            p.fast_stats = e->fast_stats_dev + lane;
-            p.fast_stride = pl.stride;
-        }
-        return p;
-    };
-    auto fast = [&](int gate) {                              // the fast kernel [and its lookups]
-        const smx::MatchParams p = fast_params(mp, gate);
-        smx::launch_match_fast(pl.fast_launch, p, n, s);
-        if (pl.capture_follows) smx::launch_match_capture_tu(pl.fast_capture, p, n, s);
-    };
+    b.range_flags = v.flags2;
+    b.fast_stats = e->fast_stats_dev + lane;
+    return b;
+}
+// ... full-resolution gray as steps 6-9 see it (column 0 of row 0 of the range's first pair, row pitch, pair stride), remembered
+// for smx_get_intermediate as of pair 0 of the call, ...
+struct GrayView { const float *l, *r; int pitch; size_t plane; };
+GrayView gray_view(smx_engine *e, const PairView &v, bool owns_gray, int first, const void *left, const void *right) {
+    const smx::EngineFacts &f = e->facts;
+    GrayView g{owns_gray ? v.gray_l + f.gpadl : (const float *)left, owns_gray ? v.gray_r + f.gpadl : (const float *)right,
+               owns_gray ? f.gpitch : e->dm.W, 0};
+    g.plane = (size_t)e->dm.H * g.pitch;
+    e->last_gray_l = g.l - (size_t)first * g.plane;
+    e->last_gray_r = g.r - (size_t)first * g.plane;
+    e->last_gray_owned = owns_gray;
+    e->last_gpitch = g.pitch;
+    e->last_gplane = g.plane;
+    return g;
+}
+// ... and the parameters of steps 6 and 7-9
+smx::RefineParams refine_params(const smx_engine *e, const PairView &v, const smx::RangePlan &pl, const GrayView &g) {
+    const smx_dims &d = e->dm;
+    const smx::EngineFacts &f = e->facts;
+    smx::RefineParams rp{};
+    rp.Lg = g.l; rp.Rg = g.r; rp.gpitch = g.pitch; rp.gplane = g.plane; rp.wta = v.wta; rp.costs = v.costs; rp.vol = v.vol;
+    rp.refined = v.refined; rp.B = e->B; rp.H = d.H; rp.W = d.W; rp.K = d.K; rp.h = d.h;
+    rp.w = d.w; rp.Dd = d.Dd; rp.R = (int)e->cfg.sad_patch_radius;
+    rp.flags2 = v.flags2;
+    rp.epoch = e->epoch;
+    rp.L8 = v.gray8_l; rp.R8 = v.gray8_r; rp.pitch8 = f.pitch8; rp.padl = f.padl;
+    rp.fp_conv = SMX_FP_PARABOLA(e->cfg.fp_convention);
+    rp.sad_exact = pl.refine.sad_exact ? 1 : 0;
+    if (pl.refine.kind == smx::REFINE_AUTO) rp.grid_flags = v.flags;
+    if (pl.refine_reports_grid) rp.grid_hint = &e->hints_dev->grid;
+    return rp;
+}
+smx::FillParams fill_params(smx_engine *e, const PairView &v, const smx::RangePlan &pl, int lane, const GrayView &g, float *out) {
+    const smx_dims &d = e->dm;
+    smx::FillParams fp{};
+    fp.Lg = g.l; fp.lpitch = g.pitch; fp.lplane = g.plane; fp.refined = v.refined; fp.out = out; fp.B = e->B; fp.H = d.H; fp.W = d.W;
+    fp.K = d.K; fp.h = d.h; fp.w = d.w; fp.thr = (float)e->cfg.threshold;
+    fp.log2k = pl.fill.log2k;
+    if (pl.fill_publishes) {
+        fp.fast_stats = e->fast_stats_dev + lane;
+        fp.fast_stats_host = &e->hints_dev->fast_density[lane];
+        fp.fast_seq = e->route.fast.next_seq();
+        fp.fast_pass1 = (d.Dd + 1) / 2;
+    }
+    return fp;
+}
+
+// The dense exact-order launch / the fast kernel of a range, each followed by its lookups of step 6 when dmin > 0 (capture route).
+void enqueue_exact(const smx::RangeParams &b, const smx::RangePlan &pl, int n, hipStream_t s) {
+    smx::launch_exact(pl.exact, smx::exact_params(b, pl.exact, n), n, s);
+    if (pl.capture_follows) smx::launch_exact2_capture(pl.exact_capture, smx::exact_capture_params(b, pl.exact_capture), n, s);
+}
+void enqueue_fast(const smx::RangeParams &b, const smx::RangePlan &pl, int n, hipStream_t s) {
+    smx::launch_match_fast(pl.fast_launch, smx::fast_params(b, pl, pl.fast_launch.gate), n, s);
+    if (pl.capture_follows) smx::launch_match_capture_tu(pl.fast_capture, smx::fast_params(b, pl, pl.fast_capture.gate), n, s);
+}
+
+// The 9 steps of stereo_matching.cc:22-43 as 4 (AUTO: 5) launches on stream `s`, for the n pairs that start
+// at pair `first` of the engine's buffers (left / right / out already point at that pair), as plan `pl` says
+// (smx_plan.h: plan_range): every launch is one of the plan's launch specs with the parameters smx_plan.h derives for it;
+// `lane`: the stream lane's report words, slice region and profile slots.
+int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePlan &pl, int lane, int first, int n,
+                  const void *left, const void *right, float *out, hipStream_t s) {
+    const smx::EngineFacts &f = e->facts;
+    const PairView v = view_from(e, first);
+    const GrayView g = gray_view(e, v, pl.owns_gray, first, left, right);
+    {
+        SlotTimer tm(e, s, lane, SMX_KERNEL_PROLOGUE);
+        smx::launch_prologue(pl.prologue, prologue_args(e, v, pl.owns_gray, left, right), n, s);
+    }
+    if (pl.status != SMX_OK) return fail(pl.status, "%s", pl.refusal);
+    if (pl.exact.slice_floats > f.slices_floats)          // the records of a split exact-order launch (0: the range has none)
+        return fail(SMX_ERR_HIP, "internal: slice buffer too small for the disparity split of %d pairs", n);
+
+    const smx::RangeParams b = range_params(e, v, call, pl, lane, first);
     switch (pl.route) {
     case smx::AGG_FILTERED: {
         smx::FilterParams fp{};
@@ -344,42 +375,29 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
         fp.two_e = f.filter_two_e; fp.range_flags = v.flags2;
         {
             SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-            if (pl.gated_dense_first) {        // the gated alternative first (see AGG_AUTO_GATED below)
-                smx::MatchParams dp = mp;
-                dp.flags = v.flags2;
-                dp.gate = 2;
-                if (int rc = exact(dp)) return rc;
-            }
-            smx::MatchParams fmp = mp;
-            fmp.unit = (float)f.filter_unit;
-            smx::launch_match_filter_tu(pl.filter, fmp, fp, n, s);
+            // the gated alternative first (see AGG_AUTO_GATED below)
+            if (pl.gated_dense_first) smx::launch_exact(pl.exact, smx::exact_params(b, pl.exact, n), n, s);
+            smx::launch_match_filter_tu(pl.filter, smx::filter_params(b, f), fp, n, s);
         }
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
-        smx::MatchParams sp = mp;
-        sp.nd_chunk = f.exact2_nd;
-        smx::launch_exact2_sparse(sp, n, v.cand, f.cand_cw, (const int *)v.flags2, e->stats_dev + 2 * lane,
+        smx::launch_exact2_sparse(smx::sparse_params(b, f), n, v.cand, f.cand_cw, (const int *)v.flags2, e->stats_dev + 2 * lane,
                                   &e->hints_dev->filter_density[lane], e->route.filt.next_seq(), s);
-        exact_capture(mp);
+        if (pl.capture_follows) smx::launch_exact2_capture(pl.exact_capture, smx::exact_capture_params(b, pl.exact_capture), n, s);
         break;
     }
     case smx::AGG_EXACT: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
-        if (int rc = exact(mp)) return rc;
-        exact_capture(mp);
+        enqueue_exact(b, pl, n, s);
         break;
     }
     case smx::AGG_FAST: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        fast(0);
+        enqueue_fast(b, pl, n, s);
         break;
     }
     case smx::AGG_AUTO_ONE_LAUNCH: {
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        smx::MatchParams p = fast_params(mp, 0);
-        p.nsplit = pl.auto_launch.nsplit;      // the off-grid branch: slices, right-tile chunk no wider than a slice, records of n pairs
-        p.pairs = n;
-        p.nd_chunk = pl.auto_launch.nd_chunk;
-        smx::launch_match_auto_small_tu(pl.auto_launch, p, n, s);
+        smx::launch_match_auto_small_tu(pl.auto_launch, smx::auto_params(b, pl, n), n, s);
         break;
     }
     default: {   // AGG_AUTO_GATED: both enqueued, the device-side grid flag lets exactly one do the work
@@ -389,48 +407,21 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
         // lane's tail), in front of it it overlaps the wait the fast kernel has anyway (NOTES.md: lanes).
         {
             SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_EXACT);
-            mp.gate = 2;
-            if (int rc = exact(mp)) return rc;
-            exact_capture(mp);
+            enqueue_exact(b, pl, n, s);
         }
         SlotTimer tm(e, s, lane, SMX_KERNEL_MATCH_FAST);
-        fast(1);
+        enqueue_fast(b, pl, n, s);
         break;
     }
     }
     e->last_call.plan = pl;
-
-    smx::RefineParams rp{};
-    rp.Lg = gl; rp.Rg = gr; rp.gpitch = gpitch; rp.gplane = gplane; rp.wta = v.wta; rp.costs = v.costs; rp.vol = v.vol;
-    rp.refined = v.refined; rp.B = e->B; rp.H = d.H; rp.W = d.W; rp.K = d.K; rp.h = d.h;
-    rp.w = d.w; rp.Dd = d.Dd; rp.R = (int)e->cfg.sad_patch_radius;
-    rp.flags2 = v.flags2;
-    rp.epoch = e->epoch;
-    rp.L8 = v.gray8_l; rp.R8 = v.gray8_r; rp.pitch8 = f.pitch8; rp.padl = f.padl;
-    rp.gate = 0;
-    rp.fp_conv = SMX_FP_PARABOLA(e->cfg.fp_convention);
-    // largest |abscissa| of the SAD parabola: d_hi = K * (dmin / K + Dd) (k_refine.h refine_finish_int: exact up to 271)
-    rp.sad_exact = (long long)d.K * ((long long)e->cfg.min_disparity / d.K + d.Dd) <= 271 ? 1 : 0;
-    if (pl.refine_kind == smx::REFINE_AUTO) rp.grid_flags = v.flags;
-    if (pl.refine_reports_grid) rp.grid_hint = &e->hints_dev->grid;
-    smx::FillParams fp{};
-    fp.Lg = gl; fp.lpitch = gpitch; fp.lplane = gplane; fp.refined = v.refined; fp.out = out; fp.B = e->B; fp.H = d.H; fp.W = d.W;
-    fp.K = d.K; fp.h = d.h; fp.w = d.w; fp.thr = (float)e->cfg.threshold;
-    fp.log2k = 0;
-    while ((1 << fp.log2k) < d.K) fp.log2k++;
-    if (pl.fill_publishes) {
-        fp.fast_stats = e->fast_stats_dev + lane;
-        fp.fast_stats_host = &e->hints_dev->fast_density[lane];
-        fp.fast_seq = e->route.fast.next_seq();
-        fp.fast_pass1 = (d.Dd + 1) / 2;
-    }
     {
         SlotTimer tm(e, s, lane, SMX_KERNEL_REFINE);
-        smx::launch_refine(pl.refine_kind, pl.kt, pl.refine_apron, rp, n, s);
+        smx::launch_refine(pl.refine, refine_params(e, v, pl, g), n, s);
     }
     {
         SlotTimer tm(e, s, lane, SMX_KERNEL_FILL);
-        smx::launch_fill(fp, n, pl.fill_px, s);
+        smx::launch_fill(pl.fill, fill_params(e, v, pl, lane, g, out), n, s);
     }
     SMX_HIP(hipGetLastError());
     return SMX_OK;
@@ -573,6 +564,9 @@ int enqueue(smx_engine *e, int in_mode, int n, const void *left, const void *rig
     smx::CallFacts call;
     call.in_mode = in_mode;
     call.on_lanes = detached;
+    // (the second half of a split call starts a whole number of pairs further on: where the block prologue applies, W % 4
+    // == 0, that is a multiple of 4 bytes, so a half is aligned exactly when the call is)
+    call.u8_aligned = (((uintptr_t)left | (uintptr_t)right) & 3u) == 0;
     call.route = e->route.decide_call(smx::call_kind(f, in_mode, detached, n0, n - n0), f.opt.fast_dense, f.exact_filter);
     e->last_call.call = call;
     e->last_call.first = 0;

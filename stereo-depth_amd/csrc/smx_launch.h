@@ -23,19 +23,10 @@ struct PrologueArgs {
     int H, W, K, h, w, grid_capable, pitch8, padl, padr, epoch, gpitch, gpadl;
     int fp_conv;             // smx_fp_convention (RGB entries: step 1)
 };
-void launch_prologue(int in_mode, const PrologueArgs &a, int n, hipStream_t s);
-
-enum RefineKind {
-    REFINE_FLOAT = 0,     // k_refine: any float input, reference summation order
-    REFINE_INT = 1,       // k_refine_int: integer-valued gray on the u8 planes
-    REFINE_INT_V = 2,     // k_refine_int_v: batches, four vertically adjacent pooled pixels per thread
-    REFINE_AUTO = 3,      // k_refine_auto: one launch, per pair INT or FLOAT by the device flag (few pairs)
-    REFINE_AUTO_V = 4     // k_refine_auto_v: ... batches
-};
-// kt: compile-time K of the specialised kernels (1, 2, 4) or 0 for the generic float kernel; apron: the gray rows
-// carry cyclic column aprons (engine-owned planes)
-void launch_refine(int kind, int kt, bool apron, const RefineParams &p, int n, hipStream_t s);
-void launch_fill(const FillParams &p, int n, int px, hipStream_t s);
+// like the aggregation family below, these three are tables from their launch spec (smx_common.h) to an instantiation
+void launch_prologue(const PrologueLaunch &x, const PrologueArgs &a, int n, hipStream_t s);
+void launch_refine(const RefineLaunch &x, const RefineParams &p, int n, hipStream_t s);
+void launch_fill(const FillLaunch &x, const FillParams &p, int n, hipStream_t s);
 void launch_flag_to_bool(const int *flag, int epoch, int *out, hipStream_t s);
 void launch_metrics(int n, const float *est, const float *gt, const uint8_t *mask, size_t pixels, float max_disparity,
                     const float thresholds[4], double *out_sums, hipStream_t s);

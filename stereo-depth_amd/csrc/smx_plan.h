@@ -2,14 +2,18 @@
 //
 // derive_facts() turns a configuration into everything the plans depend on that is fixed after smx_create; plan_range()
 // turns those facts, the call (entry, stream lanes or caller's stream, the decision of the content switches) and a range
-// of n pairs into a RangePlan: which aggregation kernels run, in which form, followed by which step-6 and fill launch.
-// Every aggregation launch of the range is named by a launch spec (smx_common.h: ExactLaunch, ExactCaptureLaunch,
-// FastLaunch, FastCaptureLaunch, AutoLaunch, FilterLaunch): the kernel instantiation -- band height as launched, pitch,
-// packed-sum form, form of the fast kernel, disparity split, rows per thread -- with its right-tile chunk, dynamic LDS and
-// slice records.  The launchers behind smx_launch.h are tables from spec to instantiation; nothing below this header
-// decides anything.  smx_engine.hip executes the plan (enqueue_range), predicts from it which content switch a call can
-// report to (call_kind) and answers its queries from it; the CPU harnesses under tests/ compile the same lines, so what a
-// call launches can be read, and swept, without a GPU.
+// of n pairs into a RangePlan: the prologue, the aggregation kernels and their form, the step-6 and the fill launch.
+// Every launch of the range is named by a launch spec (smx_common.h): PrologueLaunch (entry; generic, K = 2 two-pixel or
+// K = 4 block kernel), the aggregation family (ExactLaunch, ExactCaptureLaunch, FastLaunch, FastCaptureLaunch, AutoLaunch,
+// FilterLaunch: the kernel instantiation -- band height as launched, pitch, packed-sum form, form of the fast kernel,
+// disparity split, rows per thread -- with its right-tile chunk, dynamic LDS, slice records and its gate), RefineLaunch
+// (kernel, compile-time K, aprons, exact SAD parabola) and FillLaunch (kernel, pixels per thread).  The parameter functions
+// at the end of this header (exact_params, ..., auto_params) turn the parameters a range's launches share and a spec into
+// that launch's MatchParams.  The launchers behind smx_launch.h are tables from spec to instantiation; nothing below this
+// header decides anything.  smx_engine.hip executes the plan (enqueue_range binds the buffers and walks the route),
+// predicts from it which content switch a call can report to (call_kind) and answers its queries from it; the CPU
+// harnesses under tests/ compile the same lines, so what a call launches, and with which parameters, can be read, and
+// swept, without a GPU.
 //
 // Host-only inline functions without a HIP runtime call, like smx_route.h; the kernel headers are included for their
 // constants and for the helpers that hold the tuning (match_fast_plan, exact_split, capture_split, match_auto_nsplit,
@@ -57,6 +61,9 @@ struct EngineFacts {
     int kt = 0;                     // compile-time K of the specialised step-6 kernels (1, 2, 4) or 0: the generic float kernel
     int pitch8 = 0, padl = 0, padr = 0;   // u8 planes with cyclic aprons; pitch8 = 0: integer step-6 kernel not applicable
     int gpitch = 0, gpadl = 0;            // row pitch / left-apron width (floats) of the engine's gray planes
+    bool prologue_k2 = false;       // K = 2, even W: the gray entries pool two pixels per thread with 16-byte loads
+    bool prologue_k4 = false;       // K = 4, W a multiple of 4 and so is every pitch and apron: one pooled pixel is a 4 x 4 block of 16-byte loads
+    bool sad_exact = true;          // step 6, integer kernels: the SAD parabola is exact for every disparity (k_refine.h refine_finish_int)
     int exact_nd = 0, exact2_nd = 0;      // disparities per right-tile load: generic / register-tiled exact-order kernel
     size_t exact_lds = 0, exact2_lds = 0;
     int e2_tiles = 0;               // exact-order tiles per pair: arrival tickets of the one-launch AUTO kernel (default radii)
@@ -113,6 +120,11 @@ inline EngineFacts derive_facts(const smx_config &cfg, const smx_dims &d, int cu
             f.gpadl = 0;
         }
     }
+    f.prologue_k2 = K == 2 && (d.W & 1) == 0;
+    f.prologue_k4 = K == 4 && (d.W & 3) == 0 && f.grid_capable && (f.gpitch & 3) == 0 && (f.gpadl & 3) == 0 && (f.pitch8 & 3) == 0 &&
+                    (f.padl & 3) == 0 && (f.gpadl == 0 || f.gpadl == f.padl);
+    // largest |abscissa| of the SAD parabola: d_hi = K * (dmin / K + Dd) (k_refine.h refine_finish_int: exact up to 271)
+    f.sad_exact = (long long)K * ((long long)cfg.min_disparity / K + d.Dd) <= 271;
     if (f.default_radii) {
         // slice records of the disparity-split exact kernel and of the one-launch AUTO kernel's off-grid branch (few pairs
         // in flight): one region per stream lane, sized by the rule the launches check against (k_match_auto.h); arrival
@@ -153,6 +165,7 @@ inline EngineFacts derive_facts(const smx_config &cfg, const smx_dims &d, int cu
 struct CallFacts {
     int in_mode = IN_GRAY_F32;
     bool on_lanes = false;          // the call runs on the stream lanes
+    bool u8_aligned = true;         // u8 entries: the caller's left | right are 4-byte aligned (the prologue's one per-call input)
     CallRoute route{false, true, -1};
 };
 
@@ -167,7 +180,7 @@ enum AggRoute {
 
 // Everything enqueue_range does for one range of n pairs.
 struct RangePlan {
-    int status = SMX_OK;            // SMX_ERR_UNSUPPORTED: refused after the prologue (`refusal` says why): of the fields below only owns_gray applies
+    int status = SMX_OK;            // SMX_ERR_UNSUPPORTED: refused after the prologue (`refusal` says why): of the fields below only owns_gray and prologue apply
     const char *refusal = nullptr;
     int mode = SMX_MATCH_EXACT_ORDER;   // what smx_last_match_mode reports
     AggRoute route = AGG_EXACT;
@@ -184,11 +197,12 @@ struct RangePlan {
     bool fill_publishes = false;    // the fast launch of this range reports: its fill launch publishes
     // steps 6 and 7-9
     bool owns_gray = true;          // steps 6-9 read the engine's gray planes (false: the caller's, f32 gray entry)
-    int refine_kind = REFINE_FLOAT, kt = 0;
-    bool refine_apron = false;      // the gray rows step 6 reads carry cyclic column aprons
     bool refine_reports_grid = false;   // k_refine_auto publishes the grid flag of pair 0 (hints->grid)
-    int fill_px = 8;                // pixels per thread of the fill launch
-    // The aggregation launches of the route, as the launchers get them (value-initialised where the route has no such launch):
+    // The launches of the range, as the launchers get them: steps 1-2, 6 and 7-9 ...
+    PrologueLaunch prologue{};
+    RefineLaunch refine{};
+    FillLaunch fill{};
+    // ... and the aggregation launches of the route (value-initialised where the route has no such launch):
     ExactLaunch exact{};            // FILTERED (the gated dense launch), EXACT, AUTO_GATED
     ExactCaptureLaunch exact_capture{};   // ... followed by this when capture_follows
     FastLaunch fast_launch{};       // FAST, AUTO_GATED
@@ -300,9 +314,30 @@ inline FilterLaunch filter_launch(const EngineFacts &f, const MatchParams &mp, i
     return FilterLaunch{pl.th, pl.wide, fast_pk(f.filter_unit)};
 }
 
+// Steps 1-2.  The two-pixel kernel exists for the gray entries; the block kernel reads a u8 entry's rows with 4-byte loads.
+inline PrologueLaunch prologue_launch(const EngineFacts &f, const CallFacts &call) {
+    const bool u8 = call.in_mode == IN_GRAY_U8 || call.in_mode == IN_RGB_U8;
+    PrologueLaunch x;
+    x.in_mode = call.in_mode;
+    if (f.prologue_k2 && !is_rgb(call.in_mode)) x.kernel = PROLOGUE_K2;
+    else if (f.prologue_k4 && (!u8 || call.u8_aligned)) x.kernel = PROLOGUE_K4;
+    return x;
+}
+
+// Steps 7-9; on the stream lanes a batch's fill takes 4 pixels per thread (tu_stages.hip: launch_fill).
+inline FillLaunch fill_launch(const EngineFacts &f, bool on_lanes, int n) {
+    FillLaunch x;
+    x.K = f.K;
+    x.kernel = f.K == 1 || f.K == 2 || f.K == 4 ? FILL_4 : ((f.K & (f.K - 1)) == 0 ? FILL_POW2 : FILL_GENERIC);
+    x.px = on_lanes && n > 4 ? 4 : 8;
+    while ((1 << x.log2k) < f.K) x.log2k++;
+    return x;
+}
+
 inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, bool whole_call) {
     RangePlan p;
     p.owns_gray = call.in_mode != IN_GRAY_F32;
+    p.prologue = prologue_launch(f, call);
     if (f.match_mode == SMX_MATCH_FAST_GRID && !f.fast_ok) {
         p.status = SMX_ERR_UNSUPPORTED;
         p.refusal = "SMX_MATCH_FAST_GRID needs downscale_factor in {1,2,4,8}, ncc radius 1 and "
@@ -343,7 +378,7 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
         // per exact-order tile, the disparities that can still hold the maximum; only those are evaluated in the
         // reference's order.  Pairs whose gray leaves [0, 255] (f32 RGB only; flag from the prologue) take the dense kernel.
         p.route = AGG_FILTERED;
-        p.gated_dense_first = call.in_mode == IN_RGB_F32;
+        p.gated_dense_first = call.in_mode == IN_RGB_F32;      // (gate 2 on the range flag, below)
         p.filter = filter_launch(f, mp, n);
     } else if (p.mode == SMX_MATCH_EXACT_ORDER) {
         p.route = AGG_EXACT;
@@ -395,25 +430,92 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
         p.fast_launch = fast_launch(f, p.fast, p.dense, p.dense_small);
         if (p.capture_follows) p.fast_capture = fast_capture_launch(f, p.fast);
     }
+    // the gates: a launch runs for every pair (0), for the pairs whose flag is clear (1) or for those whose flag is set (2)
+    if (p.route == AGG_FILTERED) {
+        p.exact.gate = 2;
+        p.exact.gate_flag = GATE_RANGE_FLAG;
+    } else if (p.route == AGG_AUTO_GATED) {   // the grid flag lets exactly one of the two [pairs of] launches do the work
+        p.exact.gate = p.exact_capture.gate = 2;
+        p.fast_launch.gate = p.fast_capture.gate = 1;
+    }
 
     // step 6: integer-valued gray -> v_sad_u8 kernel; otherwise the float kernel (same results)
-    p.kt = f.kt;
+    p.refine.kt = f.kt;
+    p.refine.sad_exact = f.sad_exact;
     if (f.kt == 0 || !f.has_u8_planes() || rgb) {
-        p.refine_kind = REFINE_FLOAT;
-        p.refine_apron = p.owns_gray && f.gpadl > 0 && call.in_mode != IN_GRAY_U8;   // the u8 gray prologue writes no float aprons
+        p.refine.kind = REFINE_FLOAT;
+        p.refine.apron = p.owns_gray && f.gpadl > 0 && call.in_mode != IN_GRAY_U8;   // the u8 gray prologue writes no float aprons
     } else if (call.in_mode == IN_GRAY_U8) {
         // u8 is integer-valued by construction; the prologue wrote the padded copy.  Batches: four pooled rows per
         // thread share their row SADs (k_refine_int_v)
-        p.refine_kind = n > 4 ? REFINE_INT_V : REFINE_INT;
+        p.refine.kind = n > 4 ? REFINE_INT_V : REFINE_INT;
     } else if (n <= 4) {   // f32 gray, few pairs: one launch picks per pair (k_refine_auto) and reports the grid flag
-        p.refine_kind = REFINE_AUTO;
+        p.refine.kind = REFINE_AUTO;
         p.refine_reports_grid = whole_call;
     } else {   // f32 gray batches: the prologue wrote u8 copies and the per-pair integrality flag; one launch
         // branches on it per pair (k_refine_auto_v: a gated-out launch of the float kernel still has to be placed on
         // a chip the other lane fills, and the lane's chain waits for it)
-        p.refine_kind = REFINE_AUTO_V;
+        p.refine.kind = REFINE_AUTO_V;
     }
-    p.fill_px = call.on_lanes && n > 4 ? 4 : 8;
+    p.fill = fill_launch(f, call.on_lanes, n);
+    return p;
+}
+
+// ---- from spec to the launch's parameters -------------------------------------------------------------------------------------
+// What the aggregation launches of a range share, bound once by enqueue_range: buffers, shape, radii, epoch, the lane's slice
+// region and the tickets in `mp` (flags: the grid flag, gate 0, unit K^2), and the two words only some launches get.
+struct RangeParams {
+    MatchParams mp{};
+    const int *range_flags = nullptr;            // [B] == epoch: the pair's gray leaves [0, 255] (the prologue's second flag word)
+    unsigned long long *fast_stats = nullptr;    // this lane's counter of the sparse fast kernel's report
+};
+inline MatchParams exact_params(const RangeParams &b, const ExactLaunch &x, int n) {
+    MatchParams p = b.mp;
+    p.gate = x.gate;
+    if (x.gate_flag == GATE_RANGE_FLAG) p.flags = b.range_flags;
+    p.nd_chunk = x.nd_chunk;
+    if (x.split > 1) {
+        p.nsplit = x.split;
+        p.pairs = n;
+        p.tickets = nullptr;                     // merged by a launch of its own, not by a tile's last slice
+    }
+    return p;
+}
+inline MatchParams exact_capture_params(const RangeParams &b, const ExactCaptureLaunch &x) {
+    MatchParams p = b.mp;
+    p.gate = x.gate;
+    p.nd_chunk = x.nd_chunk;
+    p.nsplit = x.split;
+    return p;
+}
+// the fast kernel in the plan's form; the sparse form's report is published by the range's fill launch
+inline MatchParams fast_params(const RangeParams &b, const RangePlan &pl, int gate) {
+    MatchParams p = b.mp;
+    p.gate = gate;
+    p.dense = pl.dense ? 1 : 0;
+    p.dense_small = pl.dense_small ? 1 : 0;
+    if (pl.fill_publishes) {
+        p.fast_stats = b.fast_stats;
+        p.fast_stride = pl.stride;
+    }
+    return p;
+}
+// the off-grid branch: slices, a right-tile chunk no wider than a slice, records of n pairs
+inline MatchParams auto_params(const RangeParams &b, const RangePlan &pl, int n) {
+    MatchParams p = fast_params(b, pl, 0);
+    p.nsplit = pl.auto_launch.nsplit;
+    p.pairs = n;
+    p.nd_chunk = pl.auto_launch.nd_chunk;
+    return p;
+}
+inline MatchParams filter_params(const RangeParams &b, const EngineFacts &f) {
+    MatchParams p = b.mp;
+    p.unit = (float)f.filter_unit;
+    return p;
+}
+inline MatchParams sparse_params(const RangeParams &b, const EngineFacts &f) {   // (launch_exact2_sparse has no spec: one instantiation)
+    MatchParams p = b.mp;
+    p.nd_chunk = f.exact2_nd;
     return p;
 }
 

@@ -13,16 +13,30 @@
 //      a split fits the lane's slice region and belongs to a whole call of at most 4 pairs, a dense form is planned only
 //      where its instantiation exists, the dynamic LDS stays within what the engine raises the kernel to.  A call planned
 //      dense that launches the sparse instantiation (no dense one exists for it) is counted: "dense-fallback".
+//   5. The rest of the call.  PrologueLaunch, RefineLaunch and FillLaunch against launch_prologue's and launch_fill's own
+//      selection and enqueue_range's sad_exact and log2k as they were while those decided for themselves; the gates and
+//      the MatchParams of every aggregation launch (smx_plan.h: exact_params, ..., auto_params) against the four lambdas
+//      enqueue_range had, all restated here by hand (old_*), field by field over the whole sweep.  The prologue also
+//      with the caller's u8 pointers unaligned, and an extension of the sweep (K = 8; widths that are no multiple of
+//      K) that is checked and hashed like the rest but stays out of the counts and the first hash.  Invariants: the
+//      K = 2 prologue only for gray entries with even W, the K = 4 prologue only with grid_capable, W % 4 == 0 and
+//      aligned u8 input; integer step-6 kinds only with kt != 0 and u8 planes; sad_exact false exactly beyond the
+//      bound; a split launch has nsplit == split, pairs == n and no tickets; of a gated pair exactly one launch runs
+//      for either value of the flag.
 //
 // Output: a line per violation ("violation <what>: <inputs>", the first 60), then
 //   "launch-plan plans <n> kinds <n> directed <n> routes <FILTERED> <EXACT> <FAST> <AUTO_ONE_LAUNCH> <AUTO_GATED> refused <n>
 //    refine <FLOAT> <INT> <INT_V> <AUTO> <AUTO_V> hash <fnv-1a of every (inputs -> plan) of the sweep> violations <n>
 //    specs <launch specs compared> exact <GENERIC> <GENERIC_VOLUME> <TILED> split <exact launches split> form <SPARSE>
-//    <PASS1_ONLY> <DENSE> <DENSE_SMALL> dense-fallback <n>".
+//    <PASS1_ONLY> <DENSE> <DENSE_SMALL> dense-fallback <n> hash2 <fnv-1a of the fields of item 5> prologue <GENERIC> <K2> <K4>
+//    fill <FILL_4> <POW2> <GENERIC> sx0 <plans whose step 6 evaluates the parabola> params <MatchParams compared>".
+//  `hash` covers the fields it covered before item 5 existed (it does not move when only those are added); `hash2` the rest.
 //
 // Other uses (tests/test_launch_spec_gpu.py), on the CU count given:
 //   launch_plan_harness spec <cus> <radii> <K> <h> <w> <Dd> <dmin> <B> <mode> <opt dense> <opt dense small> <in_mode> <lanes>
-//                       <dense> <filter> <hint> <n> <whole>     one line "keys ..." : the spec keys of that plan
+//                       <dense> <filter> <hint> <n> <whole> <crop> <aligned>
+//                                                                one line "keys ..." : the spec keys of that plan
+//                       (crop: W = K * w - crop; aligned: the caller's u8 pointers)
 //   launch_plan_harness reach <cus>                              "reach-small ..." / "reach-large-only ...": the keys the
 //                       sweep's configurations reach at its two smallest shapes, and those only its larger shapes reach
 #include <cstdarg>
@@ -50,6 +64,7 @@ static void violation(const char *fmt, ...) {
 struct Config {
     bool default_radii = true;
     int K = 2, h = 188, w = 621, Dd = 64, dmin = 0, sad = 5, B = 64;
+    int crop = 0;                   // W = K * w - crop (< K): a width that is no multiple of K
     int match_mode = SMX_MATCH_AUTO, exact_filter = 0, cus = 256;
     PlanOptions opt;
 };
@@ -57,21 +72,21 @@ struct Config {
 static EngineFacts facts_of(const Config &c) {
     smx_config cfg;
     memset(&cfg, 0, sizeof(cfg));
-    cfg.height = (unsigned)(c.h * c.K); cfg.width = (unsigned)(c.w * c.K); cfg.downscale_factor = (unsigned)c.K;
+    cfg.height = (unsigned)(c.h * c.K); cfg.width = (unsigned)(c.w * c.K - c.crop); cfg.downscale_factor = (unsigned)c.K;
     cfg.min_disparity = c.dmin * c.K; cfg.max_disparity = (c.dmin + c.Dd) * c.K - 1;
     cfg.ncc_patch_radius = 1; cfg.sad_patch_radius = (unsigned)c.sad; cfg.threshold = 5;
     cfg.small_mbm_radius = c.default_radii ? 1 : 2; cfg.mid_mbm_radius = c.default_radii ? 4 : 3; cfg.large_mbm_radius = c.default_radii ? 10 : 8;
     cfg.max_batch = c.B; cfg.match_mode = c.match_mode; cfg.exact_filter = c.exact_filter;
     smx_dims d;
-    d.H = c.h * c.K; d.W = c.w * c.K; d.K = c.K; d.h = c.h; d.w = c.w; d.dmin = c.dmin; d.dmax = c.dmin + c.Dd - 1; d.Dd = c.Dd;
+    d.H = c.h * c.K; d.W = c.w * c.K - c.crop; d.K = c.K; d.h = c.h; d.w = c.w; d.dmin = c.dmin; d.dmax = c.dmin + c.Dd - 1; d.Dd = c.Dd;
     return derive_facts(cfg, d, c.cus, c.opt);
 }
 
 static const char *describe(const Config &c, const CallFacts &call, int n, bool whole) {
     static char buf[256];
-    snprintf(buf, sizeof(buf), "radii %d K %d %dx%d Dd %d dmin %d sad %d B %d mode %d filter %d cus %d opt %d %d | in %d lanes %d dense %d filt %d hint %d | n %d whole %d",
-             c.default_radii ? 1 : 0, c.K, c.h, c.w, c.Dd, c.dmin, c.sad, c.B, c.match_mode, c.exact_filter, c.cus, c.opt.fast_dense, c.opt.fast_dense_small,
-             call.in_mode, call.on_lanes ? 1 : 0, call.route.fast_dense ? 1 : 0, call.route.use_filter ? 1 : 0, call.route.grid_hint, n, whole ? 1 : 0);
+    snprintf(buf, sizeof(buf), "radii %d K %d %dx%d crop %d Dd %d dmin %d sad %d B %d mode %d filter %d cus %d opt %d %d | in %d al %d lanes %d dense %d filt %d hint %d | n %d whole %d",
+             c.default_radii ? 1 : 0, c.K, c.h, c.w, c.crop, c.Dd, c.dmin, c.sad, c.B, c.match_mode, c.exact_filter, c.cus, c.opt.fast_dense, c.opt.fast_dense_small,
+             call.in_mode, call.u8_aligned ? 1 : 0, call.on_lanes ? 1 : 0, call.route.fast_dense ? 1 : 0, call.route.use_filter ? 1 : 0, call.route.grid_hint, n, whole ? 1 : 0);
     return buf;
 }
 
@@ -181,6 +196,125 @@ static FilterLaunch old_launch_match_filter(const EngineFacts &f, MatchParams p,
     return FilterLaunch{pl.th, pl.wide, p.unit <= 4.0f ? 2 : (p.unit <= 16.0f ? 1 : 0)};
 }
 
+// ---- the glue around the specs of item 5, restated -------------------------------------------------------------------------
+// Written by hand from tu_stages.hip (launch_prologue / prologue_t, launch_fill) and from enqueue_range of smx_engine.hip as
+// they were while they decided for themselves; not built by calling smx_plan.h.
+static int old_launch_prologue(int in_mode, const Config &c, const EngineFacts &f, bool aligned) {
+    const int K = c.K, W = c.w * c.K - c.crop;                   // PrologueArgs as enqueue_range filled them
+    const int grid_capable = f.grid_capable ? 1 : 0, pitch8 = f.pitch8, padl = f.padl, gpitch = f.gpitch, gpadl = f.gpadl;
+    if ((in_mode == IN_GRAY_F32 || in_mode == IN_GRAY_U8) && K == 2 && (W & 1) == 0) return PROLOGUE_K2;
+    const bool U8IN = in_mode == IN_GRAY_U8 || in_mode == IN_RGB_U8;
+    if (K == 4 && (W & 3) == 0 && grid_capable && (gpitch & 3) == 0 && (gpadl & 3) == 0 && (pitch8 & 3) == 0 && (padl & 3) == 0 &&
+        (gpadl == 0 || gpadl == padl) && (!U8IN || aligned))
+        return PROLOGUE_K4;
+    return PROLOGUE_GENERIC;
+}
+struct FillInst { int kernel, K, px; };                          // k_fill4<K, px> or k_fill<pow2> (K, px 0)
+static FillInst old_launch_fill(int K, int px) {
+    const bool pow2 = (K & (K - 1)) == 0;
+    if (K == 1) return FillInst{FILL_4, 1, 4};
+    else if (K == 2 && px == 4) return FillInst{FILL_4, 2, 4};
+    else if (K == 2) return FillInst{FILL_4, 2, 8};
+    else if (K == 4 && px == 4) return FillInst{FILL_4, 4, 4};
+    else if (K == 4) return FillInst{FILL_4, 4, 8};
+    else if (pow2) return FillInst{FILL_POW2, 0, 0};
+    return FillInst{FILL_GENERIC, 0, 0};
+}
+static FillInst fill_inst(const FillLaunch &x) {                 // the instantiation the table of launch_fill names for a spec
+    if (x.kernel != FILL_4) return FillInst{x.kernel, 0, 0};
+    return FillInst{FILL_4, x.K, x.K == 1 ? 4 : x.px};
+}
+// enqueue_range's aggregation part: the shared MatchParams `mp`, the four lambdas and the switch over the route, with every
+// launch replaced by a record of the MatchParams it was handed
+static int dummy_flags[1], dummy_flags2[1];
+static unsigned dummy_tickets[1];
+static unsigned long long dummy_stats[1];
+static float dummy_f[1];
+struct OldParams { MatchParams exact, exact_capture, fast, fast_capture, auto_small, filter, sparse; };
+static OldParams old_enqueue_range(const EngineFacts &f, const RangePlan &pl, MatchParams mp, int n) {
+    OldParams o{};
+    auto exact_capture = [&](MatchParams p) {
+        if (!pl.capture_follows) return;
+        p.nd_chunk = pl.exact_capture.nd_chunk;
+        p.nsplit = pl.exact_capture.split;
+        o.exact_capture = p;
+    };
+    auto exact = [&](MatchParams p) {
+        p.nd_chunk = pl.exact.nd_chunk;
+        if (pl.exact.split > 1) {
+            p.nsplit = pl.exact.split;
+            p.pairs = n;
+            p.tickets = nullptr;
+        }
+        o.exact = p;
+    };
+    auto fast_params = [&](MatchParams p, int gate) -> MatchParams {
+        p.gate = gate;
+        p.dense = pl.dense ? 1 : 0;
+        p.dense_small = pl.dense_small ? 1 : 0;
+        if (pl.fill_publishes) {
+            p.fast_stats = dummy_stats;
+            p.fast_stride = pl.stride;
+        }
+        return p;
+    };
+    auto fast = [&](int gate) {
+        const MatchParams p = fast_params(mp, gate);
+        o.fast = p;
+        if (pl.capture_follows) o.fast_capture = p;
+    };
+    switch (pl.route) {
+    case AGG_FILTERED: {
+        if (pl.gated_dense_first) {
+            MatchParams dp = mp;
+            dp.flags = dummy_flags2;
+            dp.gate = 2;
+            exact(dp);
+        }
+        MatchParams fmp = mp;
+        fmp.unit = (float)f.filter_unit;
+        o.filter = fmp;
+        MatchParams sp = mp;
+        sp.nd_chunk = f.exact2_nd;
+        o.sparse = sp;
+        exact_capture(mp);
+        break;
+    }
+    case AGG_EXACT:
+        exact(mp);
+        exact_capture(mp);
+        break;
+    case AGG_FAST: fast(0); break;
+    case AGG_AUTO_ONE_LAUNCH: {
+        MatchParams p = fast_params(mp, 0);
+        p.nsplit = pl.auto_launch.nsplit;
+        p.pairs = n;
+        p.nd_chunk = pl.auto_launch.nd_chunk;
+        o.auto_small = p;
+        break;
+    }
+    default:
+        mp.gate = 2;
+        exact(mp);
+        exact_capture(mp);
+        fast(1);
+        break;
+    }
+    return o;
+}
+static bool same_params(const MatchParams &a, const MatchParams &b) {
+    return a.Ld == b.Ld && a.Rd == b.Rd && a.wta == b.wta && a.costs == b.costs && a.vol == b.vol && a.flags == b.flags && a.epoch == b.epoch &&
+           a.B == b.B && a.h == b.h && a.w == b.w && a.dmin == b.dmin && a.Dd == b.Dd && a.rn == b.rn && a.rs == b.rs && a.rm == b.rm && a.rl == b.rl &&
+           a.gate == b.gate && a.nd_chunk == b.nd_chunk && a.unit == b.unit && a.nsplit == b.nsplit && a.pairs == b.pairs && a.slices == b.slices &&
+           a.pass1_only == b.pass1_only && a.dense == b.dense && a.dense_small == b.dense_small && a.fast_stats == b.fast_stats &&
+           a.fast_stride == b.fast_stride && a.on_lanes == b.on_lanes && a.tickets == b.tickets;
+}
+static bool gate_runs(int gate, bool flag) { return gate == 0 || (gate == 1 && !flag) || (gate == 2 && flag); }    // MatchParams::gate
+
+static const char *const ENTRY_NAMES[] = {"gray_f32", "rgb_f32", "gray_u8", "rgb_u8"};
+static const char *const PROLOGUE_NAMES[] = {"generic", "k2", "k4"};
+static const char *const REFINE_NAMES[] = {"FLOAT", "INT", "INT_V", "AUTO", "AUTO_V"};
+static const char *const FILL_NAMES[] = {"fill4", "pow2", "generic"};
 static const char *const EXACT_NAMES[] = {"GENERIC", "GENERIC_VOLUME", "TILED"};
 static const char *const FORM_NAMES[] = {"SPARSE", "PASS1_ONLY", "DENSE", "DENSE_SMALL"};
 static bool has_exact(const RangePlan &p) { return (p.route == AGG_FILTERED && p.gated_dense_first) || p.route == AGG_EXACT || p.route == AGG_AUTO_GATED; }
@@ -212,6 +346,12 @@ static void keys_of(const RangePlan &p, std::set<std::string> &keys) {
     }
     if (p.route == AGG_AUTO_ONE_LAUNCH) key("auto.th=%d.wide=%d", p.auto_launch.th, p.auto_launch.wide ? 1 : 0);
     if (p.route == AGG_FILTERED) key("filter.th=%d.wide=%d", p.filter.th, p.filter.wide ? 1 : 0);
+    // (a field the table does not look at for the row is printed as the row's only value)
+    key("prologue.%s.%s", ENTRY_NAMES[p.prologue.in_mode], PROLOGUE_NAMES[p.prologue.kernel]);
+    key("refine.%s.kt=%d.apron=%d.sx=%d", REFINE_NAMES[p.refine.kind], p.refine.kt, p.refine.kind == REFINE_FLOAT && p.refine.apron ? 1 : 0,
+        p.refine.kind == REFINE_FLOAT || p.refine.sad_exact ? 1 : 0);
+    const FillInst fi = fill_inst(p.fill);
+    key("fill.%s.k=%d.px=%d", FILL_NAMES[fi.kernel], fi.K, fi.px);
 }
 static std::set<std::string> *reach_keys = nullptr;                 // `reach`: collect instead of checking
 
@@ -223,6 +363,15 @@ static void mix(long long v) {
         plan_hash *= 1099511628211ull;
     }
 }
+static unsigned long long plan_hash2 = 1469598103934665603ull;
+static void mix2(long long v) {
+    for (int i = 0; i < 8; ++i) {
+        plan_hash2 ^= (unsigned long long)(v >> (8 * i)) & 0xffull;
+        plan_hash2 *= 1099511628211ull;
+    }
+}
+static bool extension = false;      // the sweep's extension (item 5): checked and hashed into hash2; not in the first hash nor in the counts before hash2
+static long prologues[3] = {}, fills[3] = {}, sx0 = 0, params_compared = 0;
 static long plans = 0, kinds = 0, refused = 0, routes[AGG_ROUTES] = {}, refines[5] = {};
 static long specs = 0, exact_kernels[3] = {}, exact_splits = 0, forms[FAST_FORMS] = {}, dense_fallbacks = 0;
 
@@ -234,9 +383,9 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
     if (has_exact(p)) {
         // (the gated dense launch of the filtered route never splits; the others as the plan allows)
         const OldExact o = old_launch_exact(f, mp, f.has_volume, n, p.route == AGG_FILTERED ? false : p.exact_split, f.cus);
-        ++specs;
-        exact_kernels[p.exact.kernel]++;
-        if (p.exact.split > 1) ++exact_splits;
+        if (!extension) ++specs;
+        if (!extension) exact_kernels[p.exact.kernel]++;
+        if (p.exact.split > 1 && !extension) ++exact_splits;
         SPEC_EQ("exact.kernel", p.exact.kernel, o.kernel);
         SPEC_EQ("exact.split", p.exact.split, o.split);
         SPEC_EQ("exact.rows_per_thread", p.exact.rows_per_thread, o.rows);
@@ -252,7 +401,7 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
     }
     if (has_exact_capture(p)) {
         const ExactCaptureLaunch o = old_launch_exact2_capture(f, mp, n, p.route == AGG_FILTERED ? false : p.exact_split, f.cus);
-        ++specs;
+        if (!extension) ++specs;
         SPEC_EQ("exact_capture.split", p.exact_capture.split, o.split);
         SPEC_EQ("exact_capture.rows_per_thread", p.exact_capture.rows_per_thread, o.rows_per_thread);
         SPEC_EQ("exact_capture.nd_chunk", p.exact_capture.nd_chunk, o.nd_chunk);
@@ -264,8 +413,8 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
         mp.dense = p.dense ? 1 : 0;                               // (enqueue_range: fast())
         mp.dense_small = p.dense_small ? 1 : 0;
         const FastLaunch o = old_launch_match_fast(mp, n, f.cus), &x = p.fast_launch;
-        ++specs;
-        forms[x.form]++;
+        if (!extension) ++specs;
+        if (!extension) forms[x.form]++;
         SPEC_EQ("fast.th", x.th, o.th);
         SPEC_EQ("fast.small", x.small, o.small);
         SPEC_EQ("fast.pitch", x.pitch, o.pitch);
@@ -281,10 +430,10 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
         if (x.form == FAST_DENSE_SMALL && (!x.small || x.th != FA_TH_SMALL_TALL || f.Dd > x.pitch - 64 + 1)) violation("DENSE_SMALL without an instantiation: %s", describe(c, call, n, whole));
         if ((x.form == FAST_PASS1_ONLY) != f.capture) violation("PASS1_ONLY: %s", describe(c, call, n, whole));
         if ((x.form == FAST_DENSE && !p.dense) || (x.form == FAST_DENSE_SMALL && !p.dense_small)) violation("dense form not planned: %s", describe(c, call, n, whole));
-        if ((p.dense || p.dense_small) && x.form == FAST_SPARSE) ++dense_fallbacks;
+        if ((p.dense || p.dense_small) && x.form == FAST_SPARSE && !extension) ++dense_fallbacks;
         if (p.capture_follows) {
             const FastCaptureLaunch oc = old_launch_match_capture(mp, n, f.cus);
-            ++specs;
+            if (!extension) ++specs;
             SPEC_EQ("fast_capture.small", p.fast_capture.small, oc.small);
             SPEC_EQ("fast_capture.wide", p.fast_capture.wide, oc.wide);
             SPEC_EQ("fast_capture.pk", p.fast_capture.pk, oc.pk);
@@ -292,7 +441,7 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
     }
     if (p.route == AGG_AUTO_ONE_LAUNCH) {
         const AutoLaunch o = old_launch_match_auto_small(f, mp, n, f.cus), &x = p.auto_launch;
-        ++specs;
+        if (!extension) ++specs;
         SPEC_EQ("auto.th", x.th, o.th);
         SPEC_EQ("auto.wide", x.wide, o.wide);
         SPEC_EQ("auto.pk", x.pk, o.pk);
@@ -305,7 +454,7 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
     }
     if (p.route == AGG_FILTERED) {
         const FilterLaunch o = old_launch_match_filter(f, mp, n, f.cus);
-        ++specs;
+        if (!extension) ++specs;
         SPEC_EQ("filter.th", p.filter.th, o.th);
         SPEC_EQ("filter.wide", p.filter.wide, o.wide);
         SPEC_EQ("filter.pk", p.filter.pk, o.pk);
@@ -314,10 +463,103 @@ static void check_specs(const Config &c, const EngineFacts &f, const CallFacts &
 #undef SPEC_EQ
 }
 
+// item 5 of the head comment: the prologue (a refused plan has one too) ...
+static void check_prologue(const Config &c, const EngineFacts &f, const CallFacts &call, const RangePlan &p, int n, bool whole) {
+    const int W = c.w * c.K - c.crop;
+    const bool u8 = call.in_mode == IN_GRAY_U8 || call.in_mode == IN_RGB_U8;
+    for (int aligned = 1; aligned >= 0; --aligned) {
+        CallFacts ca = call;
+        ca.u8_aligned = aligned != 0;
+        // (an unaligned call: the whole plan once more where the entry reads u8, the spec function alone elsewhere)
+        const PrologueLaunch x = ca.u8_aligned == call.u8_aligned ? p.prologue : (u8 ? plan_range(f, ca, n, whole).prologue : prologue_launch(f, ca));
+        const int o = old_launch_prologue(ca.in_mode, c, f, ca.u8_aligned);
+        prologues[x.kernel]++;
+        mix2(x.in_mode * 4 + x.kernel);
+        if (x.in_mode != ca.in_mode || x.kernel != o) violation("spec prologue: %d, the parent's launcher %d: %s", x.kernel, o, describe(c, ca, n, whole));
+        if (x.kernel == PROLOGUE_K2 && (c.K != 2 || (ca.in_mode != IN_GRAY_F32 && ca.in_mode != IN_GRAY_U8) || (W & 1))) violation("K = 2 prologue: %s", describe(c, ca, n, whole));
+        if (x.kernel == PROLOGUE_K4 && (c.K != 4 || !f.grid_capable || (W & 3) || (u8 && !ca.u8_aligned))) violation("K = 4 prologue: %s", describe(c, ca, n, whole));
+    }
+}
+// ... step 6, the fill, the gates and the parameters of the aggregation launches
+static void check_rest(const Config &c, const EngineFacts &f, const CallFacts &call, const RangePlan &p, int n, bool whole) {
+#define d describe(c, call, n, whole)
+    // step 6: enqueue_range computed sad_exact from the configuration on every call (min_disparity = dmin * K here)
+    const bool old_sad_exact = (long long)c.K * ((long long)(c.dmin * c.K) / c.K + c.Dd) <= 271;
+    const RefineLaunch &r = p.refine;
+    if (r.sad_exact != old_sad_exact) violation("spec refine.sad_exact: %d, enqueue_range %d: %s", r.sad_exact ? 1 : 0, old_sad_exact ? 1 : 0, d);
+    if (r.sad_exact != (c.K * (c.dmin + c.Dd) <= 271)) violation("sad_exact against the bound: %s", d);
+    if (r.kind != REFINE_FLOAT && (r.kt == 0 || !f.has_u8_planes() || r.apron)) violation("integer step 6 without kt or the u8 planes: %s", d);
+    if (r.kt != 0 && r.kt != 1 && r.kt != 2 && r.kt != 4) violation("refine kt: %s", d);
+    if (r.apron && (r.kt == 0 || !p.owns_gray)) violation("refine apron: %s", d);
+    if (!r.sad_exact) ++sx0;
+    // the fill: launch_fill chose from (fp.K, px), enqueue_range computed log2k
+    int old_log2k = 0;
+    while ((1 << old_log2k) < c.K) old_log2k++;
+    const FillInst fo = old_launch_fill(c.K, call.on_lanes && n > 4 ? 4 : 8), fn = fill_inst(p.fill);
+    if (fn.kernel != fo.kernel || fn.K != fo.K || fn.px != fo.px || p.fill.K != c.K || p.fill.log2k != old_log2k)
+        violation("spec fill: %d %d %d log2k %d, the parent %d %d %d log2k %d: %s", fn.kernel, fn.K, fn.px, p.fill.log2k, fo.kernel, fo.K, fo.px, old_log2k, d);
+    fills[p.fill.kernel]++;
+    mix2(((r.sad_exact ? 1 : 0) * 4 + p.fill.kernel) * 64 + p.fill.K * 4 + p.fill.log2k);
+    // the aggregation launches: what the parent's enqueue_range handed each, against the parameter functions
+    RangeParams b;
+    b.mp = engine_params(c, f, p, call.on_lanes);
+    b.mp.Ld = b.mp.Rd = dummy_f; b.mp.wta = b.mp.costs = b.mp.slices = dummy_f;
+    b.mp.flags = dummy_flags; b.mp.epoch = 7; b.mp.tickets = dummy_tickets;
+    b.range_flags = dummy_flags2;
+    b.fast_stats = dummy_stats;
+    const OldParams o = old_enqueue_range(f, p, b.mp, n);
+    auto cmp = [&](const char *what, const MatchParams &got, const MatchParams &want) {
+        ++params_compared;
+        if (!same_params(got, want)) violation("params %s (gate %d / %d, nsplit %d / %d, pairs %d / %d, nd_chunk %d / %d): %s", what, got.gate, want.gate,
+                                               got.nsplit, want.nsplit, got.pairs, want.pairs, got.nd_chunk, want.nd_chunk, d);
+        for (long long v : {(long long)got.gate, (long long)(got.flags == dummy_flags2), (long long)got.nsplit, (long long)got.pairs, (long long)got.nd_chunk,
+                            (long long)(got.tickets != nullptr), (long long)got.dense, (long long)got.dense_small, (long long)(got.fast_stats != nullptr),
+                            (long long)got.fast_stride, (long long)got.unit})
+            mix2(v);
+    };
+    const bool gated = p.route == AGG_AUTO_GATED;
+    if (has_exact(p)) {
+        const MatchParams m = exact_params(b, p.exact, n);
+        cmp("exact", m, o.exact);
+        if (p.exact.split > 1 && (m.nsplit != p.exact.split || m.pairs != n || m.tickets)) violation("split launch parameters: %s", d);
+        if (p.exact.gate != (p.route == AGG_FILTERED || gated ? 2 : 0) || (p.exact.gate_flag == GATE_RANGE_FLAG) != (p.route == AGG_FILTERED))
+            violation("exact gate: %s", d);
+    }
+    if (has_exact_capture(p)) {
+        cmp("exact_capture", exact_capture_params(b, p.exact_capture), o.exact_capture);
+        if (p.exact_capture.gate != (gated ? 2 : 0)) violation("exact capture gate: %s", d);
+    }
+    if (has_fast(p)) {
+        cmp("fast", fast_params(b, p, p.fast_launch.gate), o.fast);
+        if (p.capture_follows) cmp("fast_capture", fast_params(b, p, p.fast_capture.gate), o.fast_capture);
+        if (p.fast_launch.gate != (gated ? 1 : 0) || (p.capture_follows && p.fast_capture.gate != p.fast_launch.gate)) violation("fast gate: %s", d);
+    }
+    if (gated)      // both on the grid flag: exactly one of the pair does the work, whatever the flag says
+        for (int flag = 0; flag < 2; ++flag)
+            if (p.exact.gate_flag != GATE_GRID_FLAG || gate_runs(p.exact.gate, flag != 0) == gate_runs(p.fast_launch.gate, flag != 0) ||
+                (p.capture_follows && gate_runs(p.exact_capture.gate, flag != 0) == gate_runs(p.fast_capture.gate, flag != 0)) ||
+                (p.capture_follows && gate_runs(p.exact_capture.gate, flag != 0) != gate_runs(p.exact.gate, flag != 0)))
+                violation("gated pair: %s", d);
+    if (p.route == AGG_AUTO_ONE_LAUNCH) cmp("auto", auto_params(b, p, n), o.auto_small);
+    if (p.route == AGG_FILTERED) {
+        cmp("filter", filter_params(b, f), o.filter);
+        cmp("sparse", sparse_params(b, f), o.sparse);
+    }
+#undef d
+}
+
 static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &call, int n, bool whole) {
     const RangePlan p = plan_range(f, call, n, whole);
     if (reach_keys) {
         if (p.status == SMX_OK) keys_of(p, *reach_keys);
+        return;
+    }
+    check_prologue(c, f, call, p, n, whole);
+    if (extension) {
+        if (p.status == SMX_OK) {
+            check_specs(c, f, call, p, n, whole);
+            check_rest(c, f, call, p, n, whole);
+        }
         return;
     }
     ++plans;
@@ -330,13 +572,13 @@ static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &c
         return;
     }
     routes[p.route]++;
-    refines[p.refine_kind]++;
+    refines[p.refine.kind]++;
     // every field enqueue_range reads, one per bit field (the stride as the launch gets it: only with a report)
     unsigned long long word = 0;
     for (unsigned v : {(unsigned)p.mode, (unsigned)p.route, (unsigned)p.gated_dense_first, (unsigned)p.exact_split, (unsigned)p.capture_follows,
                        (unsigned)p.fast.small, (unsigned)p.fast.th, (unsigned)p.fast.wide, (unsigned)p.dense, (unsigned)p.dense_small, (unsigned)p.reports,
-                       (unsigned)(p.fill_publishes ? p.stride : 0), (unsigned)p.fill_publishes, (unsigned)p.owns_gray, (unsigned)p.refine_kind,
-                       (unsigned)p.kt, (unsigned)p.refine_apron, (unsigned)p.refine_reports_grid, (unsigned)p.fill_px})
+                       (unsigned)(p.fill_publishes ? p.stride : 0), (unsigned)p.fill_publishes, (unsigned)p.owns_gray, (unsigned)p.refine.kind,
+                       (unsigned)p.refine.kt, (unsigned)p.refine.apron, (unsigned)p.refine_reports_grid, (unsigned)p.fill.px})
         word = word * 67 + v;
     mix((long long)word);
     // ... and every field of the launch specs (value-initialised where the route has no such launch)
@@ -352,6 +594,7 @@ static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &c
         sw = sw * 1000003ull + (unsigned long long)v;
     mix((long long)sw);
     check_specs(c, f, call, p, n, whole);
+    check_rest(c, f, call, p, n, whole);
     const bool rgb = call.in_mode == IN_RGB_F32 || call.in_mode == IN_RGB_U8;
     if (p.route == AGG_AUTO_ONE_LAUNCH) {
         MatchParams mp{};
@@ -370,8 +613,8 @@ static void check_plan(const Config &c, const EngineFacts &f, const CallFacts &c
     if ((p.dense || p.dense_small) && (f.capture || f.Dd > FA_BITWORDS * 32 || !p.has_fast_launch())) violation("dense form: %s", describe(c, call, n, whole));
     if ((p.mode == SMX_MATCH_EXACT_ORDER) != (p.route == AGG_FILTERED || p.route == AGG_EXACT) || (p.mode == SMX_MATCH_FAST_GRID) != (p.route == AGG_FAST))
         violation("mode: %s", describe(c, call, n, whole));
-    if (p.fill_px != (call.on_lanes && n > 4 ? 4 : 8)) violation("fill width: %s", describe(c, call, n, whole));
-    if (p.refine_reports_grid && (p.refine_kind != REFINE_AUTO || !whole)) violation("grid report: %s", describe(c, call, n, whole));
+    if (p.fill.px != (call.on_lanes && n > 4 ? 4 : 8)) violation("fill width: %s", describe(c, call, n, whole));
+    if (p.refine_reports_grid && (p.refine.kind != REFINE_AUTO || !whole)) violation("grid report: %s", describe(c, call, n, whole));
 }
 
 // what an executor of the plans of a call's range(s) under the default decision would do, against call_kind
@@ -415,8 +658,8 @@ static void sweep_facts(const Config &c) {
     for (int in_mode : {IN_GRAY_F32, IN_RGB_F32, IN_GRAY_U8, IN_RGB_U8})
         for (int on_lanes = 0; on_lanes < 2; ++on_lanes)
             for (int n = 1; n <= c.B; ++n) {
-                if (!reach_keys) check_kind(c, f, in_mode, on_lanes != 0, n, 0);
-                if (!reach_keys && on_lanes && n >= 2) check_kind(c, f, in_mode, true, (n + 1) / 2, n - (n + 1) / 2);
+                if (!reach_keys && !extension) check_kind(c, f, in_mode, on_lanes != 0, n, 0);
+                if (!reach_keys && !extension && on_lanes && n >= 2) check_kind(c, f, in_mode, true, (n + 1) / 2, n - (n + 1) / 2);
                 CallFacts call;
                 call.in_mode = in_mode;
                 call.on_lanes = on_lanes != 0;
@@ -471,6 +714,26 @@ static void sweep(int only_cus = 0, bool large = false) {
                                         }
 }
 
+// The extension of item 5: what the sweep above does not hold and the specs of item 5 depend on -- K = 8 (the power-of-two
+// generic fill, kt = 0) and widths that are no multiple of K (the prologue's fallbacks) -- in AUTO mode on 256 CUs.
+static void sweep_extension(int only_cus = 0, bool large = false) {
+    const int shapes[3][2] = {{48, 80}, {64, 128}, {187, 621}};
+    const int kc[6][2] = {{8, 0}, {8, 4}, {2, 1}, {3, 1}, {4, 1}, {4, 2}};
+    extension = true;
+    for (const auto &k : kc)
+        for (int dmin : {0, 8})
+            for (const auto &shape : shapes)
+                for (int Dd : {16, 64})
+                    for (int B : {1, 4, 64}) {
+                        if (only_cus > 0 && (shape[0] > 64) != large) continue;
+                        Config c;
+                        c.K = k[0]; c.crop = k[1]; c.dmin = dmin; c.h = shape[0]; c.w = shape[1]; c.Dd = Dd; c.B = B;
+                        c.cus = only_cus > 0 ? only_cus : 256;
+                        sweep_facts(c);
+                    }
+    extension = false;
+}
+
 // ---- the directed table ---------------------------------------------------------------------------------------------------
 // Written by hand from the rules of enqueue_range as it was before the planner existed; not generated from smx_plan.h.
 // C2's pooled 188 x 621, 64 disparities, K 2, 256 CUs, max_batch 64, default radii unless a row says otherwise: a call of
@@ -521,20 +784,20 @@ static void directed_table() {
         }
         // step 6
         p = plan_range(f, call_of(IN_RGB_F32, false, false, true, -1), 32, wc);
-        expect(p.refine_kind == REFINE_FLOAT && p.kt == 2 && p.refine_apron && p.owns_gray, "refine RGB: float, on the engine's aproned planes");
+        expect(p.refine.kind == REFINE_FLOAT && p.refine.kt == 2 && p.refine.apron && p.owns_gray, "refine RGB: float, on the engine's aproned planes");
         p = plan_range(f, call_of(IN_GRAY_U8, false, false, true, -1), 4, wc);
-        expect(p.refine_kind == REFINE_INT && p.kt == 2 && !p.refine_apron, "refine u8 gray n=4: int");
+        expect(p.refine.kind == REFINE_INT && p.refine.kt == 2 && !p.refine.apron, "refine u8 gray n=4: int");
         p = plan_range(f, call_of(IN_GRAY_U8, false, false, true, -1), 5, wc);
-        expect(p.refine_kind == REFINE_INT_V, "refine u8 gray n=5: int_v");
+        expect(p.refine.kind == REFINE_INT_V, "refine u8 gray n=5: int_v");
         p = plan_range(f, call_of(IN_GRAY_F32, false, false, true, -1), 4, wc);
-        expect(p.refine_kind == REFINE_AUTO && p.refine_reports_grid == wc && !p.owns_gray, "refine f32 gray n=4: auto, reports the grid flag iff whole call");
+        expect(p.refine.kind == REFINE_AUTO && p.refine_reports_grid == wc && !p.owns_gray, "refine f32 gray n=4: auto, reports the grid flag iff whole call");
         p = plan_range(f, call_of(IN_GRAY_F32, false, false, true, -1), 5, wc);
-        expect(p.refine_kind == REFINE_AUTO_V && !p.refine_reports_grid, "refine f32 gray n=5: auto_v");
+        expect(p.refine.kind == REFINE_AUTO_V && !p.refine_reports_grid, "refine f32 gray n=5: auto_v");
         // fill width
         for (int n : {4, 5, 32})
             for (int lanes = 0; lanes < 2; ++lanes) {
                 p = plan_range(f, call_of(IN_GRAY_U8, lanes != 0, false, true, -1), n, wc);
-                expect(p.fill_px == (lanes && n > 4 ? 4 : 8), "fill width: 4 iff on the lanes and n > 4");
+                expect(p.fill.px == (lanes && n > 4 ? 4 : 8), "fill width: 4 iff on the lanes and n > 4");
             }
         // form of the fast kernel, by content: the throughput shape (32 pairs) and the latency shape at 12-row bands (1 pair:
         // 15 windows x 24 bands of 8 rows = 360 workgroups > 256 CUs, 240 of 12 rows fit) have a dense form
@@ -625,7 +888,7 @@ static void directed_table() {
         c.match_mode = SMX_MATCH_AUTO;
         f3 = facts_of(c);
         const RangePlan p = plan_range(f3, call_of(IN_GRAY_U8, false, false, true, -1), 1, true);
-        expect(p.status == SMX_OK && p.route == AGG_EXACT && p.refine_kind == REFINE_FLOAT && p.kt == 0, "K = 3, AUTO: exact, generic step 6");
+        expect(p.status == SMX_OK && p.route == AGG_EXACT && p.refine.kind == REFINE_FLOAT && p.refine.kt == 0, "K = 3, AUTO: exact, generic step 6");
     }
     {   // sad_patch_radius 4: the generic float step-6 kernel, whatever the entry
         Config c = c2;
@@ -633,7 +896,7 @@ static void directed_table() {
         const EngineFacts f4 = facts_of(c);
         for (int in_mode : {IN_GRAY_F32, IN_RGB_F32, IN_GRAY_U8, IN_RGB_U8}) {
             const RangePlan p = plan_range(f4, call_of(in_mode, false, false, true, -1), 4, true);
-            expect(p.refine_kind == REFINE_FLOAT && p.kt == 0 && !p.refine_apron && !p.refine_reports_grid, "sad_patch_radius 4: float, kt 0");
+            expect(p.refine.kind == REFINE_FLOAT && p.refine.kt == 0 && !p.refine.apron && !p.refine_reports_grid, "sad_patch_radius 4: float, kt 0");
         }
     }
     {   // the launch specs of the examples the source comments give (k_match_exact2.h: exact_split, capture_split; tu_fast_small.hip)
@@ -662,6 +925,83 @@ static void directed_table() {
         expect(p.fast.th == 32 && p.dense && p.fast_launch.th == 32 && p.fast_launch.form == FAST_SPARSE && !p.fast_launch.argb,
                "32-row plan, dense form, Dd 257: launches 32 rows sparse (no dense instantiation)");
     }
+    {   // the specs around the aggregation: steps 1-2 ...
+        auto prologue = [](int K, int w, int crop, int in_mode, bool aligned) {
+            Config c;
+            c.K = K; c.h = 48; c.w = w; c.crop = crop; c.Dd = 16;
+            CallFacts call = call_of(in_mode, false, false, true, -1);
+            call.u8_aligned = aligned;
+            const RangePlan p = plan_range(facts_of(c), call, 1, true);
+            return p.prologue.in_mode == in_mode ? p.prologue.kernel : -1;
+        };
+        expect(prologue(2, 80, 0, IN_GRAY_F32, true) == PROLOGUE_K2 && prologue(2, 80, 0, IN_GRAY_U8, false) == PROLOGUE_K2, "K = 2, W = 160, gray: two pixels per thread, whatever the alignment");
+        expect(prologue(2, 80, 1, IN_GRAY_F32, true) == PROLOGUE_GENERIC && prologue(2, 80, 1, IN_GRAY_U8, true) == PROLOGUE_GENERIC, "K = 2, W = 159 (odd): generic");
+        expect(prologue(2, 80, 0, IN_RGB_F32, true) == PROLOGUE_GENERIC && prologue(2, 80, 0, IN_RGB_U8, true) == PROLOGUE_GENERIC, "K = 2, RGB: generic");
+        for (int in_mode : {IN_GRAY_F32, IN_RGB_F32, IN_GRAY_U8, IN_RGB_U8}) {
+            const bool u8 = in_mode == IN_GRAY_U8 || in_mode == IN_RGB_U8;
+            expect(prologue(4, 80, 0, in_mode, true) == PROLOGUE_K4, "K = 4, W = 320: the block kernel");
+            expect(prologue(4, 80, 2, in_mode, true) == PROLOGUE_GENERIC, "K = 4, W = 318: generic");
+            expect(prologue(4, 80, 0, in_mode, false) == (u8 ? PROLOGUE_GENERIC : PROLOGUE_K4), "K = 4, W = 320, pointers off by a byte: generic for the u8 entries only");
+            expect(prologue(1, 80, 0, in_mode, true) == PROLOGUE_GENERIC && prologue(3, 80, 0, in_mode, true) == PROLOGUE_GENERIC &&
+                   prologue(8, 80, 0, in_mode, true) == PROLOGUE_GENERIC, "K = 1, 3, 8: generic");
+        }
+        Config c = c2;
+        c.match_mode = SMX_MATCH_FAST_GRID;
+        c.K = 3;
+        expect(plan_range(facts_of(c), call_of(IN_RGB_U8, false, false, true, -1), 1, true).prologue.in_mode == IN_RGB_U8, "a refused plan names its prologue");
+    }
+    {   // ... step 6: the SAD parabola is exact up to |abscissa| 271 = K * (min_disparity / K + disparities) ...
+        Config c;
+        c.h = 32; c.w = 160; c.Dd = 135;                        // max_disparity 269: 2 * 135 = 270
+        EngineFacts fs = facts_of(c);
+        expect(fs.sad_exact && fs.has_u8_planes() && plan_range(fs, call_of(IN_GRAY_U8, false, false, true, -1), 1, true).refine.sad_exact, "K 2, 135 disparities: exact");
+        c.Dd = 136;                                             // max_disparity 271: 2 * 136 = 272, left apron 284 of 320 columns
+        fs = facts_of(c);
+        expect(!fs.sad_exact && fs.has_u8_planes() && fs.padl == 284, "K 2, 136 disparities: beyond the bound, u8 planes fit");
+        const int kinds[4][3] = {{IN_GRAY_U8, 1, REFINE_INT}, {IN_GRAY_U8, 5, REFINE_INT_V}, {IN_GRAY_F32, 1, REFINE_AUTO}, {IN_GRAY_F32, 5, REFINE_AUTO_V}};
+        for (const auto &k : kinds) {
+            const RangePlan p = plan_range(fs, call_of(k[0], false, false, true, -1), k[1], true);
+            expect(p.refine.kind == k[2] && p.refine.kt == 2 && !p.refine.sad_exact && !p.refine.apron, "136 disparities: the evaluating integer kernels");
+        }
+        c.Dd = 128; c.dmin = 8;                                 // min_disparity counts: 2 * (8 + 128) = 272
+        expect(!facts_of(c).sad_exact, "min_disparity 16, 128 disparities: beyond the bound");
+        c = c2;
+        c.K = 8;
+        const RangePlan p = plan_range(facts_of(c), call_of(IN_GRAY_U8, false, false, true, -1), 1, true);
+        expect(p.refine.kind == REFINE_FLOAT && p.refine.kt == 0 && !p.refine.apron, "K = 8: generic float step 6");
+    }
+    {   // ... steps 7-9 ...
+        const int rows[5][4] = {{1, FILL_4, 0, 4}, {2, FILL_4, 1, 8}, {3, FILL_GENERIC, 2, 0}, {4, FILL_4, 2, 8}, {8, FILL_POW2, 3, 0}};   // K, kernel, log2k, px on a caller's stream
+        for (const auto &r : rows) {
+            Config c = c2;
+            c.K = r[0];
+            const EngineFacts fk = facts_of(c);
+            RangePlan p = plan_range(fk, call_of(IN_GRAY_U8, false, false, true, -1), 5, true);
+            FillInst fi = fill_inst(p.fill);
+            expect(p.fill.kernel == r[1] && p.fill.K == r[0] && p.fill.log2k == r[2] && fi.px == r[3], "fill kernel, log2k and pixels per thread by K");
+            p = plan_range(fk, call_of(IN_GRAY_U8, true, false, true, -1), 5, true);
+            fi = fill_inst(p.fill);
+            expect(fi.px == (r[0] == 2 || r[0] == 4 ? 4 : r[3]), "on the lanes, 5 pairs: 4 pixels per thread at K = 2 / 4");
+        }
+    }
+    {   // ... the gates and the parameters of a split launch
+        RangePlan p = plan_range(f, call_of(IN_RGB_F32, false, false, true, -1), 32, true);
+        expect(p.route == AGG_FILTERED && p.exact.gate == 2 && p.exact.gate_flag == GATE_RANGE_FLAG && p.exact.split == 1, "filtered, f32 RGB: the dense launch runs for flagged pairs, on the range flag");
+        p = plan_range(f, call_of(IN_GRAY_F32, false, false, true, 1), 1, true);
+        expect(p.route == AGG_AUTO_GATED && p.exact.gate == 2 && p.exact.gate_flag == GATE_GRID_FLAG && p.fast_launch.gate == 1, "gated: exact-order 2, fast 1, on the grid flag");
+        RangeParams b;
+        b.mp.tickets = dummy_tickets; b.mp.flags = dummy_flags; b.range_flags = dummy_flags2;
+        MatchParams m = exact_params(b, p.exact, 1);
+        expect(p.exact.split == 8 && m.gate == 2 && m.nsplit == 8 && m.pairs == 1 && m.nd_chunk == 8 && !m.tickets && m.flags == dummy_flags, "gated split launch: 8 slices, records of 1 pair, no tickets");
+        m = fast_params(b, p, p.fast_launch.gate);
+        expect(m.gate == 1 && m.nsplit == 0 && m.tickets == dummy_tickets, "gated fast launch: gate 1");
+        p = plan_range(f, call_of(IN_GRAY_U8, false, false, true, -1), 1, true);
+        expect(p.route == AGG_FAST && p.fast_launch.gate == 0 && p.exact.gate == 0, "u8 gray: ungated");
+        Config c = c2;
+        c.dmin = 8;
+        p = plan_range(facts_of(c), call_of(IN_GRAY_F32, false, false, true, 1), 1, true);
+        expect(p.capture_follows && p.exact_capture.gate == 2 && p.fast_capture.gate == 1, "capture, gated: the lookups carry their arg-max launch's gate");
+    }
     {   // the prediction on the table's shape
         CallKind k = call_kind(f, IN_RGB_U8, false, 32, 0);
         expect(k.filter_reports && !k.fast_reports, "kind: RGB n=32 reports to the filter switch");
@@ -685,21 +1025,25 @@ int main(int argc, char **argv) {
         std::set<std::string> small, large, only;
         reach_keys = &small;
         sweep(atoi(argv[2]), false);
+        sweep_extension(atoi(argv[2]), false);
         reach_keys = &large;
         sweep(atoi(argv[2]), true);
+        sweep_extension(atoi(argv[2]), true);
         for (const std::string &k : large)
             if (!small.count(k)) only.insert(k);
         print_keys("reach-small", small);
         print_keys("reach-large-only", only);
         return 0;
     }
-    if (argc == 20 && !strcmp(argv[1], "spec")) {
-        int a[18];
-        for (int i = 0; i < 18; ++i) a[i] = atoi(argv[2 + i]);
+    if (argc == 22 && !strcmp(argv[1], "spec")) {
+        int a[20];
+        for (int i = 0; i < 20; ++i) a[i] = atoi(argv[2 + i]);
         Config c;
         c.cus = a[0]; c.default_radii = a[1] != 0; c.K = a[2]; c.h = a[3]; c.w = a[4]; c.Dd = a[5]; c.dmin = a[6]; c.B = a[7]; c.match_mode = a[8];
-        c.opt.fast_dense = a[9]; c.opt.fast_dense_small = a[10];
-        const RangePlan p = plan_range(facts_of(c), call_of(a[11], a[12] != 0, a[13] != 0, a[14] != 0, a[15]), a[16], a[17] != 0);
+        c.opt.fast_dense = a[9]; c.opt.fast_dense_small = a[10]; c.crop = a[18];
+        CallFacts call = call_of(a[11], a[12] != 0, a[13] != 0, a[14] != 0, a[15]);
+        call.u8_aligned = a[19] != 0;
+        const RangePlan p = plan_range(facts_of(c), call, a[16], a[17] != 0);
         std::set<std::string> keys;
         if (p.status == SMX_OK) keys_of(p, keys);
         print_keys("keys", keys);
@@ -707,11 +1051,13 @@ int main(int argc, char **argv) {
     }
     directed_table();
     sweep();
+    sweep_extension();
     printf("launch-plan plans %ld kinds %ld directed %ld routes %ld %ld %ld %ld %ld refused %ld refine %ld %ld %ld %ld %ld hash %016llx violations %ld "
-           "specs %ld exact %ld %ld %ld split %ld form %ld %ld %ld %ld dense-fallback %ld\n",
+           "specs %ld exact %ld %ld %ld split %ld form %ld %ld %ld %ld dense-fallback %ld hash2 %016llx prologue %ld %ld %ld fill %ld %ld %ld sx0 %ld params %ld\n",
            plans, kinds, directed, routes[AGG_FILTERED], routes[AGG_EXACT], routes[AGG_FAST], routes[AGG_AUTO_ONE_LAUNCH], routes[AGG_AUTO_GATED],
            refused, refines[REFINE_FLOAT], refines[REFINE_INT], refines[REFINE_INT_V], refines[REFINE_AUTO], refines[REFINE_AUTO_V], plan_hash, violations,
            specs, exact_kernels[EXACT_GENERIC], exact_kernels[EXACT_GENERIC_VOLUME], exact_kernels[EXACT_TILED], exact_splits, forms[FAST_SPARSE],
-           forms[FAST_PASS1_ONLY], forms[FAST_DENSE], forms[FAST_DENSE_SMALL], dense_fallbacks);
+           forms[FAST_PASS1_ONLY], forms[FAST_DENSE], forms[FAST_DENSE_SMALL], dense_fallbacks, plan_hash2, prologues[PROLOGUE_GENERIC], prologues[PROLOGUE_K2],
+           prologues[PROLOGUE_K4], fills[FILL_4], fills[FILL_POW2], fills[FILL_GENERIC], sx0, params_compared);
     return violations == 0 ? 0 : 1;
 }

@@ -17,7 +17,15 @@ forms and three CU counts, and checks
      disparity split, LDS bytes, slice records) against the launcher glue of the time when the launchers still decided
      for themselves, restated by hand in the harness: no difference over the whole sweep; a split fits the lane's slice
      region and belongs to a whole call of at most 4 pairs; a dense form is planned only where its instantiation exists
-     (calls planned dense that launch the sparse instantiation are counted); the LDS stays within the raised caps.
+     (calls planned dense that launch the sparse instantiation are counted); the LDS stays within the raised caps;
+  5. the rest of the call: the prologue, step-6 and fill specs against launch_prologue's and launch_fill's own selection
+     and enqueue_range's sad_exact and log2k of the time before those specs, the gates and the MatchParams of every
+     aggregation launch (smx_plan.h: exact_params ... auto_params) against the lambdas enqueue_range had, all restated by
+     hand -- no difference over the sweep, the prologue also with unaligned u8 pointers, plus an extension (K = 8, widths
+     that are no multiple of K); the K = 2 prologue only for gray entries with even W, the K = 4 prologue only with W % 4
+     == 0 and aligned u8 input; integer step-6 kinds only with kt != 0 and the u8 planes; sad_exact false exactly beyond
+     the bound; a split launch has nsplit == split, pairs == n and no tickets; of a gated pair exactly one runs.  The
+     summary's first hash covers what it covered before item 5 (it equals the parent's), hash2 the new fields.
 
 Built like the slice-plan harness (host code only, no HIP runtime linked), with the address and undefined-behaviour
 sanitizers when their runtimes link that way and without them otherwise.  No GPU."""
@@ -68,7 +76,8 @@ def test_prediction_invariants_and_directed_table(harness):
     r = subprocess.run([harness], capture_output=True, text=True, timeout=600, env=env)
     summary = re.search(r"^launch-plan plans (\d+) kinds (\d+) directed (\d+) routes (\d+) (\d+) (\d+) (\d+) (\d+) refused (\d+) "
                         r"refine (\d+) (\d+) (\d+) (\d+) (\d+) hash ([0-9a-f]{16}) violations (\d+) "
-                        r"specs (\d+) exact (\d+) (\d+) (\d+) split (\d+) form (\d+) (\d+) (\d+) (\d+) dense-fallback (\d+)$", r.stdout, re.M)
+                        r"specs (\d+) exact (\d+) (\d+) (\d+) split (\d+) form (\d+) (\d+) (\d+) (\d+) dense-fallback (\d+) "
+                        r"hash2 ([0-9a-f]{16}) prologue (\d+) (\d+) (\d+) fill (\d+) (\d+) (\d+) sx0 (\d+) params (\d+)$", r.stdout, re.M)
     assert summary, r.stdout[-3000:] + r.stderr[-3000:]
     print(summary.group(0))
     plans, kinds, directed = (int(v) for v in summary.groups()[:3])
@@ -91,3 +100,11 @@ def test_prediction_invariants_and_directed_table(harness):
     assert all(v >= 1000 for v in exact.values()), exact
     assert all(v >= 1000 for v in forms.values()), forms
     assert directed >= 37, summary.group(0)
+    # the rest of the call: every prologue and fill kernel, step 6 beyond the parabola's bound, more parameter sets
+    # compared with the restated lambdas than plans, and the directed rows of the three specs and the gates
+    prologue = dict(zip(("GENERIC", "K2", "K4"), map(int, summary.groups()[27:30])))
+    fill = dict(zip(("FILL_4", "POW2", "GENERIC"), map(int, summary.groups()[30:33])))
+    sx0, params = int(summary.group(34)), int(summary.group(35))
+    assert all(v >= 1000 for v in prologue.values()), prologue
+    assert all(v >= 1000 for v in fill.values()), fill
+    assert sx0 >= 1000 and params > plans and directed >= 141, summary.group(0)

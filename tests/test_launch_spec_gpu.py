@@ -1,8 +1,8 @@
 """The table from launch spec to kernel instantiation (smx_launch.h) reaches the right kernels.
 
-plan_range() (stereo-depth_amd/csrc/smx_plan.h) names every aggregation launch of a call in a launch spec -- ExactLaunch,
-ExactCaptureLaunch, FastLaunch, FastCaptureLaunch, AutoLaunch, FilterLaunch -- and the launchers only look the instantiation
-up.  No device code is new here.  Every case below is one call whose plan holds one variant of a spec, run once and compared
+plan_range() (stereo-depth_amd/csrc/smx_plan.h) names every launch of a call in a launch spec -- PrologueLaunch, ExactLaunch,
+ExactCaptureLaunch, FastLaunch, FastCaptureLaunch, AutoLaunch, FilterLaunch, RefineLaunch, FillLaunch -- and the launchers
+only look the instantiation up.  No device code is new here.  Every case below is one call whose plan holds one variant of a spec, run once and compared
 bit for bit with the oracle, every stage (test_gpu_parity._check); which spec keys a case stands for is asked of the planner
 itself: tests/launch_plan_harness.cpp, built for the device's CU count, prints them for the case's configuration, entry,
 batch and decision (`spec`), and the keys its sweep's configurations reach at the two smallest pooled shapes, 48 x 80 and
@@ -39,12 +39,17 @@ OTHER_RADII = dict(ncc_patch_radius=1, small_mbm_radius=2, mid_mbm_radius=3, lar
 # hint only for such engines).  The split exact-order launch with 4 rows per thread needs a launch that fills the chip
 # about once (60 tiles x 8 slices).  At the smallest batch of the throughput shape the filter kernel picks 27-row bands and
 # the wide tile for both small shapes.
+# The integer step-6 kernels that evaluate the SAD parabola (sx=0: K * (min_disparity / K + disparities) > 271) need the u8
+# planes as well; at K = 1 that is an image wider than 280 columns with more than 271 disparities.
 LARGE_ONLY = {"auto.th=8.wide=1", "auto.th=10.wide=1", "auto.th=12.wide=1", "exact.split=yes.rows=4", "filter.th=24.wide=0",
-              "filter.th=24.wide=1", "filter.th=27.wide=0", "filter.th=32.wide=0"}
+              "filter.th=24.wide=1", "filter.th=27.wide=0", "filter.th=32.wide=0", "refine.INT.kt=1.apron=0.sx=0",
+              "refine.INT_V.kt=1.apron=0.sx=0", "refine.AUTO.kt=1.apron=0.sx=0", "refine.AUTO_V.kt=1.apron=0.sx=0"}
 
 class Case:
     def __init__(self, name, h, w, Dd, entry, n=1, dmin=0, K=2, radii=True, warm=False, dense=0, dense_small=-1,
-                 exact_filter=0, hint=-1, launches=None):
+                 exact_filter=0, hint=-1, launches=None, crop=0, offset=0, lanes=False):
+        # crop: W = K * w - crop; offset: the u8 inputs start that many bytes into their allocation; lanes: an engine-stream call
+        self.crop, self.offset, self.lanes = crop, offset, lanes
         self.name, self.h, self.w, self.Dd, self.entry, self.n, self.dmin, self.K = name, h, w, Dd, entry, n, dmin, K
         self.radii, self.warm, self.dense, self.dense_small = radii, warm, dense, dense_small
         self.exact_filter, self.hint, self.launches = exact_filter, hint, launches
@@ -54,7 +59,7 @@ class Case:
         return self.n if self.n else fc.min_pairs(self.h, self.w, cus)
 
 
-S, M = (48, 80), (64, 128)
+S, M, T = (48, 80), (64, 128), (32, 160)
 CASES = [
     # the latency shape: AUTO on f32 gray before any grid report (gated launches, the exact-order one split) ...
     Case("gated_split_th8", *S, 16, GRAY_F32, launches=(1, 1)),
@@ -85,6 +90,42 @@ CASES = [
     Case("tall_capture_wide", *S, 194, GRAY_U8, n=0, dmin=8, launches=(1, 0)),
     Case("filtered_u8", *S, 64, RGB_U8, n=0, exact_filter=1, launches=(1, 1)),
     Case("filtered_f32_gated_dense_capture", *M, 64, RGB_F32, n=0, dmin=8, exact_filter=1, launches=(1, 1)),
+    # steps 1-2: the generic prologue for a gray entry at K = 2 (W = 159), the K = 4 block kernel for every entry and its
+    # fallbacks (W = 318; u8 input that starts one byte into its allocation)
+    Case("prologue_generic_odd_w_f32", *S, 16, GRAY_F32, crop=1, launches=(1, 1)),
+    Case("prologue_generic_odd_w_u8", *S, 16, GRAY_U8, crop=1, launches=(1, 0)),
+    Case("prologue_k4_gray_f32", *S, 16, GRAY_F32, K=4, launches=(1, 1)),
+    Case("prologue_k4_rgb_u8", *S, 16, RGB_U8, K=4, launches=(0, 1)),
+    Case("prologue_k4_rgb_f32", *S, 16, RGB_F32, K=4, launches=(0, 1)),
+    Case("prologue_k4_fallback_w318", *S, 16, GRAY_U8, K=4, crop=2, launches=(1, 0)),
+    Case("prologue_k4_fallback_unaligned_u8", *S, 16, GRAY_U8, K=4, offset=1, launches=(1, 0)),
+    # steps 6 and 7-9, generic kernels: K = 3 (no power of two), K = 8 (power of two, kt = 0)
+    Case("generic_k3", *S, 16, GRAY_U8, K=3, launches=(0, 1)),
+    Case("generic_k8", *S, 16, GRAY_U8, K=8, launches=(1, 0)),
+    # K = 1: k_fill4<1, 4>, the step-6 kernels at kt = 1 and the generic prologue for both gray entries
+    Case("k1_int", *S, 16, GRAY_U8, K=1, launches=(1, 0)),
+    Case("k1_int_v", *S, 16, GRAY_U8, K=1, n=5, launches=(1, 0)),
+    Case("k1_auto", *S, 16, GRAY_F32, K=1, launches=(1, 1)),
+    Case("k1_auto_v", *S, 16, GRAY_F32, K=1, n=5, launches=(1, 1)),
+    Case("k1_float_apron", *S, 16, RGB_U8, K=1, launches=(0, 1)),
+    Case("k1_float_no_planes", *S, 194, GRAY_U8, K=1, launches=(1, 0)),
+    # kt = 4 beside the cases above
+    Case("k4_auto_v", *S, 16, GRAY_F32, K=4, n=5, launches=(1, 1)),
+    Case("k4_float_no_planes", *S, 194, GRAY_U8, K=4, launches=(1, 0)),
+    # the fill with 4 pixels per thread: an engine-stream call of 5 pairs
+    Case("fill_px4_k2", *S, 16, GRAY_U8, n=5, lanes=True, launches=(1, 0)),
+    Case("fill_px4_k4", *S, 16, GRAY_U8, K=4, n=5, lanes=True, launches=(1, 0)),
+    # sx = 0, the integer step-6 kernels that evaluate the SAD parabola: K = 2, max_disparity 271 (136 pooled disparities,
+    # 2 * 136 = 272 > 271; the left apron of 284 columns fits the 320-wide image) ...
+    Case("sx0_int", *T, 136, GRAY_U8, launches=(1, 0)),
+    Case("sx0_int_v", *T, 136, GRAY_U8, n=5, launches=(1, 0)),
+    Case("sx0_auto", *T, 136, GRAY_F32, launches=(1, 1)),
+    Case("sx0_auto_v", *T, 136, GRAY_F32, n=5, launches=(1, 1)),
+    # ... and K = 4 on the capture route: 4 * (8 + 64) = 288
+    Case("sx0_k4_int", *S, 64, GRAY_U8, K=4, dmin=8, launches=(1, 0)),
+    Case("sx0_k4_int_v", *S, 64, GRAY_U8, K=4, dmin=8, n=5, launches=(1, 0)),
+    Case("sx0_k4_auto", *S, 64, GRAY_F32, K=4, dmin=8, launches=(1, 1)),
+    Case("sx0_k4_auto_v", *S, 64, GRAY_F32, K=4, dmin=8, n=5, launches=(1, 1)),
 ]
 
 
@@ -118,7 +159,8 @@ def _keys(harness, cus, case):
     """The spec keys of the case's plan on this device, from the planner itself."""
     n = case.pairs(cus)
     args = [cus, int(case.radii), case.K, case.h, case.w, case.Dd, case.dmin, max(n, 1), MODES["auto"], -1 if case.dense == 0 else 1,
-            case.dense_small, case.entry, 0, int(case.dense == 1), int(case.exact_filter >= 0), case.hint, n, 1]
+            case.dense_small, case.entry, int(case.lanes), int(case.dense == 1), int(case.exact_filter >= 0), case.hint, n, 1,
+            case.crop, int(case.offset % 4 == 0)]
     r = subprocess.run([harness, "spec"] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.startswith("keys"), r.stdout + r.stderr
     return set(r.stdout.split()[1:])
@@ -143,7 +185,7 @@ def test_cases_cover_what_the_sweep_reaches_at_the_two_small_shapes(cus, harness
 
 
 def _distinct_pairs(case, count):
-    H, W, D = case.h * case.K, case.w * case.K, (case.dmin + case.Dd) * case.K
+    H, W, D = case.h * case.K, case.w * case.K - case.crop, (case.dmin + case.Dd) * case.K
     if case.entry in (RGB_F32, RGB_U8):
         return [syn.random_rgb_pair(H, W, D, case.K, 40 + i, dmin=case.dmin * case.K) for i in range(count)]
     return [syn.make_pair(H, W, D, case.K, 40 + i, dmin=case.dmin * case.K)[:2] for i in range(count)]
@@ -158,12 +200,16 @@ def test_spec_variant_against_the_oracle(cd, oracle_omp, monkeypatch, cus, case)
     if case.dense_small >= 0:
         monkeypatch.setenv("SMX_FAST_DENSE_SMALL", str(case.dense_small))
     kw = OTHER_RADII if not case.radii else {}
-    cfg, ocfg = parity._cfgs(cd, case.h * case.K, case.w * case.K, case.K, case.dmin * case.K, (case.dmin + case.Dd) * case.K - 1, **kw)
+    cfg, ocfg = parity._cfgs(cd, case.h * case.K, case.w * case.K - case.crop, case.K, case.dmin * case.K, (case.dmin + case.Dd) * case.K - 1, **kw)
     pairs = _distinct_pairs(case, min(n, DISTINCT))
     u8 = case.entry in (GRAY_U8, RGB_U8)
     idx = torch.arange(n, device="cuda") % len(pairs)
     tl, tr = (torch.from_numpy(np.stack([p[k] for p in pairs])).cuda() for k in (0, 1))
     tl, tr = ((t.to(torch.uint8) if u8 else t)[idx].contiguous() for t in (tl, tr))
+    if case.offset:                                     # the same bytes, `offset` bytes into a flat allocation
+        flat = [torch.empty(t.numel() + case.offset, dtype=torch.uint8, device="cuda") for t in (tl, tr)]
+        tl, tr = (b[case.offset:].view(t.shape).copy_(t) for b, t in zip(flat, (tl, tr)))
+        assert tl.data_ptr() % 4 == case.offset % 4 and tr.data_ptr() % 4 == case.offset % 4
     sm = cd.StereoMatching(cfg, max_batch=n, exact_filter=case.exact_filter)
     if case.warm:                                       # an on-grid f32 gray call first: its report is the grid hint 0
         sm.compute_disparity_map_batch(tl[:1], tr[:1])
@@ -171,7 +217,9 @@ def test_spec_variant_against_the_oracle(cd, oracle_omp, monkeypatch, cus, case)
     info = sm.route_info()
     assert info["offgrid_hint"] == case.hint and (case.dense == 1 or info["fast_dense"] == 0), info
     sm.profile_begin(1)
-    out = sm.compute_disparity_map_batch(tl, tr)
+    out = sm.compute_disparity_map_batch(tl, tr, engine_streams=case.lanes)
+    if case.lanes:
+        sm.join()
     prof = sm.profile_end()
     torch.cuda.synchronize()
     assert (prof["match_fast"][1], prof["match_exact"][1]) == case.launches, prof

@@ -37,6 +37,7 @@
  *   -- (surface points of that volume, ordered)           smx_tsdf_extract_points, smx_tsdf_extract_workspace_bytes
  *   -- (triangles over those points: marching cubes)      smx_tsdf_extract_triangles,
  *                                                         smx_tsdf_extract_triangles_workspace_bytes
+ *   -- (disparity, normal and colour views of that volume) smx_tsdf_raycast, smx_tsdf_raycast_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -52,7 +53,8 @@
  *     8-byte values and atomics.  Every entry that takes a workspace (smx_filter_speckles,
  *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
  *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample,
- *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles) returns
+ *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles,
+ *     smx_tsdf_raycast) returns
  *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
  *   - Calls enqueue work and return without synchronising (like the reference).
  *   - One engine = one device + one set of intermediate buffers: calls on the same
@@ -855,6 +857,59 @@ size_t smx_tsdf_extract_triangles_workspace_bytes(int nx, int ny, int nz);
 int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight,
                                float min_weight, int capacity, int32_t *triangles, int32_t *count, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/* smx_tsdf_raycast: n views of a volume (smx_tsdf_integrate's state, read only) by ray casting, one ray per pixel.
+ * camera_to_world [n][3][4] f32 (device, row-major): the pose of each view (not inverted); Q: host 4x4, shared by the
+ * views, whose ray must not depend on d: Q02 = Q12 = Q22 = 0, Q30 = Q31 = 0, Q32 != 0 (what reprojection_matrix builds).
+ *   ray       pixel (px, py) of view f, u = (float)px, v = (float)py, M = camera_to_world[f]:
+ *               X' = (Q00*u + Q01*v) + Q03,  Y' = (Q10*u + Q11*v) + Q13,  Z' = (Q20*u + Q21*v) + Q23
+ *               no ray (hence no hit) unless Z' > 0;  rx = X'/Z', ry = Y'/Z'
+ *               dw_r = (M[r][0]*rx + M[r][1]*ry) + M[r][2],  e_r = M[r][3]          r = 0, 1, 2
+ *             The ray parameter lam is camera depth: the point at lam is p_a = e_a + dw_a*lam.
+ *   Tri(p)    the volume at a point p: g_a = (p_a - o_a)/s - 0.5f, f_a = floorf(g_a); p is IN BOUNDS iff
+ *             0 <= f_a <= n_a - 2 on every axis (compared as floats; NaN fails); then, with the corners
+ *             c(cx, cy, cz) = tsdf of voxel (f_x + cx, f_y + cy, f_z + cz), the fractions t_a = g_a - f_a and
+ *             lerp(a, b, t) = a + (b - a)*t:  along x  c_yz = lerp(c(0, y, z), c(1, y, z), t_x),  then y
+ *             c_z = lerp(c_0z, c_1z, t_y),  then z  Tri = lerp(c_0, c_1, t_z).
+ *   samples   lam_m = z_min + (float)m*step for m = 0 .. M-1, M = (int)floorf((z_max - z_min)/step) + 1 (float32
+ *             subtraction, division and floorf).  Every lam_m is computed from m, never accumulated.  Sample m, at the
+ *             point of lam_m, is VALID iff that point is in bounds and its eight corners have weight >= min_weight; its
+ *             value is T_m = Tri there.
+ *   hit       the first m whose sample is valid with T_m < 0 ends the ray; invalid samples are walked through.  The ray
+ *             hits iff sample m-1 exists, is valid and 0 <= T_{m-1} < 1 (a ray that starts behind a surface, and the
+ *             jump from truncated free space to the space behind a surface at an occlusion edge -- the reason
+ *             smx_tsdf_extract_points asks for |T| < 1 -- do not); a ray that no sample ends does not hit.  On a hit
+ *               lam* = lam_{m-1} + step*(T_{m-1}/(T_{m-1} - T_m)),  p*_a = e_a + dw_a*lam*
+ * Outputs, planes [n][H][W]; disp is required, each other output may be NULL and is then not written:
+ *   disp      f32  (Z'/lam* - Q33)/Q32, or invalid_disparity without a hit: the convention of every [H, W] map entry
+ *   depth     f32  lam*, or NaN without a hit
+ *   normals   [n][3][H][W] f32, world frame, toward positive T: x_a = Tri(p* with p*_a + s in place of p*_a) -
+ *             Tri(p* with p*_a - s in place of p*_a) for a = x, y, z (the corners' weights are not tested, as in
+ *             smx_tsdf_extract_points), each divided by len = sqrtf((x_x*x_x + x_y*x_y) + x_z*x_z); (0, 0, 0) where one
+ *             of the six probes is not in bounds, where len == 0, and without a hit
+ *   colors    [n][3][H][W] u8 (needs color): R, G, B of the voxel nearest to p*, index
+ *             fminf(fmaxf(floorf(g_a + 0.5f), 0.0f), (float)(n_a - 1)) per axis with g of p*; 0 without a hit
+ *   weight    f32  that voxel's weight, or 0 without a hit
+ * Three launches on `stream` (a caller's stream), no atomics, no host synchronisation, no allocation: graph-capturable.
+ * The first two write one byte per brick of 8 x 8 x 8 voxels to the workspace: whether a voxel of the brick has weight >=
+ * min_weight, and whether every voxel that a cell with its first corner in the brick can touch has weight >= min_weight
+ * and tsdf == 1.0f exactly (measured free space, where a sample is valid with T = 1 exactly: every lerp is
+ * 1 + (1 - 1)*t).  The third marches one thread per pixel and jumps over runs of samples that lie outside the volume's
+ * box, whose first corner lies in an empty brick (invalid by the rule above) or in a free one (valid with T = 1: none
+ * ends the ray).  The result is the rule's, bit for bit, whatever is jumped over.
+ * workspace: smx_tsdf_raycast_workspace_bytes(nx, ny, nz) bytes (two per brick; 0 for sizes the call rejects).
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL origin, tsdf, weight, Q, camera_to_world, disp or
+ * workspace; the volume's dimension, voxel_size and origin checks of smx_tsdf_integrate; n < 1, H or W outside 1..32768
+ * or n*H*W > 2^30; min_weight not finite and > 0; step not finite and > 0; z_min or z_max not finite, z_min < 0 or
+ * z_min > z_max; M outside 1..65536; a non-finite Q entry or a Q outside the accepted form; a non-finite
+ * invalid_disparity; colors without color; workspace_bytes below the query; an output or the workspace overlapping an
+ * input or another output; stream == SMX_STREAM_ENGINE. */
+size_t smx_tsdf_raycast_workspace_bytes(int nx, int ny, int nz);
+int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                     const float *tsdf, const float *weight, const uint8_t *color, float min_weight, int n, int H,
+                     int W, const float Q[16], const float *camera_to_world, float step, float z_min, float z_max,
+                     float invalid_disparity, float *disp, float *depth, float *normals, uint8_t *colors,
+                     float *out_weight, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

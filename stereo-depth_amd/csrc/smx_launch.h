@@ -150,4 +150,14 @@ void launch_tsdf_extract(int nx, int ny, int nz, const float origin[3], float vo
 void launch_tsdf_triangles(int nx, int ny, int nz, const float *tsdf, const float *weight, float min_weight,
                            int capacity, int32_t *triangles, int32_t *count, void *workspace, hipStream_t s);
 
+// ---- tu_raycast.hip: views of a TSDF volume by ray casting (k_raycast.h) -------------------------------------------------
+// q / origin: host values, copied into the kernel arguments; camera_to_world [n][3][4] on the device; M: the number of
+// samples per ray; color / depth / normals / colors / out_weight may be NULL (colors needs color); workspace:
+// raycast_layout(nx, ny, nz); arguments checked by smx_tsdf_raycast
+void launch_tsdf_raycast(int nx, int ny, int nz, const float origin[3], float voxel_size, const float *tsdf,
+                         const float *weight, const uint8_t *color, float min_weight, int n, int H, int W,
+                         const float q[16], const float *camera_to_world, float step, float zmin, int M, float invalid,
+                         float *disp, float *depth, float *normals, uint8_t *colors, float *out_weight, void *workspace,
+                         hipStream_t s);
+
 }  // namespace smx

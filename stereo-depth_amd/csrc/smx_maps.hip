@@ -699,4 +699,54 @@ int smx_tsdf_extract_triangles(int device_id, int nx, int ny, int nz, const floa
     });
 }
 
+size_t smx_tsdf_raycast_workspace_bytes(int nx, int ny, int nz) {
+    return tsdf_dims_ok(nx, ny, nz) ? raycast_layout(nx, ny, nz).total : 0;
+}
+
+int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3], float voxel_size,
+                     const float *tsdf, const float *weight, const uint8_t *color, float min_weight, int n, int H,
+                     int W, const float Q[16], const float *camera_to_world, float step, float z_min, float z_max,
+                     float invalid_disparity, float *disp, float *depth, float *normals, uint8_t *colors,
+                     float *out_weight, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_tsdf_raycast";
+    if (!origin || !tsdf || !weight || !Q || !camera_to_world || !disp || !workspace)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: origin, tsdf, weight, Q, camera_to_world, disp and workspace must be non-NULL", fn);
+    if (int rc = check_tsdf_volume(fn, nx, ny, nz, origin, voxel_size)) return rc;
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (int rc = check_positive(fn, "min_weight", min_weight)) return rc;
+    if (int rc = check_positive(fn, "step", step)) return rc;
+    if (!(std::isfinite(z_min) && std::isfinite(z_max) && z_min >= 0.0f && z_min <= z_max))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need finite 0 <= z_min <= z_max, got %g, %g", fn, (double)z_min,
+                    (double)z_max);
+    const float samples = floorf((z_max - z_min) / step);            // M - 1, in the header's float32 steps
+    if (!(samples >= 0.0f && samples <= 65535.0f))
+        return fail(SMX_ERR_INVALID_ARG, "%s: (z_max - z_min) / step gives %g samples per ray, the limit is 65536", fn,
+                    (double)samples + 1.0);
+    if (int rc = check_finite_array(fn, "Q", Q, 16)) return rc;
+    if (Q[2] != 0.0f || Q[6] != 0.0f || Q[10] != 0.0f || Q[12] != 0.0f || Q[13] != 0.0f || Q[14] == 0.0f)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: Q's ray must not depend on d: need Q02 = Q12 = Q22 = 0, Q30 = Q31 = 0 and Q32 != 0", fn);
+    if (!std::isfinite(invalid_disparity))
+        return fail(SMX_ERR_INVALID_ARG, "%s: invalid_disparity must be finite, got %g", fn, (double)invalid_disparity);
+    if (colors && !color) return fail(SMX_ERR_INVALID_ARG, "%s: colors needs a colour volume", fn);
+    if (int rc = check_workspace_bytes(fn, "smx_tsdf_raycast_workspace_bytes", workspace_bytes,
+                                       raycast_layout(nx, ny, nz).total))
+        return rc;
+    const size_t vox = (size_t)nx * ny * nz, px = (size_t)n * H * W;
+    if (int rc = check_disjoint(fn, {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}, {color, vox * 4},
+                                     {camera_to_world, (size_t)n * 12 * sizeof(float)}},
+                                {{disp, px * sizeof(float)}, {depth, px * sizeof(float)},
+                                 {normals, px * 3 * sizeof(float)}, {colors, px * 3}, {out_weight, px * sizeof(float)},
+                                 {workspace, workspace_bytes}}, TSDF_IN_TEXT, TSDF_OUT_TEXT))
+        return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_raycast(nx, ny, nz, origin, voxel_size, tsdf, weight, color, min_weight, n, H, W, Q,
+                                 camera_to_world, step, z_min, (int)samples + 1, invalid_disparity, disp, depth, normals,
+                                 colors, out_weight, workspace, (hipStream_t)stream);
+    });
+}
+
 }  // extern "C"

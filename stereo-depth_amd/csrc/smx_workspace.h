@@ -150,4 +150,16 @@ inline MeshLayout mesh_layout(int nx, int ny, int nz) {
                       c.take(3 * rows * sizeof(int)), c.take(scan_block_sums(3 * (long)rows) * sizeof(int)), c.at};
 }
 
+// ---- TSDF ray cast: two bytes per brick of 8 x 8 x 8 voxels, flags u8[bz][by][bx] | occ u8[bz][by][bx], b_a = ceil(n_a / 8)
+struct RaycastLayout {
+    int bx, by, bz;
+    WsPart flags, occ;
+    size_t total;
+};
+inline RaycastLayout raycast_layout(int nx, int ny, int nz) {
+    const int bx = (nx + 7) / 8, by = (ny + 7) / 8, bz = (nz + 7) / 8;
+    WsCursor c;
+    return RaycastLayout{bx, by, bz, c.take((size_t)bx * by * bz), c.take((size_t)bx * by * bz), c.at};
+}
+
 }  // namespace smx

@@ -1113,6 +1113,21 @@ class TriangleMesh:
     colors: Optional[torch.Tensor] = None
 
 
+@dataclasses.dataclass
+class RenderedView:
+    """What a TSDFVolume looks like from a camera (TSDFVolume.render): planes [H, W] for one pose [4, 4], [n, H, W] for
+    poses [n, 4, 4].  disparity: float32, in the convention of every disparity map of this library, invalid_disparity
+    where the ray hits no surface; depth: float32 camera depth of the hit, NaN without one; normals: [3, H, W] /
+    [n, 3, H, W] float32 unit normals in the world frame, toward the cameras that measured the surface, 0 without a hit
+    (None with normals=False); colors: [3, H, W] / [n, 3, H, W] uint8 RGB, 0 without a hit (None with colors=False or
+    without a colour volume); weight: float32, the fusion weight of the voxel nearest to the hit, 0 without one."""
+    disparity: torch.Tensor
+    depth: torch.Tensor
+    normals: Optional[torch.Tensor] = None
+    colors: Optional[torch.Tensor] = None
+    weight: Optional[torch.Tensor] = None
+
+
 def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
                         cx_right: Optional[float] = None) -> np.ndarray:
     """The float32 4x4 Q of a rectified pair in OpenCV's reprojectImageTo3D convention, [X' Y' Z' W'] = Q [u v d 1]:
@@ -1382,6 +1397,21 @@ def world_to_camera_poses(camera_to_world) -> np.ndarray:
     return np.ascontiguousarray(inv[:, :3, :])
 
 
+def camera_to_world_poses(camera_to_world) -> np.ndarray:
+    """[n, 3, 4] float32: the top rows of camera-to-world poses [4, 4] / [n, 4, 4], rounded once from float64 and not
+    inverted (what TSDFVolume.render hands to smx_tsdf_raycast).  A pose that is not finite or whose last row is not
+    [0, 0, 0, 1] raises RuntimeError."""
+    m = _host_matrices("camera_to_world", camera_to_world, True)
+    if not np.isfinite(m).all():
+        raise RuntimeError("camera_to_world must be finite")
+    if not np.array_equal(m[:, 3, :], np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (m.shape[0], 4))):
+        raise RuntimeError("camera_to_world's last row must be [0, 0, 0, 1]")
+    m32 = m[:, :3, :].astype(np.float32)
+    if not np.isfinite(m32).all():
+        raise RuntimeError("camera_to_world must be finite (in float32)")
+    return np.ascontiguousarray(m32)
+
+
 def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], float, Tuple[float, float, float]]:
     try:
         nx, ny, nz = dims
@@ -1411,8 +1441,9 @@ def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], 
 
 class TSDFVolume:
     """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
-    include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points) or as a triangle mesh over
-    those points (smx_tsdf_extract_triangles).  The volume has
+    include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points), as a triangle mesh over
+    those points (smx_tsdf_extract_triangles) or as disparity, normal and colour views from any pose (render:
+    smx_tsdf_raycast).  The volume has
     dims = (nx, ny, nz) voxels of edge voxel_size, its corner at origin, in the caller's world frame; voxel (i, j, k) is
     centred at origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size.  It owns the state: .tsdf and .weight float32
     [nz, ny, nx], and with color=True .color uint8 [nz, ny, nx, 4] (R, G, B, 0).  truncation (default 3 * voxel_size,
@@ -1499,6 +1530,87 @@ class TSDFVolume:
                                      n, H, W, disp.data_ptr(), qc, pc, poses.data_ptr(), ptr(confidence),
                                      float(min_confidence), z_min, z_max, float(invalid_disparity), ptr(image),
                                      channels, dtype, ws.data_ptr(), ws_bytes, _stream(self.device.index)))
+
+    def _check_render_args(self, Q, camera_to_world, shape, min_weight, step, depth_range, normals, colors,
+                           invalid_disparity):
+        """render's arguments, before the device is touched: (q, poses [n, 3, 4] f32, batched, (H, W), step,
+        (z_min, z_max))."""
+        q = _check_q(Q)
+        if (q[:3, 2] != 0).any() or q[3, 0] != 0 or q[3, 1] != 0 or q[3, 2] == 0:
+            raise RuntimeError("Q's ray must not depend on the disparity: need Q[0..2, 2] = 0, Q[3, 0] = Q[3, 1] = 0 and "
+                               "Q[3, 2] != 0 (what reprojection_matrix builds)")
+        poses = camera_to_world_poses(camera_to_world)
+        batched = (camera_to_world.dim() if isinstance(camera_to_world, torch.Tensor) else np.ndim(camera_to_world)) == 3
+        H, W = _shape2("shape", shape)
+        n = poses.shape[0]
+        if n * H * W > 2 ** 30:
+            raise RuntimeError(f"need n * H * W <= 2^30, got {n} views of {(H, W)}")
+        _number_arg("min_weight", min_weight)
+        if not (math.isfinite(min_weight) and min_weight > 0):
+            raise RuntimeError(f"min_weight must be finite and > 0, got {min_weight}")
+        step = self.voxel_size if step is None else step
+        _number_arg("step", step)
+        if not (math.isfinite(step) and step > 0):
+            raise RuntimeError(f"step must be finite and > 0, got {step}")
+        _number_arg("invalid_disparity", invalid_disparity)
+        if not math.isfinite(invalid_disparity):
+            raise RuntimeError(f"invalid_disparity must be finite, got {invalid_disparity}")
+        for name, v in (("normals", normals), ("colors", colors)):
+            if not isinstance(v, bool):
+                raise TypeError(f"{name} must be a bool")
+        if depth_range is None:                                         # no ray is longer than eye to farthest corner
+            lo = np.asarray(self.origin, np.float64)
+            hi = lo + np.asarray(self.dims, np.float64) * self.voxel_size
+            corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
+            eyes = poses[:, :, 3].astype(np.float64)
+            depth_range = (0.0, float(np.linalg.norm(corners[None] - eyes[:, None], axis=2).max()))
+        try:
+            z_min, z_max = depth_range
+        except (TypeError, ValueError):
+            raise TypeError("depth_range must be a pair (z_min, z_max)") from None
+        _number_arg("depth_range[0]", z_min)
+        _number_arg("depth_range[1]", z_max)
+        if not (math.isfinite(z_min) and math.isfinite(z_max) and 0 <= z_min <= z_max):
+            raise RuntimeError(f"depth_range must be finite with 0 <= z_min <= z_max, got {depth_range}")
+        samples = math.floor((np.float32(z_max) - np.float32(z_min)) / np.float32(step)) + 1
+        if samples > 65536:
+            raise RuntimeError(f"depth_range / step gives {samples} samples per ray, the limit is 65536")
+        return q, poses, batched, (H, W), float(step), (float(z_min), float(z_max))
+
+    def render(self, Q, camera_to_world, shape, *, min_weight: float = 1.0, step: Optional[float] = None,
+               depth_range=None, normals: bool = True, colors: bool = True,
+               invalid_disparity: float = -1.0) -> RenderedView:
+        """The volume seen from camera_to_world [4, 4] / [n, 4, 4] (numpy or tensor; rounded once to float32, not
+        inverted) through a camera with the reprojection matrix Q, as maps of shape (H, W): one ray per pixel, sampled
+        every `step` (default voxel_size) of camera depth over depth_range (default 0 .. the distance from the eye to
+        the volume's farthest corner, computed in float64 per call), hits the surface at the first change of the tsdf
+        from [0, 1) to negative between two samples whose eight voxels all have weight >= min_weight
+        (smx_tsdf_raycast; the rule is in include/stereo_mi355x.h).  Q's ray must not depend on the disparity, which
+        holds for every reprojection_matrix.  Runs on the current stream without synchronising and returns a
+        RenderedView of fresh tensors; a novel pose is as good as one that was fused."""
+        q, poses, batched, (H, W), step, (z_min, z_max) = self._check_render_args(
+            Q, camera_to_world, shape, min_weight, step, depth_range, normals, colors, invalid_disparity)
+        dev, n = self.device, poses.shape[0]
+        disp = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        weight = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        nrm = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev) if normals else None
+        col = torch.empty((n, 3, H, W), dtype=torch.uint8, device=dev) if colors and self.color is not None else None
+        pose_dev = torch.from_numpy(poses).pin_memory().to(dev, non_blocking=True)
+        nx, ny, nz = self.dims
+        ws_bytes = LIB.smx_tsdf_raycast_workspace_bytes(nx, ny, nz)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        qc = (C.c_float * 16)(*q.reshape(-1).tolist())
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(LIB.smx_tsdf_raycast(dev.index, nx, ny, nz, self._origin(), self.voxel_size, self.tsdf.data_ptr(),
+                                   self.weight.data_ptr(), ptr(self.color), float(min_weight), n, H, W, qc,
+                                   pose_dev.data_ptr(), step, z_min, z_max, float(invalid_disparity), disp.data_ptr(),
+                                   depth.data_ptr(), ptr(nrm), ptr(col), weight.data_ptr(), ws.data_ptr(), ws_bytes,
+                                   _stream(dev.index)))
+        if not batched:
+            disp, depth, weight = disp[0], depth[0], weight[0]
+            nrm, col = (None if t is None else t[0] for t in (nrm, col))
+        return RenderedView(disparity=disp, depth=depth, normals=nrm, colors=col, weight=weight)
 
     def extract_point_cloud_batched(self, capacity: int, *, min_weight: float = 1.0, normals: bool = True,
                                     colors: bool = True):

@@ -184,6 +184,14 @@ EXPORTS = {
     "smx_tsdf_extract_triangles_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "smx_tsdf_extract_triangles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # views of the volume by ray casting: (nx, ny, nz) -> workspace bytes; (device_id, nx, ny, nz, origin, voxel_size,
+    # tsdf, weight, color, min_weight, n, H, W, Q (host float32[16]), camera_to_world, step, z_min, z_max,
+    # invalid_disparity, disp, depth, normals, colors, weight out, workspace, workspace_bytes, stream)
+    "smx_tsdf_raycast_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_tsdf_raycast": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                   C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

@@ -66,6 +66,10 @@ class DepthEstimationResult:
     # voxel-downsampled with point_cloud_voxel_size > 0; None otherwise.  Keyword-only, so the positional order of the
     # earlier fields (confidence_map fourth) is unchanged.
     point_cloud: Optional["cuda_depth.PointCloud"] = dataclasses.field(default=None, kw_only=True)
+    # render_model=True: the [H, W] disparity map of the fused volume seen from this frame's camera_pose, rendered after
+    # the frame was integrated (TSDFVolume.render: a fresh tensor, invalid_disparity where no surface is hit); None
+    # otherwise.  Keyword-only as well, and declared here: confidence_map stays the last field
+    model_disparity_map: Optional[torch.Tensor] = dataclasses.field(default=None, kw_only=True)
     # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
     # None otherwise
     confidence_map: Optional[torch.Tensor] = None
@@ -122,7 +126,7 @@ class DepthEstimationPipeline:
                  point_cloud_depth_range: Tuple[float, float] = (0.0, math.inf), point_cloud_voxel_size: float = 0.0,
                  point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0,
                  tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None,
-                 right_view_synthesis: Optional[RightViewSynthesis] = None):
+                 right_view_synthesis: Optional[RightViewSynthesis] = None, render_model: bool = False):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -152,7 +156,11 @@ class DepthEstimationPipeline:
         point_cloud_min_confidence when confidence=True, and colour from the left frame the map was computed on.
         right_view_synthesis: a pipeline.synthesis.RightViewSynthesis whose full_resolution is the frames' size; a
         process() call without a right image then generates one from the left frame, as the reference's pipeline does,
-        and matches against it (None: such a call raises)."""
+        and matches against it (None: such a call raises).  render_model: True (needs tsdf_volume) renders the volume,
+        after the frame was integrated, from the frame's camera_pose at the frame's shape with the volume's defaults
+        (TSDFVolume.render) and returns the disparity map as DepthEstimationResult.model_disparity_map: the denoised,
+        hole-filled counterpart of disparity_map.  The reprojection matrix must then be one whose ray does not depend on
+        the disparity (every cuda_depth.reprojection_matrix).  False (the default) changes nothing."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
@@ -166,6 +174,16 @@ class DepthEstimationPipeline:
                                  f"got {tsdf_volume.device}")
             cuda_depth.projection_matrix(reprojection_matrix)
         self._tsdf_volume = tsdf_volume
+        if not isinstance(render_model, bool):
+            raise TypeError("render_model must be a bool")
+        if render_model:
+            if tsdf_volume is None:
+                raise ValueError("render_model needs tsdf_volume")
+            q = cuda_depth._check_q(reprojection_matrix)
+            if (q[:3, 2] != 0).any() or q[3, 0] != 0 or q[3, 1] != 0:
+                raise ValueError("render_model needs a reprojection_matrix whose ray does not depend on the disparity "
+                                 "(cuda_depth.reprojection_matrix builds one)")
+        self._render_model = render_model
         if right_view_synthesis is not None and not isinstance(right_view_synthesis, RightViewSynthesis):
             raise TypeError("right_view_synthesis must be a pipeline.synthesis.RightViewSynthesis")
         self._right_view_synthesis = right_view_synthesis
@@ -241,8 +259,13 @@ class DepthEstimationPipeline:
                                         min_confidence=self._point_cloud_min_confidence,
                                         depth_range=self._point_cloud_depth_range,
                                         invalid_disparity=self._config.invalid_disparity)
+        model = None
+        if self._render_model:
+            model = self._tsdf_volume.render(self._reprojection_matrix, camera_pose, tuple(disparity.shape[-2:]),
+                                             normals=False, colors=False,
+                                             invalid_disparity=self._config.invalid_disparity).disparity
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
-                                     confidence_map=confidence, point_cloud=cloud)
+                                     confidence_map=confidence, point_cloud=cloud, model_disparity_map=model)
 
     def _point_cloud(self, disparity: torch.Tensor, left: torch.Tensor,
                      confidence: Optional[torch.Tensor]) -> "cuda_depth.PointCloud":

@@ -38,6 +38,7 @@
  *   -- (triangles over those points: marching cubes)      smx_tsdf_extract_triangles,
  *                                                         smx_tsdf_extract_triangles_workspace_bytes
  *   -- (disparity, normal and colour views of that volume) smx_tsdf_raycast, smx_tsdf_raycast_workspace_bytes
+ *   -- (the camera pose of a frame against such a view)   smx_track_camera, smx_track_camera_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -54,7 +55,7 @@
  *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
  *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample,
  *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles,
- *     smx_tsdf_raycast) returns
+ *     smx_tsdf_raycast, smx_track_camera) returns
  *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
  *   - Calls enqueue work and return without synchronising (like the reference).
  *   - One engine = one device + one set of intermediate buffers: calls on the same
@@ -910,6 +911,86 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
                      int W, const float Q[16], const float *camera_to_world, float step, float z_min, float z_max,
                      float invalid_disparity, float *disp, float *depth, float *normals, uint8_t *colors,
                      float *out_weight, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Camera tracking -------------------------------------------------------------------------------------------------
+ * smx_track_camera: the camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against
+ * a rendered view of the model (KinectFusion's frame-to-model tracking).  It handles n independent triples (frame, model
+ * view, initial pose).  Every step below is ONE float32 operation (no fused multiply-add, correctly rounded division and
+ * sqrtf) unless it is stated as float64; float64 steps are single operations as well.
+ *   frame     disp [n][H][W] f32, optional confidence [n][H][W], Q (host 4x4).  Pixel (px, py) of frame f is ACCEPTED iff
+ *             smx_tsdf_integrate's pixel rule accepts it (d finite and != invalid_disparity, W' > 0, Zm finite in
+ *             [z_min, z_max], c >= min_confidence and c > 0) and its camera point (X, Y, Z) = (X'/W', Y'/W', Z'/W') of
+ *             smx_reproject_points is finite; its weight w is c, or 1.0f without a confidence map.  An iteration of stride
+ *             s SELECTS the pixels with px % s == 0 and py % s == 0: the selected grid has Ws = ceil(W/s) columns and
+ *             Hs = ceil(H/s) rows, selected pixel (sx, sy) being pixel (sx*s, sy*s).
+ *   model     model_depth [n][Hm][Wm] and model_normals [n][3][Hm][Wm]: the depth and normals planes smx_tsdf_raycast
+ *             wrote for the view with the reprojection matrix Qm (host 4x4, in the form that entry accepts) and the pose
+ *             model_camera_to_world [n][3][4] f32 (device); Pm (host 4x4) is inv(Qm) and model_world_to_camera [n][3][4]
+ *             the inverse pose (the Python layer inverts both in float64 and rounds once, as for smx_tsdf_integrate).
+ *   pose      pose_in [n][3][4] f32 (device), camera-to-world: T = (R, t) starts as pose_in.
+ *   terms     of a selected accepted pixel at the pose T, with Mw = model_world_to_camera[f], Mc = model_camera_to_world[f]:
+ *               p_r = ((R_r0*X + R_r1*Y) + R_r2*Z) + t_r                                   r = 0, 1, 2
+ *               c_r = ((Mw[r][0]*p_0 + Mw[r][1]*p_1) + Mw[r][2]*p_2) + Mw[r][3];  skip unless c_2 > 0
+ *               u_r = ((Pm[r][0]*c_0 + Pm[r][1]*c_1) + Pm[r][2]*c_2) + Pm[r][3]    r = 0, 1, 3;  skip unless u_3 > 0
+ *               fu = floorf(u_0/u_3 + 0.5f), fv = floorf(u_1/u_3 + 0.5f); skip unless 0 <= fu <= Wm-1 and 0 <= fv <= Hm-1
+ *               lam = model_depth[f][fv][fu]; skip unless lam is finite and > 0
+ *               nrm = model_normals[f][.][fv][fu]; skip if all three are 0
+ *               X'' = (Qm00*fu + Qm01*fv) + Qm03, Y'' and Z'' likewise; rx = X''/Z'', ry = Y''/Z''
+ *               q_r = Mc[r][3] + ((Mc[r][0]*rx + Mc[r][1]*ry) + Mc[r][2])*lam     (smx_tsdf_raycast's p* of that pixel)
+ *               dl_r = q_r - p_r; skip unless (dl_0*dl_0 + dl_1*dl_1) + dl_2*dl_2 <= max_distance*max_distance (NaN fails)
+ *               b = (nrm_0*dl_0 + nrm_1*dl_1) + nrm_2*dl_2
+ *               a = (p_1*nrm_2 - p_2*nrm_1, p_2*nrm_0 - p_0*nrm_2, p_0*nrm_1 - p_1*nrm_0, nrm_0, nrm_1, nrm_2): the row
+ *                   of a small world-frame twist (omega, tau) applied on the left, p' = p + omega x p + tau
+ *             Thirty terms, each a float32 product converted to float64: k = 0..20 (w*a_i)*a_j for i <= j in the order
+ *             (0,0), (0,1), .., (0,5), (1,1), .., (5,5); k = 21..26 (w*a_i)*b; k = 27 (w*b)*b; k = 28 w; k = 29 1 (the
+ *             inlier count).  A pixel that is skipped, not accepted or not selected contributes +0.0 to every term.
+ *   sums      float64, in an order fixed by (H, W, s) alone.  The selected grid is cut into tiles of 64 columns x 4 rows,
+ *             the tiles at the right and lower edges padded with pixels that contribute +0.0.  (1) In every tile column,
+ *             starting from +0.0, the rows' terms are added top to bottom.  (2) The 64 column sums of a tile are reduced by
+ *             an adjacent-pairs tree: columns 2i and 2i+1 first, then those sums in adjacent pairs, and so on.  (3) The
+ *             tile sums, in row-major tile order and padded with +0.0 to a power of two, are reduced by the same tree.
+ *   solve     A (symmetric 6x6 from terms 0..20) x = g (terms 21..26) by LDL^T without pivoting in float64: for
+ *             j = 0..5: v_k = L_jk*d_k for k < j; d_j = A_jj - L_j0*v_0 - .. - L_j,j-1*v_j-1 (subtracted one at a time in
+ *             that order); for i > j: L_ij = (A_ij - L_i0*v_0 - .. - L_i,j-1*v_j-1)/d_j.  Then y_i = g_i - L_i0*y_0 - ..
+ *             - L_i,i-1*y_i-1 for i = 0..5, and for i = 5..0: x_i = y_i/d_i - L_i+1,i*x_i+1 - .. - L_5i*x_5.  The triple is
+ *             LOST if the inlier count (term 29) is below min_inliers, if a pivot d_j is not finite or <= min_pivot (an
+ *             absolute bound: pivots grow with the sum of the weights), or if a component of x is not finite.
+ *   update    omega = (f32)(x_0, x_1, x_2), tau = (f32)(x_3, x_4, x_5).  The rotation is the Cayley map of omega, which is
+ *             orthogonal by construction and needs no sin or cos: a = omega*0.5f, aa = (a_0*a_0 + a_1*a_1) + a_2*a_2,
+ *             den = 1.0f + aa, k = 1.0f - aa, t_i = 2.0f*a_i,
+ *               C = | (k + t_0*a_0)/den    (t_0*a_1 - t_2)/den   (t_0*a_2 + t_1)/den |
+ *                   | (t_1*a_0 + t_2)/den  (k + t_1*a_1)/den     (t_1*a_2 - t_0)/den |
+ *                   | (t_2*a_0 - t_1)/den  (t_2*a_1 + t_0)/den   (k + t_2*a_2)/den   |
+ *             R_rc <- (C_r0*R_0c + C_r1*R_1c) + C_r2*R_2c and t_r <- ((C_r0*t_0 + C_r1*t_1) + C_r2*t_2) + tau_r.
+ *   schedule  host int32 [schedule_pairs][2] of (stride, iterations), coarse to fine: at most 8 pairs and 64 iterations in
+ *             all.  A triple stops, and its later iterations do nothing, when it is LOST, and after an update with
+ *             (omega_0^2 + omega_1^2) + omega_2^2 <= rot_eps*rot_eps and the same sum of tau <= trans_eps*trans_eps.
+ * Outputs: pose_out [n][3][4] f32 (may be pose_in itself), the pose after the last update; a LOST triple gets pose_in's
+ * bits.  Each of the following may be NULL: info [n][4] int32 = (lost, iterations run, the inlier count of the last one
+ * run, its selected accepted pixels); rms [n] f32 = sqrtf((f32)(term 27 / term 28)) of the last iteration run (the
+ * division in float64), NaN if none ran or no pixel was an inlier; normal_equations [n][30] f64, the thirty sums of the
+ * last iteration run (+0.0 if none ran): terms 0..20 are the information matrix of the pose.
+ * One launch, then two per iteration (accumulate the sums of every four tiles; combine them, solve, update) on `stream`
+ * (a caller's stream), no atomics, no host synchronisation, no allocation: graph-capturable.  The stop flags live in the
+ * workspace and the first launch of every call resets them.  The composition of float32 rotations over a long sequence
+ * drifts from orthogonality; that, loop closure and relocalisation are the caller's.
+ * workspace: smx_track_camera_workspace_bytes(n, H, W) bytes (0 for sizes the call rejects).
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL disp, Q, model_depth, model_normals, Qm, Pm,
+ * model_camera_to_world, model_world_to_camera, pose_in, pose_out or workspace; n < 1, H or W outside 1..32768,
+ * n*H*W > 2^30 or ceil(W/64)*ceil(H/4) > 32768; Hm or Wm outside 1..32768 or n*Hm*Wm > 2^30; a non-finite Q, Qm or Pm
+ * entry or a Qm outside smx_tsdf_raycast's form; a NaN z bound or z_min > z_max; a non-finite min_confidence or
+ * invalid_disparity; schedule_pairs outside 0..8, a NULL schedule with pairs, a stride outside 1..32768, a negative
+ * iteration count or more than 64 iterations in all; max_distance not finite and > 0; min_inliers < 1; min_pivot, rot_eps
+ * or trans_eps not finite and >= 0; workspace_bytes below the query; an output or the workspace overlapping an input
+ * (pose_out == pose_in excepted) or another output; stream == SMX_STREAM_ENGINE. */
+size_t smx_track_camera_workspace_bytes(int n, int H, int W);
+int smx_track_camera(int device_id, int n, int H, int W, const float *disp, const float *confidence, const float Q[16],
+                     float min_confidence, float z_min, float z_max, float invalid_disparity, int Hm, int Wm,
+                     const float *model_depth, const float *model_normals, const float Qm[16], const float Pm[16],
+                     const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
+                     int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
+                     float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
+                     double *normal_equations, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

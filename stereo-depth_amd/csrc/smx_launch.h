@@ -160,4 +160,15 @@ void launch_tsdf_raycast(int nx, int ny, int nz, const float origin[3], float vo
                          float *disp, float *depth, float *normals, uint8_t *colors, float *out_weight, void *workspace,
                          hipStream_t s);
 
+// ---- tu_track.hip: camera tracking against rendered model views (k_track.h) ----------------------------------------------
+// q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every other pointer is device memory; confidence,
+// info, rms and normal_equations may be NULL; workspace: track_layout(n, H, W); arguments checked by smx_track_camera
+void launch_track_camera(int n, int H, int W, const float *disp, const float *confidence, const float q[16],
+                         float min_confidence, float zmin, float zmax, float invalid, int Hm, int Wm,
+                         const float *model_depth, const float *model_normals, const float qm[16], const float pm[16],
+                         const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
+                         int pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
+                         float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
+                         double *normal_equations, void *workspace, hipStream_t s);
+
 }  // namespace smx

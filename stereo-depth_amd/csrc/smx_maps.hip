@@ -749,4 +749,81 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
     });
 }
 
+// ---- camera tracking ---------------------------------------------------------------------------------------------------
+static bool track_dims_ok(int n, int H, int W) {
+    return points_dims_ok(n, H, W) && track_grid(H, W, 1).tiles <= TRK_MAX_TILES;
+}
+
+size_t smx_track_camera_workspace_bytes(int n, int H, int W) {
+    return track_dims_ok(n, H, W) ? track_layout(n, H, W).total : 0;
+}
+
+int smx_track_camera(int device_id, int n, int H, int W, const float *disp, const float *confidence, const float Q[16],
+                     float min_confidence, float z_min, float z_max, float invalid_disparity, int Hm, int Wm,
+                     const float *model_depth, const float *model_normals, const float Qm[16], const float Pm[16],
+                     const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
+                     int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
+                     float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
+                     double *normal_equations, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_track_camera";
+    if (!disp || !Q || !model_depth || !model_normals || !Qm || !Pm || !model_camera_to_world || !model_world_to_camera ||
+        !pose_in || !pose_out || !workspace)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: disp, Q, model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, "
+                    "pose_in, pose_out and workspace must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (track_grid(H, W, 1).tiles > TRK_MAX_TILES)
+        return fail(SMX_ERR_INVALID_ARG, "%s: ceil(W / %d) * ceil(H / %d) = %d tiles exceed the limit of %d", fn, TRK_COLS,
+                    TRK_ROWS, track_grid(H, W, 1).tiles, TRK_MAX_TILES);
+    if (!map_dims_ok(n, Hm, Wm) || (long)n * Hm * Wm > SMX_POINTS_MAX)
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= Hm, Wm <= 32768 and n * Hm * Wm <= 2^30 (got Hm %d, Wm %d)", fn, Hm,
+                    Wm);
+    for (int k = 0; k < 16; ++k) {                            // one loop: the lower index is reported, Q, Qm, then Pm
+        if (int rc = check_finite_at(fn, "Q", Q, k)) return rc;
+        if (int rc = check_finite_at(fn, "Qm", Qm, k)) return rc;
+        if (int rc = check_finite_at(fn, "Pm", Pm, k)) return rc;
+    }
+    if (Qm[2] != 0.0f || Qm[6] != 0.0f || Qm[10] != 0.0f || Qm[12] != 0.0f || Qm[13] != 0.0f || Qm[14] == 0.0f)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: Qm's ray must not depend on d: need Qm02 = Qm12 = Qm22 = 0, Qm30 = Qm31 = 0 and Qm32 != 0", fn);
+    if (int rc = check_reprojection_args(fn, z_min, z_max, min_confidence, invalid_disparity, nullptr, 0, 0, nullptr, ""))
+        return rc;
+    if (int rc = check_int_range(fn, "schedule_pairs", schedule_pairs, 0, 8)) return rc;
+    if (schedule_pairs > 0 && !schedule) return fail(SMX_ERR_INVALID_ARG, "%s: schedule must be non-NULL", fn);
+    int iterations = 0;
+    for (int p = 0; p < schedule_pairs; ++p) {
+        if (int rc = check_int_range(fn, "a schedule stride", schedule[2 * p], 1, 32768)) return rc;
+        if (int rc = check_int_range(fn, "a schedule iteration count", schedule[2 * p + 1], 0, 64)) return rc;
+        iterations += schedule[2 * p + 1];
+    }
+    if (int rc = check_int_range(fn, "the schedule's iterations in total", iterations, 0, 64)) return rc;
+    if (int rc = check_positive(fn, "max_distance", max_distance)) return rc;
+    if (int rc = check_int_range(fn, "min_inliers", min_inliers, 1, 1 << 30)) return rc;
+    if (int rc = check_non_negative(fn, "min_pivot", min_pivot)) return rc;
+    if (int rc = check_non_negative(fn, "rot_eps", rot_eps)) return rc;
+    if (int rc = check_non_negative(fn, "trans_eps", trans_eps)) return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_track_camera_workspace_bytes", workspace_bytes,
+                                       track_layout(n, H, W).total))
+        return rc;
+    const size_t map_bytes = (size_t)n * H * W * sizeof(float), model_bytes = (size_t)n * Hm * Wm * sizeof(float);
+    const size_t pose_bytes = (size_t)n * 12 * sizeof(float);
+    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {model_depth, model_bytes},
+                                     {model_normals, 3 * model_bytes}, {model_camera_to_world, pose_bytes},
+                                     {model_world_to_camera, pose_bytes}, {pose_in != pose_out ? pose_in : nullptr, pose_bytes}},
+                                {{pose_out, pose_bytes}, {info, (size_t)n * 4 * sizeof(int32_t)},
+                                 {rms, (size_t)n * sizeof(float)}, {normal_equations, (size_t)n * TRK_TERMS * sizeof(double)},
+                                 {workspace, workspace_bytes}},
+                                "an output or the workspace overlaps an input (pose_out may be pose_in itself)",
+                                "two outputs (the workspace is one) overlap"))
+        return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_track_camera(n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity, Hm, Wm,
+                                 model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
+                                 schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps,
+                                 pose_out, info, rms, normal_equations, workspace, (hipStream_t)stream);
+    });
+}
+
 }  // extern "C"

@@ -162,4 +162,36 @@ inline RaycastLayout raycast_layout(int nx, int ny, int nz) {
     return RaycastLayout{bx, by, bz, c.take((size_t)bx * by * bz), c.take((size_t)bx * by * bz), c.at};
 }
 
+// ---- camera tracking: one state record of 32 words per triple | the sums of every group of four tiles of the selected
+// grid, double[n][groups at stride 1][TRK_SLOTS].  The constants are shared with k_track.h and fix the order of the sums.
+#ifndef SMX_TRK_ROWS                           // tuning experiments only (build.py: SMX_EXTRA_FLAGS): another value sums in
+#define SMX_TRK_ROWS 4                         // another order than the header states
+#endif
+constexpr int TRK_COLS = 64, TRK_ROWS = SMX_TRK_ROWS;   // a tile of the selected grid: one wave, one lane per column
+constexpr int TRK_WAVES = 4;                   // tiles per workgroup, consecutive in row-major order
+constexpr int TRK_TERMS = 30;                  // the sums of the header ...
+constexpr int TRK_SLOTS = 32;                  // ... then the accepted pixels, and one unused slot
+constexpr int TRK_MAX_TILES = 32768;           // of a frame at stride 1 (the combine kernel's stack: k_track.h)
+struct TrackGrid {
+    int ws, hs, tx, ty, tiles, groups;         // selected columns and rows; tiles across, down, in all; groups of 4 tiles
+};
+inline TrackGrid track_grid(int H, int W, int stride) {
+    TrackGrid g;
+    g.ws = (W + stride - 1) / stride, g.hs = (H + stride - 1) / stride;
+    g.tx = (g.ws + TRK_COLS - 1) / TRK_COLS, g.ty = (g.hs + TRK_ROWS - 1) / TRK_ROWS;
+    g.tiles = g.tx * g.ty, g.groups = (g.tiles + TRK_WAVES - 1) / TRK_WAVES;
+    return g;
+}
+struct TrackLayout {
+    int groups;                                // per triple, at stride 1 (no stride has more)
+    WsPart state, partial;
+    size_t total;
+};
+inline TrackLayout track_layout(int n, int H, int W) {
+    const int groups = track_grid(H, W, 1).groups;
+    WsCursor c;
+    return TrackLayout{groups, c.take((size_t)n * 32 * sizeof(int)),
+                       c.take((size_t)n * groups * TRK_SLOTS * sizeof(double)), c.at};
+}
+
 }  // namespace smx

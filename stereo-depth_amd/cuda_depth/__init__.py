@@ -1128,6 +1128,25 @@ class RenderedView:
     weight: Optional[torch.Tensor] = None
 
 
+@dataclasses.dataclass
+class TrackingResult:
+    """What track_camera found, as device tensors (nothing is synchronised; one frame gives the shapes on the left, a
+    batch of n the ones on the right).  pose: float32 [4, 4] / [n, 4, 4] camera-to-world, the initial pose's bits where
+    lost; lost: bool [] / [n]; iterations, inliers, accepted: int32 [] / [n] -- the iterations that ran, and the inliers
+    and the selected accepted pixels of the last one; rms: float32 [] / [n], the weighted point-to-plane residual of
+    the last iteration (NaN if none ran); information: float64 [6, 6] / [n, 6, 6], the normal matrix of the last
+    iteration over the twist (rotation, translation) in the world frame, which serves as the inverse covariance of the
+    pose up to the residual's variance; normal_equations: float64 [30] / [n, 30], the sums it is made of."""
+    pose: torch.Tensor
+    lost: torch.Tensor
+    iterations: torch.Tensor
+    inliers: torch.Tensor
+    accepted: torch.Tensor
+    rms: torch.Tensor
+    information: torch.Tensor
+    normal_equations: torch.Tensor
+
+
 def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
                         cx_right: Optional[float] = None) -> np.ndarray:
     """The float32 4x4 Q of a rectified pair in OpenCV's reprojectImageTo3D convention, [X' Y' Z' W'] = Q [u v d 1]:
@@ -1439,6 +1458,113 @@ def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], 
     return (nx, ny, nz), float(voxel_size), tuple(float(v) for v in o)
 
 
+DEFAULT_TRACKING_SCHEDULE = ((4, 4), (2, 5), (1, 10))
+_INFORMATION_INDEX = {}                                            # device -> int64 [6, 6]: the sum that holds A[i][j]
+
+
+def _check_tracking_schedule(schedule) -> np.ndarray:
+    try:
+        pairs = [(int(s), int(k)) for s, k in schedule]
+        if any(s != s0 or k != k0 for (s, k), (s0, k0) in zip(pairs, schedule)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise TypeError("schedule must be a sequence of (stride, iterations) pairs of integers") from None
+    if len(pairs) > 8 or any(s < 1 or s > 32768 or k < 0 for s, k in pairs) or sum(k for _, k in pairs) > 64:
+        raise RuntimeError("schedule: at most 8 pairs with 1 <= stride <= 32768 and iterations >= 0, 64 iterations in "
+                           f"all, got {tuple(pairs)}")
+    return np.ascontiguousarray(np.array(pairs, np.int32).reshape(-1, 2))
+
+
+def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *, model_Q=None,
+                 confidence: Optional[torch.Tensor] = None, schedule=DEFAULT_TRACKING_SCHEDULE,
+                 max_distance: float = 0.3, depth_range=(0.0, math.inf), min_inliers: int = 100,
+                 min_confidence: float = 0.0, invalid_disparity: float = -1.0, min_pivot: float = 1e-3,
+                 rot_eps: float = 0.0, trans_eps: float = 0.0) -> TrackingResult:
+    """The camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against a rendered
+    view of the model (smx_track_camera; the rule, operation by operation, is in include/stereo_mi355x.h).  disp: float32
+    [H, W] or [n, H, W] with the reprojection matrix Q; pose: the initial guess [4, 4] / [n, 4, 4] (numpy or tensor;
+    rounded once to float32); model: the RenderedView (with normals) that TSDFVolume.render made from model_pose [4, 4]
+    / [n, 4, 4] with the reprojection matrix model_Q (default Q) -- one view per frame; it need not have the frame's
+    shape.  A pixel of the frame takes part where TSDFVolume.integrate would use it (depth_range, invalid_disparity,
+    confidence >= min_confidence and > 0, which is then its weight) and where the model pixel it projects to has a
+    surface within max_distance of it.  schedule: (stride, iterations) pairs, coarse to fine: an iteration of stride s
+    uses every s-th pixel of every s-th row.  A frame is LOST -- its pose comes back unchanged -- when an iteration has
+    fewer than min_inliers inliers or its 6 x 6 system has a pivot <= min_pivot (a frame that sees one plane only);
+    rot_eps / trans_eps (radians, metres) stop a frame early once an update is smaller than both.  Runs on the current
+    stream without synchronising and returns a TrackingResult of fresh device tensors.  Rotations are composed in
+    float32: over a long sequence they drift from orthogonality, which this function does not repair; nor does it close
+    loops or relocalise a lost camera."""
+    q = _check_q(Q)
+    qm = q if model_Q is None else _check_q(model_Q)
+    if (qm[:3, 2] != 0).any() or qm[3, 0] != 0 or qm[3, 1] != 0 or qm[3, 2] == 0:
+        raise RuntimeError("model_Q's ray must not depend on the disparity (what reprojection_matrix builds)")
+    pm = projection_matrix(qm)
+    z_min, z_max = _check_reproject_params(min_confidence, depth_range, invalid_disparity)
+    sched = _check_tracking_schedule(schedule)
+    for name, v, positive in (("max_distance", max_distance, True), ("min_pivot", min_pivot, False),
+                              ("rot_eps", rot_eps, False), ("trans_eps", trans_eps, False)):
+        _number_arg(name, v)
+        if not (math.isfinite(v) and (v > 0 if positive else v >= 0)):
+            raise RuntimeError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v}")
+    if not isinstance(min_inliers, int) or isinstance(min_inliers, bool) or not 1 <= min_inliers <= 2 ** 30:
+        raise RuntimeError(f"min_inliers must be an int in 1..2^30, got {min_inliers!r}")
+    _check_input("disp", disp)
+    if disp.dtype != torch.float32 or disp.dim() not in (2, 3) or not disp.is_cuda:
+        raise RuntimeError(f"disp must be float32 [H, W] or [n, H, W] on the GPU, got {disp.dtype} {tuple(disp.shape)} "
+                           f"on {disp.device}")
+    dev = disp.device
+    batched = disp.dim() == 3
+    n, H, W = disp.shape if batched else (1,) + tuple(disp.shape)
+    if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768 and n * H * W <= 2 ** 30):
+        raise RuntimeError(f"need n >= 1, 1 <= H, W <= 32768 and n * H * W <= 2^30, got {tuple(disp.shape)}")
+    if -(-W // 64) * -(-H // 4) > 32768:
+        raise RuntimeError(f"need ceil(W / 64) * ceil(H / 4) <= 32768, got a frame of {(H, W)}")
+    if confidence is not None:
+        _check_like("confidence", confidence, torch.float32, disp.shape, dev)
+    if not isinstance(model, RenderedView):
+        raise TypeError("model must be a RenderedView (TSDFVolume.render)")
+    if model.normals is None:
+        raise RuntimeError("model has no normals: render it with normals=True")
+    lead = (n,) if batched else ()
+    Hm, Wm = model.depth.shape[-2:]
+    _check_like("model.depth", model.depth, torch.float32, lead + (Hm, Wm), dev)
+    _check_like("model.normals", model.normals, torch.float32, lead + (3, Hm, Wm), dev)
+    pose_in = camera_to_world_poses(pose)
+    c2w = camera_to_world_poses(model_pose)
+    w2c = world_to_camera_poses(model_pose)
+    if pose_in.shape[0] != n or c2w.shape[0] != n:
+        raise RuntimeError(f"{n} frame(s) need {n} pose(s) and {n} model pose(s), got {pose_in.shape[0]} and {c2w.shape[0]}")
+    poses = torch.from_numpy(np.stack([pose_in, c2w, w2c])).pin_memory().to(dev, non_blocking=True)
+    pose_out = torch.empty((n, 3, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    rms = torch.empty((n,), dtype=torch.float32, device=dev)
+    sums = torch.empty((n, 30), dtype=torch.float64, device=dev)
+    ws_bytes = LIB.smx_track_camera_workspace_bytes(n, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    f16 = lambda m: (C.c_float * 16)(*m.reshape(-1).tolist())  # noqa: E731
+    sc = (C.c_int32 * max(sched.size, 1))(*sched.reshape(-1).tolist())
+    check(LIB.smx_track_camera(dev.index, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(),
+                               f16(q), float(min_confidence), z_min, z_max, float(invalid_disparity), Hm, Wm,
+                               model.depth.data_ptr(), model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(),
+                               poses[2].data_ptr(), poses[0].data_ptr(), sched.shape[0], sc, float(max_distance),
+                               min_inliers, float(min_pivot), float(rot_eps), float(trans_eps), pose_out.data_ptr(),
+                               info.data_ptr(), rms.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
+                               _stream(dev.index)))
+    index = _INFORMATION_INDEX.get(dev)
+    if index is None:
+        host = np.zeros((6, 6), np.int64)
+        for k, (i, j) in enumerate((i, j) for i in range(6) for j in range(i, 6)):
+            host[i, j] = host[j, i] = k
+        index = _INFORMATION_INDEX[dev] = torch.from_numpy(host).to(dev)
+    pose4 = torch.zeros((n, 4, 4), dtype=torch.float32, device=dev)
+    pose4[:, :3] = pose_out
+    pose4[:, 3, 3] = 1.0
+    out = (pose4, info[:, 0] != 0, info[:, 1], info[:, 2], info[:, 3], rms, sums[:, index], sums)
+    if not batched:
+        out = tuple(t[0] for t in out)
+    return TrackingResult(*out)
+
+
 class TSDFVolume:
     """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
     include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points), as a triangle mesh over
@@ -1611,6 +1737,21 @@ class TSDFVolume:
             disp, depth, weight = disp[0], depth[0], weight[0]
             nrm, col = (None if t is None else t[0] for t in (nrm, col))
         return RenderedView(disparity=disp, depth=depth, normals=nrm, colors=col, weight=weight)
+
+    def track(self, disp: torch.Tensor, Q, pose_guess, *, render_shape=None, min_weight: float = 1.0,
+              step: Optional[float] = None, render_depth_range=None, **track_args) -> TrackingResult:
+        """The pose of the frame(s) disp (float32 [H, W] / [n, H, W], reprojection matrix Q) against this volume: renders
+        it from pose_guess [4, 4] / [n, 4, 4] (render, at render_shape -- default the frame's -- with min_weight, step
+        and render_depth_range as its depth_range, depth and normals only) and tracks the frame against that view from
+        the same pose (track_camera, which takes track_args).  Frame-to-model tracking: fuse the frame at the returned
+        pose if it is not lost, and pass that pose as the next frame's guess."""
+        if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
+            raise RuntimeError("disp must be a float32 tensor [H, W] or [n, H, W]")
+        shape = tuple(disp.shape[-2:]) if render_shape is None else render_shape
+        invalid = track_args.get("invalid_disparity", -1.0)
+        view = self.render(Q, pose_guess, shape, min_weight=min_weight, step=step, depth_range=render_depth_range,
+                           normals=True, colors=False, invalid_disparity=invalid)
+        return track_camera(disp, Q, pose_guess, view, pose_guess, model_Q=Q, **track_args)
 
     def extract_point_cloud_batched(self, capacity: int, *, min_weight: float = 1.0, normals: bool = True,
                                     colors: bool = True):

@@ -192,6 +192,17 @@ EXPORTS = {
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                    C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # camera tracking: (n, H, W) -> workspace bytes; (device_id, n, H, W, disp, confidence, Q (host float32[16]),
+    # min_confidence, z_min, z_max, invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm (host float32[16]),
+    # model_camera_to_world, model_world_to_camera, pose_in, schedule_pairs, schedule (host int32[pairs][2]),
+    # max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out, info, rms, normal_equations, workspace,
+    # workspace_bytes, stream)
+    "smx_track_camera_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_track_camera": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*

@@ -13,6 +13,7 @@ import dataclasses
 import math
 from typing import Any, Optional, Tuple
 
+import numpy as np
 import torch
 
 import cuda_depth
@@ -70,6 +71,11 @@ class DepthEstimationResult:
     # the frame was integrated (TSDFVolume.render: a fresh tensor, invalid_disparity where no surface is hit); None
     # otherwise.  Keyword-only as well, and declared here: confidence_map stays the last field
     model_disparity_map: Optional[torch.Tensor] = dataclasses.field(default=None, kw_only=True)
+    # track_camera=True: the camera-to-world pose [4, 4] float64 (numpy) the frame was given -- initial_pose for the first
+    # frame, the tracked pose after it, the last good pose where tracking was lost -- and whether it was lost (the frame is
+    # then not integrated); None otherwise.  Keyword-only as well
+    camera_pose: Optional[Any] = dataclasses.field(default=None, kw_only=True)
+    tracking_lost: Optional[bool] = dataclasses.field(default=None, kw_only=True)
     # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
     # None otherwise
     confidence_map: Optional[torch.Tensor] = None
@@ -112,6 +118,7 @@ def _make_backend(config: DepthEstimationPipelineConfig, sgm: dict, **post: Any)
 
 
 class DepthEstimationPipeline:
+    _track_camera = False                                            # off unless __init__ turns it on
 
     def __init__(self, config: Optional[DepthEstimationPipelineConfig] = None, *, speckle_max_size: int = 0,
                  speckle_max_diff: float = 1.0, fill_invalid: bool = False, median_radius: int = 0,
@@ -126,7 +133,8 @@ class DepthEstimationPipeline:
                  point_cloud_depth_range: Tuple[float, float] = (0.0, math.inf), point_cloud_voxel_size: float = 0.0,
                  point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0,
                  tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None,
-                 right_view_synthesis: Optional[RightViewSynthesis] = None, render_model: bool = False):
+                 right_view_synthesis: Optional[RightViewSynthesis] = None, render_model: bool = False,
+                 track_camera: bool = False, initial_pose=None, tracking_args: Optional[dict] = None):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -160,7 +168,14 @@ class DepthEstimationPipeline:
         after the frame was integrated, from the frame's camera_pose at the frame's shape with the volume's defaults
         (TSDFVolume.render) and returns the disparity map as DepthEstimationResult.model_disparity_map: the denoised,
         hole-filled counterpart of disparity_map.  The reprojection matrix must then be one whose ray does not depend on
-        the disparity (every cuda_depth.reprojection_matrix).  False (the default) changes nothing."""
+        the disparity (every cuda_depth.reprojection_matrix).  False (the default) changes nothing.  track_camera /
+        initial_pose / tracking_args: track_camera=True (needs tsdf_volume and such a reprojection matrix) makes the
+        pipeline find the poses itself, and process() then takes no camera_pose: the first frame is integrated at
+        initial_pose [4, 4] (default the identity); every later frame is tracked against the volume rendered from the
+        last pose (TSDFVolume.track with point_cloud_depth_range, the confidence map and point_cloud_min_confidence, and
+        tracking_args on top), its twelve pose values and its lost flag are read back -- one small device-to-host copy,
+        hence one synchronisation, per frame -- and it is integrated at the tracked pose unless it is lost.  The result
+        carries camera_pose and tracking_lost; reset_tracking() forgets the last pose."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
@@ -184,6 +199,23 @@ class DepthEstimationPipeline:
                 raise ValueError("render_model needs a reprojection_matrix whose ray does not depend on the disparity "
                                  "(cuda_depth.reprojection_matrix builds one)")
         self._render_model = render_model
+        if not isinstance(track_camera, bool):
+            raise TypeError("track_camera must be a bool")
+        if not track_camera and (initial_pose is not None or tracking_args is not None):
+            raise ValueError("initial_pose and tracking_args need track_camera=True")
+        self._track_camera = track_camera
+        self._tracking_args = dict(tracking_args or {})
+        self._initial_pose = self._last_pose = None
+        if track_camera:
+            if tsdf_volume is None:
+                raise ValueError("track_camera needs tsdf_volume")
+            q = cuda_depth._check_q(reprojection_matrix)
+            if (q[:3, 2] != 0).any() or q[3, 0] != 0 or q[3, 1] != 0:
+                raise ValueError("track_camera needs a reprojection_matrix whose ray does not depend on the disparity "
+                                 "(cuda_depth.reprojection_matrix builds one)")
+            pose = np.eye(4) if initial_pose is None else initial_pose
+            cuda_depth.world_to_camera_poses(pose)
+            self._initial_pose = cuda_depth._host_matrices("initial_pose", pose, False)[0]
         if right_view_synthesis is not None and not isinstance(right_view_synthesis, RightViewSynthesis):
             raise TypeError("right_view_synthesis must be a pipeline.synthesis.RightViewSynthesis")
         self._right_view_synthesis = right_view_synthesis
@@ -218,6 +250,11 @@ class DepthEstimationPipeline:
         """Forgets the temporal filter's history (temporal=True), e.g. at a cut in the stream; a no-op otherwise."""
         self._stereo_matching.reset_temporal()
 
+    def reset_tracking(self) -> None:
+        """Forgets the last pose (track_camera=True): the next frame is integrated at initial_pose without tracking, as
+        the first one was; a no-op otherwise.  The volume is the caller's and is not touched."""
+        self._last_pose = None
+
     def get_configuration(self) -> DepthEstimationPipelineConfig:
         return self._config
 
@@ -233,7 +270,10 @@ class DepthEstimationPipeline:
         returned as the result's right_image ([3, H, W] float32 in 0..255, the synthesiser's persistent buffer).
         camera_pose: the left camera's camera-to-world pose [4, 4] for this frame, required with tsdf_volume and
         refused without one; the final map is integrated into the volume on the current stream."""
-        if (camera_pose is None) != (self._tsdf_volume is None):
+        if self._track_camera:
+            if camera_pose is not None:
+                raise ValueError("camera_pose must not be given with track_camera=True: the pipeline tracks it")
+        elif (camera_pose is None) != (self._tsdf_volume is None):
             raise ValueError("camera_pose is required with tsdf_volume" if camera_pose is None
                              else "camera_pose needs a pipeline with tsdf_volume")
         if camera_pose is not None:
@@ -253,7 +293,10 @@ class DepthEstimationPipeline:
         cloud = None
         if self._reprojection_matrix is not None:
             cloud = self._point_cloud(disparity, left_on_device, confidence)
-        if self._tsdf_volume is not None:
+        lost = None
+        if self._track_camera:
+            camera_pose, lost = self._track(disparity, confidence)
+        if self._tsdf_volume is not None and not lost:
             self._tsdf_volume.integrate(disparity, self._reprojection_matrix, camera_pose,
                                         image=self._colour_source(left_on_device), confidence=confidence,
                                         min_confidence=self._point_cloud_min_confidence,
@@ -265,7 +308,24 @@ class DepthEstimationPipeline:
                                              normals=False, colors=False,
                                              invalid_disparity=self._config.invalid_disparity).disparity
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
-                                     confidence_map=confidence, point_cloud=cloud, model_disparity_map=model)
+                                     confidence_map=confidence, point_cloud=cloud, model_disparity_map=model,
+                                     camera_pose=camera_pose if self._track_camera else None, tracking_lost=lost)
+
+    def _track(self, disparity: torch.Tensor, confidence: Optional[torch.Tensor]):
+        """(pose [4, 4] float64, lost) of this frame: initial_pose for the first frame, else the frame tracked against
+        the volume seen from the last pose; the last pose moves on unless tracking was lost."""
+        if self._last_pose is None:
+            self._last_pose = self._initial_pose.copy()
+            return self._last_pose.copy(), False
+        args = dict(confidence=confidence, min_confidence=self._point_cloud_min_confidence,
+                    depth_range=self._point_cloud_depth_range, invalid_disparity=self._config.invalid_disparity)
+        args.update(self._tracking_args)
+        found = self._tsdf_volume.track(disparity, self._reprojection_matrix, self._last_pose, **args)
+        packed = torch.cat([found.pose.reshape(-1), found.lost.reshape(1).to(torch.float32)]).cpu().numpy()
+        lost = bool(packed[16] != 0)
+        if not lost:
+            self._last_pose = packed[:16].reshape(4, 4).astype(np.float64)
+        return self._last_pose.copy(), lost
 
     def _point_cloud(self, disparity: torch.Tensor, left: torch.Tensor,
                      confidence: Optional[torch.Tensor]) -> "cuda_depth.PointCloud":

@@ -14,6 +14,7 @@ from __future__ import annotations
 import glob
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -30,7 +31,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 # whose arrays (the running-sum histories) only live in registers when the loop is FULLY unrolled; LLVM gives up on a
 # pragma'd loop whose unrolled size exceeds 16 K (silently under -Wno-pass-failed) and the arrays then go to scratch -- a 4x
 # slower kernel, same results.  The capture kernel's march (24-row bands, per-row lookup tests) is the one that crosses it.
-PER_FILE_FLAGS = {"tu_capture.hip": ["-mllvm", "-pragma-unroll-threshold=65536"]}
+# The stacked bands' march of 72 row steps crosses it as well (without the flag: 147 registers and 2,896 bytes of scratch per lane).
+PER_FILE_FLAGS = {"tu_capture.hip": ["-mllvm", "-pragma-unroll-threshold=65536"],
+                  "tu_fast_stack.hip": ["-mllvm", "-pragma-unroll-threshold=65536", "-Rpass-analysis=kernel-resource-usage"]}
+# Units whose k_match_fast instantiations must live in registers alone (the compiler's resource remarks are checked): the
+# stacked bands share a SIMD with the other stream lane's step 6 only within their register budget, and scratch would
+# mean that the march was not unrolled.
+NO_SCRATCH = {"tu_fast_stack.hip"}
 
 
 def hipcc() -> str:
@@ -42,6 +49,22 @@ def hipcc() -> str:
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def check_resources(unit: str, remarks: str) -> None:
+    """Raises if a k_match_fast instantiation of `unit` reports scratch or a spilled register (-Rpass-analysis=kernel-resource-usage)."""
+    name, seen = None, 0
+    for line in remarks.splitlines():
+        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill): (\S+)", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = m.group(2)
+            seen += "k_match_fast" in name
+        elif name and "k_match_fast" in name and int(m.group(2)) != 0:
+            raise RuntimeError(f"{unit}: {name} reports {m.group(1)} = {m.group(2)}: the march must stay in registers")
+    if seen == 0:
+        raise RuntimeError(f"{unit}: no resource remarks for k_match_fast (is -Rpass-analysis=kernel-resource-usage still among its flags?)")
 
 
 def _flags():
@@ -108,6 +131,8 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
             raise RuntimeError(f"hipcc failed on {os.path.basename(src)}:\n" + r.stdout + r.stderr)
         if r.stderr.strip() and verbose:
             print(r.stderr, file=sys.stderr)
+        if os.path.basename(src) in NO_SCRATCH:
+            check_resources(os.path.basename(src), r.stderr)
         open(obj + ".flags", "w").write(stamp)
 
     if jobs:

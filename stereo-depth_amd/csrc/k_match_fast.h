@@ -545,6 +545,100 @@ __device__ __forceinline__ void fast_stats_report(const MatchParams &p, int b, i
     if (v != 0ull) (void)__hip_atomic_fetch_add(p.fast_stats, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Stacked bands (k_match_fast<TH > 32>: throughput shape, sparse form, byte-packed winners): pass 1 of match_fast_body marches
+// NH unit bands of TU rows in one go -- one set of 22 halo rows for all of them -- and this function does what follows pass 1
+// there, once per unit band and on the tile that is already staged: everything behind pass 1 is written for at most 32 band
+// rows (one table bit per band row, rowmask, dup_left, the packed argpk).  The same steps as in match_fast_body, where the
+// comments are; a unit band differs from a band in its tile rows (hh * TU further down), its image rows and its slice of
+// best / arg.  The waves' needed-set tables are reused: a wave clears its own table behind its second pass (LDS executes a
+// wave's operations in order).  Each unit band that holds image rows counts as one window in the report.
+template <int TU, int NH, int PR, int PK16, class StageRight>
+__device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
+                                                  const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
+                                                  bool active, StageRight &&stage_right) {
+    constexpr int ND = PR - FA_WGCOLS + 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int h = p.h, w = p.w, Dd = p.Dd, BW = fast_bitwords(Dd);
+    const bool all_needed = Dd > FA_BITWORDS * 32;
+    unsigned *wbits = bits + wv * BW;
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+        float bh[TU];
+        int ah[TU];
+#pragma unroll
+        for (int o = 0; o < TU; ++o) {
+            bh[o] = best[hh * TU + o];
+            ah[o] = (argb[(hh * TU + o) >> 2] >> (8 * ((hh * TU + o) & 3))) & 0xff;      // byte-packed indices -> one register per row
+        }
+        FastLane lh = ln;
+        lh.lptr = ln.lptr + hh * TU * FA_PL;
+        lh.row0 = ln.row0 + (size_t)(hh * TU) * w;
+        lh.rows_ok = max(0, min(TU, h - x0 - hh * TU));
+        const unsigned short *Rh = Rt + hh * TU * PR;                 // the unit band's first tile row
+        unsigned dup_left = 0u;
+#ifndef SMX_FA_NO_DEDUP
+        if (!all_needed) {
+#pragma unroll
+            for (int o = 0; o < TU; ++o) {
+                const int la = __builtin_amdgcn_update_dpp(-1, ah[o], 0x138, 0xf, 0xf, false);
+                dup_left |= (la == ah[o] ? 1u : 0u) << o;
+            }
+            const int left_ok = __builtin_amdgcn_update_dpp(0, lh.store_ok ? 1 : 0, 0x138, 0xf, 0xf, false);
+            if (!left_ok) dup_left = 0u;
+        }
+#endif
+        if (lh.store_ok) {
+#pragma unroll
+            for (int o = 0; o < TU; ++o) {
+                if (o < lh.rows_ok) {
+                    const unsigned off = (unsigned)(o * w + lh.colidx);
+                    store_u32off(p.wta + lh.row0, off, (float)ah[o] + (float)p.dmin);
+                    const bool nv = !(bh[o] > SMX_FLT_MIN);
+                    store_u32off(p.costs + lh.row0, off, nv ? 0.0f : bh[o] * lh.inv);
+                    if (!all_needed && !((dup_left >> o) & 1u)) {
+                        const int dn = (ah[o] + 1 == Dd) ? 0 : ah[o] + 1;
+                        const int dp = (ah[o] == 0) ? Dd - 1 : ah[o] - 1;
+                        atomicOr(&wbits[dn], 1u << o);
+                        atomicOr(&wbits[dp], 1u << o);
+                    }
+                }
+            }
+        }
+        int marches2 = 0;
+        unsigned argpk[(TU + 1) / 2];
+#pragma unroll
+        for (int o = 0; o < (TU + 1) / 2; ++o) argpk[o] = 0u;
+#pragma unroll
+        for (int o = 0; o < TU; ++o)
+            argpk[o >> 1] |= ((lh.store_ok && o < lh.rows_ok) ? (unsigned)ah[o] : 0xffffu) << (16 * (o & 1));
+        for (int d0 = 0; d0 < Dd; d0 += ND) {
+            const int nd = min(ND, Dd - d0);
+            if (Dd > ND) stage_right(d0, nd);
+            else __syncthreads();
+            if (active) {
+                auto march = [&](int dda, int ddb, unsigned rows) {
+                    const int da = d0 + dda, db = d0 + ddb;
+                    ++marches2;
+                    lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
+                    fast_pass_pair<TU, PR, false, PK16, 1>(p, lh, da, false, bh, ah, Rh + wcol + lane + (nd - 1 - ddb), db, argpk,
+                                                           da == 0 ? Dd - 1 : da - 1, da + 1 == Dd ? 0 : da + 1,
+                                                           db == 0 ? Dd - 1 : db - 1, db + 1 == Dd ? 0 : db + 1, nullptr, nullptr, rows);
+                };
+                int pend = -1;
+                unsigned pend_rows = 0u;
+                SMX_FOR_EACH_NEEDED(wbits + d0, 0, nd, all_needed, lane, dd, rows, {
+                    if (pend < 0) { pend = dd; pend_rows = rows; }
+                    else { march(pend, dd, pend_rows | rows); pend = -1; }
+                })
+                if (pend >= 0) march(pend, pend, pend_rows);
+            }
+        }
+        if (lane == 0) fast_stats_report<false>(p, blk.z, (int)(blk.x + gridDim.x * blk.y), wv, marches2, active && lh.rows_ok > 0);
+        if (hh + 1 < NH)
+            for (int e = lane; e < BW; e += 64) wbits[e] = 0u;
+    }
+}
+
 // DSPLIT = false (throughput): the 4 waves of a workgroup own 4 adjacent column windows.
 // DSPLIT = true  (latency, few pairs in flight): the FA_DS_WAVES waves own the SAME window and a share of
 // the disparity range each; (best, arg) and the neighbour costs are merged through LDS, in
@@ -556,6 +650,11 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     constexpr int NW = DSPLIT ? FA_DS_WAVES : FA_WAVES;           // waves of this workgroup
     constexpr int WGCOLS = DSPLIT ? 64 : FA_WGCOLS;               // staged left columns
     constexpr int ND = PR - WGCOLS + 1;                           // disparities per staged right tile
+    // stacked bands (TH > 32): NH unit bands of TU rows per wave; what follows pass 1 is fast_stacked_tail's
+    constexpr int NH = TH > 32 ? 2 : 1;
+    constexpr int TU = TH / NH;
+    static_assert(NH == 1 || (TH == 2 * TU && TU <= 32 && ARGB && !DSPLIT && !DENSE && !P1ONLY),
+                  "stacked bands: two unit bands, byte-packed winners, throughput shape, sparse form");
     const int b = blk.z;
 
     extern __shared__ __attribute__((aligned(16))) unsigned short fsmem[];
@@ -632,6 +731,10 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
                     fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg);
             }
         }
+    }
+    if constexpr (NH > 1) {
+        fast_stacked_tail<TU, NH, PR, PK16>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
+        return;
     }
     if (ARGB) {            // byte-packed indices -> one register per row (the march's registers are free now)
         int packed[(TH + 3) / 4];
@@ -907,15 +1010,51 @@ inline void launch_match_fast_tall(const FastLaunch &fl, const MatchParams &p, i
     else launch_match_fast_t<TH, 320, false>(fl, p, n, s);
 }
 
+// Stacked bands (throughput shape, sparse form, byte-packed winners): a wave marches `stack` unit bands of FA_TH rows in one go
+// -- 2 x 24 output rows for 70 marched ones instead of 27 for 49.  The 70-row tile of pitch 256 (68.6 KB) fits a CU's 160 KB
+// exactly twice, so the kernel is compiled for two waves per SIMD (tu_fast_stack.hip); its workgroups are limited by LDS, not
+// by registers, and a step-6, fill or prologue wave of the other stream lane finds room beside them.
+constexpr int FA_STACK = 2;
+constexpr int FA_STACK_TH = FA_STACK * FA_TH;
+template <int PR> inline bool fast_stack_fits(int Dd) {          // twice into 160 KB, at the 1280-byte allocation granule
+    const size_t granule = 1280, lds = fast_lds_bytes<PR>(FA_STACK_TH, Dd);
+    return 2 * ((lds + granule - 1) / granule * granule) <= 160 * 1024;
+}
+// ... at pitch 256 only (up to 67 disparities)
+inline bool fast_stack_instantiated(int pitch, int Dd) { return pitch == 256 && fast_stack_fits<256>(Dd); }
+
+template <int PR>
+inline void launch_match_fast_stacked(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s) {
+    const dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + FA_STACK_TH - 1) / FA_STACK_TH, n);
+    const size_t lds = fast_lds_bytes<PR>(FA_STACK_TH, p.Dd);
+    const dim3 block(64 * FA_WAVES);
+    if (fl.pk == 2) hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 2, true, false>), grid, block, lds, s, p);
+    else if (fl.pk == 1) hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 1, true, false>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 0, true, false>), grid, block, lds, s, p);
+}
+// (the tile exceeds the 64 KB a kernel gets without asking)
+template <int PR>
+inline hipError_t fast_stacked_raise_lds_caps() {
+    const int cap = (int)fast_lds_bytes<PR>(FA_STACK_TH, PR - FA_WGCOLS + 1);
+    const void *kernels[3] = {reinterpret_cast<const void *>(&k_match_fast<FA_STACK_TH, PR, false, false, 2, true, false>),
+                              reinterpret_cast<const void *>(&k_match_fast<FA_STACK_TH, PR, false, false, 1, true, false>),
+                              reinterpret_cast<const void *>(&k_match_fast<FA_STACK_TH, PR, false, false, 0, true, false>)};
+    for (const void *k : kernels)
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, cap); e != hipSuccess) return e;
+    return hipSuccess;
+}
+
 // Shape of a fast-kernel launch of n pairs in its sparse form (also reported by smx_match_geometry; what is launched:
 // smx_plan.h: fast_launch).
 struct FastPlan {
     bool small;      // few pairs in flight: short bands, disparity range split over the 4 waves
     int th;          // output rows per band
     bool wide;       // right-tile pitch 320 instead of 256
+    int stack = 1;   // unit bands of th rows a wave marches in one go (throughput shape: 1 or FA_STACK)
 };
 
-inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus) {
+// stack_opt: SMX_FAST_STACK (1 / 0: the stacked bands wherever their instantiation exists / never, -1: by the rule below)
+inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus, int stack_opt = -1) {
     FastPlan pl{};
     // Few pairs in flight: short bands and the disparity range split over the waves of a
     // workgroup (16x the waves of the throughput shape) cut the latency of a call; large batches:
@@ -968,6 +1107,15 @@ inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus) {
 #ifdef SMX_FA_FORCE_TH
     pl.th = SMX_FA_FORCE_TH;           // tuning experiments only (24, 27 or 32)
 #endif
+    // Stacked bands: the sparse form on the stream lanes, where the other lane's small kernels fill the issue slots that two
+    // waves per SIMD leave empty (on a caller's stream the same geometry loses: NOTES.md), and only if fewer rows are marched.
+    if (stack_opt != 0 && !p.dense && !p.pass1_only && fast_stack_instantiated(fast_tall_pitch(p.Dd), p.Dd)) {
+        const long rows_stack = (long)((p.h + FA_STACK_TH - 1) / FA_STACK_TH) * (FA_STACK_TH + 22);
+        if (stack_opt == 1 || (p.on_lanes && rows_stack < (long)((p.h + pl.th - 1) / pl.th) * (pl.th + 22))) {
+            pl.th = FA_TH;
+            pl.stack = FA_STACK;
+        }
+    }
     return pl;
 }
 

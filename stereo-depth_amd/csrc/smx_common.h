@@ -223,6 +223,7 @@ struct FastLaunch {
     bool argb = false;           // the arg-max indices are kept as bytes
     int form = FAST_SPARSE;
     int gate = 0;                // (on the grid flag, like the two capture launches)
+    int stack = 1;               // unit bands of th rows a wave marches in one go: 1, or 2 (throughput shape, sparse form: k_match_fast.h FA_STACK)
 };
 struct FastCaptureLaunch { bool small = false, wide = false; int pk = 0, gate = 0; };
 struct AutoLaunch { int th = 0; bool wide = false; int pk = 0, nsplit = 1, nd_chunk = 0; size_t lds_bytes = 0; };

@@ -193,6 +193,7 @@ hipError_t raise_lds_caps(int device) {
     if (hipError_t e = smx::exact_raise_lds_caps(SMX_EXACT2_LDS_CAP + (int)((smx::E2_CAPBITS + 2 * smx::E2_SPARSE_WORDS) * sizeof(unsigned)));
         e != hipSuccess) return e;
     if (hipError_t e = smx::match_auto_raise_caps(); e != hipSuccess) return e;
+    if (hipError_t e = smx::fast_stack_raise_caps(); e != hipSuccess) return e;
     done.push_back(device);
     return hipSuccess;
 }
@@ -803,6 +804,7 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     // environment switches are read here, once (never per call)
     smx::PlanOptions opt;
     opt.fast_dense = env_is("SMX_FAST_DENSE", '1') ? 1 : (env_is("SMX_FAST_DENSE", '0') ? 0 : -1);
+    opt.fast_stack = env_is("SMX_FAST_STACK", '1') ? 1 : (env_is("SMX_FAST_STACK", '0') ? 0 : -1);
     opt.fast_dense_small = env_is("SMX_FAST_DENSE_SMALL", '1') ? 1 : (env_is("SMX_FAST_DENSE_SMALL", '0') ? 0 : -1);
     e->opt_lane_priority = env_is("SMX_LANE_PRIORITY", '0') ? 0 : 1;
     e->opt_debug_hints = std::getenv("SMX_DEBUG_HINTS") != nullptr;

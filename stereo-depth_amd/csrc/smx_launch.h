@@ -49,6 +49,8 @@ void launch_match_fast(const FastLaunch &fl, const MatchParams &p, int n, hipStr
 void launch_match_fast_tall_24(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_27(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
 void launch_match_fast_tall_32(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);
+void launch_match_fast_stack(const FastLaunch &fl, const MatchParams &p, int n, hipStream_t s);     // tu_fast_stack.hip: fl.stack == 2
+hipError_t fast_stack_raise_caps();       // ... whose tile needs more than 64 KB of LDS
 void launch_match_auto_small_tu(const AutoLaunch &al, const MatchParams &p, int n, hipStream_t s);
 hipError_t match_auto_raise_caps();       // k_match_auto.h: MATCH_AUTO_LDS_CAP
 

@@ -41,6 +41,7 @@ constexpr int SMX_EXACT2_LDS_CAP = 80 * 1024;
 struct PlanOptions {
     int fast_dense = -1;            // SMX_FAST_DENSE
     int fast_dense_small = -1;      // SMX_FAST_DENSE_SMALL: the latency shape at 12-row bands
+    int fast_stack = -1;            // SMX_FAST_STACK: the stacked bands of the throughput shape (-1: on the stream lanes, where they march fewer rows)
 };
 
 // Everything the launch plans depend on that is fixed after smx_create.
@@ -224,7 +225,7 @@ inline MatchParams plan_params(const EngineFacts &f, bool on_lanes) {
     return mp;
 }
 // Shape of a fast-kernel launch of n pairs; `small` is also the engine's notion of "few pairs in flight".
-inline FastPlan range_fast_plan(const EngineFacts &f, bool on_lanes, int n) { return match_fast_plan(plan_params(f, on_lanes), n, f.cus); }
+inline FastPlan range_fast_plan(const EngineFacts &f, bool on_lanes, int n) { return match_fast_plan(plan_params(f, on_lanes), n, f.cus, f.opt.fast_stack); }
 
 // ---- the launch specs ------------------------------------------------------------------------------------------------------
 // The dense exact-order launch of n pairs.  Default radii without the volume: the register-tiled kernel, for few pairs
@@ -285,6 +286,7 @@ inline FastLaunch fast_launch(const EngineFacts &f, const FastPlan &pl, bool den
         dense_here = dense && x.argb && x.th <= FA_DENSE_MAX_TH;
     }
     x.form = f.capture ? FAST_PASS1_ONLY : (!dense_here ? FAST_SPARSE : (pl.small ? FAST_DENSE_SMALL : FAST_DENSE));
+    x.stack = pl.stack;              // (match_fast_plan stacks the sparse form only)
     return x;
 }
 
@@ -366,7 +368,7 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
         else if (rgb) p.mode = SMX_MATCH_EXACT_ORDER;
     }
     const MatchParams mp = plan_params(f, call.on_lanes);
-    p.fast = match_fast_plan(mp, n, f.cus);
+    p.fast = match_fast_plan(mp, n, f.cus, f.opt.fast_stack);
     const bool small = p.fast.small;
     // dmin > 0 (capture route): the match kernels stop after the arg-max; a sparse second kernel looks up the
     // three aggregated costs step 6 reads (k_match_capture.h; the workgroup that owns pixel 0 of a pair evaluates that pixel's
@@ -420,6 +422,11 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
             if (dense) (tall12 ? p.dense_small : p.dense) = true;
             else p.fill_publishes = p.reports;
         }
+    }
+    if (p.dense && p.fast.stack > 1) {           // the stacked bands have no dense form: a dense call takes the plan without them
+        MatchParams md = mp;
+        md.dense = 1;
+        p.fast = match_fast_plan(md, n, f.cus, f.opt.fast_stack);
     }
 
     if (p.route == AGG_FILTERED || p.route == AGG_EXACT || p.route == AGG_AUTO_GATED) {
@@ -545,10 +552,10 @@ inline void match_geometry(const EngineFacts &f, bool on_lanes, int n, smx_match
     }
     const FastPlan pl = range_fast_plan(f, on_lanes, n);
     g->kernel = pl.small ? SMX_KERNEL_FAST_SPLIT : SMX_KERNEL_FAST_WINDOW;
-    g->band_rows = pl.th;
+    g->band_rows = pl.th * pl.stack;
     g->waves_per_workgroup = pl.small ? FA_DS_WAVES : FA_WAVES;
     const int cols_per_wg = FA_VALID * (pl.small ? 1 : FA_WAVES);
-    const long wgs = (long)((f.w + cols_per_wg - 1) / cols_per_wg) * ((f.h + pl.th - 1) / pl.th);
+    const long wgs = (long)((f.w + cols_per_wg - 1) / cols_per_wg) * ((f.h + g->band_rows - 1) / g->band_rows);
     g->rows_marched = g->band_rows + 22;
     g->workgroups = (int)(wgs * n);
     const long waves = wgs * g->waves_per_workgroup;

@@ -19,6 +19,8 @@ void launch_match_fast(const FastLaunch &fl, const MatchParams &p, int n, hipStr
             if (fl.pitch == 256) launch_match_fast_t<FA_TH_SMALL, 256, true>(fl, p, n, s);
             else launch_match_fast_t<FA_TH_SMALL, 320, true>(fl, p, n, s);
         }
+    } else if (fl.stack == FA_STACK) {
+        launch_match_fast_stack(fl, p, n, s);
     } else if (fl.th == 27) {
         launch_match_fast_tall_27(fl, p, n, s);
     } else if (fl.th == 32) {

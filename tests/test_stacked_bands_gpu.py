@@ -16,6 +16,10 @@ Shapes, chosen for what the halves can get wrong (pooled sizes):
   B  30 x 190: one band, the first half full, the second with 6 rows.
   C  98 x 190, 33 disparities (an unpaired last disparity): two full bands and a tail of 2 rows.
   D  96 x 190: two full bands, 2 x 70 marched rows against 4 x 49 -- planned by the rule, nothing forced.
+Limits of the form, each forced unless the rule stacks by itself (H73): the ranges 67 (the LDS cap), 66, 65 (one needed word
+alone in the second 64-word ballot group), 32 (a one-group table), 3 and 2 (both neighbours the same disparity) at shape A;
+the widths 168 (no idle wave), 169 (a workgroup column of one pixel column), 43 (wave 1 owns one column) and 100 at 57 rows;
+the heights 24 (second half empty), 25 (one row), 48, 49 (a second band of one row) and 73 at width 100; K = 4 and K = 8 at 25 x 100.
 Content: banded, scene-like and noise pairs (noise fills the needed sets of both halves), tiled over the batch.  One more
 call is an AUTO batch of f32 gray with one off-grid pair (the gated launches), one is split over both lanes (both shape D)."""
 import numpy as np
@@ -94,6 +98,24 @@ CASES = [
     ("B_one_partial_band", 2, 30, 190, 64, "1"),
     ("C_odd_range", 2, 98, 190, 33, "1"),
     ("D_by_rule", 2, 96, 190, 64, None),
+    # the limits of the form (shape A's 57 x 190 unless said otherwise; six distinct pairs each)
+    ("R67_lds_cap", 2, 57, 190, 67, "1"),            # the largest instantiation (fast_stacked_raise_lds_caps): 68 table words
+    ("R66", 2, 57, 190, 66, "1"),
+    ("R65_lone_word_in_group_2", 2, 57, 190, 65, "1"),   # needed word 64 alone in the second ballot group: a pending partner crosses groups
+    ("R32_one_group", 2, 57, 190, 32, "1"),
+    ("R3", 2, 57, 190, 3, "1"),
+    ("R2_both_neighbours_one_march", 2, 57, 190, 2, "1"),     # dn == dp: both cost planes come from one march
+    ("W168_no_idle_wave", 2, 57, 168, 64, "1"),      # one full workgroup column
+    ("W169_one_pixel_column", 2, 57, 169, 64, "1"),  # the second workgroup column owns one pixel column
+    ("W43_wave_1_one_column", 2, 57, 43, 64, "1"),
+    ("W100", 2, 57, 100, 64, "1"),
+    ("H24_second_half_empty", 2, 24, 100, 64, "1"),
+    ("H25_second_half_one_row", 2, 25, 100, 64, "1"),
+    ("H48", 2, 48, 100, 64, "1"),
+    ("H49_second_band_one_row", 2, 49, 100, 64, "1"),
+    ("H73_by_rule", 2, 73, 100, 64, None),           # 2 x 70 marched rows against 3 x 49 of 27-row bands: the rule stacks
+    ("H25_k4", 4, 25, 100, 64, "1"),                 # the other packed-sum forms through a one-row half
+    ("H25_k8", 8, 25, 100, 64, "1"),
 ]
 D_SHAPE = (2, 96, 190, 64)
 
@@ -110,6 +132,8 @@ def test_stacked_call_against_the_oracle_and_the_plain_bands(cd, oracle_omp, mon
     assert geo["kernel"] == "fast_window" and geo["band_rows"] == 48 and geo["rows_marched"] == 70, geo
     geo0, plain = _call(cd, cfg, tl, tr, n, "0", monkeypatch)
     assert geo0["kernel"] == "fast_window" and geo0["band_rows"] in (24, 27, 32), geo0
+    if name == "H73_by_rule":                        # match_fast_plan: `rows_stack < ceil(h / th) * (th + 22)`
+        assert geo0["band_rows"] == 27 and -(-h // 48) * 70 == 140 < -(-h // 27) * 49 == 147, geo0
     for k in got:
         assert torch.equal(got[k], plain[k]), f"{name}: {k} differs from the engine with the stacked bands forbidden"
     for i, (ref_out, ref) in enumerate(_oracle_runs(oracle_omp, ocfg, (K, h, w, Dd), pairs)):

@@ -7,8 +7,8 @@ tu_stages.hip) with the kernel constants passed in, so that tests/test_scale_geo
 it reads from the sources and fail loudly when a retuned constant leaves a case below its threshold.
 
 The second half holds the cases of tests/test_launch_caps_gpu.py: the map entries (confidence, temporal filter, SGM,
-weighted median, WLS, rectification, the LR pack and check) past the caps of their launchers' grids, with many tiny maps
-tiled from TILE_PERIOD distinct ones."""
+weighted median, WLS, rectification, the LR pack and check, camera tracking) past the caps of their launchers' grids, with
+many tiny maps tiled from TILE_PERIOD distinct ones."""
 from __future__ import annotations
 
 C2_H, C2_W = 375, 1242                        # KITTI C2 maps
@@ -87,6 +87,15 @@ LR_PACK_K, LR_PACK_D = 2, 128
 
 # 16. the mirrored LR check on rows too wide for LDS: (n, H, W, K, D); W % 4 != 0 selects the scalar loop
 LR_WIDE_CASES = [(1, 24, 4104, 2, 16), (1, 24, 4102, 2, 16)]
+
+# 17. camera tracking: (n, frame shape, model view shape) triples on k_track_accum's grid.y and k_track_solve's grid.x;
+# a schedule of two strides and three iterations, so that a lost triple's `continue` alternates with work on both loops'
+# second trips, launch after launch.  Triple i is (model view, displacement, the model view misses) number i % 7.
+TRACK_CAP_CASE = (65538, (11, 18), (12, 16))
+TRACK_CAP_SCHEDULE = ((2, 1), (1, 2))
+TRACK_CAP_MIN_INLIERS = 10                    # the 5 x 9 pixels of the stride-2 iteration hold more inliers in the twin
+TRACK_CAP_TRIPLES = (("outside", 0, False), ("left", 1, False), ("outside", 2, False), ("left", 0, True),
+                     ("outside", 1, False), ("left", 2, False), ("left", 0, False))
 
 
 def cdiv(a: int, b: int) -> int:
@@ -198,6 +207,12 @@ def lr_pack_geometry(rows: int, W: int, elem_bytes: int, threads: int, items: in
     tail = half - chunks * (16 // elem_bytes)
     return dict(blocks=blocks, stride=stride, vec=vec, chunk_trips=stride_trips(chunks, stride),
                 element_trips=stride_trips(tail, stride), mirrored_trips=stride_trips(mirrored, stride))
+
+
+def track_triple_grids(n: int, cap: int):
+    """((grid.y, stride, trips) of k_track_accum: f += gridDim.y, (grid.x, stride, trips) of k_track_solve: f += gridDim.x)."""
+    g = capped_grid(n, cap)
+    return (g, g, stride_trips(n, g)), (g, g, stride_trips(n, g))
 
 
 def tile_period_ok(strides) -> bool:

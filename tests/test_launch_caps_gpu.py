@@ -21,6 +21,8 @@ case still crosses its cap.
     test_lr_pack_strides              k_lr_pack: straight halves in 16-byte chunks and in elements, mirrored halves
     test_mirrored_lr_check_on_rows_wider_than_lds
                                       k_lr_check<MIRRORED, no LDS>, float4 rows and scalar rows
+    test_track_past_the_triple_cap    k_track_accum: f += gridDim.y, and k_track_solve: f += gridDim.x, three iterations
+                                      at two strides, with a lost triple's `continue` between tracked ones
 
 How 10^5 to 10^8 maps get a reference: TILE_PERIOD = 7 distinct maps (pairs, streams) drawn from the generators of the
 entry's own test module, their expectation from the entry's reference, and map i of the call = distinct map i % 7, tiled
@@ -49,7 +51,9 @@ import test_median_gpu as t_med                     # noqa: E402
 import test_rectify_gpu as t_rect                   # noqa: E402
 import test_sgm_gpu as t_sgm                        # noqa: E402
 import test_temporal_gpu as t_temp                  # noqa: E402
+import test_track_gpu as t_track                    # noqa: E402
 import test_wls_gpu as t_wls                        # noqa: E402
+import track_cases as trk                           # noqa: E402
 from lr_ref import lr_rule                          # noqa: E402
 from oracle_lib import OracleConfig                 # noqa: E402
 
@@ -82,11 +86,14 @@ def tile_dev(distinct, n):
 def sentinel(shape, dtype=torch.float32):
     if dtype == torch.uint8:
         return torch.full(shape, SENTINEL_BYTE, dtype=torch.uint8, device="cuda")
-    return torch.full(shape, SENTINEL_BITS, dtype=torch.int32, device="cuda").view(torch.float32)
+    if dtype == torch.float64:                                   # the sentinel word twice: a NaN as a double too
+        return torch.full(tuple(shape[:-1]) + (2 * shape[-1],), SENTINEL_BITS, dtype=torch.int32, device="cuda").view(dtype)
+    words = torch.full(shape, SENTINEL_BITS, dtype=torch.int32, device="cuda")
+    return words if dtype == torch.int32 else words.view(torch.float32)
 
 
 def as_bits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
+    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int64) if t.dtype == torch.float64 else t
 
 
 def assert_tiled(got, distinct_expected, what):
@@ -100,10 +107,11 @@ def assert_tiled(got, distinct_expected, what):
     flat = int(bad.reshape(-1).nonzero()[0])
     i, k = divmod(flat, bad.shape[1])
     gv, ev = int(g.reshape(g.shape[0], -1)[i, k]), int(e.reshape(g.shape[0], -1)[i, k])
-    marks = int((g == (SENTINEL_BYTE if got.dtype == torch.uint8 else SENTINEL_BITS)).sum())
+    mark = {torch.uint8: SENTINEL_BYTE, torch.float64: SENTINEL_BITS << 32 | SENTINEL_BITS}.get(got.dtype, SENTINEL_BITS)
+    marks, mask = int((g == mark).sum()), (1 << 8 * g.element_size()) - 1
     raise AssertionError(f"{what}: {int(bad.sum())} elements of {int(bad.any(1).sum())} maps differ, first at map {i} "
-                         f"(distinct map {i % exp.shape[0]}) element {k}: got {gv & 0xFFFFFFFF:#x}, expected "
-                         f"{ev & 0xFFFFFFFF:#x}; {marks} elements still hold the sentinel")
+                         f"(distinct map {i % exp.shape[0]}) element {k}: got {gv & mask:#x}, expected "
+                         f"{ev & mask:#x}; {marks} elements still hold the sentinel")
 
 
 def assert_distinct(distinct_expected, what):
@@ -447,3 +455,50 @@ def test_mirrored_lr_check_on_rows_wider_than_lds(cd, oracle_omp, n, H, W, K, D)
                                       max_diff=1.0, invalid_disparity=INVALID)
     assert_bitwise(right_out[0], want_r, "right_out")
     assert_bitwise(out[0], want, "out")
+
+
+# ---- 9. camera tracking --------------------------------------------------------------------------------------------------
+
+def track_distinct():
+    """The distinct triples' operands (frames, model views and their poses, start poses) and the twin's four outputs."""
+    _, shape, model_shape = sc.TRACK_CAP_CASE
+    margin = trk.run_margin(sc.TRACK_CAP_SCHEDULE)                # the frames scaled_expected tracks
+    frames = [trk.scaled_frame(shape, k, view, margin)[0] for view, k, _ in sc.TRACK_CAP_TRIPLES]
+    models = [trk.scaled_model(view, model_shape, misses) for view, _, misses in sc.TRACK_CAP_TRIPLES]
+    want = [trk.scaled_expected(shape, sc.TRACK_CAP_SCHEDULE, k, view, model_shape, misses,
+                               min_inliers=sc.TRACK_CAP_MIN_INLIERS) for view, k, misses in sc.TRACK_CAP_TRIPLES]
+    ops = dict(disp=np.stack(frames), depth=np.stack([m["depth"] for m in models]),
+               normals=np.stack([m["normals"] for m in models]), c2w=np.stack([m["c2w"] for m in models]),
+               w2c=np.stack([m["w2c"] for m in models]),
+               pose_in=np.stack([trk.start_pose(view) for view, _, _ in sc.TRACK_CAP_TRIPLES]))
+    outs = dict(pose_out=np.stack([w["pose"] for w in want]), info=np.stack([w["info"] for w in want]).astype(np.int32),
+                rms=np.array([w["rms"] for w in want], np.float32), sums=np.stack([w["sums"] for w in want]))
+    return ops, outs, trk.scaled_q(shape, margin), models[0]["Qm"], models[0]["Pm"]
+
+
+def test_track_past_the_triple_cap(cd):
+    """Through the C entry, so that the outputs and the workspace (the triples' state and partial sums, which one launch
+    hands to the next) start as sentinels."""
+    from cuda_depth import _native as N
+    n, shape, model_shape = sc.TRACK_CAP_CASE
+    ops, outs, Q, Qm, Pm = track_distinct()
+    for name, e in outs.items():
+        assert_distinct(e, f"track {name}")
+    lost = outs["info"][:, 0] != 0
+    assert [bool(v) for v in lost] == [m for _, _, m in sc.TRACK_CAP_TRIPLES] and lost.any() and not lost.all()
+    iterations = sum(k for _, k in sc.TRACK_CAP_SCHEDULE)
+    assert (outs["info"][~lost, 1] == iterations).all() and (outs["info"][lost, 1] == 1).all(), "a tracked triple runs on"
+    assert (outs["info"][~lost, 2] >= sc.TRACK_CAP_MIN_INLIERS).all()
+    tiled = {k: tile_dev(v, n) for k, v in ops.items()}
+    got = dict(pose_out=sentinel((n, 3, 4)), info=sentinel((n, 4), torch.int32), rms=sentinel((n,)),
+               sums=sentinel((n, 30), torch.float64))
+    ws_bytes = int(N.LIB.smx_track_camera_workspace_bytes(n, *shape))
+    assert ws_bytes > 0
+    ws = torch.full((ws_bytes,), SENTINEL_BYTE, dtype=torch.uint8, device="cuda")
+    call = t_track.Direct.of(n, shape, model_shape, Q, Qm, Pm, sc.TRACK_CAP_SCHEDULE, ws=ws, **tiled, **got)
+    assert call.call(min_inliers=sc.TRACK_CAP_MIN_INLIERS) == 0, call.native.last_error()
+    torch.cuda.synchronize()
+    for name, e in outs.items():
+        assert_tiled(got[name], e, f"track {name}")
+    assert_tiled(tiled["disp"], ops["disp"], "disp untouched")
+    assert_tiled(tiled["pose_in"], ops["pose_in"], "pose_in untouched")

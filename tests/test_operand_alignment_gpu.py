@@ -19,19 +19,27 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import raycast_cases as rc_cases                    # noqa: E402
+import raycast_ref as rc                            # noqa: E402
 import stereo_synthetic as syn                      # noqa: E402
+import synthesis_ref                                # noqa: E402
 import test_confidence_gpu as t_conf                # noqa: E402  (the generators of each entry's own tests)
 import test_lr_check_gpu as t_lr                    # noqa: E402
 import test_median_gpu as t_med                     # noqa: E402
+import test_raycast_gpu as t_ray                    # noqa: E402
 import test_sgm_gpu as t_sgm                        # noqa: E402
+import test_synthesis_gpu as t_syn                  # noqa: E402
 import test_temporal_gpu as t_temp                  # noqa: E402
+import test_track_gpu as t_track                    # noqa: E402
 import test_wls_gpu as t_wls                        # noqa: E402
+import track_cases as tc                            # noqa: E402
+from test_track_gpu import views, volume            # noqa: E402,F401  (the library's model views, tied to the twin's bits)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SENTINEL_BITS = 0x7FD5A5A5                          # a quiet NaN with a payload: no kernel here produces it
 SENTINEL_BYTE = 0xA5
 GUARD_BYTES = 256                                   # of sentinel on each side of a view (at least 64 are required)
-OFFSETS = (1, 2, 3)                                 # elements: floats for float32 operands, bytes for uint8
+OFFSETS = (1, 2, 3)                                 # elements: floats, int32 words, doubles; bytes for uint8
 
 
 @pytest.fixture(scope="module")
@@ -45,8 +53,9 @@ def cd():
 def _sentinel_flat(count, dtype):
     if dtype == torch.uint8:
         return torch.full((count,), SENTINEL_BYTE, dtype=torch.uint8, device="cuda")
-    assert dtype == torch.float32
-    return torch.full((count,), SENTINEL_BITS, dtype=torch.int32, device="cuda").view(torch.float32)
+    assert dtype in (torch.float32, torch.int32, torch.float64)
+    words = torch.full((count * (2 if dtype == torch.float64 else 1),), SENTINEL_BITS, dtype=torch.int32, device="cuda")
+    return words if dtype == torch.int32 else words.view(dtype)    # a double of two sentinel words is a NaN as well
 
 
 def offset_view(t, k):
@@ -68,7 +77,8 @@ def sentinel_view(shape, k, dtype=torch.float32):
 
 
 def as_bits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
+    """float32 as its words, float64 as its pairs of words (the last dimension doubles), everything else as it is."""
+    return t.view(torch.int32) if t.dtype in (torch.float32, torch.float64) else t
 
 
 def assert_guards(view, what):
@@ -77,7 +87,8 @@ def assert_guards(view, what):
     assert base is not None and base.dim() == 1
     mark = SENTINEL_BYTE if view.dtype == torch.uint8 else SENTINEL_BITS
     b = as_bits(base)
-    before, after = b[:off] != mark, b[off + view.numel():] != mark
+    first, last = (i * view.element_size() // b.element_size() for i in (off, off + view.numel()))   # in b's elements
+    before, after = b[:first] != mark, b[last:] != mark
     assert not bool(before.any()), f"{what}: {int(before.sum())} guard elements before the view were written"
     assert not bool(after.any()), f"{what}: {int(after.sum())} guard elements after the view were written"
 
@@ -278,3 +289,95 @@ def test_map_entry_with_every_operand_off_alignment(cd, entry):
     for i, (g, w) in enumerate(zip(got, want)):
         assert g.data_ptr() % 16 == 4, "the operand is not where the case wants it"
         check_output(g, w, f"{entry}: output {i}")
+
+
+# ---- camera tracking, ray casting and right-view synthesis: inputs, outputs and both, one to three elements off ---------
+
+PLACEMENTS = (("inputs", True, False), ("outputs", False, True), ("all", True, True))
+
+
+def run_placed(ins, outs, k_in, k_out, launch):
+    """launch(inputs, outputs) on the inputs moved to offset k_in and sentinel outputs of the shapes and types `outs` at
+    offset k_out; returns the outputs after checking that the inputs are what they were."""
+    a = {name: offset_view(t, k_in) if k_in else t for name, t in ins.items()}
+    o = {name: sentinel_view(shape, k_out, dtype) for name, (shape, dtype) in outs.items()}
+    launch(a, o)
+    torch.cuda.synchronize()
+    for name, t in ins.items():
+        assert a[name].data_ptr() % 256 == k_in * t.element_size(), "the operand is not where the case wants it"
+        assert_same(a[name], t, f"{name} untouched")
+    return o
+
+
+def check_placements(ins, outs, k, launch, what):
+    """The aligned call's outputs after comparing every placement at offset k with them."""
+    want = run_placed(ins, outs, 0, 0, launch)
+    for moved, move_in, move_out in PLACEMENTS:
+        got = run_placed(ins, outs, k if move_in else 0, k if move_out else 0, launch)
+        for name in outs:
+            assert got[name].data_ptr() % 256 == (k if move_out else 0) * got[name].element_size()
+            check_output(got[name], want[name], f"{what}: {name} with {moved} at offset {k}")
+    return want
+
+
+@pytest.mark.parametrize("k", OFFSETS)
+def test_track_camera(cd, views, k):
+    """The C entry on two triples with confidence maps, strides 2 and 1; float64 sums and int32 info move by whole
+    elements.  The workspace stays aligned."""
+    d = t_track.Direct(cd, views, schedule=((2, 2), (1, 2)))
+    conf = dev(np.stack([tc.frame(v, s, i, True)[3] for v, s, i, *_ in d.triples]))
+    ins = dict(disp=d.disp, confidence=conf, depth=d.depth, normals=d.normals, c2w=d.c2w, w2c=d.w2c, pose_in=d.pose_in)
+    outs = dict(pose_out=((d.n, 3, 4), torch.float32), info=((d.n, 4), torch.int32), rms=((d.n,), torch.float32),
+                sums=((d.n, 30), torch.float64))
+
+    def launch(a, o):
+        assert d.call(min_confidence=0.1, **a, **o) == 0, d.native.last_error()
+
+    got = check_placements(ins, outs, k, launch, "track_camera")
+    for i, (v, s, j, *_) in enumerate(d.triples):                         # the aligned call is the twin's, confidence and all
+        want = tc.expected(v, s, j, confidence=True, schedule=((2, 2), (1, 2)))
+        assert want["info"][0] == 0 and want["info"][1] == 4
+        tc.assert_same({"pose": got["pose_out"][i].cpu().numpy(), "info": got["info"][i].cpu().numpy(),
+                        "rms": got["rms"][i].cpu().numpy(), "sums": got["sums"][i].cpu().numpy()}, want, f"triple {i}")
+
+
+@pytest.mark.parametrize("k", OFFSETS)
+def test_tsdf_raycast(cd, k):
+    """The C entry with all five outputs.  The colour volume is one aligned 32-bit word per voxel (the header's state
+    layout), so it moves by words; the colour output is uint8 and moves by bytes."""
+    import types
+
+    import cuda_depth._native as native
+    vol = t_ray.upload(cd, rc_cases.fused_state())
+    n, (H, W) = len(t_ray.THREE), rc_cases.SHAPE
+    ins = dict(tsdf=vol.tsdf, weight=vol.weight, color=vol.color.view(torch.int32),
+               poses=dev(rc.view_pose(rc_cases.poses_of(t_ray.THREE))))
+    outs = dict(disparity=((n, H, W), torch.float32), depth=((n, H, W), torch.float32), normals=((n, 3, H, W), torch.float32),
+                colors=((n, 3, H, W), torch.uint8), weight=((n, H, W), torch.float32))
+    ws = torch.empty(native.LIB.smx_tsdf_raycast_workspace_bytes(*rc_cases.DIMS), dtype=torch.uint8, device="cuda")
+
+    def launch(a, o):
+        v = types.SimpleNamespace(dims=vol.dims, origin=vol.origin, voxel_size=vol.voxel_size, tsdf=a["tsdf"],
+                                  weight=a["weight"], color=a["color"])
+        t_ray.raycast_call(native, v, n, rc_cases.SHAPE, rc_cases.q_of("kitti"), a["poses"], t_ray.step_of(1.0),
+                           rc_cases.DEPTH_RANGE, o["disparity"], o["depth"], o["normals"], o["colors"], o["weight"], ws,
+                           torch.cuda.current_stream().cuda_stream)
+
+    got = check_placements(ins, outs, k, launch, "tsdf_raycast")
+    rc_cases.assert_same({name: t.cpu().numpy() for name, t in got.items()}, rc_cases.expected(t_ray.THREE, "kitti", 1.0, 1.0),
+                         "the aligned call")
+
+
+@pytest.mark.parametrize("u8", [False, True], ids=["f32", "u8"])
+@pytest.mark.parametrize("k", OFFSETS)
+def test_synthesize_right_view(cd, k, u8):
+    shape = n, C, D, h, w, S = synthesis_ref.SHAPES[1]                    # ragged tile rows and columns, two frames
+    prob, left, want = t_syn.case(shape, u8)
+    ins = dict(probabilities=dev(prob), left=dev(left))
+    outs = dict(out=(left.shape, torch.float32))
+
+    def launch(a, o):
+        assert cd.synthesize_right_view(a["probabilities"], a["left"], scale=S, out=o["out"]) is o["out"]
+
+    got = check_placements(ins, outs, k, launch, f"synthesize_right_view {'u8' if u8 else 'f32'}")
+    t_syn.assert_bitwise(got["out"], want, "the aligned call")

@@ -156,6 +156,7 @@ def m():
     c["LR_THREADS"] = one(r"^constexpr int LR_THREADS = (\d+);", "k_lr.h")
     c["LR_PACK_ITEMS"] = one(r"^constexpr int LR_PACK_ITEMS = (\d+);", "k_lr.h")
     c["LR_LDS_W"] = one(r"^constexpr int LR_LDS_W = (\d+);", "k_lr.h")
+    c["TRACK_TRIPLES"] = one(r"const unsigned triples = \(unsigned\)\(n < (\d+) \? n : \1\);", "tu_track.hip")
     # the loops the cases are there to send on a second trip, and what the launchers divide by
     for name, text in (("k_confidence.h", "m += gridDim.y"), ("k_temporal.h", "m += gridDim.y"),
                        ("k_sgm.h", "z += gridDim.y"), ("k_sgm.h", "p += waves"), ("k_median.h", "tile += gridDim.x"),
@@ -166,7 +167,11 @@ def m():
                        ("tu_wls.hip", "grid_of((size_t)n * H, WLS_LINES)"),
                        ("tu_wls.hip", "grid_of((size_t)n * W, WLS_COL_THREADS)"),
                        ("tu_sgm.hip", "(pixels + SGM_THREADS / 64 - 1) / (SGM_THREADS / 64)"),
-                       ("tu_lr.hip", "const bool lds = W <= LR_LDS_W;")):
+                       ("tu_lr.hip", "const bool lds = W <= LR_LDS_W;"),
+                       ("k_track.h", "for (int f = blockIdx.y; f < a.n; f += gridDim.y)"),
+                       ("k_track.h", "for (int f = blockIdx.x; f < a.n; f += gridDim.x)"),
+                       ("tu_track.hip", "k_track_accum, dim3((unsigned)g.groups, triples)"),
+                       ("tu_track.hip", "k_track_solve, dim3(triples)")):
         assert text in source(name), f"{name} no longer holds {text!r}: restate the case's geometry in scale_cases.py"
     return c
 
@@ -235,6 +240,20 @@ def test_remap_takes_more_images_per_thread_and_a_partial_last_chunk(m):
     runs = sc.REMAP_CAP_RUNS
     assert {(d, c) for d, c, _, _ in runs} >= {("u8", 1), ("f32", 3)}
     assert {b for _, _, b, _ in runs} == {"constant", "replicate"} and any(not both for _, _, _, both in runs)
+
+
+def test_track_triples_take_a_second_trip_in_both_kernels(m):
+    n, shape, model_shape = sc.TRACK_CAP_CASE
+    (ag, astride, atrips), (sg, sstride, strips) = sc.track_triple_grids(n, m["TRACK_TRIPLES"])
+    assert ag == sg == m["TRACK_TRIPLES"] and atrips >= 2 and strips >= 2, f"n = {n} no longer passes the triples cap"
+    assert n - m["TRACK_TRIPLES"] >= 2, "more than one workgroup must take the second trip"
+    assert sc.tile_period_ok([astride, sstride]), (astride, sstride)
+    assert len(sc.TRACK_CAP_TRIPLES) == sc.TILE_PERIOD
+    lost = [i for i, (_, _, misses) in enumerate(sc.TRACK_CAP_TRIPLES) if misses]
+    assert lost and all(0 < i < sc.TILE_PERIOD - 1 for i in lost), "a lost triple between tracked ones: continue, then work"
+    assert len(sc.TRACK_CAP_SCHEDULE) >= 2 and sum(k for _, k in sc.TRACK_CAP_SCHEDULE) >= 3
+    operands = n * 4 * (shape[0] * shape[1] + 4 * model_shape[0] * model_shape[1])
+    assert operands < 2 ** 31 and n * shape[0] * shape[1] <= 2 ** 30, "the call's frames and model views stay under 2 GB"
 
 
 def test_lr_pack_halves_stride_and_wide_rows_leave_lds(m):

@@ -169,7 +169,7 @@ class Direct:
     def __init__(self, cd, views, schedule=tr.DEFAULT_SCHEDULE):
         import cuda_depth._native as native
         self.native = native
-        self.shape = tc.FRAME_SHAPES[0]
+        self.shape, self.model_shape = tc.FRAME_SHAPES[0], tc.MODEL_SHAPE
         self.triples = [("outside", self.shape, 0, False, False), ("left", self.shape, 1, False, False)]
         self.n = 2
         frames = [tc.frame(v, s, k, c) for v, s, k, c, _ in self.triples]
@@ -190,13 +190,26 @@ class Direct:
         self.schedule = np.asarray(schedule, np.int32).reshape(-1, 2)
         self.want = [tc.expected(v, s, k, schedule=schedule) for v, s, k, *_ in self.triples]
 
+    @classmethod
+    def of(cls, n, shape, model_shape, Q, Qm, Pm, schedule, **operands):
+        """A direct call on operands of the caller's: disp, depth, normals, c2w, w2c, pose_in, pose_out, info, rms, sums
+        and ws, all device tensors."""
+        import cuda_depth._native as native
+        d = cls.__new__(cls)
+        d.native, d.n, d.shape, d.model_shape, d.Q, d.Qm, d.Pm = native, n, shape, model_shape, Q, Qm, Pm
+        d.schedule = np.asarray(schedule, np.int32).reshape(-1, 2)
+        for name in ("disp", "depth", "normals", "c2w", "w2c", "pose_in", "pose_out", "info", "rms", "sums", "ws"):
+            setattr(d, name, operands.pop(name))
+        assert not operands, list(operands)
+        return d
+
     def call(self, stream=None, **over):
         """The status of the call with the named arguments replaced."""
         H, W = self.shape
         f16 = lambda m: (C.c_float * 16)(*np.asarray(m, f32).reshape(-1).tolist())  # noqa: E731
         ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())  # noqa: E731
         a = dict(n=self.n, H=H, W=W, disp=self.disp, confidence=None, Q=self.Q, min_confidence=0.0,
-                 z_min=tc.DEPTH_RANGE[0], z_max=tc.DEPTH_RANGE[1], invalid=-1.0, Hm=tc.MODEL_SHAPE[0], Wm=tc.MODEL_SHAPE[1],
+                 z_min=tc.DEPTH_RANGE[0], z_max=tc.DEPTH_RANGE[1], invalid=-1.0, Hm=self.model_shape[0], Wm=self.model_shape[1],
                  depth=self.depth, normals=self.normals, Qm=self.Qm, Pm=self.Pm, c2w=self.c2w, w2c=self.w2c,
                  pose_in=self.pose_in, schedule=self.schedule, max_distance=tc.MAX_DISTANCE, min_inliers=tc.MIN_INLIERS,
                  min_pivot=1e-3, rot_eps=0.0, trans_eps=0.0, pose_out=self.pose_out, info=self.info, rms=self.rms,

@@ -13,7 +13,8 @@ each case names the queries it expects, so a case whose workspaces were not plac
 
 The shapes are the smallest at which the roundings and every part of a layout matter: odd maps whose parts end off a
 256-byte boundary, both roundings of SGM's disparity pitch, more than one 4096-point radix tile, two 64-voxel chunks per
-volume row."""
+volume row, brick counts that are multiples of nothing, an odd number of tracking groups that only the last launches
+fill."""
 import numpy as np
 import pytest
 
@@ -21,13 +22,18 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import raycast_cases as rc_cases                    # noqa: E402
 import test_mesh_gpu as t_mesh                      # noqa: E402  (the generators of each entry's own tests)
 import test_operand_alignment_gpu as t_align        # noqa: E402  (SENTINEL_BYTE, the guard check, the bitwise comparison)
 import test_points3d_gpu as t_pts                   # noqa: E402
 import test_postprocess_gpu as t_post               # noqa: E402
+import test_raycast_gpu as t_ray                    # noqa: E402
 import test_sgm_gpu as t_sgm                        # noqa: E402
+import test_track_gpu as t_track                    # noqa: E402
 import test_tsdf_gpu as t_tsdf                      # noqa: E402
 import test_wls_gpu as t_wls                        # noqa: E402
+import track_cases as tc                            # noqa: E402
+from test_track_gpu import views, volume            # noqa: E402,F401  (the library's model views, tied to the twin's bits)
 
 ROOMY_BYTES = 4096
 MIN_GUARD_BYTES = 4096
@@ -179,6 +185,41 @@ def test_tsdf_integrate_with_colour_then_extract_points(cd, monkeypatch):
 
     check_exact_against_roomy(cd, monkeypatch, call, [lib().smx_tsdf_integrate_workspace_bytes(n, H, W),
                                                       lib().smx_tsdf_extract_workspace_bytes(*dims)])
+
+
+def test_tsdf_raycast(cd, monkeypatch):
+    """The flag and occupancy bytes of 5 x 4 x 6 bricks: 120 bytes each, no multiple of anything."""
+    assert [-(-d // 8) for d in rc_cases.DIMS] == [5, 4, 6]
+    vol = t_ray.upload(cd, rc_cases.fused_state())
+    names = ("outside", "inside", "oblique")
+
+    def call():
+        view = vol.render(rc_cases.q_of("kitti"), rc_cases.poses_of(names), rc_cases.SHAPE, depth_range=rc_cases.DEPTH_RANGE)
+        assert bool(torch.isfinite(view.depth).any()) and not bool(torch.isfinite(view.depth).all())
+        return [(k, getattr(view, k)) for k in ("disparity", "depth", "normals", "colors", "weight")]
+
+    queried = lib().smx_tsdf_raycast_workspace_bytes(*rc_cases.DIMS)
+    assert queried == 2 * 256                                 # each part rounded up from its 120 bytes
+    check_exact_against_roomy(cd, monkeypatch, call, [queried])
+
+
+def test_track_camera(cd, monkeypatch, views):
+    """Three triples of 37 x 70: five groups of four tiles at stride 1, two at stride 2, so the partial buffer's rows are
+    used in part by the first launches and in full, to the last byte of the workspace, by the later ones."""
+    shape, schedule = tc.FRAME_SHAPES[0], ((2, 2), (1, 2))
+    groups = [tc.track_grid(shape, s)["groups"] for s, _ in schedule]
+    assert groups == [2, 5] and groups[-1] % 2 == 1
+    triples = [("outside", shape, 0, False, False), ("left", shape, 1, False, True), ("left", shape, 2, False, False)]
+
+    def call():
+        got, res = t_track.track(cd, views, triples, schedule)
+        assert res.lost.tolist() == [False, True, False]
+        return [("pose", res.pose), ("lost", res.lost), ("iterations", res.iterations), ("inliers", res.inliers),
+                ("accepted", res.accepted), ("rms", res.rms), ("normal_equations", res.normal_equations)]
+
+    queried = lib().smx_track_camera_workspace_bytes(3, *shape)
+    assert queried == 512 + 3 * groups[-1] * 32 * 8           # the states' 384 bytes rounded up, then the partial sums
+    check_exact_against_roomy(cd, monkeypatch, call, [queried])
 
 
 def test_tsdf_extract_triangles(cd, monkeypatch):

@@ -3,7 +3,9 @@
 views are its 33 x 45 renderings (the twin's here; the GPU tests render them with the library and check the bits are
 these); the frames are renderings of the same volume by the raycast twin from poses a few centimetres and about a degree
 away, at 37 x 70 (wider than one 64-column tile, no multiple of it or of the 4 tile rows) and 33 x 45, with disparity noise,
-5 % invalid, 1 % NaN and 1 % outlier pixels.  Every twin result is computed once and shared."""
+5 % invalid, 1 % NaN and 1 % outlier pixels.  A second set of frames, up to 32765 x 193, sees the whole model view at any
+shape and reaches the deep forms of the solve kernel's sum tree (tests/test_track_tree_gpu.py; tests/test_track_cpu.py
+holds the conditions that make them worth running).  Every twin result is computed once and shared."""
 import functools
 
 import numpy as np
@@ -53,6 +55,17 @@ def model(view, misses=False):
     return tr.model_view(depth, normals, Qm, model_pose(view))
 
 
+def spoil(d, rng):
+    """In place: disparity noise on the hits, then 5 % invalid, 1 % NaN and 1 % outlier pixels."""
+    hit = d != -1.0
+    d[hit] += rng.normal(0, 0.02, int(hit.sum())).astype(f32)
+    r = rng.random(d.shape)
+    d[r < 0.05] = -1.0
+    d[(r >= 0.05) & (r < 0.06)] = np.nan
+    out = (r >= 0.06) & (r < 0.07)
+    d[out] = rng.uniform(1.0, 40.0, int(out.sum())).astype(f32)
+
+
 @functools.lru_cache(maxsize=None)
 def frame(view, shape, k=0, confidence=False):
     """(disp [H, W] f32, Q, true pose, confidence [H, W] or None) of a noisy frame near `view`."""
@@ -62,13 +75,7 @@ def frame(view, shape, k=0, confidence=False):
     pose = displaced(model_pose(view), k)
     d = rc.raycast_ref(cases.fused_state(), cases.DIMS, cases.ORIGIN, cases.VS, Q, rc.view_pose(pose), shape,
                        depth_range=cases.DEPTH_RANGE)["disparity"][0].copy()
-    hit = d != -1.0
-    d[hit] += rng.normal(0, 0.02, int(hit.sum())).astype(f32)
-    r = rng.random((H, W))
-    d[r < 0.05] = -1.0
-    d[(r >= 0.05) & (r < 0.06)] = np.nan
-    out = (r >= 0.06) & (r < 0.07)
-    d[out] = rng.uniform(1.0, 40.0, int(out.sum())).astype(f32)
+    spoil(d, rng)
     conf = None
     if confidence:
         conf = rng.uniform(0.2, 1.0, (H, W)).astype(f32)
@@ -116,6 +123,170 @@ def assert_same(got, want, what):
         gs = np.ascontiguousarray(got["sums"], np.float64).view(np.uint64)
         es = np.ascontiguousarray(want["sums"], np.float64).view(np.uint64)
         assert np.array_equal(gs, es), f"{what}: sums differ at {np.flatnonzero(gs != es)}"
+
+
+# ---- frames whose sums need the deep forms of k_track_solve's tree (tests/test_track_tree_gpu.py) --------------------------
+# k_track_solve sums a triple's group partials in 32 chunks of len = padded groups / 32; every frame above has at most 6
+# groups (len 1).  These frames keep the model view's field of view whatever their shape -- q_of keeps the focal length,
+# so a large frame would see the volume in a tenth of its pixels and most tiles would add +0.0 -- by a Q whose scale and
+# centre follow the frame (anisotropic: only the model's Q has a required form).
+TREE_VIEW = "outside"
+LIMIT_SHAPE = (32765, 193)                                           # 8192 x 4 = TRK_MAX_TILES tiles, exactly: accepted
+LIMIT_SOURCE = (4100, 193)                                           # the limit frame repeats this frame's rows
+LIMIT_BAND = 256                                                     # tile rows the twin evaluates at a time there
+TREE_LENS = {2, 4, 8, 16, 32, 64, 256}
+# (shape, stride, len) of the one-iteration cases; a case's sums are compared, so its tree is the one under test
+TREE_CASES = (((176, 130), 1, 2), ((300, 257), 1, 4), ((1027, 193), 1, 16), ((1027, 193), 2, 4), ((1027, 193), 3, 2),
+              ((2100, 193), 1, 32), ((4100, 193), 1, 64), ((4100, 193), 2, 16), ((4100, 193), 3, 8), (LIMIT_SHAPE, 1, 256))
+TREE_SHAPES = tuple(dict.fromkeys(s for s, _, _ in TREE_CASES if s != LIMIT_SHAPE))
+TREE_TWO = ((1, 2),)                                                 # a second iteration on the first one's pose
+TREE_MARGIN = 2                                                      # scaled_q's, for schedules of several iterations
+TREE_MIXED = ((4100, 193), ((3, 1), (2, 1), (1, 1)))                 # groups change between launches, partial_stride stays
+# every (shape, schedule) the GPU tests run; the last pair's stride is the one whose sums are compared
+TREE_RUNS = (tuple((s, ((stride, 1),)) for s, stride, _ in TREE_CASES) + tuple((s, TREE_TWO) for s in TREE_SHAPES) +
+             (TREE_MIXED,))
+TILE_COLS, TILE_ROWS, GROUP_TILES, CHUNKS = 64, 4, 4, 32             # smx_workspace.h, k_track.h
+
+
+def run_id(run):
+    (H, W), schedule = run
+    return f"{H}x{W}-" + "+".join(f"{k}@{s}" for s, k in schedule)
+
+
+def track_grid(shape, stride):
+    """smx_workspace.h's track_grid, restated: dict of ws, hs, tx, ty, tiles, groups."""
+    H, W = shape
+    ws, hs = -(-W // stride), -(-H // stride)
+    tx, ty = -(-ws // TILE_COLS), -(-hs // TILE_ROWS)
+    return dict(ws=ws, hs=hs, tx=tx, ty=ty, tiles=tx * ty, groups=-(-tx * ty // GROUP_TILES))
+
+
+def tree_len(shape, stride):
+    """The partials per chunk of k_track_solve for a frame at a stride."""
+    groups, padded = track_grid(shape, stride)["groups"], 1
+    while padded < groups:
+        padded *= 2
+    return padded // CHUNKS if padded > CHUNKS else 1
+
+
+def scaled_q(shape, margin=0):
+    """The 33 x 45 model view's Q for a frame of another shape that sees the same field of view: pixel (u, v) stands for
+    the model pixel ((u + 0.5) / sx - 0.5, (v + 0.5) / sy - 0.5) with s = shape / (33, 45).  margin: the frame sees the
+    model view without its outer `margin` pixels, s = shape / (33 - 2 margin, 45 - 2 margin): a frame that is tracked
+    for more than one iteration then still lands on the model view, border tiles included, after a step of a degree."""
+    q = cases.q_of("kitti", MODEL_SHAPE).astype(np.float64)
+    sy, sx = shape[0] / (MODEL_SHAPE[0] - 2 * margin), shape[1] / (MODEL_SHAPE[1] - 2 * margin)
+    q[0, 3] += q[0, 0] * (0.5 / sx - 0.5 + margin)
+    q[1, 3] += q[1, 1] * (0.5 / sy - 0.5 + margin)
+    q[0, 0] /= sx
+    q[1, 1] /= sy
+    return q.astype(f32)
+
+
+def run_margin(schedule):
+    """The margin of the frame a schedule is run on: none for one iteration (the first starts on the model's own pose),
+    TREE_MARGIN model pixels for more."""
+    return TREE_MARGIN if sum(k for _, k in schedule) > 1 else 0
+
+
+@functools.lru_cache(maxsize=None)
+def _scaled_render(view, shape, k, margin):
+    return rc.raycast_ref(cases.fused_state(), cases.DIMS, cases.ORIGIN, cases.VS, scaled_q(shape, margin),
+                          rc.view_pose(displaced(model_pose(view), k)), shape, depth_range=cases.DEPTH_RANGE)["disparity"][0]
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_frame(shape, k=0, view=TREE_VIEW, margin=0):
+    """(disp [H, W] f32, Q) of a noisy frame near `view` under scaled_q(shape, margin).  The limit frame repeats the rows
+    of the LIMIT_SOURCE frame's rendering (the twin's rendering of 6.3 M pixels would take most of a minute; a frame is
+    input, not expectation) and takes its noise and spoilt pixels at its own size."""
+    H, W = shape
+    if shape == LIMIT_SHAPE:
+        src = _scaled_render(view, LIMIT_SOURCE, k, margin)
+        d = src[((2 * np.arange(H) + 1) * LIMIT_SOURCE[0]) // (2 * H)].copy()
+    else:
+        d = _scaled_render(view, shape, k, margin).copy()
+    spoil(d, np.random.default_rng(300 + 7 * k + H))
+    d.setflags(write=False)
+    return d, scaled_q(shape, margin)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_confidence(shape, k=0):
+    """confidence [H, W] f32 for scaled_frame(shape, k): weights spread log-uniformly over 2^-20 .. 1, with 3 % zeros and
+    2 % NaNs.  The terms are float32 products, and float64 sums of a few thousand float32 values of like magnitude are
+    exact in any order; weights over twenty binades make every tile's sums inexact, so that each level of the tree
+    rounds, and a wrong order at any level -- inside one leaf of eight partials too -- changes bits."""
+    rng = np.random.default_rng(900 + 7 * k + shape[0])
+    conf = np.exp2(-rng.uniform(0.0, 20.0, shape)).astype(f32)
+    c = rng.random(shape)
+    conf[c < 0.03] = 0.0
+    conf[(c >= 0.03) & (c < 0.05)] = np.nan
+    conf.setflags(write=False)
+    return conf
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_model(view, shape, misses=False):
+    """model() at another shape, under scaled_q(shape)."""
+    Qm = scaled_q(shape)
+    out = rc.raycast_ref(cases.fused_state(), cases.DIMS, cases.ORIGIN, cases.VS, Qm, rc.view_pose(model_pose(view)), shape,
+                         depth_range=cases.DEPTH_RANGE)
+    depth, normals = out["depth"][0], out["normals"][0]
+    if misses:
+        depth, normals = np.full_like(depth, np.nan), np.zeros_like(normals)
+    return tr.model_view(depth, normals, Qm, model_pose(view))
+
+
+@functools.lru_cache(maxsize=None)
+def _scaled_expected(shape, schedule, k, view, model_shape, misses, confidence, extra):
+    d, Q = scaled_frame(shape, k, view, run_margin(schedule))
+    kw = dict(PARAMS)
+    kw.update(dict(extra))
+    m = model(view, misses) if model_shape == MODEL_SHAPE else scaled_model(view, model_shape, misses)
+    return tr.track_ref(d, Q, start_pose(view), m, schedule=schedule, keep_tiles=True,
+                        confidence=wide_confidence(shape, k) if confidence else None,
+                        band_tile_rows=LIMIT_BAND if shape == LIMIT_SHAPE else None, **kw)
+
+
+def scaled_expected(shape, schedule, k=0, view=TREE_VIEW, model_shape=MODEL_SHAPE, misses=False, confidence=False,
+                    **extra):
+    """The twin's result for scaled_frame(shape, k, view, run_margin(schedule)) against the model view of `view` (shared;
+    read only), with the tile sums of its last iteration.  confidence: weighted by wide_confidence(shape, k)."""
+    return _scaled_expected(shape, tuple(tuple(p) for p in schedule), k, view, model_shape, misses, confidence,
+                            _freeze(extra))
+
+
+def tree_expected(run):
+    """scaled_expected of a run of TREE_RUNS: under wide_confidence, as tests/test_track_tree_gpu.py calls the library."""
+    shape, schedule = run
+    return scaled_expected(shape, schedule, confidence=True)
+
+
+def sums_in_order(tiles, grid, order):
+    """[31] float64: the tile sums [31, ty * tx] added in `order`: "tree", the header's; "left_to_right", one after the
+    other in row-major order; "column_major", the pairs tree over the tiles taken column by column; "leaves_in_turn", the
+    header's tree but for every aligned run of eight group partials, which is added one partial after the other."""
+    if order == "tree":
+        return tr._pairs_tree(tiles)
+    if order == "left_to_right":
+        return np.cumsum(tiles, axis=1)[:, -1]
+    if order == "leaves_in_turn":
+        part = group_partials(tiles)
+        pad = np.zeros((part.shape[0], -(-part.shape[1] // 8) * 8), np.float64)
+        pad[:, :part.shape[1]] = part
+        return tr._pairs_tree(np.cumsum(pad.reshape(part.shape[0], -1, 8), axis=2)[:, :, -1])
+    assert order == "column_major"
+    K = tiles.shape[0]
+    return tr._pairs_tree(np.ascontiguousarray(tiles.reshape(K, grid["ty"], grid["tx"]).transpose(0, 2, 1)).reshape(K, -1))
+
+
+def group_partials(tiles):
+    """[31, groups] float64: the sums of every four consecutive tiles, (t0 + t1) + (t2 + t3), as k_track_accum leaves them."""
+    K, n = tiles.shape
+    pad = np.zeros((K, -(-n // GROUP_TILES) * GROUP_TILES), np.float64)
+    pad[:, :n] = tiles
+    return tr._pairs_tree(pad.reshape(K, -1, GROUP_TILES))
 
 
 # ---- a short sequence for the pipeline: five frames of the volume along a small trajectory, then an empty frame -----------

@@ -103,8 +103,9 @@ def _pairs_tree(x):
     return x[..., 0]
 
 
-def reduce_terms(terms):
-    """[K] float64 from [K, Hs, Ws] float64, in the header's order."""
+def tile_sums(terms):
+    """[K, ty * tx] float64 from [K, Hs, Ws] float64: the sum of every 64 x 4 tile of the selected grid in the header's
+    order, the tiles in row-major order."""
     K, Hs, Ws = terms.shape
     tx, ty = -(-Ws // COLS), -(-Hs // ROWS)
     pad = np.zeros((K, ty * ROWS, tx * COLS), np.float64)
@@ -113,8 +114,25 @@ def reduce_terms(terms):
     col = np.zeros((K, ty, tx, COLS), np.float64)
     for r in range(ROWS):                                             # a tile column, top to bottom, from +0.0
         col = col + t[:, :, r]
-    tiles = _pairs_tree(col.reshape(K, ty * tx, COLS))                # the 64 columns of every tile
-    return _pairs_tree(tiles)                                         # the tiles in row-major order
+    return _pairs_tree(col.reshape(K, ty * tx, COLS))                 # the 64 columns of every tile
+
+
+def reduce_terms(terms):
+    """[K] float64 from [K, Hs, Ws] float64, in the header's order."""
+    return _pairs_tree(tile_sums(terms))                              # the tiles in row-major order
+
+
+def iteration_tile_sums(points, T, model, stride, max_distance, band_tile_rows=None):
+    """[31, ty * tx] float64: tile_sums(pixel_terms(...)) of one iteration.  band_tile_rows: evaluate that many tile rows
+    at a time (a tile's sum does not depend on the band it is evaluated in, so the bits are the same; the memory is the
+    band's)."""
+    if band_tile_rows is None:
+        return tile_sums(pixel_terms(points, T, model, stride, max_distance))
+    rows = int(band_tile_rows) * ROWS * stride                        # frame rows per band: whole tile rows
+    assert rows > 0
+    H = points[0].shape[0]
+    return np.concatenate([tile_sums(pixel_terms(tuple(a[r:r + rows] for a in points), T, model, stride, max_distance))
+                           for r in range(0, H, rows)], axis=1)
 
 
 def solve(S, min_pivot):
@@ -182,22 +200,25 @@ def update(T, x):
 
 def track_ref(disp, Q, pose_in, model, *, confidence=None, schedule=DEFAULT_SCHEDULE, max_distance=0.3,
               depth_range=(0.0, np.inf), min_confidence=0.0, invalid_disparity=-1.0, min_inliers=100, min_pivot=1e-6,
-              rot_eps=0.0, trans_eps=0.0):
+              rot_eps=0.0, trans_eps=0.0, band_tile_rows=None, keep_tiles=False):
     """One triple: disp [H, W], pose_in [3, 4] / [4, 4] (taken as float32), model: model_view()'s dict.  Returns a dict of
-    pose [3, 4] f32, info [4] int32 (lost, iterations, inliers, accepted), rms f32 and sums [30] f64."""
+    pose [3, 4] f32, info [4] int32 (lost, iterations, inliers, accepted), rms f32 and sums [30] f64; with keep_tiles
+    also tiles [31, ty * tx] f64, the tile sums of the last iteration that ran (None if none did).  band_tile_rows:
+    iteration_tile_sums's."""
     pts = frame_points(disp, Q, confidence, min_confidence, depth_range, invalid_disparity)
     T0 = np.ascontiguousarray(np.asarray(pose_in, f32)[:3])
     T = T0.copy()
     info = np.zeros(4, np.int32)
     rms = f32(np.nan)
     sums = np.zeros(TERMS, np.float64)
-    done = False
+    done, tiles = False, None
     with np.errstate(all="ignore"):
         for stride, iterations in schedule:
             for _ in range(iterations):
                 if done:
                     break
-                S = reduce_terms(pixel_terms(pts, T, model, stride, max_distance))
+                tiles = iteration_tile_sums(pts, T, model, stride, max_distance, band_tile_rows)
+                S = _pairs_tree(tiles)
                 sums = S[:TERMS].copy()
                 info[1] += 1
                 info[2], info[3] = int(S[29]), int(S[TERMS])
@@ -208,7 +229,10 @@ def track_ref(disp, Q, pose_in, model, *, confidence=None, schedule=DEFAULT_SCHE
                     break
                 T, ww, tt = update(T, x)
                 done = bool(ww <= f32(rot_eps) * f32(rot_eps) and tt <= f32(trans_eps) * f32(trans_eps))
-    return {"pose": T, "info": info, "rms": f32(rms), "sums": sums}
+    out = {"pose": T, "info": info, "rms": f32(rms), "sums": sums}
+    if keep_tiles:
+        out["tiles"] = tiles
+    return out
 
 
 def information(sums):

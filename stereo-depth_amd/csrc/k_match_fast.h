@@ -30,6 +30,17 @@
 //   Cs += R9[q-6]  - R9[q-15]   (9x9 box)                        10-deep
 //   Hs += R21[q-9] - R21[q-12]  (3x21 box)                        3-deep
 //   AGG = (Hs*Vs)*Cs -> running arg-max of the pixel  (2 registers per pixel: best, arg)
+// That is ten packed adds per row for the three boxes (two each for R9, R21, Vs, Cs, Hs).  PREFIX form (K <= 2, chosen per
+// instantiation: fast_prefix_form): all of it is linear in R3, so the running prefix down the tile rows goes through the
+// same two exchanges instead of R3 and the boxes are differences of prefixes -- eight packed adds, same LDS traffic, same
+// history depths (22 / 10 / 4), and P is the only row-to-row dependency chain left (the three accumulators are temporaries):
+//   P[q]  = P[q-1] + R3[q]
+//   PC    = P[c-3] + P[c] + P[c+3]                   prefix of R9, from tile row 5 (one exchange row earlier)
+//   PH    = PC[c-6] + PC[c+6] + P[c]                 prefix of R21, from tile row 8 (one exchange row earlier)
+//   Vs = P[q] - P[q-21],  Cs = PC[q-6] - PC[q-15],  Hs = PH[q-9] - PH[q-12]
+// Integers again, so the same bits -- provided every prefix is below 2^24: PH at tile row TH + 10 reaches
+// (TH + 11) * 48,195 * K^2 (fast_prefix_exact).  K = 2: 11.4 M at the stacked bands' 48 rows, fine up to 76 rows; K = 4 would
+// reach 45 M there, so the K = 4 and K = 8 kernels (PK16 < 2) keep the sliding sums.
 // The 11 lanes at either edge of the window carry halo columns only (42 valid columns per
 // wave).  Step 6 also needs AGG[arg-1] and AGG[arg+1] (cyclic): instead of tracking them for
 // every pixel through the whole disparity loop (3 more registers per pixel, i.e. shorter
@@ -147,6 +158,28 @@ constexpr int FA_XCH_FLOATS = 2 * FA_XCH_ROWS * FA_XROW;
 // Rows of the latency shape's merge buffer ([waves][rows][64 lanes][best, arg]): bands taller than 8 rows merge in two halves
 // through a buffer of half the height, so that two workgroups still fit a CU (10 rows: 61 instead of 81 KB)
 __host__ __device__ constexpr int fast_merge_rows(int th) { return th > 8 ? (th + 1) / 2 : th; }
+
+// The prefix form of the box sums (fast_pass_pair<..., PREFIX>) is bit-exact while every prefix is an exact float32 integer.
+// The largest is PH at tile row th + 10 on saturated content: (th + 11) rows of R21 = 7 * 27 * 255 K^2 = 48,195 K^2 units.
+// K = 2: 11.4 M at 48-row bands, true up to 76 rows; K = 4: false from 11 rows on (48 rows: 45 M), so the form is tied to
+// PK16 == 2 and the K = 4 / 8 kernels keep the sliding sums at every band height.
+__host__ __device__ constexpr bool fast_prefix_exact(int th, int k_max) {
+    return (long long)(th + 11) * 48195 * k_max * k_max < (1LL << 24);
+}
+// Which instantiations take the prefix form: K <= 2 (PK16 == 2) only, and there by what the compiler reports for each
+// (profiles/r06_kernel_resources.txt: same waves-per-SIMD class, no more spills or scratch than the sliding form).  The
+// 8- and 10-row latency shapes cross 128 registers or gain a spill and keep the sliding sums; k_match_capture.h never asks.
+// SMX_FA_NO_PREFIX (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the sliding form everywhere.
+__host__ __device__ constexpr bool fast_prefix_form(int th, int pr, bool p1only, bool dsplit, int pk16, bool argb, bool dense) {
+#ifdef SMX_FA_NO_PREFIX
+    return false;
+#else
+    if (pk16 != 2 || !fast_prefix_exact(th, 2)) return false;
+    if (dsplit) return th == FA_TH_SMALL_TALL;
+    (void)pr; (void)p1only; (void)argb; (void)dense;
+    return true;
+#endif
+}
 
 template <int PR> inline size_t fast_lds_bytes(int th, int Dd, bool dsplit = false) {
     const size_t nw = dsplit ? FA_DS_WAVES : FA_WAVES;
@@ -296,7 +329,10 @@ __device__ __forceinline__ void argb_update(int kbyte, int &word, float m, float
 // the sparse second pass has nothing left to fetch but the cyclic wrap AGG[0] of the pixels whose winner is the LAST
 // disparity.  A NaN in dma[o] means "the cost that follows the winner has not been marched yet" (the winner is the second
 // disparity of its pair): the next march's first cost resolves it.  Costs are finite, so NaN is free as the marker.
-template <int TH, int PR, bool P1ONLY, int PK16, int MODE = 0, bool ARGB = false, bool DENSE = false>
+//
+// PREFIX (every MODE; PK16 == 2 only): the box sums as differences of prefix sums down the tile rows (file header); r3 / r9 /
+// r21 then hold P / PC / PH.  The caller asks fast_prefix_form, once per kernel, so that all its marches share one form.
+template <int TH, int PR, bool P1ONLY, int PK16, int MODE = 0, bool ARGB = false, bool DENSE = false, bool PREFIX = false>
 __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastLane &ln, int d,
                                                bool valid_b, float (&best)[TH], int (&arg)[TH],
                                                const unsigned short *rptr_b_in = nullptr, int db = 0,
@@ -305,7 +341,10 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                                                unsigned *hits = nullptr, unsigned rowmask = ~0u,
                                                float *dmb = nullptr, float *dma = nullptr, float *dcp = nullptr,
                                                float *dfirst = nullptr) {
+    static_assert(!PREFIX || (PK16 == 2 && fast_prefix_exact(TH, 2)), "prefix form: K <= 2 and every prefix below 2^24");
     constexpr int NQ = TH + 20;              // tile rows of the 3x3 cost slice (q index)
+    // PREFIX: r3 / r9 / r21 hold the prefixes P / PC / PH, which the boxes reach one tile row further back (5 and 8)
+    constexpr int Q9 = PREFIX ? 11 : 12, Q21 = PREFIX ? 17 : 18;
     f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};  // s[r-1], s[r-2]
     unsigned k1 = 0u, k2 = 0u;               // ... packed (PK16)
     const unsigned c255pk = ln.c255 * 0x10001u;
@@ -364,18 +403,19 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                     x3.x = (dpp_shr1(cv.x) + cv.x) + dpp_shl1(cv.x);
                     x3.y = (dpp_shr1(cv.y) + cv.y) + dpp_shl1(cv.y);
                 }
-                r3[q] = x3;
-                if (q >= 12) r9[q - 6] = (t_m3 + r3[q - 6]) + t_p3;             // R9 of tile row q-6
-                if (q >= 18) r21[q - 9] = (u_m6 + u_p6) + r3[q - 9];            // R21 of tile row q-9
+                if (PREFIX && q > 0) r3[q] = r3[q > 0 ? q - 1 : 0] + x3;        // P: the one row-to-row chain of the prefix form
+                else r3[q] = x3;
+                if (q >= Q9) r9[q - 6] = (t_m3 + r3[q - 6]) + t_p3;             // R9 (PC) of tile row q-6
+                if (q >= Q21) r21[q - 9] = (u_m6 + u_p6) + r3[q - 9];           // R21 (PH) of tile row q-9
                 // Cross-lane by +-3 / +-6 columns through the wave's LDS row: ds_write_b64 + two
                 // ds_read_b64 for both disparities (ds_bpermute costs ~3x on the shared LDS pipe).
                 // LDS executes a wave's operations in order, so no barrier is needed; the results
                 // are consumed one row step later.
 #ifdef SMX_EXP_NOXCH
-                if (q >= 11 && q + 1 < NQ) { t_m3 = r3[q - 5]; t_p3 = r3[q - 4]; }
-                if (q >= 17 && q + 1 < NQ) { u_m6 = r9[q - 8]; u_p6 = r9[q - 7]; }
+                if (q >= Q9 - 1 && q + 1 < NQ) { t_m3 = r3[q - 5]; t_p3 = r3[q - 4]; }
+                if (q >= Q21 - 1 && q + 1 < NQ) { u_m6 = r9[q - 8]; u_p6 = r9[q - 7]; }
 #else
-                if (q >= 11 && q + 1 < NQ) {
+                if (q >= Q9 - 1 && q + 1 < NQ) {
                     f32x2 *x3b = (f32x2 *)ln.xch + lane_;          // entry (lane - 6) of the padded row
                     x3b[6] = r3[q - 5];
                     __builtin_amdgcn_wave_barrier();
@@ -385,7 +425,7 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                         t_m3 = xr[3]; t_p3 = xr[9];
                     }
                 }
-                if (q >= 17 && q + 1 < NQ) {
+                if (q >= Q21 - 1 && q + 1 < NQ) {
                     f32x2 *x9b = (f32x2 *)(ln.xch + (FA_XCH_ROWS > 1 ? 2 * FA_XROW : 0)) + lane_;
                     x9b[6] = r9[q - 8];
                     __builtin_amdgcn_wave_barrier();
@@ -395,12 +435,20 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                     }
                 }
 #endif
-                vs += r3[q];
-                if (q >= 21) vs -= r3[q - 21];
-                if (q >= 12) cs += r9[q - 6];
-                if (q >= 21) cs -= r9[q - 15];
-                if (q >= 18) hs += r21[q - 9];
-                if (q >= 21) hs -= r21[q - 12];
+                if (PREFIX) {                                    // box sums as differences of prefixes: temporaries of the row
+                    if (q >= 20) {
+                        vs = q >= 21 ? r3[q] - r3[q - 21] : r3[q];
+                        cs = r9[q - 6] - r9[q - 15];
+                        hs = r21[q - 9] - r21[q - 12];
+                    }
+                } else {
+                    vs += r3[q];
+                    if (q >= 21) vs -= r3[q - 21];
+                    if (q >= 12) cs += r9[q - 6];
+                    if (q >= 21) cs -= r9[q - 15];
+                    if (q >= 18) hs += r21[q - 9];
+                    if (q >= 21) hs -= r21[q - 12];
+                }
                 if (q >= 20) {
                     const int o = q - 20;
                     const f32x2 agg = (hs * vs) * cs;            // aggregation .cu:87 (in units)
@@ -498,6 +546,14 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                         (void)dsel;                                // timing experiment only (wrong results)
 #endif
                         best[o] = m;
+                        // Measured in round 6 and not adopted (profiles/r06_prefix_sums.txt): the in-place form for the stacked
+                        // bands -- t = v_max_f32(agg.x, agg.y), compare and byte update against the old best, then
+                        // `v_max_f32 best, best, t` with best as a read-write operand.  With v_max3_f32 the new best goes to a
+                        // fresh register (the compare still reads the old one) and the compiler copies all 48 back at the
+                        // march's back edge; the in-place form removes those 48 v_mov_b32 per march (and 121 s_nop of the
+                        // kernel) at 186 registers all the same, for 96 v_max_f32 instead of 48 v_max3_f32: `value` 99,964 /
+                        // 100,177 / 100,177 without it, 99,814 / 99,538 / 100,370 with it -- nothing.  Applied to every
+                        // instantiation it adds 5 - 10 spilled registers to the pitch-320 one-register-per-winner bands.
 #else
                         // Measured in round 4 and not adopted (SMX_FA_ARGMAX2, profiles/r04_match_fast_candidates.txt): the
                         // reference's loop body twice -- compare, conditional index update, v_max_f32 per disparity.  Six
@@ -552,7 +608,7 @@ __device__ __forceinline__ void fast_stats_report(const MatchParams &p, int b, i
 // comments are; a unit band differs from a band in its tile rows (hh * TU further down), its image rows and its slice of
 // best / arg.  The waves' needed-set tables are reused: a wave clears its own table behind its second pass (LDS executes a
 // wave's operations in order).  Each unit band that holds image rows counts as one window in the report.
-template <int TU, int NH, int PR, int PK16, class StageRight>
+template <int TU, int NH, int PR, int PK16, bool PREFIX, class StageRight>
 __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
                                                   const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
                                                   bool active, StageRight &&stage_right) {
@@ -620,7 +676,7 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
                     const int da = d0 + dda, db = d0 + ddb;
                     ++marches2;
                     lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
-                    fast_pass_pair<TU, PR, false, PK16, 1>(p, lh, da, false, bh, ah, Rh + wcol + lane + (nd - 1 - ddb), db, argpk,
+                    fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX>(p, lh, da, false, bh, ah, Rh + wcol + lane + (nd - 1 - ddb), db, argpk,
                                                            da == 0 ? Dd - 1 : da - 1, da + 1 == Dd ? 0 : da + 1,
                                                            db == 0 ? Dd - 1 : db - 1, db + 1 == Dd ? 0 : db + 1, nullptr, nullptr, rows);
                 };
@@ -653,6 +709,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     // stacked bands (TH > 32): NH unit bands of TU rows per wave; what follows pass 1 is fast_stacked_tail's
     constexpr int NH = TH > 32 ? 2 : 1;
     constexpr int TU = TH / NH;
+    constexpr bool PREFIX = fast_prefix_form(TH, PR, P1ONLY, DSPLIT, PK16, ARGB, DENSE);     // one form for all marches of a kernel
     static_assert(NH == 1 || (TH == 2 * TU && TU <= 32 && ARGB && !DSPLIT && !DENSE && !P1ONLY),
                   "stacked bands: two unit bands, byte-packed winners, throughput shape, sparse form");
     const int b = blk.z;
@@ -724,16 +781,16 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
             for (int dd = dd_lo; dd < dd_hi; dd += 2) {
                 ln.rptr = Rt + wcol + lane + (nd - 1 - dd);
                 if constexpr (DENSE)
-                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, true>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg, nullptr, 0, nullptr,
+                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, true, PREFIX>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg, nullptr, 0, nullptr,
                                                                          0, 0, 0, 0, nullptr, nullptr, ~0u, dmb, dma, dcp,
                                                                          DSPLIT && dd == dd_lo ? dfirst : nullptr);
                 else
-                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg);
+                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, false, PREFIX>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg);
             }
         }
     }
     if constexpr (NH > 1) {
-        fast_stacked_tail<TU, NH, PR, PK16>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
+        fast_stacked_tail<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
         return;
     }
     if (ARGB) {            // byte-packed indices -> one register per row (the march's registers are free now)
@@ -893,7 +950,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
                 const int da = d0 + dda, db = d0 + ddb;
                 ++marches2;
                 ln.rptr = Rt + wcol + lane + (nd - 1 - dda);
-                fast_pass_pair<TH, PR, false, PK16, 1>(p, ln, da, false, best, arg, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
+                fast_pass_pair<TH, PR, false, PK16, 1, false, false, PREFIX>(p, ln, da, false, best, arg, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
                                                        da == 0 ? Dd - 1 : da - 1, da + 1 == Dd ? 0 : da + 1,
                                                        db == 0 ? Dd - 1 : db - 1, db + 1 == Dd ? 0 : db + 1, nullptr, nullptr, rows);
             };

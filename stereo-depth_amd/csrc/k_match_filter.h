@@ -69,6 +69,7 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_filter(Matc
     constexpr int NW = FA_WAVES;
     constexpr int WGCOLS = FA_WGCOLS;
     constexpr int ND = PR - WGCOLS + 1;
+    constexpr bool PREFIX = fast_prefix_form(TH, PR, true, false, PK16, false, false);    // box sums from prefix sums (k_match_fast.h)
 
     extern __shared__ __attribute__((aligned(16))) unsigned short fsmem[];
     unsigned short *Lt = fsmem;                                   // [TH+22][FA_PL]
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_filter(Matc
             for (int dd = 0; dd < nd; dd += 2 * FILTER_A_GAP) {
                 const int ddb = dd + FILTER_A_GAP < nd ? dd + FILTER_A_GAP : dd;
                 ln.rptr = Rt + wcol + lane + (nd - 1 - dd);
-                fast_pass_pair<TH, PR, true, PK16, 4>(p, ln, d0 + dd, ddb != dd, best, arg, Rt + wcol + lane + (nd - 1 - ddb));
+                fast_pass_pair<TH, PR, true, PK16, 4, false, false, PREFIX>(p, ln, d0 + dd, ddb != dd, best, arg, Rt + wcol + lane + (nd - 1 - ddb));
             }
         }
     }
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_filter(Matc
                 ln.rptr = Rt + wcol + lane + (nd - 1 - dd);
                 const int da = d0 + dd, db = vb ? da + 1 : da;
                 unsigned hits = 0u;              // wave-uniform: [tile row 0..2][db in b, db in a, da in b, da in a]
-                fast_pass_pair<TH, PR, true, PK16, 3>(p, ln, da, vb, best, arg, nullptr, db, nullptr, 0, 0, 0, 0, nullptr, &hits);
+                fast_pass_pair<TH, PR, true, PK16, 3, false, false, PREFIX>(p, ln, da, vb, best, arg, nullptr, db, nullptr, 0, 0, 0, 0, nullptr, &hits);
                 hits = __builtin_amdgcn_readfirstlane(hits);
                 if (hits != 0u && lane == FA_HALO) {
                     for (unsigned tr = 0; tr < 3; ++tr) {

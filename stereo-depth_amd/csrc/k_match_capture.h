@@ -47,8 +47,13 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_capture(Mat
     const bool active = cw0 < w;
     const int x0 = blk.y * TH;
     const int col = cw0 - FA_HALO + lane;
+    // staging by the fast kernel's rule (k_match_fast.h: fast_units_form).  This kernel keeps no winners in registers, so it
+    // asks as the byte form does: every instantiation, pitch 320 included, takes the unit planes (no spill, none gained)
+    constexpr bool UNITS = fast_units_form(TH, PR, false, true);
     const float *Lp = p.Ld + (size_t)b * h * w;
     const float *Rp = p.Rd + (size_t)b * h * w;
+    const unsigned short *Lup = p.Lu + (size_t)b * h * p.upitch;
+    const unsigned short *Rup = p.Ru + (size_t)b * h * p.upitch;
     const float unit = p.unit;
 
     FastLane ln;
@@ -62,7 +67,9 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_capture(Mat
     ln.colidx = ln.store_ok ? col : 0;
     ln.lptr = Lt + wcol + lane;
 
-    fast_stage<(WGCOLS + 63) / 64, FA_WAVES>(Lt, FA_PL, Lp, h, w, x0 - FA_HALO, cwg0 - FA_HALO, TH + 22, WGCOLS, unit, wv, lane);
+    // (the left tile is staged with the first chunk of right rows: k_match_fast.h fast_stage_units)
+    if constexpr (!UNITS)
+        fast_stage<(WGCOLS + 63) / 64, FA_WAVES>(Lt, FA_PL, Lp, h, w, x0 - FA_HALO, cwg0 - FA_HALO, TH + 22, WGCOLS, unit, wv, lane);
     for (int e = tid; e < FA_WAVES * BW; e += 64 * FA_WAVES) bits[e] = 0u;
     __syncthreads();
 
@@ -107,18 +114,26 @@ __global__ __launch_bounds__(64 * FA_WAVES, SMX_FA_OCC) void k_match_capture(Mat
         vpk[o >> 1] |= V << (16 * (o & 1));
     }
 
-    auto stage_right = [&](int d0, int nd) {
+    auto stage_right = [&](int d0, int nd, bool with_left = false) {
         __syncthreads();
         const int cbase = cwg0 - FA_HALO - (p.dmin + d0 + nd - 1);
-        fast_stage<(PR + 63) / 64, FA_WAVES>(Rt, PR, Rp, h, w, x0 - FA_HALO, cbase, TH + 22, WGCOLS + nd - 1, unit, wv, lane);
+        if constexpr (!UNITS)
+            fast_stage<(PR + 63) / 64, FA_WAVES>(Rt, PR, Rp, h, w, x0 - FA_HALO, cbase, TH + 22, WGCOLS + nd - 1, unit, wv, lane);
+        else if (with_left)
+            fast_stage_units<(PR + 255) / 256, FA_WAVES, true>(Rt, PR, Rup, cbase, WGCOLS + nd - 1, Lt, Lup, cwg0 - FA_HALO, WGCOLS, h, w,
+                                                               p.upitch, x0 - FA_HALO, TH + 22, wv, lane);
+        else
+            fast_stage_units<(PR + 255) / 256, FA_WAVES, false>(Rt, PR, Rup, cbase, WGCOLS + nd - 1, nullptr, nullptr, 0, 0, h, w,
+                                                                p.upitch, x0 - FA_HALO, TH + 22, wv, lane);
         __syncthreads();
     };
 
     float best[TH];            // unused by MODE 2 (signature of fast_pass_pair)
     int arg[TH];
+    stage_right(0, min(ND, Dd), true);
     for (int d0 = 0; d0 < Dd; d0 += ND) {
         const int nd = min(ND, Dd - d0);
-        stage_right(d0, nd);
+        if (d0 > 0) stage_right(d0, nd);
         if (active) {
             const unsigned *mybits = bits + wv * BW;
             auto march = [&](int dda, int ddb, unsigned rows) {

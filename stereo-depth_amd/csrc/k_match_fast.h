@@ -260,6 +260,78 @@ __device__ __forceinline__ void fast_stage(unsigned short *tile, int pitch, cons
     }
 }
 
+// The same tile from the pooled plane in grid units (MatchParams::Lu / Ru, written once by the prologue): no arithmetic, and
+// a lane moves FOUR columns per row -- one 8-byte load from a 2-byte-aligned address and one aligned ds_write_b64.  Lane l
+// covers tile columns 4l .. 4l+3 (group k of NK: + 256 k, tiles wider than 256 columns); its source column wraps once per
+// tile, and the plane's cyclic apron of three (smx_common.h: unit_plane_pitch) keeps the four columns inside the row.
+// Wave wv of NW takes rows wv, wv+NW, ... with a wave-uniform incremental wrap; SMX_FA_STAGE_LOADS loads (NB rows) are issued
+// before the first LDS store -- of both tiles when the left one comes along (WITH_LEFT: first chunk; same rows, one barrier
+// pair) -- so a 70-row tile pair costs a wave five memory round trips instead of one per two rows.  A row's columns cols ..
+// round_up(cols, 4) - 1 receive what was loaded: tile pitches are multiples of 8 >= cols, and the marches read tile columns
+// below cols only (lptr: wcol + lane <= 189; rptr: that + nd - 1 - dd <= cols - 1).
+// Which instantiations stage from the unit planes: all but those that would gain a spilled register by the compiler's report
+// (profiles/r07_kernel_resources.txt) -- the 10-row latency shape, which sits at its 128 registers, and the pitch-320 bands
+// with one register per winner (more than 256 disparities), which sit at their 168; they keep the f32 form, like the filter.
+// SMX_FA_STAGE_F32 (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the f32 form everywhere.
+__host__ __device__ constexpr bool fast_units_form(int th, int pr, bool dsplit, bool argb) {
+#ifdef SMX_FA_STAGE_F32
+    (void)th; (void)pr; (void)dsplit; (void)argb;
+    return false;
+#else
+    return dsplit ? th != FA_TH_SMALL_MID : (pr != 320 || argb);
+#endif
+}
+#ifndef SMX_FA_STAGE_LOADS
+#define SMX_FA_STAGE_LOADS 8             // 8-byte loads of a batch: 16 registers
+#endif
+template <int NK, int NW, bool WITH_LEFT>
+__device__ __forceinline__ void fast_stage_units(unsigned short *tile, int pitch, const unsigned short *img, int col0, int cols,
+                                                 unsigned short *ltile, const unsigned short *limg, int lcol0, int lcols,
+                                                 int h, int w, int upitch, int row0, int rows, int wv, int lane) {
+    constexpr int NB = SMX_FA_STAGE_LOADS / (NK + (WITH_LEFT ? 1 : 0));      // rows per batch
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    unsigned coff[NK], lcoff = 0u;                    // byte offset of the lane's source column in a plane row
+    bool in[NK], lin = false;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        in[k] = 256 * k + 4 * lane < cols;
+        coff[k] = 2u * (unsigned)wrapi(col0 + 256 * k + 4 * lane, w);
+    }
+    if (WITH_LEFT) {
+        lin = 4 * lane < lcols;
+        lcoff = 2u * (unsigned)wrapi(lcol0 + 4 * lane, w);
+    }
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    int ra = wrapi(row0 + wvu, h);                    // image row of tile row r0
+    const int rstep = NW % h;
+    for (int r0 = wvu; r0 < rows; r0 += NB * NW) {
+        u32x2 v[NB][NK], lv[NB];
+        // No branch between the loads (one would put a wait in front of each): every lane loads -- a wrapped column is a
+        // column of the plane whether the tile holds it or not -- and a batch that ends past the tile loads image rows all
+        // the same; only the LDS stores are conditional.
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const size_t roff = (size_t)ra * upitch;
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                __builtin_memcpy(&v[j][k], __builtin_assume_aligned((const char *)(img + roff) + coff[k], 2), 8);
+            if (WITH_LEFT) __builtin_memcpy(&lv[j], __builtin_assume_aligned((const char *)(limg + roff) + lcoff, 2), 8);
+            ra += rstep;
+            ra = ra >= h ? ra - h : ra;
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int r = r0 + j * NW;
+            if (r < rows) {
+#pragma unroll
+                for (int k = 0; k < NK; ++k)
+                    if (in[k]) __builtin_memcpy(__builtin_assume_aligned(tile + r * pitch + 256 * k + 4 * lane, 8), &v[j][k], 8);
+                if (WITH_LEFT && lin) __builtin_memcpy(__builtin_assume_aligned(ltile + r * FA_PL + 4 * lane, 8), &lv[j], 8);
+            }
+        }
+    }
+}
+
 struct FastLane {            // per-lane constants of a pass
     const unsigned short *lptr, *rptr;
     float *xch;                    // this wave's LDS exchange buffer
@@ -730,8 +802,11 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     const bool active = cw0 < w;                                 // idle waves still join the barriers
     const int x0 = blk.y * TH;
     const int col = cw0 - FA_HALO + lane;                        // may be < 0 or >= w: wraps (pad_index)
+    constexpr bool UNITS = fast_units_form(TH, PR, DSPLIT, ARGB);   // stage from the unit planes (else: from the f32 planes)
     const float *Lp = p.Ld + (size_t)b * h * w;
     const float *Rp = p.Rd + (size_t)b * h * w;
+    const unsigned short *Lup = p.Lu + (size_t)b * h * p.upitch;
+    const unsigned short *Rup = p.Ru + (size_t)b * h * p.upitch;
     const float unit = p.unit;                                   // K^2
 
     FastLane ln;
@@ -756,23 +831,32 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
 #pragma unroll
     for (int o = 0; o < (DENSE && DSPLIT ? TH : 1); ++o) dfirst[o] = 0.f;
 
-    // ---- stage the left rows once (float on the 1/K^2 grid -> exact u16 units) ----
-    fast_stage<(WGCOLS + 63) / 64, NW>(Lt, FA_PL, Lp, h, w, x0 - FA_HALO, cwg0 - FA_HALO, TH + 22, WGCOLS, unit, wv, lane);
+    // ---- the left rows are staged once, with the first chunk of right rows (exact u16 units: fast_stage_units) ----
+    if constexpr (!UNITS)
+        fast_stage<(WGCOLS + 63) / 64, NW>(Lt, FA_PL, Lp, h, w, x0 - FA_HALO, cwg0 - FA_HALO, TH + 22, WGCOLS, unit, wv, lane);
     for (int e = tid; e < NW * BW; e += 64 * NW) bits[e] = 0u;
 
     // right rows for disparities dmin+d0 .. dmin+d0+nd-1: tile column k is image column
     // (cwg0 - 11 - (dmin+d0+nd-1) + k); lane column c at chunk-local dd sits at k = c + (nd-1-dd)
-    auto stage_right = [&](int d0, int nd) {
+    auto stage_right = [&](int d0, int nd, bool with_left = false) {
         __syncthreads();
         const int cbase = cwg0 - FA_HALO - (p.dmin + d0 + nd - 1);
-        fast_stage<(PR + 63) / 64, NW>(Rt, PR, Rp, h, w, x0 - FA_HALO, cbase, TH + 22, WGCOLS + nd - 1, unit, wv, lane);
+        if constexpr (!UNITS)
+            fast_stage<(PR + 63) / 64, NW>(Rt, PR, Rp, h, w, x0 - FA_HALO, cbase, TH + 22, WGCOLS + nd - 1, unit, wv, lane);
+        else if (with_left)
+            fast_stage_units<(PR + 255) / 256, NW, true>(Rt, PR, Rup, cbase, WGCOLS + nd - 1, Lt, Lup, cwg0 - FA_HALO, WGCOLS, h, w, p.upitch,
+                                                         x0 - FA_HALO, TH + 22, wv, lane);
+        else
+            fast_stage_units<(PR + 255) / 256, NW, false>(Rt, PR, Rup, cbase, WGCOLS + nd - 1, nullptr, nullptr, 0, 0, h, w, p.upitch,
+                                                          x0 - FA_HALO, TH + 22, wv, lane);
         __syncthreads();
     };
 
     // ---- pass 1: all disparities, two per march, running (best, arg) ----
+    if constexpr (UNITS) stage_right(0, min(ND, Dd), true);     // (in front of the loop: what only the left tile needs is dead behind it)
     for (int d0 = 0; d0 < Dd; d0 += ND) {
         const int nd = min(ND, Dd - d0);
-        stage_right(d0, nd);
+        if (!UNITS || d0 > 0) stage_right(d0, nd);
         if (active) {
             // DSPLIT: wave wv takes the wv-th share (even start) of this chunk's disparities
             const int q4 = ((nd + 2 * NW - 1) / (2 * NW)) * 2;

@@ -32,6 +32,33 @@ __device__ __forceinline__ float load_gray(const void *img, size_t plane, size_t
     }
 }
 
+// The pooled planes in grid units (MatchParams::Lu / Ru: what the fast kernels stage): every kernel below writes
+// (unsigned short)(unit * pooled) -- the expression fast_stage evaluates on the f32 plane -- for each pooled pixel, and the
+// threads that own columns 0 .. 2 write the cyclic apron behind column w - 1 as well: column w + j repeats column j % w.
+// units_l == NULL (smx_plan.h: RangePlan::writes_units): the call takes an exact-order route, which reads the f32 planes only.
+// SMX_PROLOGUE_PK8_F32 (build.py --variant with SMX_EXTRA_FLAGS; PK8 below): the gray f32 entries at K = 2 / 4 build the bytes
+// of the u8 planes with v_cvt_pk_u8_f32 and take the integrality flag from the round trip.  Measured neutral in the step for
+// 9 more registers in k_prologue_k2 (45 instead of 37; NOTES.md R7.1), so the test on the float value and the truncating cast
+// stay the product's form.
+#ifdef SMX_PROLOGUE_PK8_F32
+#define SMX_PROLOGUE_PK8(MODE) ((MODE) == IN_GRAY_F32)
+#else
+#define SMX_PROLOGUE_PK8(MODE) false
+#endif
+// (plane: the pair's plane, wave-uniform; row: x * upitch -- 32-bit element offsets, no 64-bit address per store)
+__device__ __forceinline__ void store_unit_u16(uint16_t *plane, unsigned at, uint16_t u) {
+    *(uint16_t *)((char *)plane + (size_t)(2u * at)) = u;
+}
+__device__ __forceinline__ void store_unit_apron(uint16_t *plane, unsigned row, int w, int y, uint16_t u) {
+    if (y < 3) {
+        store_unit_u16(plane, row + (unsigned)(w + y), u);
+        if (w < 3) {                                   // (wave-uniform and rare: the apron goes round more than once)
+            if (y + w < 3) store_unit_u16(plane, row + (unsigned)(w + y + w), u);
+            if (y + 2 * w < 3) store_unit_u16(plane, row + (unsigned)(w + y + 2 * w), u);
+        }
+    }
+}
+
 // grid: (ceil(w/64), ceil(h/4), B), block (64,4).  One thread = one pooled pixel of both images.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_prologue(const void *left, const void *right,
@@ -40,7 +67,8 @@ __global__ __launch_bounds__(256) void k_prologue(const void *left, const void *
                                                   uint8_t *g8_l, uint8_t *g8_r, int *flags2,
                                                   int H, int W, int K, int h, int w, int grid_capable,
                                                   int pitch8, int padl, int padr, int epoch,
-                                                  int gpitch, int gpadl, int fp_conv) {
+                                                  int gpitch, int gpadl, int fp_conv,
+                                                  uint16_t *units_l, uint16_t *units_r, int upitch) {
     // gray_l / gray_r rows have `gpitch` floats; with gpadl > 0 they carry the same cyclic column
     // aprons as the u8 planes (gpadl = padl floats before column 0, padr after column W-1), so the
     // float step-6 kernel never wraps a column index either
@@ -106,6 +134,11 @@ __global__ __launch_bounds__(256) void k_prologue(const void *left, const void *
             (side ? down_r : down_l)[((size_t)b * h + x) * w + y] = pooled;
             const float s = pooled * unit;
             bad = bad || !(s == rintf(s) && pooled >= 0.0f && pooled <= 255.0f);
+            if (units_l != nullptr) {     // (uniform; NULL: the call takes an exact-order route and nothing reads the planes)
+                uint16_t *uplane = (side ? units_r : units_l) + (size_t)b * h * upitch;
+                store_unit_u16(uplane, (unsigned)(x * upitch + y), (unsigned short)s);
+                store_unit_apron(uplane, (unsigned)(x * upitch), w, y, (unsigned short)s);
+            }
         }
     }
     // block = (64,4): one wave per threadIdx.y row, lane == threadIdx.x
@@ -129,11 +162,13 @@ __global__ __launch_bounds__(256) void k_prologue_k2(const void *left, const voi
                                                      uint8_t *g8_l, uint8_t *g8_r, int *flags2,
                                                      int H, int W, int h, int w,
                                                      int pitch8, int padl, int padr, int epoch,
-                                                     int gpitch, int gpadl) {
+                                                     int gpitch, int gpadl,
+                                                     uint16_t *units_l, uint16_t *units_r, int upitch) {
     const int yp = (blockIdx.x * 64 + threadIdx.x) * 2;      // first of two pooled columns
     const int x = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
     const size_t plane = (size_t)H * W;
+    constexpr bool PK8 = SMX_PROLOGUE_PK8(MODE);
     bool bad = false, bad8 = false;
     if (x < h && yp < w) {
         const int Y0 = yp * 2;                               // first of (up to) four full-res columns
@@ -179,22 +214,30 @@ __global__ __launch_bounds__(256) void k_prologue_k2(const void *left, const voi
             float *dn = (side ? down_r : down_l) + ((size_t)b * h + x) * w + yp;
             dn[0] = pooled[0];
             if (ncol == 4) dn[1] = pooled[1];
+            const float s4[2] = {pooled[0] * 4.0f, pooled[1] * 4.0f};
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (k == 0 || ncol == 4) {
-                    const float s4 = pooled[k] * 4.0f;
-                    bad = bad || !(s4 == rintf(s4) && pooled[k] >= 0.0f && pooled[k] <= 255.0f);
-                }
+                if (k == 0 || ncol == 4) bad = bad || !(s4[k] == rintf(s4[k]) && pooled[k] >= 0.0f && pooled[k] <= 255.0f);
             }
+            const uint32_t upk = (uint32_t)(unsigned short)s4[0] | ((uint32_t)(unsigned short)s4[1] << 16);    // in grid units
             if (pitch8 > 0) {
                 uint8_t *g8 = (side ? g8_r : g8_l);
                 uint32_t w0 = 0u, w1 = 0u;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (j < ncol) {
-                        if (MODE == IN_GRAY_F32)
-                            bad8 = bad8 || !(v0[j] == rintf(v0[j]) && v0[j] >= 0.f && v0[j] <= 255.f) ||
-                                   (row1_in && !(v1[j] == rintf(v1[j]) && v1[j] >= 0.f && v1[j] <= 255.f));
+                    if (MODE == IN_GRAY_F32 && !PK8 && j < ncol)
+                        bad8 = bad8 || !(v0[j] == rintf(v0[j]) && v0[j] >= 0.f && v0[j] <= 255.f) ||
+                               (row1_in && !(v1[j] == rintf(v1[j]) && v1[j] >= 0.f && v1[j] <= 255.f));
+                    if (PK8) {
+                        // v_cvt_pk_u8_f32 converts, saturates and inserts the byte; a value is an integer in [0, 255] exactly
+                        // when the byte converts back to it (NaN, negative, > 255 and fractional values all fail; -0 passes
+                        // as 0).  The bytes of a value that fails may differ from the truncating cast: step 6 reads these
+                        // planes only for pairs whose flag is clear (k_refine.h).  Columns past ncol hold 0, and a clamped
+                        // second row repeats the first: neither can raise the flag on its own.
+                        w0 = __builtin_amdgcn_cvt_pk_u8_f32(v0[j], j, w0);
+                        w1 = __builtin_amdgcn_cvt_pk_u8_f32(v1[j], j, w1);
+                        bad8 |= ((float)((w0 >> (8 * j)) & 0xffu) != v0[j]) | ((float)((w1 >> (8 * j)) & 0xffu) != v1[j]);
+                    } else if (j < ncol) {
                         w0 |= (uint32_t)(uint8_t)v0[j] << (8 * j);
                         w1 |= (uint32_t)(uint8_t)v1[j] << (8 * j);
                     }
@@ -217,6 +260,18 @@ __global__ __launch_bounds__(256) void k_prologue_k2(const void *left, const voi
                             if (yj < padr) { r0[padl + W + yj] = a; if (row1_in) r1[padl + W + yj] = c; }
                         }
                     }
+                }
+            }
+            if (units_l != nullptr) {
+                // the two pooled values in grid units as one 32-bit store (upitch is a multiple of 4, yp is even); last, where
+                // the full-resolution values are dead
+                uint16_t *uplane = (side ? units_r : units_l) + (size_t)b * h * upitch;           // wave-uniform
+                const unsigned urow = (unsigned)x * (unsigned)upitch;
+                if (ncol == 4) *(uint32_t *)((char *)uplane + (size_t)(2u * (urow + (unsigned)yp))) = upk;
+                else store_unit_u16(uplane, urow + (unsigned)yp, (uint16_t)upk);
+                if (yp < 3) {
+                    store_unit_apron(uplane, urow, w, yp, (uint16_t)upk);
+                    if (ncol == 4) store_unit_apron(uplane, urow, w, yp + 1, (uint16_t)(upk >> 16));
                 }
             }
         }
@@ -242,7 +297,8 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
                                                      uint8_t *g8_l, uint8_t *g8_r, int *flags2,
                                                      int H, int W, int h, int w,
                                                      int pitch8, int padl, int padr, int epoch,
-                                                     int gpitch, int gpadl, int fp_conv) {
+                                                     int gpitch, int gpadl, int fp_conv,
+                                                     uint16_t *units_l, uint16_t *units_r, int upitch) {
     constexpr bool RGB = MODE == IN_RGB_F32 || MODE == IN_RGB_U8;
     constexpr bool U8 = MODE == IN_GRAY_U8 || MODE == IN_RGB_U8;
     const int y = blockIdx.x * 64 + threadIdx.x;             // pooled column
@@ -250,6 +306,7 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
     const int b = blockIdx.z;
     const size_t plane = (size_t)H * W;
     const size_t pair_elems = RGB ? 3 * plane : plane;
+    constexpr bool PK8 = SMX_PROLOGUE_PK8(MODE);
     bool bad = false, bad8 = false;
     if (x < h && y < w) {
         const int Y0 = y * 4;                                // W % 4 == 0: the four columns are inside the image
@@ -318,6 +375,11 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
             (side ? down_r : down_l)[((size_t)b * h + x) * w + y] = pooled;
             const float s16 = pooled * 16.0f;
             bad = bad || !(s16 == rintf(s16) && pooled >= 0.0f && pooled <= 255.0f);
+            if (units_l != nullptr) {
+                uint16_t *uplane = (side ? units_r : units_l) + (size_t)b * h * upitch;
+                store_unit_u16(uplane, (unsigned)(x * upitch + y), (unsigned short)s16);
+                store_unit_apron(uplane, (unsigned)(x * upitch), w, y, (unsigned short)s16);
+            }
             if (!RGB && pitch8 > 0) {
                 uint8_t *g8 = (side ? g8_r : g8_l);
 #pragma unroll
@@ -326,8 +388,13 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
                     uint32_t wd = 0u;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        if (MODE == IN_GRAY_F32) bad8 = bad8 || !(v[i][j] == rintf(v[i][j]) && v[i][j] >= 0.f && v[i][j] <= 255.f);
-                        wd |= (uint32_t)(uint8_t)v[i][j] << (8 * j);
+                        if (MODE == IN_GRAY_F32 && !PK8) bad8 = bad8 || !(v[i][j] == rintf(v[i][j]) && v[i][j] >= 0.f && v[i][j] <= 255.f);
+                        if (PK8) {                            // convert, saturate, insert; flag = round trip (k_prologue_k2)
+                            wd = __builtin_amdgcn_cvt_pk_u8_f32(v[i][j], j, wd);
+                            bad8 |= (float)((wd >> (8 * j)) & 0xffu) != v[i][j];
+                        } else {
+                            wd |= (uint32_t)(uint8_t)v[i][j] << (8 * j);
+                        }
                     }
                     uint8_t *r8 = g8 + ((size_t)b * H + x * 4 + i) * pitch8;
                     *(uint32_t *)(r8 + padl + Y0) = wd;                          // padl, pitch8, Y0: multiples of 4

@@ -19,6 +19,10 @@ __device__ __forceinline__ int wrapi(int g, int n) {
     return g < 0 ? g + n : g;
 }
 
+// Row pitch (u16 elements) of the pooled planes in grid units (MatchParams::Lu / Ru): w columns, a cyclic apron of three --
+// column w + j repeats column j % w -- and rows that start 8-byte aligned.
+__host__ __device__ constexpr int unit_plane_pitch(int w) { return (w + 3 + 3) & ~3; }
+
 // The reference's pad_index verbatim, negative for index > n (used for oracle rule S6 only).
 __device__ __forceinline__ int pad_index_ref(int index, int n) {
     if (index >= 0 && index < n) return index;
@@ -174,6 +178,10 @@ enum { SMX_SL_BEST = 0, SMX_SL_ARG, SMX_SL_M0, SMX_SL_MA, SMX_SL_MB, SMX_SL_FIRS
 
 struct MatchParams {
     const float *Ld, *Rd;   // [B][h][w]
+    // the same planes in grid units, (unsigned short)(unit * pooled): [B][h][upitch], upitch = unit_plane_pitch(w); columns
+    // w .. w+2 of a row repeat its columns 0 .. 2 (cyclic apron), so four columns from any column < w never wrap
+    const unsigned short *Lu, *Ru;
+    int upitch;
     float *wta;             // [B][h][w]   float(arg) + dmin
     float *costs;           // [3][B][h][w]  AGG at (d, d+1, d-1)           (dmin == 0)
     float *vol;             // [B][h][w][Dd] aggregated volume or nullptr   (dmin  > 0)

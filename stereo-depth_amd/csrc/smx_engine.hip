@@ -80,6 +80,7 @@ struct smx_engine {
     // device buffers (reference device_buffer.hh:12-19, minus the two cost volumes)
     float *gray_l = nullptr, *gray_r = nullptr;   // [B][H][W]  (RGB / u8 entries)
     float *down_l = nullptr, *down_r = nullptr;   // [B][h][w]
+    uint16_t *units_l = nullptr, *units_r = nullptr;   // [B][h][facts.upitch] the pooled planes in grid units (fast kernels' staging)
     float *wta = nullptr, *refined = nullptr;     // [B][h][w]
     float *costs = nullptr;                       // [3][B][h][w]
     float *vol = nullptr;                         // [B][h][w][Dd] only when dmin > 0
@@ -153,7 +154,7 @@ void free_events(smx_engine *e) {
 void free_buffers(smx_engine *e) {
     void *ptrs[] = {e->gray_l, e->gray_r, e->down_l, e->down_r, e->wta,     e->refined,  e->costs,
                     e->vol,    e->flags,  e->gray8_l, e->gray8_r, e->slices, e->cand,    e->stats_dev, e->tickets, e->fast_stats_dev,
-                    e->lr_in_l, e->lr_in_r, e->lr_raw};
+                    e->lr_in_l, e->lr_in_r, e->lr_raw, e->units_l, e->units_r};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (e->hints) (void)hipHostFree(e->hints);
@@ -209,6 +210,7 @@ struct PairView {
     float *gray_l, *gray_r, *down_l, *down_r, *wta, *refined, *costs, *vol;
     int *flags, *flags2;
     uint8_t *gray8_l, *gray8_r;
+    uint16_t *units_l, *units_r;
     unsigned *cand;
 };
 PairView view_from(const smx_engine *e, int first) {
@@ -220,6 +222,8 @@ PairView view_from(const smx_engine *e, int first) {
     v.gray_r = e->gray_r + f * d.H * ef.gpitch;
     v.down_l = e->down_l + f * hw;
     v.down_r = e->down_r + f * hw;
+    v.units_l = e->units_l + f * d.h * ef.upitch;
+    v.units_r = e->units_r + f * d.h * ef.upitch;
     v.wta = e->wta + f * hw;
     v.refined = e->refined + f * hw;
     v.costs = e->costs + f * hw;
@@ -268,7 +272,7 @@ smx::PrologueArgs prologue_args(const smx_engine *e, const PairView &v, bool own
     const smx::EngineFacts &f = e->facts;
     smx::PrologueArgs a{};
     a.left = left; a.right = right; a.gray_l = owns_gray ? v.gray_l : nullptr; a.gray_r = owns_gray ? v.gray_r : nullptr;
-    a.down_l = v.down_l; a.down_r = v.down_r;
+    a.down_l = v.down_l; a.down_r = v.down_r; a.units_l = v.units_l; a.units_r = v.units_r; a.upitch = f.upitch;
     a.flags = v.flags; a.flags2 = v.flags2; a.g8_l = v.gray8_l; a.g8_r = v.gray8_r;
     a.H = d.H; a.W = d.W; a.K = d.K; a.h = d.h; a.w = d.w; a.grid_capable = f.grid_capable ? 1 : 0;
     a.pitch8 = f.pitch8; a.padl = f.padl; a.padr = f.padr; a.epoch = e->epoch; a.gpitch = f.gpitch; a.gpadl = f.gpadl;
@@ -281,7 +285,7 @@ smx::RangeParams range_params(const smx_engine *e, const PairView &v, const smx:
     const smx::EngineFacts &f = e->facts;
     smx::RangeParams b;
     smx::MatchParams &mp = b.mp;
-    mp.Ld = v.down_l; mp.Rd = v.down_r; mp.wta = v.wta; mp.costs = v.costs; mp.vol = v.vol;
+    mp.Ld = v.down_l; mp.Rd = v.down_r; mp.Lu = v.units_l; mp.Ru = v.units_r; mp.upitch = f.upitch; mp.wta = v.wta; mp.costs = v.costs; mp.vol = v.vol;
     mp.flags = v.flags; mp.epoch = e->epoch; mp.B = e->B; mp.h = d.h; mp.w = d.w; mp.dmin = d.dmin; mp.Dd = d.Dd;
     mp.rn = (int)e->cfg.ncc_patch_radius; mp.rs = e->cfg.small_mbm_radius;
     mp.rm = e->cfg.mid_mbm_radius; mp.rl = e->cfg.large_mbm_radius;
@@ -362,7 +366,9 @@ int enqueue_range(smx_engine *e, const smx::CallFacts &call, const smx::RangePla
     const GrayView g = gray_view(e, v, pl.owns_gray, first, left, right);
     {
         SlotTimer tm(e, s, lane, SMX_KERNEL_PROLOGUE);
-        smx::launch_prologue(pl.prologue, prologue_args(e, v, pl.owns_gray, left, right), n, s);
+        smx::PrologueArgs pa = prologue_args(e, v, pl.owns_gray, left, right);
+        if (!pl.writes_units) pa.units_l = pa.units_r = nullptr;      // (the exact-order routes: nothing would read them)
+        smx::launch_prologue(pl.prologue, pa, n, s);
     }
     if (pl.status != SMX_OK) return fail(pl.status, "%s", pl.refusal);
     if (pl.exact.slice_floats > f.slices_floats)          // the records of a split exact-order launch (0: the range has none)
@@ -827,6 +833,8 @@ int smx_create(const smx_config *cfg, smx_engine **out_engine) {
     alloc((void **)&e->gray_r, B * (size_t)d.H * f.gpitch * sizeof(float));
     alloc((void **)&e->down_l, B * hw * sizeof(float));
     alloc((void **)&e->down_r, B * hw * sizeof(float));
+    alloc((void **)&e->units_l, B * (size_t)d.h * f.upitch * sizeof(uint16_t));
+    alloc((void **)&e->units_r, B * (size_t)d.h * f.upitch * sizeof(uint16_t));
     alloc((void **)&e->wta, B * hw * sizeof(float));
     alloc((void **)&e->refined, B * hw * sizeof(float));
     alloc((void **)&e->costs, 3 * B * hw * sizeof(float));

@@ -20,7 +20,8 @@ struct PrologueArgs {
     float *gray_l, *gray_r, *down_l, *down_r;
     int *flags, *flags2;
     uint8_t *g8_l, *g8_r;
-    int H, W, K, h, w, grid_capable, pitch8, padl, padr, epoch, gpitch, gpadl;
+    uint16_t *units_l, *units_r;      // [n][h][upitch] the pooled planes in grid units (smx_common.h: MatchParams::Lu)
+    int H, W, K, h, w, grid_capable, pitch8, padl, padr, epoch, gpitch, gpadl, upitch;
     int fp_conv;             // smx_fp_convention (RGB entries: step 1)
 };
 // like the aggregation family below, these three are tables from their launch spec (smx_common.h) to an instantiation

@@ -62,6 +62,7 @@ struct EngineFacts {
     int kt = 0;                     // compile-time K of the specialised step-6 kernels (1, 2, 4) or 0: the generic float kernel
     int pitch8 = 0, padl = 0, padr = 0;   // u8 planes with cyclic aprons; pitch8 = 0: integer step-6 kernel not applicable
     int gpitch = 0, gpadl = 0;            // row pitch / left-apron width (floats) of the engine's gray planes
+    int upitch = 0;                       // row pitch (u16) of the pooled planes in grid units (smx_common.h: unit_plane_pitch)
     bool prologue_k2 = false;       // K = 2, even W: the gray entries pool two pixels per thread with 16-byte loads
     bool prologue_k4 = false;       // K = 4, W a multiple of 4 and so is every pitch and apron: one pooled pixel is a 4 x 4 block of 16-byte loads
     bool sad_exact = true;          // step 6, integer kernels: the SAD parabola is exact for every disparity (k_refine.h refine_finish_int)
@@ -121,6 +122,7 @@ inline EngineFacts derive_facts(const smx_config &cfg, const smx_dims &d, int cu
             f.gpadl = 0;
         }
     }
+    f.upitch = unit_plane_pitch(d.w);
     f.prologue_k2 = K == 2 && (d.W & 1) == 0;
     f.prologue_k4 = K == 4 && (d.W & 3) == 0 && f.grid_capable && (f.gpitch & 3) == 0 && (f.gpadl & 3) == 0 && (f.pitch8 & 3) == 0 &&
                     (f.padl & 3) == 0 && (f.gpadl == 0 || f.gpadl == f.padl);
@@ -188,6 +190,7 @@ struct RangePlan {
     bool gated_dense_first = false; // FILTERED, f32 RGB: pairs whose gray leaves [0, 255] take the dense kernel, enqueued first
     bool exact_split = false;       // the dense exact-order launch (and its capture launch) may split the disparity range
     bool capture_follows = false;   // dmin > 0: every arg-max launch is followed by its sparse lookup launch
+    bool writes_units = false;      // the prologue writes the pooled planes in grid units: some launch of the range stages from them
     FastPlan fast{};                // shape of a sparse fast-kernel launch of these n pairs (what smx_get_match_geometry reports; launched: fast_launch)
     // form of the fast kernel, on the routes that launch it (k_match_fast.h DENSE: the pass that keeps the winner's neighbours
     // instead of fetching them in a sparse second pass; min_disparity = 0 only).  Both shapes that have a dense form follow
@@ -465,6 +468,7 @@ inline RangePlan plan_range(const EngineFacts &f, const CallFacts &call, int n, 
         p.refine.kind = REFINE_AUTO_V;
     }
     p.fill = fill_launch(f, call.on_lanes, n);
+    p.writes_units = p.route != AGG_EXACT && p.route != AGG_FILTERED;     // (those two read the f32 planes only)
     return p;
 }
 

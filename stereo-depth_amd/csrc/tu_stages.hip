@@ -20,18 +20,18 @@ void prologue_t(int kernel, const PrologueArgs &a, int n, hipStream_t s) {
             constexpr int M2 = (MODE == IN_GRAY_U8) ? IN_GRAY_U8 : IN_GRAY_F32;
             hipLaunchKernelGGL((k_prologue_k2<M2>), dim3((a.w + 127) / 128, grid.y, n), block, 0, s, a.left, a.right, a.gray_l, a.gray_r,
                                a.down_l, a.down_r, a.flags, a.g8_l, a.g8_r, a.flags2, a.H, a.W, a.h, a.w,
-                               a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl);
+                               a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl, a.units_l, a.units_r, a.upitch);
             return;
         }
         case PROLOGUE_K4:     // one pooled pixel = a 4 x 4 block read with four 16-byte loads per image and plane (K = 4, W a multiple of 4)
             hipLaunchKernelGGL((k_prologue_k4<MODE>), grid, block, 0, s, a.left, a.right, a.gray_l, a.gray_r, a.down_l,
                                a.down_r, a.flags, a.g8_l, a.g8_r, a.flags2, a.H, a.W, a.h, a.w,
-                               a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl, a.fp_conv);
+                               a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl, a.fp_conv, a.units_l, a.units_r, a.upitch);
             return;
         default:
             hipLaunchKernelGGL((k_prologue<MODE>), grid, block, 0, s, a.left, a.right, a.gray_l, a.gray_r, a.down_l,
                                a.down_r, a.flags, a.g8_l, a.g8_r, a.flags2, a.H, a.W, a.K, a.h, a.w,
-                               a.grid_capable, a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl, a.fp_conv);
+                               a.grid_capable, a.pitch8, a.padl, a.padr, a.epoch, a.gpitch, a.gpadl, a.fp_conv, a.units_l, a.units_r, a.upitch);
     }
 }
 }  // namespace

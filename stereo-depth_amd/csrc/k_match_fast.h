@@ -181,6 +181,23 @@ __host__ __device__ constexpr bool fast_prefix_form(int th, int pr, bool p1only,
 #endif
 }
 
+// Needed-set tables of a wave: one, or one per unit band of the stacked bands (th > 32: fast_stacked_tail fills both before
+// it marches).  SMX_FA_STACK_TAIL_HALVES (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the tail that finishes one
+// unit band after the other on one table.
+__host__ __device__ constexpr int fast_tables(int th) {
+#ifdef SMX_FA_STACK_TAIL_HALVES
+    (void)th;
+    return 1;
+#else
+    return th > 32 ? 2 : 1;
+#endif
+}
+// The second table takes the place of the second exchange row: a kernel with two tables sends both exchanges of a row step
+// through ONE per-wave row (what SMX_FA_XCH_ROWS = 1 does for every kernel; measured equal in round 4,
+// profiles/r04_match_fast_candidates.txt), so the workgroup's LDS -- fast_lds_bytes, the tile that fits a CU exactly twice --
+// stays what it was: 2 tables of at most 68 words are 272 bytes more per wave, an exchange row is 608.
+__host__ __device__ constexpr int fast_xch_rows(int th) { return fast_tables(th) > 1 ? 1 : FA_XCH_ROWS; }
+
 template <int PR> inline size_t fast_lds_bytes(int th, int Dd, bool dsplit = false) {
     const size_t nw = dsplit ? FA_DS_WAVES : FA_WAVES;
     return (size_t)(th + 22) * (FA_PL + PR) * sizeof(unsigned short) + nw * fast_bitwords(Dd) * sizeof(unsigned) +
@@ -404,7 +421,8 @@ __device__ __forceinline__ void argb_update(int kbyte, int &word, float m, float
 //
 // PREFIX (every MODE; PK16 == 2 only): the box sums as differences of prefix sums down the tile rows (file header); r3 / r9 /
 // r21 then hold P / PC / PH.  The caller asks fast_prefix_form, once per kernel, so that all its marches share one form.
-template <int TH, int PR, bool P1ONLY, int PK16, int MODE = 0, bool ARGB = false, bool DENSE = false, bool PREFIX = false>
+// XR: exchange rows of the kernel (fast_xch_rows; 1: the R9 exchange goes through the row of the R3 exchange).
+template <int TH, int PR, bool P1ONLY, int PK16, int MODE = 0, bool ARGB = false, bool DENSE = false, bool PREFIX = false, int XR = FA_XCH_ROWS>
 __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastLane &ln, int d,
                                                bool valid_b, float (&best)[TH], int (&arg)[TH],
                                                const unsigned short *rptr_b_in = nullptr, int db = 0,
@@ -412,7 +430,7 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                                                int am_b = 0, int ap_b = 0, const unsigned *vpk = nullptr,
                                                unsigned *hits = nullptr, unsigned rowmask = ~0u,
                                                float *dmb = nullptr, float *dma = nullptr, float *dcp = nullptr,
-                                               float *dfirst = nullptr) {
+                                               float *dfirst = nullptr, unsigned rowmask_hi = 0u) {
     static_assert(!PREFIX || (PK16 == 2 && fast_prefix_exact(TH, 2)), "prefix form: K <= 2 and every prefix below 2^24");
     constexpr int NQ = TH + 20;              // tile rows of the 3x3 cost slice (q index)
     // PREFIX: r3 / r9 / r21 hold the prefixes P / PC / PH, which the boxes reach one tile row further back (5 and 8)
@@ -498,7 +516,7 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                     }
                 }
                 if (q >= Q21 - 1 && q + 1 < NQ) {
-                    f32x2 *x9b = (f32x2 *)(ln.xch + (FA_XCH_ROWS > 1 ? 2 * FA_XROW : 0)) + lane_;
+                    f32x2 *x9b = (f32x2 *)(ln.xch + (XR > 1 ? 2 * FA_XROW : 0)) + lane_;
                     x9b[6] = r9[q - 8];
                     __builtin_amdgcn_wave_barrier();
                     {
@@ -524,8 +542,9 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                 if (q >= 20) {
                     const int o = q - 20;
                     const f32x2 agg = (hs * vs) * cs;            // aggregation .cu:87 (in units)
-                    if ((MODE == 1 || MODE == 2) && !((rowmask >> o) & 1u)) {
-                        // nobody in this band row reads either disparity of this march (rowmask is wave-uniform)
+                    if ((MODE == 1 || MODE == 2) && !(((o < 32 ? rowmask : rowmask_hi) >> (o & 31)) & 1u)) {
+                        // nobody in this band row reads either disparity of this march (rowmask is wave-uniform; bands taller
+                        // than 32 rows: rowmask_hi holds the rows from 32 on)
                     } else if (MODE == 2) {
                         // dmin > 0 (k_match_capture): this lane's pixel f holds AGG[f][ia] / AGG[f][ib].  argpk = U
                         // (absolute WTA disparity of f), vpk = 2*Dd - U of the flat successor f+1 (0xffff: none).
@@ -674,16 +693,19 @@ __device__ __forceinline__ void fast_stats_report(const MatchParams &p, int b, i
 }
 
 // Stacked bands (k_match_fast<TH > 32>: throughput shape, sparse form, byte-packed winners): pass 1 of match_fast_body marches
-// NH unit bands of TU rows in one go -- one set of 22 halo rows for all of them -- and this function does what follows pass 1
-// there, once per unit band and on the tile that is already staged: everything behind pass 1 is written for at most 32 band
-// rows (one table bit per band row, rowmask, dup_left, the packed argpk).  The same steps as in match_fast_body, where the
-// comments are; a unit band differs from a band in its tile rows (hh * TU further down), its image rows and its slice of
-// best / arg.  The waves' needed-set tables are reused: a wave clears its own table behind its second pass (LDS executes a
-// wave's operations in order).  Each unit band that holds image rows counts as one window in the report.
+// NH unit bands of TU rows in one go -- one set of 22 halo rows for all of them -- and fast_stacked_tail does what follows
+// pass 1 there, on the tile that is already staged.  The store block (WTA map, cost plane 0, dup_left, the marks) is written
+// for at most 32 band rows and runs once per unit band, as in match_fast_body, where the comments are; a unit band differs
+// from a band in its tile rows (hh * TU further down), its image rows and its slice of best / arg.  Each unit band that
+// holds image rows counts as one window in the report.
+//
+// This form (SMX_FA_STACK_TAIL_HALVES, A/B builds only) also runs the second pass once per unit band: a table, a walk and
+// marches of TU + 22 tile rows each, the wave's one table cleared in between -- a disparity that both unit bands need is
+// marched over 2 x (TU + 22) rows where the TU * NH + 22 staged ones hold everything.
 template <int TU, int NH, int PR, int PK16, bool PREFIX, class StageRight>
-__device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
-                                                  const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
-                                                  bool active, StageRight &&stage_right) {
+__device__ __forceinline__ void fast_stacked_tail_halves(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
+                                                         const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
+                                                         bool active, StageRight &&stage_right) {
     constexpr int ND = PR - FA_WGCOLS + 1;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int h = p.h, w = p.w, Dd = p.Dd, BW = fast_bitwords(Dd);
@@ -767,6 +789,231 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
     }
 }
 
+// The second pass of the stacked bands, both unit bands at once.  A needed disparity of a wave's window is read by pixels of
+// both unit bands, of the upper one only or of the lower one only.  Two of a class share a march: "both" pairs march the
+// whole staged tile (2 TU + 22 rows, MODE 1 of the TH = 2 TU march with a row mask of 2 TU bits), "upper" and "lower" pairs
+// the TU + 22 tile rows of their unit band.  What is left when the walk ends is at most one disparity of each class, and
+// fast_tail_leftover says how those go -- by rows marched, F = 2 TU + 22 for a full march and H = TU + 22 for a half one:
+//   both alone, both + upper, both + lower      one full march (F; the per-band tail marched 2 H)
+//   upper + lower                               one full march of the two (F < 2 H: each rides along in the other's rows, where
+//                                               no pixel reads it -- its table word of that band is empty)
+//   both + upper + lower                        upper march (both, upper), then lower march (both, lower): 2 H < F + H
+//   upper alone, lower alone                    its own half march with both pipelines on it (H)
+// Against the per-band tail, which marches H * (ceil((B + U) / 2) + ceil((B + L) / 2)) rows for B / U / L disparities of
+// the three classes: every pair of "both" saves 2 H - F = 22 rows, pairs of the other classes cost the same, and each
+// leftover row above costs at most what it did (2 H, 2 H, 2 H; 2 H; 2 H; H) -- never more rows for any window
+// (fast_tail_rows <= fast_tail_rows_halves, tests/test_stacked_tail_cpu.py).  Host and device share these functions.
+enum FastTailLeftover { FT_NONE = 0, FT_FULL_BB, FT_FULL_BU, FT_FULL_BL, FT_FULL_UL, FT_HALVES, FT_UPPER, FT_LOWER };
+__host__ __device__ constexpr int fast_tail_leftover(bool both, bool upper, bool lower) {
+    return both ? (upper ? (lower ? FT_HALVES : FT_FULL_BU) : (lower ? FT_FULL_BL : FT_FULL_BB))
+                : (upper ? (lower ? FT_FULL_UL : FT_UPPER) : (lower ? FT_LOWER : FT_NONE));
+}
+__host__ __device__ constexpr int fast_tail_leftover_rows(int code, int tu) {
+    return code == FT_NONE ? 0 : (code == FT_UPPER || code == FT_LOWER ? tu + 22 : (code == FT_HALVES ? 2 * (tu + 22) : 2 * tu + 22));
+}
+// tile rows marched by the second pass for one window and right-tile chunk with nb / nu / nl needed disparities per class
+__host__ __device__ constexpr long fast_tail_rows(int nb, int nu, int nl, int tu) {
+    return (long)(nb / 2) * (2 * tu + 22) + (long)(nu / 2 + nl / 2) * (tu + 22) +
+           fast_tail_leftover_rows(fast_tail_leftover(nb & 1, nu & 1, nl & 1), tu);
+}
+// ... by the per-band tail (fast_stacked_tail_halves)
+__host__ __device__ constexpr long fast_tail_rows_halves(int nb, int nu, int nl, int tu) {
+    return (long)((nb + nu + 1) / 2 + (nb + nl + 1) / 2) * (tu + 22);
+}
+
+// fast_stacked_tail: the store block of both unit bands first, each marking its own table (two tables of one word per
+// disparity and wave, fast_tables; nothing is cleared: every table is filled once per launch), then ONE walk over the
+// range that fetches the words of both tables -- the same one-read-per-64-words / ballot / v_readlane scheme as
+// SMX_FOR_EACH_NEEDED, written as a loop with a single dispatch point, so that each of the three march forms is inlined
+// exactly once (the walk and the leftover rule both feed it; a needed disparity waits in `pst` for a partner of its class
+// as `pend` does in match_fast_body).  The report keeps its meaning -- marches of a per-band second pass, per unit band:
+// ceil(needed disparities of that band / 2) -- and is counted from the tables, not from the marches run.
+template <int TU, int NH, int PR, int PK16, bool PREFIX>
+__device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
+                                                  const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
+                                                  bool active) {
+    static_assert(NH == 2 && TU % 2 == 0 && TU < 32 && fast_tables(TU * NH) == NH, "two unit bands, a table each; argpk holds two rows a word");
+    // One right tile holds the whole range: the stacked bands exist at pitch 256 for ranges the plan keeps below FA_WIDE_FROM
+    // (match_fast_plan: fast_stack_instantiated), so the tile of pass 1 is still staged and `nd` is the range itself.
+    static_assert(PR == 256 && FA_WIDE_FROM <= PR - FA_WGCOLS + 1, "stacked bands: a single right-tile chunk");
+    constexpr int TH = TU * NH, XR = fast_xch_rows(TH);              // (the kernel's one exchange row: every march of it)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int h = p.h, w = p.w, Dd = p.Dd, nd = p.Dd, BW = fast_bitwords(Dd);
+    const bool all_needed = Dd > FA_BITWORDS * 32;
+    unsigned *wbits = bits + wv * NH * BW;                           // [NH][BW]: the wave's table of unit band hh
+    unsigned argpk[TH / 2];                                           // the winners of all TH rows, two to a register
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+        float bh[TU];
+        int ah[TU];
+#pragma unroll
+        for (int o = 0; o < TU; ++o) {
+            bh[o] = best[hh * TU + o];
+            ah[o] = (argb[(hh * TU + o) >> 2] >> (8 * ((hh * TU + o) & 3))) & 0xff;      // byte-packed indices -> one register per row
+        }
+        FastLane lh = ln;
+        lh.row0 = ln.row0 + (size_t)(hh * TU) * w;
+        lh.rows_ok = max(0, min(TU, h - x0 - hh * TU));
+        unsigned *hbits = wbits + hh * BW;
+        unsigned dup_left = 0u;
+#ifndef SMX_FA_NO_DEDUP
+        if (!all_needed) {
+#pragma unroll
+            for (int o = 0; o < TU; ++o) {
+                const int la = __builtin_amdgcn_update_dpp(-1, ah[o], 0x138, 0xf, 0xf, false);
+                dup_left |= (la == ah[o] ? 1u : 0u) << o;
+            }
+            const int left_ok = __builtin_amdgcn_update_dpp(0, lh.store_ok ? 1 : 0, 0x138, 0xf, 0xf, false);
+            if (!left_ok) dup_left = 0u;
+        }
+#endif
+        if (lh.store_ok) {
+#pragma unroll
+            for (int o = 0; o < TU; ++o) {
+                if (o < lh.rows_ok) {
+                    const unsigned off = (unsigned)(o * w + lh.colidx);
+                    store_u32off(p.wta + lh.row0, off, (float)ah[o] + (float)p.dmin);
+                    const bool nv = !(bh[o] > SMX_FLT_MIN);
+                    store_u32off(p.costs + lh.row0, off, nv ? 0.0f : bh[o] * lh.inv);
+                    if (!all_needed && !((dup_left >> o) & 1u)) {
+                        const int dn = (ah[o] + 1 == Dd) ? 0 : ah[o] + 1;
+                        const int dp = (ah[o] == 0) ? Dd - 1 : ah[o] - 1;
+                        atomicOr(&hbits[dn], 1u << o);
+                        atomicOr(&hbits[dp], 1u << o);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < TU / 2; ++o) argpk[hh * (TU / 2) + o] = 0u;
+#pragma unroll
+        for (int o = 0; o < TU; ++o)
+            argpk[hh * (TU / 2) + (o >> 1)] |= ((lh.store_ok && o < lh.rows_ok) ? (unsigned)ah[o] : 0xffffu) << (16 * (o & 1));
+    }
+    // No workgroup barrier from here on: a wave reads its own marks only (LDS executes a wave's operations in order), and the
+    // tile of pass 1 stays as it is -- the waves of a workgroup run their second passes independently.
+    // (SMX_FA_STACK_TAIL_BARRIER, A/B builds only: the barrier the per-band tail has in front of each second pass.)
+#ifdef SMX_FA_STACK_TAIL_BARRIER
+    __syncthreads();
+#endif
+    __builtin_amdgcn_wave_barrier();
+    // The report, in front of the second pass (nothing waits for it, and neither the counter's address nor a count stays
+    // live across the marches): per unit band that holds image rows one window, and its needed disparities two by two.
+    if (p.fast_stats && active) {
+#pragma unroll
+        for (int hh = 0; hh < NH; ++hh) {
+            int n = 0;
+            for (int g0 = 0; g0 < nd; g0 += 64) {
+                const bool in = g0 + lane < nd;
+                n += __builtin_popcountll(__ballot(in && (all_needed || wbits[hh * BW + g0 + lane] != 0u)));
+            }
+            if (lane == 0) fast_stats_report<false>(p, blk.z, (int)(blk.x + gridDim.x * blk.y), wv, (n + 1) / 2, h - x0 - hh * TU > 0);
+        }
+    }
+    {
+        if (active) {
+            enum { K_NONE, K_FULL, K_UPPER, K_LOWER };
+            const unsigned *tbl_u = wbits, *tbl_l = wbits + BW;
+            // A disparity of each class waiting for a partner (-1: none; P_B = -2: see FT_HALVES below) and the rows that
+            // read it, of the upper / the lower unit band.  Wave-uniform: seven scalars live across the marches.
+            enum { P_B, P_U, P_L, R_BU, R_BL, R_U, R_L };
+            int pst[7] = {-1, -1, -1, 0, 0, 0, 0};
+            auto pget = [&](int i) { return pst[i]; };
+            auto pset = [&](int i, int v) { pst[i] = v; };
+            int g = -64;                                     // first word of the 64 the lanes hold
+            unsigned word_u = 0u, word_l = 0u;
+            unsigned long long m = 0ull;
+            for (;;) {
+                int kind = K_NONE, dda = 0, ddb = 0;
+                unsigned r_u = 0u, r_l = 0u;                 // rows of the march: upper / lower unit band (a half march: its own in r_u)
+                const int pb = pget(P_B);
+                if (pb == -2) {                              // FT_HALVES: the lower march (both, lower) behind its upper one
+                    kind = K_LOWER; dda = pget(P_U); ddb = pget(P_L); r_u = (unsigned)pget(R_L);
+                    pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
+                } else if (m != 0ull) {
+                    const int k = __builtin_ctzll(m);
+                    m &= m - 1ull;
+                    const int dd = g + k;
+                    const unsigned ru = (unsigned)__builtin_amdgcn_readlane((int)word_u, k);
+                    const unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)word_l, k);
+                    if (ru != 0u && rl != 0u) {
+                        if (pb < 0) { pset(P_B, dd); pset(R_BU, (int)ru); pset(R_BL, (int)rl); }
+                        else { kind = K_FULL; dda = pb; ddb = dd; r_u = (unsigned)pget(R_BU) | ru; r_l = (unsigned)pget(R_BL) | rl; pset(P_B, -1); }
+                    } else if (ru != 0u) {
+                        const int pu = pget(P_U);
+                        if (pu < 0) { pset(P_U, dd); pset(R_U, (int)ru); }
+                        else { kind = K_UPPER; dda = pu; ddb = dd; r_u = (unsigned)pget(R_U) | ru; pset(P_U, -1); }
+                    } else {
+                        const int pl = pget(P_L);
+                        if (pl < 0) { pset(P_L, dd); pset(R_L, (int)rl); }
+                        else { kind = K_LOWER; dda = pl; ddb = dd; r_u = (unsigned)pget(R_L) | rl; pset(P_L, -1); }
+                    }
+                } else if (g + 64 < nd) {                    // the next 64 words of both tables: one LDS read each
+                    g += 64;
+                    const int idx = g + lane;
+                    word_u = 0u;
+                    word_l = 0u;
+                    if (idx < nd) {
+                        word_u = all_needed ? ~0u : tbl_u[idx];
+                        word_l = all_needed ? ~0u : tbl_l[idx];
+                    }
+                    m = __ballot((word_u | word_l) != 0u);
+                } else {                                     // the walk is over: the odd ones out (fast_tail_leftover)
+                    const int pu = pget(P_U), pl = pget(P_L);
+                    const int code = fast_tail_leftover(pb >= 0, pu >= 0, pl >= 0);
+                    if (code == FT_NONE) break;
+                    const unsigned pb_u = (unsigned)pget(R_BU), pb_l = (unsigned)pget(R_BL), pu_r = (unsigned)pget(R_U), pl_r = (unsigned)pget(R_L);
+                    if (code == FT_FULL_BB) { kind = K_FULL; dda = pb; ddb = pb; r_u = pb_u; r_l = pb_l; }
+                    else if (code == FT_FULL_BU) { kind = K_FULL; dda = pb; ddb = pu; r_u = pb_u | pu_r; r_l = pb_l; }
+                    else if (code == FT_FULL_BL) { kind = K_FULL; dda = pb; ddb = pl; r_u = pb_u; r_l = pb_l | pl_r; }
+                    else if (code == FT_FULL_UL) { kind = K_FULL; dda = pu; ddb = pl; r_u = pu_r; r_l = pl_r; }
+                    else if (code == FT_UPPER) { kind = K_UPPER; dda = pu; ddb = pu; r_u = pu_r; }
+                    else if (code == FT_LOWER) { kind = K_LOWER; dda = pl; ddb = pl; r_u = pl_r; }
+                    if (code == FT_HALVES) {                 // upper march (both, upper) now; (both, lower) waits in (P_U, P_L), P_B = -2
+                        kind = K_UPPER; dda = pb; ddb = pu; r_u = pb_u | pu_r;
+                        pset(R_L, (int)(pl_r | pb_l)); pset(P_U, pb); pset(P_B, -2);
+                    } else {
+                        pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
+                    }
+                }
+                if (kind == K_NONE) continue;
+                const int da = dda, db = ddb;
+                const int am_a = da == 0 ? Dd - 1 : da - 1, ap_a = da + 1 == Dd ? 0 : da + 1;
+                const int am_b = db == 0 ? Dd - 1 : db - 1, ap_b = db + 1 == Dd ? 0 : db + 1;
+                if (kind == K_FULL) {
+                    float bd[TH];                            // (best / arg: unused by MODE 1, the march's signature)
+                    int ad[TH];
+#pragma unroll
+                    for (int o = 0; o < TH; ++o) { bd[o] = 0.f; ad[o] = 0; }
+                    FastLane lf = ln;
+                    lf.rptr = Rt + wcol + lane + (nd - 1 - dda);
+                    fast_pass_pair<TH, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lf, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
+                                                                                 am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u | (r_l << TU), nullptr,
+                                                                                 nullptr, nullptr, nullptr, r_l >> (32 - TU));
+                } else {
+                    float bd[TU];
+                    int ad[TU];
+#pragma unroll
+                    for (int o = 0; o < TU; ++o) { bd[o] = 0.f; ad[o] = 0; }
+                    FastLane lh = ln;
+                    if (kind == K_UPPER) {
+                        lh.rptr = Rt + wcol + lane + (nd - 1 - dda);
+                        fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
+                                                                                     am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
+                    } else {
+                        const unsigned short *Rh = Rt + TU * PR;      // the lower unit band's first tile row
+                        lh.lptr = ln.lptr + TU * FA_PL;
+                        lh.row0 = ln.row0 + (size_t)TU * w;
+                        lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
+                        fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rh + wcol + lane + (nd - 1 - ddb), db,
+                                                                                     argpk + TU / 2, am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
+                    }
+                }
+            }
+        }
+    }
+}
+
 // DSPLIT = false (throughput): the 4 waves of a workgroup own 4 adjacent column windows.
 // DSPLIT = true  (latency, few pairs in flight): the FA_DS_WAVES waves own the SAME window and a share of
 // the disparity range each; (best, arg) and the neighbour costs are merged through LDS, in
@@ -789,7 +1036,11 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     extern __shared__ __attribute__((aligned(16))) unsigned short fsmem[];
     unsigned short *Lt = fsmem;                                   // [TH+22][FA_PL]
     unsigned short *Rt = fsmem + (TH + 22) * FA_PL;               // [TH+22][PR]
-    unsigned *bits = (unsigned *)(Rt + (TH + 22) * PR);           // [NW][BW]
+    unsigned *bits = (unsigned *)(Rt + (TH + 22) * PR);           // [NW][NT][BW]
+    constexpr int NT = fast_tables(TH);                           // needed-set tables per wave
+    constexpr int XR = fast_xch_rows(TH);                         // exchange rows per wave (one where a second table takes the other's place)
+    static_assert(NT == 1 || (XR == 1 && FA_XCH_ROWS == 2 && (NT - 1) * ((ND + 1) & ~1) <= 2 * FA_XROW),
+                  "the second table fits the exchange row it replaces: fast_lds_bytes is unchanged");
     const int BW = fast_bitwords(p.Dd);
 
     const int tid = threadIdx.x;
@@ -810,7 +1061,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     const float unit = p.unit;                                   // K^2
 
     FastLane ln;
-    ln.xch = (float *)(bits + NW * BW) + wv * FA_XCH_FLOATS;
+    ln.xch = (float *)(bits + NW * NT * BW) + wv * (2 * XR * FA_XROW);
     ln.c255 = (unsigned)(255.0f * unit);
     ln.inv = 1.0f / (unit * unit * unit);
     ln.store_ok = active && lane >= FA_HALO && lane < FA_HALO + FA_VALID && col < w;
@@ -834,7 +1085,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     // ---- the left rows are staged once, with the first chunk of right rows (exact u16 units: fast_stage_units) ----
     if constexpr (!UNITS)
         fast_stage<(WGCOLS + 63) / 64, NW>(Lt, FA_PL, Lp, h, w, x0 - FA_HALO, cwg0 - FA_HALO, TH + 22, WGCOLS, unit, wv, lane);
-    for (int e = tid; e < NW * BW; e += 64 * NW) bits[e] = 0u;
+    for (int e = tid; e < NW * NT * BW; e += 64 * NW) bits[e] = 0u;
 
     // right rows for disparities dmin+d0 .. dmin+d0+nd-1: tile column k is image column
     // (cwg0 - 11 - (dmin+d0+nd-1) + k); lane column c at chunk-local dd sits at k = c + (nd-1-dd)
@@ -865,16 +1116,20 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
             for (int dd = dd_lo; dd < dd_hi; dd += 2) {
                 ln.rptr = Rt + wcol + lane + (nd - 1 - dd);
                 if constexpr (DENSE)
-                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, true, PREFIX>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg, nullptr, 0, nullptr,
+                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, true, PREFIX, XR>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg, nullptr, 0, nullptr,
                                                                          0, 0, 0, 0, nullptr, nullptr, ~0u, dmb, dma, dcp,
                                                                          DSPLIT && dd == dd_lo ? dfirst : nullptr);
                 else
-                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, false, PREFIX>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg);
+                    fast_pass_pair<TH, PR, P1ONLY, PK16, 0, ARGB, false, PREFIX, XR>(p, ln, d0 + dd, dd + 1 < dd_hi, best, arg);
             }
         }
     }
     if constexpr (NH > 1) {
-        fast_stacked_tail<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
+#ifdef SMX_FA_STACK_TAIL_HALVES
+        fast_stacked_tail_halves<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
+#else
+        fast_stacked_tail<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active);
+#endif
         return;
     }
     if (ARGB) {            // byte-packed indices -> one register per row (the march's registers are free now)
@@ -884,7 +1139,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
 #pragma unroll
         for (int o = 0; o < TH; ++o) arg[o] = (packed[o >> 2] >> (8 * (o & 3))) & 0xff;
     }
-    float *mrg = (float *)(bits + NW * BW) + NW * FA_XCH_FLOATS;   // [NW][MR][64][2] (DSPLIT)
+    float *mrg = (float *)(bits + NW * NT * BW) + NW * FA_XCH_FLOATS;   // [NW][MR][64][2] (DSPLIT)
     if constexpr (DSPLIT && DENSE) {
         // Latency shape, dense form (single right-tile chunk: wave k marched the disparities [k q4, (k+1) q4) and holds, per
         // row, its winner with both neighbours, the first and the last cost of its share).  The slices are merged in

@@ -3,8 +3,8 @@
 //
 // Register budget.  A workgroup's 68.6 KB tile fits a CU twice, so every SIMD holds two of this kernel's waves.  Step 6 of
 // the other stream lane (k_refine_auto_v<2>: 117 registers, allocated in blocks of 8 as 120) has to fit beside them in the
-// 512 registers of a SIMD: 2 x 192 + 120 = 504.  The kernel takes 186 (K <= 2, box sums from prefix sums) / 179 (K = 4) /
-// 184 (K = 8) registers (profiles/r06_kernel_resources.txt), allocated as 192 at most, and is held to 192 (amdgpu_num_vgpr
+// 512 registers of a SIMD: 2 x 192 + 120 = 504.  The kernel takes 182 (K <= 2, box sums from prefix sums) / 184 (K = 4) /
+// 188 (K = 8) registers (profiles/r08_kernel_resources.txt), allocated as 192 at most, and is held to 192 (amdgpu_num_vgpr
 // through SMX_FA_NUM_VGPR).
 // The march of 72 row steps only stays in registers when it is fully unrolled (build.py: PER_FILE_FLAGS); build.py
 // refuses this unit if an instantiation reports scratch or a spill.

@@ -45,13 +45,7 @@ inline int exact_split(int tiles, int n, int Dd, int cus) {
     const long slots = 2L * cus, wgs = (long)tiles * n;
     int best = 1;
     long best_cost = ((wgs + slots - 1) / slots) * Dd;
-#ifndef SMX_E2_MIN_PER
-#define SMX_E2_MIN_PER 8
-#endif
-#ifndef SMX_E2_MAX_SPLIT
-#define SMX_E2_MAX_SPLIT 8
-#endif
-    for (int sp = 2; sp <= SMX_E2_MAX_SPLIT && Dd / sp >= SMX_E2_MIN_PER; ++sp) {
+    for (int sp = 2; sp <= 8 && Dd / sp >= 8; ++sp) {      // at most 8 slices of at least 8 disparities
         const long per = (Dd + sp - 1) / sp;
         const long cost = ((wgs * sp + slots - 1) / slots) * per + 2;
         if (cost < best_cost) { best_cost = cost; best = sp; }
@@ -112,14 +106,11 @@ __device__ __forceinline__ void e2_pin(float (&a)[NR][2]) {
 // similarity value is -0).  A thread owns E2_IR rows x 4 columns of the slice per step: (E2_IR+2) x 6
 // staged left/right values give the similarity values shared by its 4*E2_IR sums (12 VALU
 // operations and 4 LDS floats per element at E2_IR = 6, instead of 21 and 12 one by one), 128-bit LDS reads (see e2_load_item), and the reads of step it+1 are issued before the arithmetic of step it.
-#ifndef SMX_E2_IR
-#define SMX_E2_IR 6
-#endif
 constexpr int E2_IC = 4;
 constexpr int E2_NIC = E2_CCOLS / E2_IC;                    // 37 items per slice row block
 // rows per phase-A item: 6 for 256 threads (222 items), 3 for 512 threads (444 items): one item per thread either way
 template <int NR> struct E2A {
-    static constexpr int IR = NR == 2 ? 3 : SMX_E2_IR;
+    static constexpr int IR = NR == 2 ? 3 : 6;
     static constexpr int ITEMS = (E2_CROWS / IR) * E2_NIC;
     static constexpr int ITERS = (ITEMS + E2K<NR>::THREADS - 1) / E2K<NR>::THREADS;
     static_assert(E2_CCOLS % E2_IC == 0 && E2_CROWS % IR == 0, "slice must tile into items");
@@ -384,14 +375,12 @@ __device__ __forceinline__ void match_exact2_body(const MatchParams &p, int tile
         for (int dd = 0; dd < nd; ++dd) {
             const int d = d0 + dd;
             const int roff = nd - 1 - dd;
-#ifndef SMX_EXP_E2_NOA
             switch (roff & 3) {
             case 0: e2_phase_a<0, E2_NR>(Lt, Rt, CVt, rpitch, roff, tid); break;
             case 1: e2_phase_a<1, E2_NR>(Lt, Rt, CVt, rpitch, roff, tid); break;
             case 2: e2_phase_a<2, E2_NR>(Lt, Rt, CVt, rpitch, roff, tid); break;
             default: e2_phase_a<3, E2_NR>(Lt, Rt, CVt, rpitch, roff, tid); break;
             }
-#endif
             __syncthreads();
 
             float aggv[E2_NR][2];

@@ -55,24 +55,12 @@ namespace smx {
 
 constexpr int FA_HALO = 11;                 // large radius 10 + ncc radius 1
 constexpr int FA_VALID = 64 - 2 * FA_HALO;  // 42 output columns per wave
-#ifndef SMX_FA_WAVES
-#define SMX_FA_WAVES 4
-#endif
-constexpr int FA_WAVES = SMX_FA_WAVES;      // waves (column windows) per workgroup
-#ifndef SMX_FA_DS_WAVES
-#define SMX_FA_DS_WAVES 8
-#endif
+constexpr int FA_WAVES = 4;                 // waves (column windows) per workgroup
 // waves of a disparity-split workgroup (latency variant: all waves work on ONE window, a share of the disparity
 // range each).  8 instead of 4: 56.9 -> 51.6 us per C2 pair, 35.5 -> 30.6 us at C1 (tools/latency_fastgrid.py)
-constexpr int FA_DS_WAVES = SMX_FA_DS_WAVES;
-#ifndef SMX_FA_TH
-#define SMX_FA_TH 24
-#endif
-constexpr int FA_TH = SMX_FA_TH;            // output rows per wave band (throughput)
-#ifndef SMX_FA_TH_SMALL
-#define SMX_FA_TH_SMALL 8
-#endif
-constexpr int FA_TH_SMALL = SMX_FA_TH_SMALL;  // ... when only a few pairs are in flight (latency)
+constexpr int FA_DS_WAVES = 8;
+constexpr int FA_TH = 24;                   // output rows per wave band (throughput)
+constexpr int FA_TH_SMALL = 8;              // ... when only a few pairs are in flight (latency)
 // ... and the taller latency shape: when the 8-row bands of a call make more than one but fewer than two workgroups per CU,
 // the CUs that get two decide the duration; 12-row bands that fit one workgroup per CU (compiled for 2 waves per SIMD: no
 // register limit to fight) are faster -- a C2 pair 49.4 -> 44.1 us, C5's shape 58.2 -> 50.9, 384x1280 42.0 -> 39.6
@@ -82,34 +70,20 @@ constexpr int FA_TH_SMALL_TALL = 12;
 // of workgroups: a 2160p pair at K = 4 (23 windows x 68 bands = 1,564 workgroups = 3.05 rounds of 512 at 8 rows,
 // 1,242 = 2.4 rounds at 10) 156 -> 141 us.  Not for the arg-max-only form (min_disparity > 0), which spills 36 registers there.
 constexpr int FA_TH_SMALL_MID = 10;
-#ifndef SMX_FA_PF
-#define SMX_FA_PF 2
-#endif
-constexpr int FA_PF = SMX_FA_PF;            // row steps between issuing an LDS read and using it
-#ifndef SMX_FA_SB_PERIOD
-#define SMX_FA_SB_PERIOD 2
-#endif
+constexpr int FA_PF = 2;                    // row steps between issuing an LDS read and using it
+constexpr int FA_SB_PERIOD = 2;             // row steps between two scheduling barriers of a march
 #ifndef SMX_FA_OCC
-#define SMX_FA_OCC 3
+#define SMX_FA_OCC 3                // waves per SIMD the throughput-shape kernels are compiled for (tu_fast_stack.hip: 2)
 #endif
-#ifndef SMX_FA_DS_OCC
-#define SMX_FA_DS_OCC 4             // waves per SIMD the latency-shape kernels are compiled for (128 registers)
-#endif
+constexpr int FA_DS_OCC = 4;                // waves per SIMD the latency-shape kernels are compiled for (128 registers)
 constexpr int FA_WGCOLS = FA_VALID * FA_WAVES + 2 * FA_HALO;   // 190 staged left columns
-#ifndef SMX_FA_WIDE_FROM
-#define SMX_FA_WIDE_FROM (256 - FA_WGCOLS + 1)
-#endif
 // disparity ranges above this take the pitch-320 right tile (131 disparities per chunk) instead of chunks of 67 at pitch 256
-constexpr int FA_WIDE_FROM = SMX_FA_WIDE_FROM;
+constexpr int FA_WIDE_FROM = 256 - FA_WGCOLS + 1;
 // ... and between the two, for the throughput shape: pitch 288 holds 99 disparities in one chunk, and a 27-row band of it still
 // fits three times into a CU's LDS (53.4 KB; at pitch 320 only 24-row bands do): 7 % fewer marched rows for ranges of
 // 68 .. 99 pooled disparities -- C5's 96 and the 95 of the reference's default range at K = 2
 constexpr int FA_MID_PITCH = 288;
-#ifdef SMX_FA_NO_MID_PITCH
-constexpr int FA_MID_UPTO = 0;                                  // (A/B runs: never)
-#else
 constexpr int FA_MID_UPTO = FA_MID_PITCH - FA_WGCOLS + 1;      // 99
-#endif
 constexpr int FA_PL = (FA_VALID * FA_WAVES + 2 * FA_HALO + 7) & ~7;   // LDS row pitch of the left tile (u16 elements): 192
 constexpr int FA_BITWORDS = 64;             // the sparse pass keeps a needed set for up to 64 * 32 = 2048 disparities
 // Per-wave "who needs disparity d" table of the sparse pass: ONE WORD PER DISPARITY whose bit o says that some pixel of
@@ -145,13 +119,10 @@ __host__ __device__ inline int fast_bitwords(int Dd) {
 
 constexpr int FA_DENSE_MAX_TH = 27;         // the dense form keeps 4 more registers per band row: 237 of the 256 two waves per SIMD leave at 27 rows
 constexpr int FA_XROW = 64 + 12;            // exchange row: 64 lanes + 6 entries of slack on either side
-#ifndef SMX_FA_XCH_ROWS
-#define SMX_FA_XCH_ROWS 2
-#endif
-// per-wave exchange buffer: rows of 64-bit entries (2 disparities each).  SMX_FA_XCH_ROWS = 2: one row for the R3 exchange
-// and one for the R9 exchange; 1: both exchanges go through the same row -- LDS executes a wave's operations in order, so
-// the R9 store cannot overtake the R3 loads issued before it (2.4 KB less LDS per workgroup: 32-row bands fit three times)
-constexpr int FA_XCH_ROWS = SMX_FA_XCH_ROWS;
+// per-wave exchange buffer: rows of 64-bit entries (2 disparities each), one row for the R3 exchange and one for the R9
+// exchange.  (A kernel may send both through the same row, fast_xch_rows: LDS executes a wave's operations in order, so the
+// R9 store cannot overtake the R3 loads issued before it.)
+constexpr int FA_XCH_ROWS = 2;
 constexpr int FA_XCH_FLOATS = 2 * FA_XCH_ROWS * FA_XROW;
 
 // PR = LDS row pitch of the right tile; ND = disparities per staged right tile (PR >= 190 + ND - 1)
@@ -169,40 +140,29 @@ __host__ __device__ constexpr bool fast_prefix_exact(int th, int k_max) {
 // Which instantiations take the prefix form: K <= 2 (PK16 == 2) only, and there by what the compiler reports for each
 // (profiles/r06_kernel_resources.txt: same waves-per-SIMD class, no more spills or scratch than the sliding form).  The
 // 8- and 10-row latency shapes cross 128 registers or gain a spill and keep the sliding sums; k_match_capture.h never asks.
-// SMX_FA_NO_PREFIX (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the sliding form everywhere.
 __host__ __device__ constexpr bool fast_prefix_form(int th, int pr, bool p1only, bool dsplit, int pk16, bool argb, bool dense) {
-#ifdef SMX_FA_NO_PREFIX
-    return false;
-#else
     if (pk16 != 2 || !fast_prefix_exact(th, 2)) return false;
     if (dsplit) return th == FA_TH_SMALL_TALL;
     (void)pr; (void)p1only; (void)argb; (void)dense;
     return true;
-#endif
 }
 
 // Needed-set tables of a wave: one, or one per unit band of the stacked bands (th > 32: fast_stacked_tail fills both before
-// it marches).  SMX_FA_STACK_TAIL_HALVES (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the tail that finishes one
-// unit band after the other on one table.
-__host__ __device__ constexpr int fast_tables(int th) {
-#ifdef SMX_FA_STACK_TAIL_HALVES
-    (void)th;
-    return 1;
-#else
-    return th > 32 ? 2 : 1;
-#endif
-}
+// it marches).
+__host__ __device__ constexpr int fast_tables(int th) { return th > 32 ? 2 : 1; }
 // The second table takes the place of the second exchange row: a kernel with two tables sends both exchanges of a row step
-// through ONE per-wave row (what SMX_FA_XCH_ROWS = 1 does for every kernel; measured equal in round 4,
-// profiles/r04_match_fast_candidates.txt), so the workgroup's LDS -- fast_lds_bytes, the tile that fits a CU exactly twice --
-// stays what it was: 2 tables of at most 68 words are 272 bytes more per wave, an exchange row is 608.
+// through ONE per-wave row (measured equal for every kernel in round 4, profiles/r04_match_fast_candidates.txt), so the
+// workgroup's LDS -- fast_lds_bytes, the tile that fits a CU exactly twice -- stays what it was: 2 tables of at most 68 words are 272 bytes more per wave, an exchange row is 608.
 __host__ __device__ constexpr int fast_xch_rows(int th) { return fast_tables(th) > 1 ? 1 : FA_XCH_ROWS; }
 
-template <int PR> inline size_t fast_lds_bytes(int th, int Dd, bool dsplit = false) {
+inline size_t fast_lds_bytes_at(int pr, int th, int Dd, bool dsplit = false) {
     const size_t nw = dsplit ? FA_DS_WAVES : FA_WAVES;
-    return (size_t)(th + 22) * (FA_PL + PR) * sizeof(unsigned short) + nw * fast_bitwords(Dd) * sizeof(unsigned) +
+    return (size_t)(th + 22) * (FA_PL + pr) * sizeof(unsigned short) + nw * fast_bitwords(Dd) * sizeof(unsigned) +
            nw * FA_XCH_FLOATS * sizeof(float) + (dsplit ? nw * fast_merge_rows(th) * 64 * 2 * sizeof(float) : 0);
 }
+template <int PR> inline size_t fast_lds_bytes(int th, int Dd, bool dsplit = false) { return fast_lds_bytes_at(PR, th, Dd, dsplit); }
+// ... as a CU allocates them: in granules of 1,280 bytes
+inline size_t fast_lds_alloc(size_t bytes) { return (bytes + 1279) / 1280 * 1280; }
 
 __device__ __forceinline__ float dpp_shr1(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
@@ -281,7 +241,7 @@ __device__ __forceinline__ void fast_stage(unsigned short *tile, int pitch, cons
 // a lane moves FOUR columns per row -- one 8-byte load from a 2-byte-aligned address and one aligned ds_write_b64.  Lane l
 // covers tile columns 4l .. 4l+3 (group k of NK: + 256 k, tiles wider than 256 columns); its source column wraps once per
 // tile, and the plane's cyclic apron of three (smx_common.h: unit_plane_pitch) keeps the four columns inside the row.
-// Wave wv of NW takes rows wv, wv+NW, ... with a wave-uniform incremental wrap; SMX_FA_STAGE_LOADS loads (NB rows) are issued
+// Wave wv of NW takes rows wv, wv+NW, ... with a wave-uniform incremental wrap; FA_STAGE_LOADS loads (NB rows) are issued
 // before the first LDS store -- of both tiles when the left one comes along (WITH_LEFT: first chunk; same rows, one barrier
 // pair) -- so a 70-row tile pair costs a wave five memory round trips instead of one per two rows.  A row's columns cols ..
 // round_up(cols, 4) - 1 receive what was loaded: tile pitches are multiples of 8 >= cols, and the marches read tile columns
@@ -289,23 +249,15 @@ __device__ __forceinline__ void fast_stage(unsigned short *tile, int pitch, cons
 // Which instantiations stage from the unit planes: all but those that would gain a spilled register by the compiler's report
 // (profiles/r07_kernel_resources.txt) -- the 10-row latency shape, which sits at its 128 registers, and the pitch-320 bands
 // with one register per winner (more than 256 disparities), which sit at their 168; they keep the f32 form, like the filter.
-// SMX_FA_STAGE_F32 (build.py --variant with SMX_EXTRA_FLAGS): A/B builds, the f32 form everywhere.
 __host__ __device__ constexpr bool fast_units_form(int th, int pr, bool dsplit, bool argb) {
-#ifdef SMX_FA_STAGE_F32
-    (void)th; (void)pr; (void)dsplit; (void)argb;
-    return false;
-#else
     return dsplit ? th != FA_TH_SMALL_MID : (pr != 320 || argb);
-#endif
 }
-#ifndef SMX_FA_STAGE_LOADS
-#define SMX_FA_STAGE_LOADS 8             // 8-byte loads of a batch: 16 registers
-#endif
+constexpr int FA_STAGE_LOADS = 8;        // 8-byte loads of a batch: 16 registers
 template <int NK, int NW, bool WITH_LEFT>
 __device__ __forceinline__ void fast_stage_units(unsigned short *tile, int pitch, const unsigned short *img, int col0, int cols,
                                                  unsigned short *ltile, const unsigned short *limg, int lcol0, int lcols,
                                                  int h, int w, int upitch, int row0, int rows, int wv, int lane) {
-    constexpr int NB = SMX_FA_STAGE_LOADS / (NK + (WITH_LEFT ? 1 : 0));      // rows per batch
+    constexpr int NB = FA_STAGE_LOADS / (NK + (WITH_LEFT ? 1 : 0));      // rows per batch
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     unsigned coff[NK], lcoff = 0u;                    // byte offset of the lane's source column in a plane row
     bool in[NK], lin = false;
@@ -443,10 +395,6 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
     f32x2 vs = {0.f, 0.f}, cs = {0.f, 0.f}, hs = {0.f, 0.f};
     f32x2 t_m3 = {0.f, 0.f}, t_p3 = {0.f, 0.f}, u_m6 = {0.f, 0.f}, u_p6 = {0.f, 0.f};   // pending exchanges
     const int lane_ = threadIdx.x & 63;
-#ifdef SMX_FA_ARGMAX2
-    int dva = d, dvb = d + 1;                // the two indices of this march in vector registers (byte-select operands of argb_update)
-    if (ARGB && MODE == 0) asm volatile("" : "+v"(dva), "+v"(dvb));
-#endif
     const unsigned short *rptr_b = (MODE == 0 || MODE == 3) ? ln.rptr - (valid_b ? 1 : 0) : rptr_b_in;   // MODE 4: any sampled disparity
     (void)db;
 #pragma unroll
@@ -501,10 +449,6 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                 // ds_read_b64 for both disparities (ds_bpermute costs ~3x on the shared LDS pipe).
                 // LDS executes a wave's operations in order, so no barrier is needed; the results
                 // are consumed one row step later.
-#ifdef SMX_EXP_NOXCH
-                if (q >= Q9 - 1 && q + 1 < NQ) { t_m3 = r3[q - 5]; t_p3 = r3[q - 4]; }
-                if (q >= Q21 - 1 && q + 1 < NQ) { u_m6 = r9[q - 8]; u_p6 = r9[q - 7]; }
-#else
                 if (q >= Q9 - 1 && q + 1 < NQ) {
                     f32x2 *x3b = (f32x2 *)ln.xch + lane_;          // entry (lane - 6) of the padded row
                     x3b[6] = r3[q - 5];
@@ -524,7 +468,6 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                         u_m6 = xr[0]; u_p6 = xr[12];
                     }
                 }
-#endif
                 if (PREFIX) {                                    // box sums as differences of prefixes: temporaries of the row
                     if (q >= 20) {
                         vs = q >= 21 ? r3[q] - r3[q - 21] : r3[q];
@@ -618,13 +561,11 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                             dcp[o] = agg.y;
                             if (dfirst) dfirst[o] = agg.x;      // (wave-uniform: only the first march of a wave's share passes the array)
                         }
-#if !defined(SMX_FA_ARGMAX2)
                         // running arg-max over (d, d+1) in 5 operations: the new best is max3; it
                         // changed iff one of the two beat the old one (strict '>'), and then d wins
                         // iff agg.x attains it (first maximum).  All costs are finite and >= +0.
                         const float m = __builtin_fmaxf(__builtin_fmaxf(best[o], agg.x), agg.y);
                         const int dsel = (agg.x == m) ? d : d + 1;
-#ifndef SMX_EXP_NOARG
                         if (ARGB) {
                             // (measured: skipping the three update instructions of a row step in which no lane improves,
                             //  behind a wave-uniform branch, costs more than it saves: 0.662 against 0.630 ms per 64 pairs)
@@ -633,9 +574,6 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                             const bool changed = m > best[o];
                             arg[o] = changed ? dsel : arg[o];
                         }
-#else
-                        (void)dsel;                                // timing experiment only (wrong results)
-#endif
                         best[o] = m;
                         // Measured in round 6 and not adopted (profiles/r06_prefix_sums.txt): the in-place form for the stacked
                         // bands -- t = v_max_f32(agg.x, agg.y), compare and byte update against the old best, then
@@ -645,25 +583,12 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
                         // kernel) at 186 registers all the same, for 96 v_max_f32 instead of 48 v_max3_f32: `value` 99,964 /
                         // 100,177 / 100,177 without it, 99,814 / 99,538 / 100,370 with it -- nothing.  Applied to every
                         // instantiation it adds 5 - 10 spilled registers to the pitch-320 one-register-per-winner bands.
-#else
-                        // Measured in round 4 and not adopted (SMX_FA_ARGMAX2, profiles/r04_match_fast_candidates.txt): the
-                        // reference's loop body twice -- compare, conditional index update, v_max_f32 per disparity.  Six
-                        // instructions instead of five, but two of them fp32 VOP2 (2.7 clocks against 5.1 for v_max3_f32 in
-                        // the issue-rate benchmark): 14.9 against 19.3 clocks per row on paper, 0.613 - 0.617 against
-                        // 0.617 - 0.627 ms per 64 pairs in the kernel (within the run-to-run spread) and no gain in the
-                        // pipelined rate -- the two dependent compare/update/max steps per row lengthen the chain.
-                        if (ARGB) {
-                            argb_update(o & 3, arg[o >> 2], agg.x, best[o], dva);
-                            best[o] = __builtin_fmaxf(best[o], agg.x);
-                            argb_update(o & 3, arg[o >> 2], agg.y, best[o], dvb);
-                            best[o] = __builtin_fmaxf(best[o], agg.y);
-                        } else {
-                            const float m = __builtin_fmaxf(__builtin_fmaxf(best[o], agg.x), agg.y);
-                            const int dsel = (agg.x == m) ? d : d + 1;
-                            arg[o] = m > best[o] ? dsel : arg[o];
-                            best[o] = m;
-                        }
-#endif
+                        // Measured in round 4 and not adopted (profiles/r04_match_fast_candidates.txt): the reference's loop
+                        // body twice -- compare, conditional index update, v_max_f32 per disparity.  Six instructions instead of
+                        // five, but two of them fp32 VOP2 (2.7 clocks against 5.1 for v_max3_f32 in the issue-rate benchmark):
+                        // 14.9 against 19.3 clocks per row on paper, 0.613 - 0.617 against 0.617 - 0.627 ms per 64 pairs in the
+                        // kernel (within the run-to-run spread) and no gain in the pipelined rate -- the two dependent
+                        // compare/update/max steps per row lengthen the chain.
                     }
                 }
             }
@@ -672,10 +597,16 @@ __device__ __forceinline__ void fast_pass_pair(const MatchParams &p, const FastL
             k2 = k1;
             k1 = k0;
         }
-        if ((rr_ % SMX_FA_SB_PERIOD) == SMX_FA_SB_PERIOD - 1)
+        if ((rr_ % FA_SB_PERIOD) == FA_SB_PERIOD - 1)
             __builtin_amdgcn_sched_barrier(0);   // keep the unrolled row steps in order: bounded live ranges
     }
 }
+
+// The neighbours of disparity d on the cyclic axis: the reference's pad_index(d - 1, Dd) and pad_index(d + 1, Dd), d in [0, Dd).
+// (Used where the winners are marked.  The marches' argument lists keep the expressions written out: with a call in their
+// place the compiler orders the scalar selects differently and the kernels are no longer the same code, NOTES.md Round 9.)
+__host__ __device__ __forceinline__ constexpr int pad_index_before(int d, int Dd) { return d == 0 ? Dd - 1 : d - 1; }
+__host__ __device__ __forceinline__ constexpr int pad_index_after(int d, int Dd) { return d + 1 == Dd ? 0 : d + 1; }
 
 // The sparse form's report: a relaxed device-scope 64-bit add WITHOUT return (fire and forget: nothing waits for it) to one
 // counter of the stream lane -- [marches of the second pass : 40][windows : 24] -- from a SAMPLE of the launch (same-address
@@ -699,96 +630,6 @@ __device__ __forceinline__ void fast_stats_report(const MatchParams &p, int b, i
 // from a band in its tile rows (hh * TU further down), its image rows and its slice of best / arg.  Each unit band that
 // holds image rows counts as one window in the report.
 //
-// This form (SMX_FA_STACK_TAIL_HALVES, A/B builds only) also runs the second pass once per unit band: a table, a walk and
-// marches of TU + 22 tile rows each, the wave's one table cleared in between -- a disparity that both unit bands need is
-// marched over 2 x (TU + 22) rows where the TU * NH + 22 staged ones hold everything.
-template <int TU, int NH, int PR, int PK16, bool PREFIX, class StageRight>
-__device__ __forceinline__ void fast_stacked_tail_halves(const MatchParams &p, const BlockIdx3 &blk, const FastLane &ln, const float (&best)[TU * NH],
-                                                         const int (&argb)[TU * NH], const unsigned short *Rt, unsigned *bits, int wcol, int x0,
-                                                         bool active, StageRight &&stage_right) {
-    constexpr int ND = PR - FA_WGCOLS + 1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int h = p.h, w = p.w, Dd = p.Dd, BW = fast_bitwords(Dd);
-    const bool all_needed = Dd > FA_BITWORDS * 32;
-    unsigned *wbits = bits + wv * BW;
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-        float bh[TU];
-        int ah[TU];
-#pragma unroll
-        for (int o = 0; o < TU; ++o) {
-            bh[o] = best[hh * TU + o];
-            ah[o] = (argb[(hh * TU + o) >> 2] >> (8 * ((hh * TU + o) & 3))) & 0xff;      // byte-packed indices -> one register per row
-        }
-        FastLane lh = ln;
-        lh.lptr = ln.lptr + hh * TU * FA_PL;
-        lh.row0 = ln.row0 + (size_t)(hh * TU) * w;
-        lh.rows_ok = max(0, min(TU, h - x0 - hh * TU));
-        const unsigned short *Rh = Rt + hh * TU * PR;                 // the unit band's first tile row
-        unsigned dup_left = 0u;
-#ifndef SMX_FA_NO_DEDUP
-        if (!all_needed) {
-#pragma unroll
-            for (int o = 0; o < TU; ++o) {
-                const int la = __builtin_amdgcn_update_dpp(-1, ah[o], 0x138, 0xf, 0xf, false);
-                dup_left |= (la == ah[o] ? 1u : 0u) << o;
-            }
-            const int left_ok = __builtin_amdgcn_update_dpp(0, lh.store_ok ? 1 : 0, 0x138, 0xf, 0xf, false);
-            if (!left_ok) dup_left = 0u;
-        }
-#endif
-        if (lh.store_ok) {
-#pragma unroll
-            for (int o = 0; o < TU; ++o) {
-                if (o < lh.rows_ok) {
-                    const unsigned off = (unsigned)(o * w + lh.colidx);
-                    store_u32off(p.wta + lh.row0, off, (float)ah[o] + (float)p.dmin);
-                    const bool nv = !(bh[o] > SMX_FLT_MIN);
-                    store_u32off(p.costs + lh.row0, off, nv ? 0.0f : bh[o] * lh.inv);
-                    if (!all_needed && !((dup_left >> o) & 1u)) {
-                        const int dn = (ah[o] + 1 == Dd) ? 0 : ah[o] + 1;
-                        const int dp = (ah[o] == 0) ? Dd - 1 : ah[o] - 1;
-                        atomicOr(&wbits[dn], 1u << o);
-                        atomicOr(&wbits[dp], 1u << o);
-                    }
-                }
-            }
-        }
-        int marches2 = 0;
-        unsigned argpk[(TU + 1) / 2];
-#pragma unroll
-        for (int o = 0; o < (TU + 1) / 2; ++o) argpk[o] = 0u;
-#pragma unroll
-        for (int o = 0; o < TU; ++o)
-            argpk[o >> 1] |= ((lh.store_ok && o < lh.rows_ok) ? (unsigned)ah[o] : 0xffffu) << (16 * (o & 1));
-        for (int d0 = 0; d0 < Dd; d0 += ND) {
-            const int nd = min(ND, Dd - d0);
-            if (Dd > ND) stage_right(d0, nd);
-            else __syncthreads();
-            if (active) {
-                auto march = [&](int dda, int ddb, unsigned rows) {
-                    const int da = d0 + dda, db = d0 + ddb;
-                    ++marches2;
-                    lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
-                    fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX>(p, lh, da, false, bh, ah, Rh + wcol + lane + (nd - 1 - ddb), db, argpk,
-                                                           da == 0 ? Dd - 1 : da - 1, da + 1 == Dd ? 0 : da + 1,
-                                                           db == 0 ? Dd - 1 : db - 1, db + 1 == Dd ? 0 : db + 1, nullptr, nullptr, rows);
-                };
-                int pend = -1;
-                unsigned pend_rows = 0u;
-                SMX_FOR_EACH_NEEDED(wbits + d0, 0, nd, all_needed, lane, dd, rows, {
-                    if (pend < 0) { pend = dd; pend_rows = rows; }
-                    else { march(pend, dd, pend_rows | rows); pend = -1; }
-                })
-                if (pend >= 0) march(pend, pend, pend_rows);
-            }
-        }
-        if (lane == 0) fast_stats_report<false>(p, blk.z, (int)(blk.x + gridDim.x * blk.y), wv, marches2, active && lh.rows_ok > 0);
-        if (hh + 1 < NH)
-            for (int e = lane; e < BW; e += 64) wbits[e] = 0u;
-    }
-}
-
 // The second pass of the stacked bands, both unit bands at once.  A needed disparity of a wave's window is read by pixels of
 // both unit bands, of the upper one only or of the lower one only.  Two of a class share a march: "both" pairs march the
 // whole staged tile (2 TU + 22 rows, MODE 1 of the TH = 2 TU march with a row mask of 2 TU bits), "upper" and "lower" pairs
@@ -816,7 +657,8 @@ __host__ __device__ constexpr long fast_tail_rows(int nb, int nu, int nl, int tu
     return (long)(nb / 2) * (2 * tu + 22) + (long)(nu / 2 + nl / 2) * (tu + 22) +
            fast_tail_leftover_rows(fast_tail_leftover(nb & 1, nu & 1, nl & 1), tu);
 }
-// ... by the per-band tail (fast_stacked_tail_halves)
+// ... by a second pass that finishes one unit band after the other, H rows a march (host-side model only: what
+// tests/test_stacked_tail_cpu.py holds fast_tail_rows against)
 __host__ __device__ constexpr long fast_tail_rows_halves(int nb, int nu, int nl, int tu) {
     return (long)((nb + nu + 1) / 2 + (nb + nl + 1) / 2) * (tu + 22);
 }
@@ -856,7 +698,6 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
         lh.rows_ok = max(0, min(TU, h - x0 - hh * TU));
         unsigned *hbits = wbits + hh * BW;
         unsigned dup_left = 0u;
-#ifndef SMX_FA_NO_DEDUP
         if (!all_needed) {
 #pragma unroll
             for (int o = 0; o < TU; ++o) {
@@ -866,7 +707,6 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
             const int left_ok = __builtin_amdgcn_update_dpp(0, lh.store_ok ? 1 : 0, 0x138, 0xf, 0xf, false);
             if (!left_ok) dup_left = 0u;
         }
-#endif
         if (lh.store_ok) {
 #pragma unroll
             for (int o = 0; o < TU; ++o) {
@@ -876,8 +716,7 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
                     const bool nv = !(bh[o] > SMX_FLT_MIN);
                     store_u32off(p.costs + lh.row0, off, nv ? 0.0f : bh[o] * lh.inv);
                     if (!all_needed && !((dup_left >> o) & 1u)) {
-                        const int dn = (ah[o] + 1 == Dd) ? 0 : ah[o] + 1;
-                        const int dp = (ah[o] == 0) ? Dd - 1 : ah[o] - 1;
+                        const int dn = pad_index_after(ah[o], Dd), dp = pad_index_before(ah[o], Dd);
                         atomicOr(&hbits[dn], 1u << o);
                         atomicOr(&hbits[dp], 1u << o);
                     }
@@ -892,10 +731,6 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
     }
     // No workgroup barrier from here on: a wave reads its own marks only (LDS executes a wave's operations in order), and the
     // tile of pass 1 stays as it is -- the waves of a workgroup run their second passes independently.
-    // (SMX_FA_STACK_TAIL_BARRIER, A/B builds only: the barrier the per-band tail has in front of each second pass.)
-#ifdef SMX_FA_STACK_TAIL_BARRIER
-    __syncthreads();
-#endif
     __builtin_amdgcn_wave_barrier();
     // The report, in front of the second pass (nothing waits for it, and neither the counter's address nor a count stays
     // live across the marches): per unit band that holds image rows one window, and its needed disparities two by two.
@@ -910,105 +745,102 @@ __device__ __forceinline__ void fast_stacked_tail(const MatchParams &p, const Bl
             if (lane == 0) fast_stats_report<false>(p, blk.z, (int)(blk.x + gridDim.x * blk.y), wv, (n + 1) / 2, h - x0 - hh * TU > 0);
         }
     }
-    {
-        if (active) {
-            enum { K_NONE, K_FULL, K_UPPER, K_LOWER };
-            const unsigned *tbl_u = wbits, *tbl_l = wbits + BW;
-            // A disparity of each class waiting for a partner (-1: none; P_B = -2: see FT_HALVES below) and the rows that
-            // read it, of the upper / the lower unit band.  Wave-uniform: seven scalars live across the marches.
-            enum { P_B, P_U, P_L, R_BU, R_BL, R_U, R_L };
-            int pst[7] = {-1, -1, -1, 0, 0, 0, 0};
-            auto pget = [&](int i) { return pst[i]; };
-            auto pset = [&](int i, int v) { pst[i] = v; };
-            int g = -64;                                     // first word of the 64 the lanes hold
-            unsigned word_u = 0u, word_l = 0u;
-            unsigned long long m = 0ull;
-            for (;;) {
-                int kind = K_NONE, dda = 0, ddb = 0;
-                unsigned r_u = 0u, r_l = 0u;                 // rows of the march: upper / lower unit band (a half march: its own in r_u)
-                const int pb = pget(P_B);
-                if (pb == -2) {                              // FT_HALVES: the lower march (both, lower) behind its upper one
-                    kind = K_LOWER; dda = pget(P_U); ddb = pget(P_L); r_u = (unsigned)pget(R_L);
-                    pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
-                } else if (m != 0ull) {
-                    const int k = __builtin_ctzll(m);
-                    m &= m - 1ull;
-                    const int dd = g + k;
-                    const unsigned ru = (unsigned)__builtin_amdgcn_readlane((int)word_u, k);
-                    const unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)word_l, k);
-                    if (ru != 0u && rl != 0u) {
-                        if (pb < 0) { pset(P_B, dd); pset(R_BU, (int)ru); pset(R_BL, (int)rl); }
-                        else { kind = K_FULL; dda = pb; ddb = dd; r_u = (unsigned)pget(R_BU) | ru; r_l = (unsigned)pget(R_BL) | rl; pset(P_B, -1); }
-                    } else if (ru != 0u) {
-                        const int pu = pget(P_U);
-                        if (pu < 0) { pset(P_U, dd); pset(R_U, (int)ru); }
-                        else { kind = K_UPPER; dda = pu; ddb = dd; r_u = (unsigned)pget(R_U) | ru; pset(P_U, -1); }
-                    } else {
-                        const int pl = pget(P_L);
-                        if (pl < 0) { pset(P_L, dd); pset(R_L, (int)rl); }
-                        else { kind = K_LOWER; dda = pl; ddb = dd; r_u = (unsigned)pget(R_L) | rl; pset(P_L, -1); }
-                    }
-                } else if (g + 64 < nd) {                    // the next 64 words of both tables: one LDS read each
-                    g += 64;
-                    const int idx = g + lane;
-                    word_u = 0u;
-                    word_l = 0u;
-                    if (idx < nd) {
-                        word_u = all_needed ? ~0u : tbl_u[idx];
-                        word_l = all_needed ? ~0u : tbl_l[idx];
-                    }
-                    m = __ballot((word_u | word_l) != 0u);
-                } else {                                     // the walk is over: the odd ones out (fast_tail_leftover)
-                    const int pu = pget(P_U), pl = pget(P_L);
-                    const int code = fast_tail_leftover(pb >= 0, pu >= 0, pl >= 0);
-                    if (code == FT_NONE) break;
-                    const unsigned pb_u = (unsigned)pget(R_BU), pb_l = (unsigned)pget(R_BL), pu_r = (unsigned)pget(R_U), pl_r = (unsigned)pget(R_L);
-                    if (code == FT_FULL_BB) { kind = K_FULL; dda = pb; ddb = pb; r_u = pb_u; r_l = pb_l; }
-                    else if (code == FT_FULL_BU) { kind = K_FULL; dda = pb; ddb = pu; r_u = pb_u | pu_r; r_l = pb_l; }
-                    else if (code == FT_FULL_BL) { kind = K_FULL; dda = pb; ddb = pl; r_u = pb_u; r_l = pb_l | pl_r; }
-                    else if (code == FT_FULL_UL) { kind = K_FULL; dda = pu; ddb = pl; r_u = pu_r; r_l = pl_r; }
-                    else if (code == FT_UPPER) { kind = K_UPPER; dda = pu; ddb = pu; r_u = pu_r; }
-                    else if (code == FT_LOWER) { kind = K_LOWER; dda = pl; ddb = pl; r_u = pl_r; }
-                    if (code == FT_HALVES) {                 // upper march (both, upper) now; (both, lower) waits in (P_U, P_L), P_B = -2
-                        kind = K_UPPER; dda = pb; ddb = pu; r_u = pb_u | pu_r;
-                        pset(R_L, (int)(pl_r | pb_l)); pset(P_U, pb); pset(P_B, -2);
-                    } else {
-                        pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
-                    }
-                }
-                if (kind == K_NONE) continue;
-                const int da = dda, db = ddb;
-                const int am_a = da == 0 ? Dd - 1 : da - 1, ap_a = da + 1 == Dd ? 0 : da + 1;
-                const int am_b = db == 0 ? Dd - 1 : db - 1, ap_b = db + 1 == Dd ? 0 : db + 1;
-                if (kind == K_FULL) {
-                    float bd[TH];                            // (best / arg: unused by MODE 1, the march's signature)
-                    int ad[TH];
+    if (!active) return;
+    enum { K_NONE, K_FULL, K_UPPER, K_LOWER };
+    const unsigned *tbl_u = wbits, *tbl_l = wbits + BW;
+    // A disparity of each class waiting for a partner (-1: none; P_B = -2: see FT_HALVES below) and the rows that
+    // read it, of the upper / the lower unit band.  Wave-uniform: seven scalars live across the marches.
+    enum { P_B, P_U, P_L, R_BU, R_BL, R_U, R_L };
+    int pst[7] = {-1, -1, -1, 0, 0, 0, 0};
+    auto pget = [&](int i) { return pst[i]; };
+    auto pset = [&](int i, int v) { pst[i] = v; };
+    int g = -64;                                     // first word of the 64 the lanes hold
+    unsigned word_u = 0u, word_l = 0u;
+    unsigned long long m = 0ull;
+    for (;;) {
+        int kind = K_NONE, dda = 0, ddb = 0;
+        unsigned r_u = 0u, r_l = 0u;                 // rows of the march: upper / lower unit band (a half march: its own in r_u)
+        const int pb = pget(P_B);
+        if (pb == -2) {                              // FT_HALVES: the lower march (both, lower) behind its upper one
+            kind = K_LOWER; dda = pget(P_U); ddb = pget(P_L); r_u = (unsigned)pget(R_L);
+            pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
+        } else if (m != 0ull) {
+            const int k = __builtin_ctzll(m);
+            m &= m - 1ull;
+            const int dd = g + k;
+            const unsigned ru = (unsigned)__builtin_amdgcn_readlane((int)word_u, k);
+            const unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)word_l, k);
+            if (ru != 0u && rl != 0u) {
+                if (pb < 0) { pset(P_B, dd); pset(R_BU, (int)ru); pset(R_BL, (int)rl); }
+                else { kind = K_FULL; dda = pb; ddb = dd; r_u = (unsigned)pget(R_BU) | ru; r_l = (unsigned)pget(R_BL) | rl; pset(P_B, -1); }
+            } else if (ru != 0u) {
+                const int pu = pget(P_U);
+                if (pu < 0) { pset(P_U, dd); pset(R_U, (int)ru); }
+                else { kind = K_UPPER; dda = pu; ddb = dd; r_u = (unsigned)pget(R_U) | ru; pset(P_U, -1); }
+            } else {
+                const int pl = pget(P_L);
+                if (pl < 0) { pset(P_L, dd); pset(R_L, (int)rl); }
+                else { kind = K_LOWER; dda = pl; ddb = dd; r_u = (unsigned)pget(R_L) | rl; pset(P_L, -1); }
+            }
+        } else if (g + 64 < nd) {                    // the next 64 words of both tables: one LDS read each
+            g += 64;
+            const int idx = g + lane;
+            word_u = 0u;
+            word_l = 0u;
+            if (idx < nd) {
+                word_u = all_needed ? ~0u : tbl_u[idx];
+                word_l = all_needed ? ~0u : tbl_l[idx];
+            }
+            m = __ballot((word_u | word_l) != 0u);
+        } else {                                     // the walk is over: the odd ones out (fast_tail_leftover)
+            const int pu = pget(P_U), pl = pget(P_L);
+            const int code = fast_tail_leftover(pb >= 0, pu >= 0, pl >= 0);
+            if (code == FT_NONE) break;
+            const unsigned pb_u = (unsigned)pget(R_BU), pb_l = (unsigned)pget(R_BL), pu_r = (unsigned)pget(R_U), pl_r = (unsigned)pget(R_L);
+            if (code == FT_FULL_BB) { kind = K_FULL; dda = pb; ddb = pb; r_u = pb_u; r_l = pb_l; }
+            else if (code == FT_FULL_BU) { kind = K_FULL; dda = pb; ddb = pu; r_u = pb_u | pu_r; r_l = pb_l; }
+            else if (code == FT_FULL_BL) { kind = K_FULL; dda = pb; ddb = pl; r_u = pb_u; r_l = pb_l | pl_r; }
+            else if (code == FT_FULL_UL) { kind = K_FULL; dda = pu; ddb = pl; r_u = pu_r; r_l = pl_r; }
+            else if (code == FT_UPPER) { kind = K_UPPER; dda = pu; ddb = pu; r_u = pu_r; }
+            else if (code == FT_LOWER) { kind = K_LOWER; dda = pl; ddb = pl; r_u = pl_r; }
+            if (code == FT_HALVES) {                 // upper march (both, upper) now; (both, lower) waits in (P_U, P_L), P_B = -2
+                kind = K_UPPER; dda = pb; ddb = pu; r_u = pb_u | pu_r;
+                pset(R_L, (int)(pl_r | pb_l)); pset(P_U, pb); pset(P_B, -2);
+            } else {
+                pset(P_B, -1); pset(P_U, -1); pset(P_L, -1);
+            }
+        }
+        if (kind == K_NONE) continue;
+        const int da = dda, db = ddb;
+        const int am_a = da == 0 ? Dd - 1 : da - 1, ap_a = da + 1 == Dd ? 0 : da + 1;
+        const int am_b = db == 0 ? Dd - 1 : db - 1, ap_b = db + 1 == Dd ? 0 : db + 1;
+        if (kind == K_FULL) {
+            float bd[TH];                            // (best / arg: unused by MODE 1, the march's signature)
+            int ad[TH];
 #pragma unroll
-                    for (int o = 0; o < TH; ++o) { bd[o] = 0.f; ad[o] = 0; }
-                    FastLane lf = ln;
-                    lf.rptr = Rt + wcol + lane + (nd - 1 - dda);
-                    fast_pass_pair<TH, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lf, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
-                                                                                 am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u | (r_l << TU), nullptr,
-                                                                                 nullptr, nullptr, nullptr, r_l >> (32 - TU));
-                } else {
-                    float bd[TU];
-                    int ad[TU];
+            for (int o = 0; o < TH; ++o) { bd[o] = 0.f; ad[o] = 0; }
+            FastLane lf = ln;
+            lf.rptr = Rt + wcol + lane + (nd - 1 - dda);
+            fast_pass_pair<TH, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lf, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
+                                                                         am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u | (r_l << TU), nullptr,
+                                                                         nullptr, nullptr, nullptr, r_l >> (32 - TU));
+        } else {
+            float bd[TU];
+            int ad[TU];
 #pragma unroll
-                    for (int o = 0; o < TU; ++o) { bd[o] = 0.f; ad[o] = 0; }
-                    FastLane lh = ln;
-                    if (kind == K_UPPER) {
-                        lh.rptr = Rt + wcol + lane + (nd - 1 - dda);
-                        fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
-                                                                                     am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
-                    } else {
-                        const unsigned short *Rh = Rt + TU * PR;      // the lower unit band's first tile row
-                        lh.lptr = ln.lptr + TU * FA_PL;
-                        lh.row0 = ln.row0 + (size_t)TU * w;
-                        lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
-                        fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rh + wcol + lane + (nd - 1 - ddb), db,
-                                                                                     argpk + TU / 2, am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
-                    }
-                }
+            for (int o = 0; o < TU; ++o) { bd[o] = 0.f; ad[o] = 0; }
+            FastLane lh = ln;
+            if (kind == K_UPPER) {
+                lh.rptr = Rt + wcol + lane + (nd - 1 - dda);
+                fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rt + wcol + lane + (nd - 1 - ddb), db, argpk,
+                                                                             am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
+            } else {
+                const unsigned short *Rh = Rt + TU * PR;      // the lower unit band's first tile row
+                lh.lptr = ln.lptr + TU * FA_PL;
+                lh.row0 = ln.row0 + (size_t)TU * w;
+                lh.rptr = Rh + wcol + lane + (nd - 1 - dda);
+                fast_pass_pair<TU, PR, false, PK16, 1, false, false, PREFIX, XR>(p, lh, da, false, bd, ad, Rh + wcol + lane + (nd - 1 - ddb), db,
+                                                                             argpk + TU / 2, am_a, ap_a, am_b, ap_b, nullptr, nullptr, r_u);
             }
         }
     }
@@ -1125,11 +957,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
         }
     }
     if constexpr (NH > 1) {
-#ifdef SMX_FA_STACK_TAIL_HALVES
-        fast_stacked_tail_halves<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active, stage_right);
-#else
         fast_stacked_tail<TU, NH, PR, PK16, PREFIX>(p, blk, ln, best, arg, Rt, bits, wcol, x0, active);
-#endif
         return;
     }
     if (ARGB) {            // byte-packed indices -> one register per row (the march's registers are free now)
@@ -1223,7 +1051,6 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
     // word serialise (54 atomics per lane x a 40-way conflict were ~5 % of the kernel).  Computed before the divergent
     // block below (DPP reads a neighbour's register only while that lane is enabled).
     unsigned dup_left = 0u;
-#ifndef SMX_FA_NO_DEDUP
     if (!DENSE && !P1ONLY && !all_needed) {
 #pragma unroll
         for (int o = 0; o < TH; ++o) {
@@ -1233,7 +1060,6 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
         const int left_ok = __builtin_amdgcn_update_dpp(0, ln.store_ok ? 1 : 0, 0x138, 0xf, 0xf, false);
         if (!left_ok) dup_left = 0u;           // the neighbour marks nothing (halo lane or beyond the image)
     }
-#endif
     if (ln.store_ok) {
         unsigned *wbits = bits + (DSPLIT ? 0 : wv) * BW;
 #pragma unroll
@@ -1258,8 +1084,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
                     }
                 } else
                 if (!P1ONLY && !all_needed && !((dup_left >> o) & 1u)) {
-                    const int dn = (arg[o] + 1 == Dd) ? 0 : arg[o] + 1;    // pad_index(Dd, Dd) = 0
-                    const int dp = (arg[o] == 0) ? Dd - 1 : arg[o] - 1;    // pad_index(-1, Dd) = Dd-1
+                    const int dn = pad_index_after(arg[o], Dd), dp = pad_index_before(arg[o], Dd);
                     atomicOr(&wbits[dn], 1u << o);                         // band row o reads AGG[dn] and AGG[dp]
                     atomicOr(&wbits[dp], 1u << o);
                 }
@@ -1295,7 +1120,6 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
             };
             int pend = -1;                       // a needed disparity waiting for a partner
             unsigned pend_rows = 0u;             // ... and the band rows that read it
-#ifndef SMX_EXP_NOPASS2
             if constexpr (DSPLIT) {
                 // the waves of the workgroup share ONE window: they take the needed disparities pair by pair in turn (by rank,
                 // not by sub-range -- on a slanted surface the needed disparities sit in one or two of the eight sub-ranges and
@@ -1317,7 +1141,6 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
                     else { march(pend, dd, pend_rows | rows); pend = -1; }
                 })
             }
-#endif
             if (pend >= 0) march(pend, pend, pend_rows);    // odd count: both pipelines march the last one
         }
     }
@@ -1333,7 +1156,7 @@ __device__ __forceinline__ void match_fast_body(const MatchParams &p, const Bloc
 #define SMX_FA_VGPR_ATTR
 #endif
 template <int TH, int PR, bool P1ONLY, bool DSPLIT, int PK16, bool ARGB, bool DENSE = false>
-__global__ __launch_bounds__(64 * (DSPLIT ? FA_DS_WAVES : FA_WAVES), DENSE ? 2 : (DSPLIT ? (TH >= FA_TH_SMALL_TALL ? 2 : SMX_FA_DS_OCC) : SMX_FA_OCC)) SMX_FA_VGPR_ATTR void k_match_fast(MatchParams p) {
+__global__ __launch_bounds__(64 * (DSPLIT ? FA_DS_WAVES : FA_WAVES), DENSE ? 2 : (DSPLIT ? (TH >= FA_TH_SMALL_TALL ? 2 : FA_DS_OCC) : SMX_FA_OCC)) SMX_FA_VGPR_ATTR void k_match_fast(MatchParams p) {
     const BlockIdx3 blk = xcd_block_index();          // neighbouring bands / windows share an L2
     if ((p.gate == 1 && p.flags[blk.z] == p.epoch) || (p.gate == 2 && p.flags[blk.z] != p.epoch)) {      // uniform per workgroup
         return;
@@ -1364,12 +1187,6 @@ inline void launch_match_fast_a(const FastLaunch &fl, const MatchParams &p, int 
     const dim3 grid((p.w + FA_VALID * win_per_wg - 1) / (FA_VALID * win_per_wg), (p.h + TH - 1) / TH, n);
     const size_t lds = fast_lds_bytes<PR>(TH, p.Dd, DSPLIT);
     const dim3 block(64 * (DSPLIT ? FA_DS_WAVES : FA_WAVES));
-#ifdef SMX_FA_FORCE_TH
-    if (lds > 64 * 1024) {       // tuning experiments only: tall forced bands need the raised dynamic-LDS limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_match_fast<TH, PR, false, DSPLIT, 2, ARGB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-#endif
     if (fl.form == FAST_DENSE_SMALL) {
         if constexpr (DSPLIT && TH == FA_TH_SMALL_TALL) launch_match_fast_k<TH, PR, false, true, false, true>(fl.pk, grid, block, lds, p, s);
     } else if (fl.form == FAST_DENSE) {      // content whose windows hold many winners (the engine's choice, smx_route.h)
@@ -1412,9 +1229,8 @@ inline void launch_match_fast_tall(const FastLaunch &fl, const MatchParams &p, i
 // by registers, and a step-6, fill or prologue wave of the other stream lane finds room beside them.
 constexpr int FA_STACK = 2;
 constexpr int FA_STACK_TH = FA_STACK * FA_TH;
-template <int PR> inline bool fast_stack_fits(int Dd) {          // twice into 160 KB, at the 1280-byte allocation granule
-    const size_t granule = 1280, lds = fast_lds_bytes<PR>(FA_STACK_TH, Dd);
-    return 2 * ((lds + granule - 1) / granule * granule) <= 160 * 1024;
+template <int PR> inline bool fast_stack_fits(int Dd) {          // twice into 160 KB
+    return 2 * fast_lds_alloc(fast_lds_bytes<PR>(FA_STACK_TH, Dd)) <= 160 * 1024;
 }
 // ... at pitch 256 only (up to 67 disparities)
 inline bool fast_stack_instantiated(int pitch, int Dd) { return pitch == 256 && fast_stack_fits<256>(Dd); }
@@ -1424,9 +1240,7 @@ inline void launch_match_fast_stacked(const FastLaunch &fl, const MatchParams &p
     const dim3 grid((p.w + FA_VALID * FA_WAVES - 1) / (FA_VALID * FA_WAVES), (p.h + FA_STACK_TH - 1) / FA_STACK_TH, n);
     const size_t lds = fast_lds_bytes<PR>(FA_STACK_TH, p.Dd);
     const dim3 block(64 * FA_WAVES);
-    if (fl.pk == 2) hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 2, true, false>), grid, block, lds, s, p);
-    else if (fl.pk == 1) hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 1, true, false>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((k_match_fast<FA_STACK_TH, PR, false, false, 0, true, false>), grid, block, lds, s, p);
+    launch_match_fast_k<FA_STACK_TH, PR, false, false, true, false>(fl.pk, grid, block, lds, p, s);
 }
 // (the tile exceeds the 64 KB a kernel gets without asking)
 template <int PR>
@@ -1470,16 +1284,10 @@ inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus, int stack_
         const long wg_small = windows * ((p.h + FA_TH_SMALL - 1) / FA_TH_SMALL), wg_tall = windows * ((p.h + FA_TH_SMALL_TALL - 1) / FA_TH_SMALL_TALL);
         if (wg_small > cus && wg_tall <= cus) {
             pl.th = FA_TH_SMALL_TALL;
-#ifndef SMX_FA_NO_MID
-#ifdef SMX_FA_MID_P1
-        } else {
-#else
         } else if (!p.pass1_only) {
-#endif
             const long wg_mid = windows * ((p.h + FA_TH_SMALL_MID - 1) / FA_TH_SMALL_MID), slots = 2L * cus;
             const long r_small = (wg_small + slots - 1) / slots, r_mid = (wg_mid + slots - 1) / slots;
             if (r_mid * (FA_TH_SMALL_MID + 22) < r_small * (FA_TH_SMALL + 22)) pl.th = FA_TH_SMALL_MID;
-#endif
         }
         return pl;
     }
@@ -1492,17 +1300,11 @@ inline FastPlan match_fast_plan(const MatchParams &p, int n, int cus, int stack_
     int best = 24;
     long best_rows = -1;
     for (int th : cand) {
-        const int pr = fast_tall_pitch(p.Dd);
-        const size_t lds = pr == 256 ? fast_lds_bytes<256>(th, p.Dd) : (pr == FA_MID_PITCH ? fast_lds_bytes<FA_MID_PITCH>(th, p.Dd) : fast_lds_bytes<320>(th, p.Dd));
-        const size_t granule = 1280;                                  // LDS allocation granularity
-        const bool three_per_cu = 3 * ((lds + granule - 1) / granule * granule) <= 160 * 1024;
+        const bool three_per_cu = 3 * fast_lds_alloc(fast_lds_bytes_at(fast_tall_pitch(p.Dd), th, p.Dd)) <= 160 * 1024;
         const long rows = (long)((p.h + th - 1) / th) * (th + 22) * (th == 32 ? 106 : 100) * (three_per_cu ? 100 : 130);
         if (best_rows < 0 || rows < best_rows) { best_rows = rows; best = th; }
     }
     pl.th = best;
-#ifdef SMX_FA_FORCE_TH
-    pl.th = SMX_FA_FORCE_TH;           // tuning experiments only (24, 27 or 32)
-#endif
     // Stacked bands: the sparse form on the stream lanes, where the other lane's small kernels fill the issue slots that two
     // waves per SIMD leave empty (on a caller's stream the same geometry loses: NOTES.md), and only if fewer rows are marched.
     if (stack_opt != 0 && !p.dense && !p.pass1_only && fast_stack_instantiated(fast_tall_pitch(p.Dd), p.Dd)) {

@@ -43,10 +43,7 @@ inline double filter_error_bound_units(double u) {
     return (1.05 * rounding + 1e-4 * Hmax * Hmax * Cmax) * u * u * u;
 }
 
-#ifndef SMX_FILTER_A_GAP
-#define SMX_FILTER_A_GAP 1
-#endif
-constexpr int FILTER_A_GAP = SMX_FILTER_A_GAP;     // pass A samples every FILTER_A_GAP-th disparity (1: all of them)
+constexpr int FILTER_A_GAP = 1;                        // pass A samples every FILTER_A_GAP-th disparity (1: all of them)
 constexpr int FILTER_TILE_H = 16, FILTER_TILE_W = 128;      // = E2_TH, E2_TW (static_assert in k_match_exact2.h)
 __host__ __device__ inline int filter_cand_words(int Dd) { return (Dd + 31) / 32; }
 

@@ -36,15 +36,9 @@ __device__ __forceinline__ float load_gray(const void *img, size_t plane, size_t
 // (unsigned short)(unit * pooled) -- the expression fast_stage evaluates on the f32 plane -- for each pooled pixel, and the
 // threads that own columns 0 .. 2 write the cyclic apron behind column w - 1 as well: column w + j repeats column j % w.
 // units_l == NULL (smx_plan.h: RangePlan::writes_units): the call takes an exact-order route, which reads the f32 planes only.
-// SMX_PROLOGUE_PK8_F32 (build.py --variant with SMX_EXTRA_FLAGS; PK8 below): the gray f32 entries at K = 2 / 4 build the bytes
-// of the u8 planes with v_cvt_pk_u8_f32 and take the integrality flag from the round trip.  Measured neutral in the step for
-// 9 more registers in k_prologue_k2 (45 instead of 37; NOTES.md R7.1), so the test on the float value and the truncating cast
-// stay the product's form.
-#ifdef SMX_PROLOGUE_PK8_F32
-#define SMX_PROLOGUE_PK8(MODE) ((MODE) == IN_GRAY_F32)
-#else
-#define SMX_PROLOGUE_PK8(MODE) false
-#endif
+// (Measured and not adopted, NOTES.md R7.1: the gray f32 entries at K = 2 / 4 building the bytes of the u8 planes with
+// v_cvt_pk_u8_f32 and taking the integrality flag from the round trip -- neutral in the step for 9 more registers in
+// k_prologue_k2, 45 instead of 37.)
 // (plane: the pair's plane, wave-uniform; row: x * upitch -- 32-bit element offsets, no 64-bit address per store)
 __device__ __forceinline__ void store_unit_u16(uint16_t *plane, unsigned at, uint16_t u) {
     *(uint16_t *)((char *)plane + (size_t)(2u * at)) = u;
@@ -168,7 +162,6 @@ __global__ __launch_bounds__(256) void k_prologue_k2(const void *left, const voi
     const int x = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
     const size_t plane = (size_t)H * W;
-    constexpr bool PK8 = SMX_PROLOGUE_PK8(MODE);
     bool bad = false, bad8 = false;
     if (x < h && yp < w) {
         const int Y0 = yp * 2;                               // first of (up to) four full-res columns
@@ -225,19 +218,10 @@ __global__ __launch_bounds__(256) void k_prologue_k2(const void *left, const voi
                 uint32_t w0 = 0u, w1 = 0u;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (MODE == IN_GRAY_F32 && !PK8 && j < ncol)
+                    if (MODE == IN_GRAY_F32 && j < ncol)
                         bad8 = bad8 || !(v0[j] == rintf(v0[j]) && v0[j] >= 0.f && v0[j] <= 255.f) ||
                                (row1_in && !(v1[j] == rintf(v1[j]) && v1[j] >= 0.f && v1[j] <= 255.f));
-                    if (PK8) {
-                        // v_cvt_pk_u8_f32 converts, saturates and inserts the byte; a value is an integer in [0, 255] exactly
-                        // when the byte converts back to it (NaN, negative, > 255 and fractional values all fail; -0 passes
-                        // as 0).  The bytes of a value that fails may differ from the truncating cast: step 6 reads these
-                        // planes only for pairs whose flag is clear (k_refine.h).  Columns past ncol hold 0, and a clamped
-                        // second row repeats the first: neither can raise the flag on its own.
-                        w0 = __builtin_amdgcn_cvt_pk_u8_f32(v0[j], j, w0);
-                        w1 = __builtin_amdgcn_cvt_pk_u8_f32(v1[j], j, w1);
-                        bad8 |= ((float)((w0 >> (8 * j)) & 0xffu) != v0[j]) | ((float)((w1 >> (8 * j)) & 0xffu) != v1[j]);
-                    } else if (j < ncol) {
+                    if (j < ncol) {
                         w0 |= (uint32_t)(uint8_t)v0[j] << (8 * j);
                         w1 |= (uint32_t)(uint8_t)v1[j] << (8 * j);
                     }
@@ -306,7 +290,6 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
     const int b = blockIdx.z;
     const size_t plane = (size_t)H * W;
     const size_t pair_elems = RGB ? 3 * plane : plane;
-    constexpr bool PK8 = SMX_PROLOGUE_PK8(MODE);
     bool bad = false, bad8 = false;
     if (x < h && y < w) {
         const int Y0 = y * 4;                                // W % 4 == 0: the four columns are inside the image
@@ -388,13 +371,8 @@ __global__ __launch_bounds__(256) void k_prologue_k4(const void *left, const voi
                     uint32_t wd = 0u;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        if (MODE == IN_GRAY_F32 && !PK8) bad8 = bad8 || !(v[i][j] == rintf(v[i][j]) && v[i][j] >= 0.f && v[i][j] <= 255.f);
-                        if (PK8) {                            // convert, saturate, insert; flag = round trip (k_prologue_k2)
-                            wd = __builtin_amdgcn_cvt_pk_u8_f32(v[i][j], j, wd);
-                            bad8 |= (float)((wd >> (8 * j)) & 0xffu) != v[i][j];
-                        } else {
-                            wd |= (uint32_t)(uint8_t)v[i][j] << (8 * j);
-                        }
+                        if (MODE == IN_GRAY_F32) bad8 = bad8 || !(v[i][j] == rintf(v[i][j]) && v[i][j] >= 0.f && v[i][j] <= 255.f);
+                        wd |= (uint32_t)(uint8_t)v[i][j] << (8 * j);
                     }
                     uint8_t *r8 = g8 + ((size_t)b * H + x * 4 + i) * pitch8;
                     *(uint32_t *)(r8 + padl + Y0) = wd;                          // padl, pitch8, Y0: multiples of 4

@@ -51,12 +51,10 @@ int main() {
     // the 8- and 10-row latency shapes keep the sliding sums
     expect(!fast_prefix_form(8, 256, false, true, 2, false, false) && !fast_prefix_form(10, 256, false, true, 2, false, false) &&
            !fast_prefix_form(8, 320, true, true, 2, false, false), "8- and 10-row latency shapes: sliding sums");
-#ifndef SMX_FA_NO_PREFIX
     expect(fast_prefix_form(48, 256, false, false, 2, true, false), "stacked bands at K <= 2: prefix form");
     expect(fast_prefix_form(24, 256, false, false, 2, true, false) && fast_prefix_form(27, 288, false, false, 2, true, true) &&
            fast_prefix_form(32, 320, true, false, 2, false, false), "tall bands at K <= 2: prefix form");
     expect(fast_prefix_form(12, 256, false, true, 2, false, false) && fast_prefix_form(12, 320, false, true, 2, false, true), "12-row latency shape: prefix form");
-#endif
     printf("prefix-exact checks %d failures %d\n", checks, failures);
     return failures ? 1 : 0;
 }

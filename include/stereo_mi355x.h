@@ -38,6 +38,7 @@
  *   -- (triangles over those points: marching cubes)      smx_tsdf_extract_triangles,
  *                                                         smx_tsdf_extract_triangles_workspace_bytes
  *   -- (disparity, normal and colour views of that volume) smx_tsdf_raycast, smx_tsdf_raycast_workspace_bytes
+ *   -- (a window of that volume: shift, crop, grow, spill) smx_tsdf_window
  *   -- (the camera pose of a frame against such a view)   smx_track_camera, smx_track_camera_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
@@ -911,6 +912,38 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
                      int W, const float Q[16], const float *camera_to_world, float step, float z_min, float z_max,
                      float invalid_disparity, float *disp, float *depth, float *normals, uint8_t *colors,
                      float *out_weight, void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_tsdf_window: a window of a volume's state as the state of a volume of its own -- what moves a volume with the
+ * camera in whole-voxel steps (the same dims, the start = the shift), crops or grows it, and cuts out the slab a shift
+ * leaves behind.  The source is smx_tsdf_integrate's state of nx * ny * nz voxels, read only; the window starts at source
+ * voxel (x0, y0, z0), of any sign, and has bx * by * bz voxels: the dims of the destination arrays tsdf_out, weight_out
+ * [bz][by][bx] f32 and color_out [bz][by][bx][4] u8.  It may lie partly or wholly outside the source.
+ *   For every destination voxel (i, j, k), 0 <= i < bx, 0 <= j < by, 0 <= k < bz, the source voxel is
+ *   (x0 + i, y0 + j, z0 + k).  If 0 <= x0 + i < nx, 0 <= y0 + j < ny and 0 <= z0 + k < nz, the destination's three state
+ *   words are the source voxel's, copied bit for bit (NaN payloads and -0.0f are kept and the colour word is whole: no
+ *   float operation touches a value); otherwise all three are the empty state, all-zero bits.
+ * The destination describes the same world when its origin is the source's moved by (x0, y0, z0) voxels: the caller's
+ * arithmetic (the Python layer keeps the first origin and an integer offset, and multiplies once, in float64).
+ * A shift by (dx, dy, dz) is the window (dx, dy, dz) at the volume's own dims, written to a second set of arrays that
+ * then becomes the state: a volume that shifts needs twice its state's memory while that spare set exists.  What a
+ * shift leaves behind is cut out BEFORE it, as one box per axis with a non-zero component: the whole cross-section in
+ * the other two axes and, along its own axis a with n = n_a and d = d_a, the layers [0, min(n, d + margin)) for d > 0 or
+ * [max(0, n + d - margin), n) for d < 0 -- the leaving layers plus `margin` layers of the staying side, so that with
+ * margin >= 1 a crossing between a leaving voxel and a staying one is in a box.  Surface elements wholly inside a margin
+ * layer then exist twice, in the box and in the shifted volume, and so do those in the corner two boxes share;
+ * smx_voxel_downsample at voxel_size removes the duplicates from point clouds.  Boxes are ordinary volumes for every
+ * entry above.  Not addressed: fusing boxes back when the volume returns to a place it left (it finds that place empty),
+ * loop closure and relocalisation.
+ * color and color_out are both NULL or both given.  The call is out of place: a destination array may overlap neither a
+ * source array nor another destination array.
+ * One launch on `stream` (a caller's stream), no atomics, no workspace, no host synchronisation and no allocation:
+ * graph-capturable.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL tsdf, weight, tsdf_out or weight_out; color without
+ * color_out or color_out without color; nx, ny, nz or bx, by, bz outside 1..4096 or a product > 2^30; |x0|, |y0| or |z0|
+ * > 8192; a destination array overlapping a source array or another destination array; stream == SMX_STREAM_ENGINE. */
+int smx_tsdf_window(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight, const uint8_t *color,
+                    int x0, int y0, int z0, int bx, int by, int bz, float *tsdf_out, float *weight_out,
+                    uint8_t *color_out, void *stream);
 
 /* ---- Camera tracking -------------------------------------------------------------------------------------------------
  * smx_track_camera: the camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against

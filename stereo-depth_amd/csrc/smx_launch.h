@@ -163,6 +163,12 @@ void launch_tsdf_raycast(int nx, int ny, int nz, const float origin[3], float vo
                          float *disp, float *depth, float *normals, uint8_t *colors, float *out_weight, void *workspace,
                          hipStream_t s);
 
+// ---- tu_tsdf_window.hip: a window of a volume's state as a volume of its own (k_tsdf_window.h) ---------------------------
+// color and color_out both NULL or both given; one launch, no workspace; arguments checked by smx_tsdf_window
+void launch_tsdf_window(int nx, int ny, int nz, const float *tsdf, const float *weight, const uint8_t *color, int x0,
+                        int y0, int z0, int bx, int by, int bz, float *tsdf_out, float *weight_out, uint8_t *color_out,
+                        hipStream_t s);
+
 // ---- tu_track.hip: camera tracking against rendered model views (k_track.h) ----------------------------------------------
 // q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every other pointer is device memory; confidence,
 // info, rms and normal_equations may be NULL; workspace: track_layout(n, H, W); arguments checked by smx_track_camera

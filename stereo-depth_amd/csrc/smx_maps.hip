@@ -749,6 +749,34 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
     });
 }
 
+int smx_tsdf_window(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight, const uint8_t *color,
+                    int x0, int y0, int z0, int bx, int by, int bz, float *tsdf_out, float *weight_out,
+                    uint8_t *color_out, void *stream) {
+    const char *fn = "smx_tsdf_window";
+    if (!tsdf || !weight || !tsdf_out || !weight_out)
+        return fail(SMX_ERR_INVALID_ARG, "%s: tsdf, weight, tsdf_out and weight_out must be non-NULL", fn);
+    if ((color == nullptr) != (color_out == nullptr))
+        return fail(SMX_ERR_INVALID_ARG, "%s: color and color_out must both be NULL or both be given", fn);
+    if (int rc = check_tsdf_dims(fn, nx, ny, nz)) return rc;
+    if (!tsdf_dims_ok(bx, by, bz))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= bx, by, bz <= 4096 and bx * by * bz <= 2^30 (got %d, %d, %d)", fn, bx,
+                    by, bz);
+    if (int rc = check_int_range(fn, "x0", x0, -8192, 8192)) return rc;
+    if (int rc = check_int_range(fn, "y0", y0, -8192, 8192)) return rc;
+    if (int rc = check_int_range(fn, "z0", z0, -8192, 8192)) return rc;
+    const size_t vox = (size_t)nx * ny * nz, out = (size_t)bx * by * bz;
+    if (int rc = check_disjoint(fn, {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}, {color, vox * 4}},
+                                {{tsdf_out, out * sizeof(float)}, {weight_out, out * sizeof(float)}, {color_out, out * 4}},
+                                "a destination array overlaps a source array (the call is out of place)",
+                                "two destination arrays overlap"))
+        return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_window(nx, ny, nz, tsdf, weight, color, x0, y0, z0, bx, by, bz, tsdf_out, weight_out, color_out,
+                                (hipStream_t)stream);
+    });
+}
+
 // ---- camera tracking ---------------------------------------------------------------------------------------------------
 static bool track_dims_ok(int n, int H, int W) {
     return points_dims_ok(n, H, W) && track_grid(H, W, 1).tiles <= TRK_MAX_TILES;

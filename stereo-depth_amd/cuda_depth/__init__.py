@@ -1565,6 +1565,67 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     return TrackingResult(*out)
 
 
+WINDOW_START_MAX = 8192                                            # smx_tsdf_window: |x0|, |y0|, |z0|
+
+
+def _int_triple(name: str, v, limit: Optional[int] = None) -> Tuple[int, int, int]:
+    try:
+        t = tuple(v)
+    except TypeError:
+        raise TypeError(f"{name} must be three ints") from None
+    if len(t) != 3:
+        raise TypeError(f"{name} must be three ints")
+    for c in t:
+        _int_arg(name, c)
+        if limit is not None and abs(c) > limit:
+            raise RuntimeError(f"{name}: at most {limit} voxels per axis, got {t}")
+    return tuple(int(c) for c in t)
+
+
+def tsdf_window_origin(origin, offset, voxel_size: float) -> Tuple[float, float, float]:
+    """The world position of the corner of a volume that was built at `origin` and has moved by `offset` whole voxels:
+    origin + offset * voxel_size per axis, one float64 product and sum from the two values that are kept, so that a
+    volume's origin does not drift however many shifts made up the offset."""
+    return tuple(float(o) if k == 0 else float(o) + k * float(voxel_size) for o, k in zip(origin, offset))
+
+
+def tsdf_spill_boxes(dims, voxels, margin: int = 1):
+    """What TSDFVolume.shift(voxels, spill=True) hands back, as [(start, dims), ...] windows of the volume before the
+    shift: one box per axis with a non-zero component, in the order x, y, z.  A box covers the volume's whole
+    cross-section in the other two axes; along its own axis a, with n = dims[a] and d = voxels[a], it covers the layers
+    that leave -- [0, d) for d > 0, [n + d, n) for d < 0 -- extended by `margin` layers into the staying side and clipped
+    to [0, n)."""
+    dims, d = _int_triple("dims", dims), _int_triple("voxels", voxels)
+    _int_arg("margin", margin)
+    if margin < 0:
+        raise RuntimeError(f"margin must be >= 0, got {margin}")
+    boxes = []
+    for a in range(3):
+        n = dims[a]
+        if d[a] == 0:
+            continue
+        lo, hi = (0, min(n, d[a] + margin)) if d[a] > 0 else (max(0, n + d[a] - margin), n)
+        start, size = [0, 0, 0], list(dims)
+        start[a], size[a] = lo, hi - lo
+        boxes.append((tuple(start), tuple(size)))
+    return boxes
+
+
+def tsdf_follow_shift(position, origin, dims, voxel_size: float, anchor=(0.5, 0.5, 0.5)) -> Tuple[int, int, int]:
+    """The whole-voxel shift that brings a volume's anchor point, origin + anchor * dims * voxel_size, to `position`: per
+    axis (position - anchor point) / voxel_size in float64, rounded half away from zero."""
+    out = []
+    for p, o, n, a in zip(position, origin, dims, anchor):
+        x = (float(p) - (float(o) + float(a) * n * float(voxel_size))) / float(voxel_size)
+        if not math.isfinite(x):
+            raise RuntimeError(f"the camera position {tuple(position)} is not finite in voxels")
+        whole = math.floor(abs(x))
+        if abs(x) - whole >= 0.5:                                   # an exact difference: floor(abs(x) + 0.5) is not
+            whole += 1
+        out.append(int(whole) if x >= 0 else -int(whole))
+    return tuple(out)
+
+
 class TSDFVolume:
     """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
     include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points), as a triangle mesh over
@@ -1574,7 +1635,28 @@ class TSDFVolume:
     centred at origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size.  It owns the state: .tsdf and .weight float32
     [nz, ny, nx], and with color=True .color uint8 [nz, ny, nx, 4] (R, G, B, 0).  truncation (default 3 * voxel_size,
     must exceed voxel_size) is the band around each surface that a measurement updates; the weight of a voxel is capped at
-    max_weight, so older frames fade once it is reached.  Memory is fixed: 8 (12 with colour) bytes per voxel."""
+    max_weight, so older frames fade once it is reached.  Memory is fixed: 8 (12 with colour) bytes per voxel -- twice
+    that from the first shift() until release_spare().
+
+    The volume can follow the camera (shift, follow; window crops and grows): it moves in whole voxels, and .offset
+    (ints) counts how far it has moved from where it was built.  .origin is always the constructor's origin +
+    offset * voxel_size, computed in float64 from those two, so it does not drift; a volume that is never shifted
+    behaves bit for bit as one without these methods.  Assigning .origin places the volume anew (offset 0)."""
+
+    _offset = (0, 0, 0)                                              # whole voxels moved since construction
+    _spare = None                                                    # shift's second set of state tensors
+
+    @property
+    def origin(self) -> Tuple[float, float, float]:
+        return tsdf_window_origin(self._origin0, self._offset, self.voxel_size)
+
+    @origin.setter
+    def origin(self, value) -> None:
+        self._origin0, self._offset = tuple(value), (0, 0, 0)
+
+    @property
+    def offset(self) -> Tuple[int, int, int]:
+        return self._offset
 
     def __init__(self, dims, voxel_size: float, origin, *, truncation: Optional[float] = None, max_weight: float = 64.0,
                  color: bool = True, device=None):
@@ -1601,7 +1683,8 @@ class TSDFVolume:
         self._capacity = min(3 * nx * ny * nz, 2 ** 30, max(4096, 2 * (nx * ny + ny * nz + nx * nz)))
 
     def reset(self) -> None:
-        """Returns the volume to empty (every state value 0), on the current stream."""
+        """Returns the volume to empty (every state value 0), on the current stream.  It stays where it is: .offset and
+        .origin are kept."""
         self.tsdf.zero_()
         self.weight.zero_()
         if self.color is not None:
@@ -1609,6 +1692,108 @@ class TSDFVolume:
 
     def _origin(self):
         return (C.c_float * 3)(*self.origin)
+
+    def _state_like(self, dims):
+        """Uninitialised state tensors (tsdf, weight, color or None) for a volume of `dims` like this one."""
+        nx, ny, nz = dims
+        return (torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device),
+                torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device),
+                None if self.color is None else torch.empty((nz, ny, nx, 4), dtype=torch.uint8, device=self.device))
+
+    def _window_into(self, start, dims, tsdf: torch.Tensor, weight: torch.Tensor, color: Optional[torch.Tensor]) -> None:
+        nx, ny, nz = self.dims
+        check(LIB.smx_tsdf_window(self.device.index, nx, ny, nz, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                  None if self.color is None else self.color.data_ptr(), *start, *dims, tsdf.data_ptr(),
+                                  weight.data_ptr(), None if color is None else color.data_ptr(),
+                                  _stream(self.device.index)))
+
+    def window(self, start, dims) -> "TSDFVolume":
+        """A new volume that holds the window of this one that starts at voxel `start` = (x0, y0, z0), of any sign, and
+        has `dims` voxels (smx_tsdf_window, on the current stream without synchronising): the part inside this volume is
+        copied bit for bit, the rest is empty.  Same voxel_size, truncation, max_weight, colour-ness and device; its
+        origin is this volume's moved by `start` voxels (it keeps the constructor's origin, and its .offset is this
+        volume's plus start).  Crops with a window inside the volume, grows it with one around it."""
+        start = _int_triple("start", start, WINDOW_START_MAX)
+        dims, _, _ = _check_tsdf_volume(dims, self.voxel_size, self._origin0)
+        out = object.__new__(TSDFVolume)
+        out.dims, out.voxel_size, out.device = dims, self.voxel_size, self.device
+        out._origin0, out._offset = self._origin0, tuple(a + b for a, b in zip(self._offset, start))
+        out.truncation, out.max_weight = self.truncation, self.max_weight
+        out.tsdf, out.weight, out.color = self._state_like(dims)
+        nx, ny, nz = dims
+        out._capacity = min(3 * nx * ny * nz, 2 ** 30, max(4096, 2 * (nx * ny + ny * nz + nx * nz)))
+        self._window_into(start, dims, out.tsdf, out.weight, out.color)
+        return out
+
+    def shift(self, voxels, *, spill: bool = False, margin: int = 1) -> list:
+        """Moves the volume's window in the world by voxels = (dx, dy, dz) whole voxels, on the current stream without
+        synchronising: afterwards voxel (i, j, k) holds what (i + dx, j + dy, k + dz) held, the voxels that entered are
+        empty, .offset has grown by voxels and .origin is the constructor's origin + offset * voxel_size.  (0, 0, 0)
+        does nothing and launches nothing.
+
+        The shift is one smx_tsdf_window into a SPARE set of state tensors, which then becomes the state: .tsdf, .weight
+        and .color are different tensors after a shift (hold the volume, not its tensors), and the earlier ones are the
+        next shift's spare.  The spare is allocated by the first shift and reused from then on, so a volume that shifts
+        needs twice its state's memory until release_spare().
+
+        spill=True returns what left as a list of TSDFVolumes -- ordinary volumes for extract_point_cloud,
+        extract_triangle_mesh and render -- one box per axis with a non-zero component, in the order x, y, z
+        (tsdf_spill_boxes): the whole cross-section of the volume before the shift in the other two axes and, along its
+        own axis, the layers that leave plus `margin` layers of the staying side, clipped to the volume.  margin=1 keeps
+        the crossings between a leaving voxel and a staying one, which neither the shifted volume nor a box without
+        margin contains.  Surface elements can then appear twice: those wholly inside a margin layer (in the box and in
+        the shifted volume) and those in the corner that two boxes share; voxel_downsample at voxel_size removes the
+        duplicates from point clouds.  Without spill the list is empty and what left is gone.  Boxes are not fused back
+        when the volume returns to a place it has left."""
+        d = _int_triple("voxels", voxels, WINDOW_START_MAX)
+        if not isinstance(spill, bool):
+            raise TypeError("spill must be a bool")
+        boxes = tsdf_spill_boxes(self.dims, d, margin)
+        if d == (0, 0, 0):
+            return []
+        spilled = [self.window(start, dims) for start, dims in boxes] if spill else []
+        if self._spare is None:
+            self._spare = self._state_like(self.dims)
+        tsdf, weight, color = self._spare
+        self._window_into(d, self.dims, tsdf, weight, color)
+        self._spare = (self.tsdf, self.weight, self.color)
+        self.tsdf, self.weight, self.color = tsdf, weight, color
+        self._offset = tuple(a + b for a, b in zip(self._offset, d))
+        return spilled
+
+    def release_spare(self) -> None:
+        """Frees shift's spare state tensors; the next shift allocates them again."""
+        self._spare = None
+
+    def follow(self, camera_to_world, *, threshold: Optional[int] = None, anchor=(0.5, 0.5, 0.5), spill: bool = False,
+               margin: int = 1):
+        """Keeps the camera at the volume's anchor point, origin + anchor * dims * voxel_size: with d the camera position
+        of camera_to_world [4, 4] (of the last pose of [n, 4, 4]) minus that point, in voxels, rounded half away from
+        zero (tsdf_follow_shift; host arithmetic in float64), shifts by d once max |d_a| >= threshold and returns
+        (d, shift(d, spill=spill, margin=margin)); returns ((0, 0, 0), []) otherwise.  threshold: a positive int,
+        default max(1, min(dims) // 8)."""
+        m = _host_matrices("camera_to_world", camera_to_world, True)
+        if not np.isfinite(m).all():
+            raise RuntimeError("camera_to_world must be finite")
+        if threshold is None:
+            threshold = max(1, min(self.dims) // 8)
+        _int_arg("threshold", threshold)
+        if threshold < 1:
+            raise RuntimeError(f"threshold must be a positive int, got {threshold}")
+        try:
+            anchor = tuple(anchor)
+        except TypeError:
+            raise TypeError("anchor must be three numbers") from None
+        if len(anchor) != 3:
+            raise TypeError("anchor must be three numbers")
+        for v in anchor:
+            _number_arg("anchor", v)
+            if not math.isfinite(v):
+                raise RuntimeError(f"anchor must be finite, got {anchor}")
+        d = tsdf_follow_shift(m[-1, :3, 3].tolist(), self.origin, self.dims, self.voxel_size, anchor)
+        if max(abs(c) for c in d) < threshold:
+            return (0, 0, 0), []
+        return d, self.shift(d, spill=spill, margin=margin)
 
     def integrate(self, disp: torch.Tensor, Q, camera_to_world, *, image: Optional[torch.Tensor] = None,
                   confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0, depth_range=(0.0, math.inf),

@@ -192,6 +192,11 @@ EXPORTS = {
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                    C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # a window of the volume's state: (device_id, nx, ny, nz, tsdf, weight, color, x0, y0, z0, bx, by, bz, tsdf_out,
+    # weight_out, color_out, stream)
+    "smx_tsdf_window": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     # camera tracking: (n, H, W) -> workspace bytes; (device_id, n, H, W, disp, confidence, Q (host float32[16]),
     # min_confidence, z_min, z_max, invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm (host float32[16]),
     # model_camera_to_world, model_world_to_camera, pose_in, schedule_pairs, schedule (host int32[pairs][2]),

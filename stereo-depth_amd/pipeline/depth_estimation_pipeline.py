@@ -76,6 +76,11 @@ class DepthEstimationResult:
     # then not integrated); None otherwise.  Keyword-only as well
     camera_pose: Optional[Any] = dataclasses.field(default=None, kw_only=True)
     tracking_lost: Optional[bool] = dataclasses.field(default=None, kw_only=True)
+    # follow_camera=True: how far the volume moved before this frame was integrated, in whole voxels (TSDFVolume.follow;
+    # (0, 0, 0) for a frame that did not move it and without follow_camera), and with keep_spill=True what left it then
+    # (TSDFVolume.shift's boxes, new volumes; empty otherwise).  Keyword-only as well
+    volume_shift: Tuple[int, int, int] = dataclasses.field(default=(0, 0, 0), kw_only=True)
+    spilled_volumes: list = dataclasses.field(default_factory=list, kw_only=True)
     # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
     # None otherwise
     confidence_map: Optional[torch.Tensor] = None
@@ -134,7 +139,9 @@ class DepthEstimationPipeline:
                  point_cloud_min_points: int = 1, point_cloud_min_confidence: float = 0.0,
                  tsdf_volume: Optional["cuda_depth.TSDFVolume"] = None,
                  right_view_synthesis: Optional[RightViewSynthesis] = None, render_model: bool = False,
-                 track_camera: bool = False, initial_pose=None, tracking_args: Optional[dict] = None):
+                 track_camera: bool = False, initial_pose=None, tracking_args: Optional[dict] = None,
+                 follow_camera: bool = False, follow_threshold: Optional[int] = None,
+                 follow_anchor: Tuple[float, float, float] = (0.5, 0.5, 0.5), keep_spill: bool = False):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -175,7 +182,15 @@ class DepthEstimationPipeline:
         last pose (TSDFVolume.track with point_cloud_depth_range, the confidence map and point_cloud_min_confidence, and
         tracking_args on top), its twelve pose values and its lost flag are read back -- one small device-to-host copy,
         hence one synchronisation, per frame -- and it is integrated at the tracked pose unless it is lost.  The result
-        carries camera_pose and tracking_lost; reset_tracking() forgets the last pose."""
+        carries camera_pose and tracking_lost; reset_tracking() forgets the last pose.  follow_camera /
+        follow_threshold / follow_anchor / keep_spill: follow_camera=True (needs tsdf_volume) lets the volume follow the
+        camera: before a frame is integrated the volume is shifted in whole voxels so that the frame's pose -- the
+        tracked one with track_camera=True, else the caller's camera_pose -- stays at its anchor point
+        (TSDFVolume.follow with follow_threshold, default min(dims) // 8, and follow_anchor), so the next frame's model
+        view is rendered from the shifted volume; a lost frame does not move it.  The result carries volume_shift and,
+        with keep_spill=True, what left the volume as spilled_volumes (TSDFVolume.shift(spill=True): the caller's to
+        extract or drop; they are not fused back).  The volume then holds a spare copy of its state (twice the memory).
+        False (the default) changes nothing."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
@@ -216,6 +231,19 @@ class DepthEstimationPipeline:
             pose = np.eye(4) if initial_pose is None else initial_pose
             cuda_depth.world_to_camera_poses(pose)
             self._initial_pose = cuda_depth._host_matrices("initial_pose", pose, False)[0]
+        for name, flag in (("follow_camera", follow_camera), ("keep_spill", keep_spill)):
+            if not isinstance(flag, bool):
+                raise TypeError(f"{name} must be a bool")
+        if follow_camera and tsdf_volume is None:
+            raise ValueError("follow_camera needs tsdf_volume")
+        if not follow_camera and (follow_threshold is not None or keep_spill
+                                  or tuple(follow_anchor) != (0.5, 0.5, 0.5)):
+            raise ValueError("follow_threshold, follow_anchor and keep_spill need follow_camera=True")
+        if follow_threshold is not None and (isinstance(follow_threshold, bool) or not isinstance(follow_threshold, int)
+                                             or follow_threshold < 1):
+            raise ValueError(f"follow_threshold must be a positive int, got {follow_threshold!r}")
+        self._follow_camera, self._keep_spill = follow_camera, keep_spill
+        self._follow_threshold, self._follow_anchor = follow_threshold, tuple(follow_anchor)
         if right_view_synthesis is not None and not isinstance(right_view_synthesis, RightViewSynthesis):
             raise TypeError("right_view_synthesis must be a pipeline.synthesis.RightViewSynthesis")
         self._right_view_synthesis = right_view_synthesis
@@ -296,6 +324,10 @@ class DepthEstimationPipeline:
         lost = None
         if self._track_camera:
             camera_pose, lost = self._track(disparity, confidence)
+        shift, spilled = (0, 0, 0), []
+        if self._follow_camera and not lost:
+            shift, spilled = self._tsdf_volume.follow(camera_pose, threshold=self._follow_threshold,
+                                                      anchor=self._follow_anchor, spill=self._keep_spill)
         if self._tsdf_volume is not None and not lost:
             self._tsdf_volume.integrate(disparity, self._reprojection_matrix, camera_pose,
                                         image=self._colour_source(left_on_device), confidence=confidence,
@@ -309,7 +341,8 @@ class DepthEstimationPipeline:
                                              invalid_disparity=self._config.invalid_disparity).disparity
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
                                      confidence_map=confidence, point_cloud=cloud, model_disparity_map=model,
-                                     camera_pose=camera_pose if self._track_camera else None, tracking_lost=lost)
+                                     camera_pose=camera_pose if self._track_camera else None, tracking_lost=lost,
+                                     volume_shift=shift, spilled_volumes=spilled)
 
     def _track(self, disparity: torch.Tensor, confidence: Optional[torch.Tensor]):
         """(pose [4, 4] float64, lost) of this frame: initial_pose for the first frame, else the frame tracked against

@@ -29,6 +29,8 @@
  *   Deep3D's selection layer, upsampling and rescale      smx_synthesize_right_view (the head only: the
  *     python/pipeline/synthesis/deep3d.py:155,162-183,      network is the caller's)
  *     synthesis/kernels/rescale_generated_view.cu
+ *   the same layer inside the reference's training loop   smx_synthesis_head_forward, smx_synthesis_head_backward
+ *     python/pipeline/synthesis/trainer.py (autograd)       (the view in 0..1 and the volume's gradient)
  *   -- (semi-global matching, census cost: 2nd matcher)   smx_sgm, smx_sgm_workspace_bytes,
  *                                                         smx_sgm_with_right_map
  *   -- (metric 3D points, coloured, compacted)            smx_reproject_points, smx_reproject_workspace_bytes
@@ -635,6 +637,40 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
  * h * scale or w * scale > 32768, the overlaps above, stream == SMX_STREAM_ENGINE. */
 int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
                               const float *prob, const void *left, float *out, void *stream);
+
+/* The synthesis head for training: the view a loss sees, and the gradient of the volume.  Notation, operands, ranges
+ * and argument rules are smx_synthesize_right_view's.
+ *   - smx_synthesis_head_forward (the training form): that rule up to and including acc_c, without the rescale step:
+ *     view[c][X][Y] = acc_c, float32, unclamped (0..1 for a soft-maxed volume and a frame in 0..1).  The output of
+ *     smx_synthesize_right_view is the rescale of this view, bit for bit.  view: [n][C][H][W] f32.
+ *   - smx_synthesis_head_backward: given g = dL/dview as grad_view [n][C][H][W] f32, grad_prob [n][D][h][w] f32 =
+ *     dL/dprob.  left gets no gradient.  For each frame and each d = 0 .. D-1:
+ *       Plane gradient, for the columns with Y + d < W:  G[X][Y] = g_0 * v_0[X][Y + d];  for C = 3 then
+ *         G = G + g_1 * v_1[X][Y + d];  G = G + g_2 * v_2[X][Y + d]  (each product and each sum rounded).  Columns with
+ *         Y + d >= W contribute no term below: they are skipped, not added as zeros, as in the forward rule.
+ *       Horizontal transpose, for every row X and low-resolution column j:  T[X][j] starts at +0.0f; for
+ *         Y = 0, 1, ..., W-1 in this order:  if c0[Y] == j:  T = T + b0[Y] * G[X][Y];  then, if c1[Y] == j:
+ *         T = T + b1[Y] * G[X][Y].  A column whose two taps are the same cell adds both terms, b0 first; a term with a
+ *         zero weight is still added.
+ *       Vertical transpose, for every cell (i, j):  grad_prob[d][i][j] starts at +0.0f; for X = 0, 1, ..., H-1 in this
+ *         order:  if r0[X] == i:  acc = acc + a0[X] * T[X][j];  then, if r1[X] == i:  acc = acc + a1[X] * T[X][j].
+ *     For d >= W the plane is all zeros.  The indices that reach a cell are contiguous: 2 scale of them in the interior,
+ *     at most 2 scale + scale / 2 at the borders.
+ * Every operation is one float32 round-to-nearest with no fused operation, denormals are kept, NaNs and infinities
+ * spread as the operations say.  The order of each sum is part of the rule, so every implementation gives the same
+ * bits, whatever its tiles, its chunks of the disparity axis, or whether it computes a G once or once per cell that
+ * uses it.  In exact arithmetic the rule is the gradient of the training form; in float32 each value lies within
+ * (C + terms per row cell + terms per column cell + 2) 2^-24 of the sum of its terms' absolute values.
+ * An output must not overlap an input; inputs may alias each other.  One launch each on `stream` (a caller's stream),
+ * with no workspace, no atomics, no host synchronisation and no allocation, so the calls can be captured into a HIP
+ * graph.  Engine-free: device_id only selects the device.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched, in smx_synthesize_right_view's order: a NULL operand,
+ * n < 1 (or n frames larger than the address space), channels not 1 or 3, an unknown dtype, D outside 1..256, scale
+ * outside 1..16, h or w < 1 or h * scale or w * scale > 32768, the overlaps above, stream == SMX_STREAM_ENGINE. */
+int smx_synthesis_head_forward(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                               const float *prob, const void *left, float *view, void *stream);
+int smx_synthesis_head_backward(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                                const float *grad_view, const void *left, float *grad_prob, void *stream);
 
 /* Semi-global matching (Hirschmueller, TPAMI 2008) with a census cost: a second matcher beside the engine, engine-free.
  * The rule is integer up to one float32 division, so every implementation gives the same bits.

@@ -104,7 +104,10 @@ __device__ __forceinline__ void syn_march(float (&acc)[SYN_ROWS][C], int nd, con
     }
 }
 
-template <int C, bool F32> __global__ __launch_bounds__(SYN_THREADS) void k_synthesis(SynArgs a) {
+// RESCALE: the rule's last step (smx_synthesize_right_view); without it the sums themselves are stored, the training
+// form of smx_synthesis_head_forward.
+template <int C, bool F32, bool RESCALE = true>
+__global__ __launch_bounds__(SYN_THREADS) void k_synthesis(SynArgs a) {
     extern __shared__ float lds[];
     constexpr int LS = syn_left_stride(C);
     const int PS = syn_patch_stride(a.dc);
@@ -180,9 +183,11 @@ template <int C, bool F32> __global__ __launch_bounds__(SYN_THREADS) void k_synt
             const int X = x0 + wv * SYN_ROWS + j;
             if (X >= a.H) break;
 #pragma unroll
-            for (int c = 0; c < C; ++c)
-                a.out[((size_t)m * C + c) * HW + (size_t)X * a.W + Y] =
-                    fminf(fmaxf(__fadd_rn(__fmul_rn(acc[j][c], 255.0f), 0.5f), 0.0f), 255.0f);
+            for (int c = 0; c < C; ++c) {
+                float *dst = a.out + ((size_t)m * C + c) * HW + (size_t)X * a.W + Y;
+                if constexpr (RESCALE) *dst = fminf(fmaxf(__fadd_rn(__fmul_rn(acc[j][c], 255.0f), 0.5f), 0.0f), 255.0f);
+                else *dst = acc[j][c];
+            }
         }
     }
 }

@@ -113,6 +113,14 @@ void launch_remap_pairs(int n, int C, bool f32, int Hi, int Wi, int Ho, int Wo, 
 // left / out: [n][C][h*S][w*S], C 1 or 3; arguments checked by smx_synthesize_right_view
 void launch_synthesis(int n, int C, bool f32, int D, int h, int w, int S, const float *prob, const void *left, float *out,
                       hipStream_t s);
+// the training form: the sums themselves, without the rescale; arguments checked by smx_synthesis_head_forward
+void launch_synthesis_view(int n, int C, bool f32, int D, int h, int w, int S, const float *prob, const void *left,
+                           float *view, hipStream_t s);
+
+// ---- tu_synthesis_grad.hip: backward of the synthesis head (k_synthesis_grad.h) --------------------------------------
+// grad_view / left: [n][C][h*S][w*S]; grad_prob: [n][D][h][w]; arguments checked by smx_synthesis_head_backward
+void launch_synthesis_grad(int n, int C, bool f32, int D, int h, int w, int S, const float *grad_view, const void *left,
+                           float *grad_prob, hipStream_t s);
 
 // ---- tu_sgm.hip: semi-global matching (k_sgm.h) ----------------------------------------------------------------------
 // workspace: smx_workspace.h: sgm_layout(n, H, W, D); right_out NULL: not written (the

@@ -1,5 +1,6 @@
 // smx_maps.hip -- the engine-free entries of the C ABI of include/stereo_mi355x.h: operations on maps and frames the
 // caller already has, checked here and enqueued on the caller's stream through the launchers of smx_launch.h.
+#include <cstdio>
 #include <initializer_list>
 #include <type_traits>
 
@@ -368,10 +369,15 @@ int smx_remap_pairs(int device_id, int n, int channels, int dtype, int H_in, int
     });
 }
 
-int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
-                              const float *prob, const void *left, float *out, void *stream) {
-    const char *fn = "smx_synthesize_right_view";
-    if (!prob || !left || !out) return fail(SMX_ERR_INVALID_ARG, "%s: prob, left and out must be non-NULL", fn);
+// The rules the three entries of the synthesis head share, in their order.  vol: the [n][D][h][w] operand (prob or
+// grad_prob), img: the second [n][C][H][W] f32 operand (out, view or grad_view); out_is_vol: which of the two is written.
+static int check_synthesis_args(const char *fn, int n, int channels, int dtype, int D, int h, int w, int scale,
+                                const void *vol, const char *vol_name, const void *left, const void *img,
+                                const char *img_name, bool out_is_vol, void *stream) {
+    if (!vol || !left || !img) {
+        const char *first = out_is_vol ? img_name : vol_name, *last = out_is_vol ? vol_name : img_name;
+        return fail(SMX_ERR_INVALID_ARG, "%s: %s, left and %s must be non-NULL", fn, first, last);
+    }
     if (n < 1) return fail(SMX_ERR_INVALID_ARG, "%s: need n >= 1, got %d", fn, n);
     if (channels != 1 && channels != 3) return fail(SMX_ERR_INVALID_ARG, "%s: channels must be 1 or 3, got %d", fn, channels);
     if (int rc = check_dtype(fn, "", dtype)) return rc;
@@ -384,14 +390,43 @@ int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int
     const size_t frame = ((size_t)D * h * w > px * channels ? (size_t)D * h * w : px * channels) * sizeof(float);
     if ((size_t)n > SIZE_MAX / frame)                                       // frame <= 2^40: the byte sizes below do not overflow
         return fail(SMX_ERR_INVALID_ARG, "%s: n = %d frames do not fit the address space", fn, n);
-    const size_t prob_bytes = (size_t)n * D * h * w * sizeof(float);
-    const size_t left_bytes = (size_t)n * channels * px * (dtype == SMX_DTYPE_F32 ? 4 : 1);
-    if (int rc = check_disjoint(fn, {{prob, prob_bytes}, {left, left_bytes}}, {{out, (size_t)n * channels * px * sizeof(float)}},
-                                "out must not overlap prob or left"))
+    const Span v{vol, (size_t)n * D * h * w * sizeof(float)}, i{img, (size_t)n * channels * px * sizeof(float)};
+    const Span l{left, (size_t)n * channels * px * (dtype == SMX_DTYPE_F32 ? 4 : 1)};
+    char text[96];
+    if (out_is_vol) snprintf(text, sizeof text, "%s must not overlap %s or left", vol_name, img_name);
+    else snprintf(text, sizeof text, "%s must not overlap %s or left", img_name, vol_name);
+    if (int rc = out_is_vol ? check_disjoint(fn, {i, l}, {v}, text) : check_disjoint(fn, {v, l}, {i}, text)) return rc;
+    return check_caller_stream(fn, stream);
+}
+
+int smx_synthesize_right_view(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                              const float *prob, const void *left, float *out, void *stream) {
+    if (int rc = check_synthesis_args("smx_synthesize_right_view", n, channels, dtype, D, h, w, scale, prob, "prob", left, out,
+                                      "out", false, stream))
         return rc;
-    if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_synthesis(n, channels, dtype == SMX_DTYPE_F32, D, h, w, scale, prob, left, out, (hipStream_t)stream);
+    });
+}
+
+int smx_synthesis_head_forward(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                               const float *prob, const void *left, float *view, void *stream) {
+    if (int rc = check_synthesis_args("smx_synthesis_head_forward", n, channels, dtype, D, h, w, scale, prob, "prob", left, view,
+                                      "view", false, stream))
+        return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_synthesis_view(n, channels, dtype == SMX_DTYPE_F32, D, h, w, scale, prob, left, view, (hipStream_t)stream);
+    });
+}
+
+int smx_synthesis_head_backward(int device_id, int n, int channels, int dtype, int D, int h, int w, int scale,
+                                const float *grad_view, const void *left, float *grad_prob, void *stream) {
+    if (int rc = check_synthesis_args("smx_synthesis_head_backward", n, channels, dtype, D, h, w, scale, grad_prob, "grad_prob",
+                                      left, grad_view, "grad_view", true, stream))
+        return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_synthesis_grad(n, channels, dtype == SMX_DTYPE_F32, D, h, w, scale, grad_view, left, grad_prob,
+                                   (hipStream_t)stream);
     });
 }
 

@@ -747,6 +747,146 @@ def synthesize_right_view(probabilities: torch.Tensor, left: torch.Tensor, scale
     return out
 
 
+def _head_volume_geometry(probabilities: torch.Tensor, left: torch.Tensor, scale: int):
+    """(n, channels, D, h, w) of synthesis_head's operands, or the TypeError / ValueError that names the mistake."""
+    _int_arg("scale", scale)
+    if probabilities.dtype != torch.float32:
+        raise TypeError(f"probabilities must be float32, got {probabilities.dtype}")
+    if left.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"left must be uint8 or float32, got {left.dtype}")
+    if not 1 <= scale <= 16:
+        raise ValueError(f"scale must be in 1..16, got {scale}")
+    if probabilities.dim() not in (3, 4) or probabilities.numel() == 0:
+        raise ValueError(f"probabilities must be a non-empty [n, D, h, w] or [D, h, w], got {tuple(probabilities.shape)}")
+    batched = probabilities.dim() == 4
+    if left.dim() not in ((4,) if batched else (2, 3)):
+        raise ValueError(f"left must be {'[n, C, H, W]' if batched else '[C, H, W] or [H, W]'} beside probabilities "
+                         f"{tuple(probabilities.shape)}, got {tuple(left.shape)}")
+    n = int(probabilities.shape[0]) if batched else 1
+    D, h, w = (int(v) for v in probabilities.shape[-3:])
+    channels = 1 if left.dim() == 2 else int(left.shape[-3])
+    if channels not in (1, 3):
+        raise ValueError(f"left must have 1 or 3 channels, got {channels}")
+    if not 1 <= D <= 256:
+        raise ValueError(f"probabilities must hold 1..256 disparity planes, got {D}")
+    if tuple(left.shape[-2:]) != (h * scale, w * scale) or (batched and int(left.shape[0]) != n):
+        raise ValueError(f"left must be {'%d frames of ' % n if batched else ''}{h * scale} x {w * scale} "
+                         f"(probabilities {h} x {w}, scale {scale}), got {tuple(left.shape)}")
+    if h * scale > 32768 or w * scale > 32768:
+        raise ValueError(f"frames may be at most 32768 x 32768, got {h * scale} x {w * scale}")
+    if not left.is_contiguous():
+        raise ValueError("left must be contiguous")
+    if not probabilities.is_cuda or left.device != probabilities.device:
+        raise ValueError(f"probabilities and left must live on one GPU, got {probabilities.device} and {left.device}")
+    return n, channels, D, h, w
+
+
+def synthesis_head_backward(grad_view: torch.Tensor, left: torch.Tensor, D: int, scale: int = 4,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of the probability volume from the gradient of synthesis_head's view (smx_synthesis_head_backward; the
+    rule is in include/stereo_mi355x.h), on the current stream, in one launch that stores neither the upsampled gradient
+    nor the shifted frames.  grad_view: [n, C, H, W], [C, H, W] or [H, W] float32 on a GPU; left: the frame the view was
+    made from, in the shape of grad_view, float32 (0..1) or uint8; D in 1..256 planes; scale in 1..16 divides H and W.
+    Returns float32 [n, D, H / scale, W / scale] ([D, h, w] for unbatched operands); out: the tensor to write (it must
+    not overlap the inputs).  TypeError for a dtype mistake, ValueError for a shape or device mismatch or a
+    non-contiguous operand, before anything is launched."""
+    for name, t in (("grad_view", grad_view), ("left", left)) + ((("out", out),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _int_arg("D", D)
+    _int_arg("scale", scale)
+    if grad_view.dtype != torch.float32:
+        raise TypeError(f"grad_view must be float32, got {grad_view.dtype}")
+    if left.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"left must be uint8 or float32, got {left.dtype}")
+    if out is not None and out.dtype != torch.float32:
+        raise TypeError(f"out must be float32, got {out.dtype}")
+    if not 1 <= scale <= 16:
+        raise ValueError(f"scale must be in 1..16, got {scale}")
+    if not 1 <= D <= 256:
+        raise ValueError(f"D must be in 1..256 disparity planes, got {D}")
+    if grad_view.dim() not in (2, 3, 4) or grad_view.numel() == 0:
+        raise ValueError(f"grad_view must be a non-empty [n, C, H, W], [C, H, W] or [H, W], got {tuple(grad_view.shape)}")
+    if tuple(left.shape) != tuple(grad_view.shape):
+        raise ValueError(f"left must be {tuple(grad_view.shape)} like grad_view, got {tuple(left.shape)}")
+    n = int(grad_view.shape[0]) if grad_view.dim() == 4 else 1
+    channels = 1 if grad_view.dim() == 2 else int(grad_view.shape[-3])
+    H, W = (int(v) for v in grad_view.shape[-2:])
+    if channels not in (1, 3):
+        raise ValueError(f"grad_view must have 1 or 3 channels, got {channels}")
+    if H % scale or W % scale:
+        raise ValueError(f"scale {scale} must divide the frame's {H} x {W}")
+    if H > 32768 or W > 32768:
+        raise ValueError(f"frames may be at most 32768 x 32768, got {H} x {W}")
+    h, w = H // scale, W // scale
+    shape = ((n,) if grad_view.dim() == 4 else ()) + (D, h, w)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError(f"out must be {shape}, got {tuple(out.shape)}")
+    for name, t in (("grad_view", grad_view), ("left", left)) + ((("out", out),) if out is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not grad_view.is_cuda or left.device != grad_view.device:
+        raise ValueError(f"grad_view and left must live on one GPU, got {grad_view.device} and {left.device}")
+    if out is not None and out.device != left.device:
+        raise ValueError(f"out must live on {left.device}, got {out.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=left.device)
+    dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
+    dev = left.device.index
+    check(LIB.smx_synthesis_head_backward(dev, n, channels, dt, D, h, w, int(scale), grad_view.data_ptr(),
+                                          left.data_ptr(), out.data_ptr(), _stream(dev)))
+    return out
+
+
+class _SynthesisHead(torch.autograd.Function):
+    """smx_synthesis_head_forward / _backward as one differentiable operation; only `left` is saved."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, probabilities, left, scale):
+        n, channels, D, h, w = _head_volume_geometry(probabilities, left, scale)
+        probabilities = probabilities.contiguous()
+        view = torch.empty(left.shape, dtype=torch.float32, device=left.device)
+        dt = _native.DTYPE_U8 if left.dtype == torch.uint8 else _native.DTYPE_F32
+        dev = left.device.index
+        check(LIB.smx_synthesis_head_forward(dev, n, channels, dt, D, h, w, int(scale), probabilities.data_ptr(),
+                                             left.data_ptr(), view.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(left)
+        ctx.D, ctx.scale = D, int(scale)
+        return view
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_view):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (left,) = ctx.saved_tensors
+        grad_view = grad_view.to(torch.float32).contiguous()
+        return synthesis_head_backward(grad_view, left, ctx.D, ctx.scale), None, None
+
+
+def synthesis_head(probabilities: torch.Tensor, left: torch.Tensor, scale: int = 4) -> torch.Tensor:
+    """The training form of synthesize_right_view (smx_synthesis_head_forward): the same fused head without the rescale,
+    so the view is float32 in 0..1 and unclamped, in the shape of left -- what Deep3D's L1 loss compares with the true
+    right frame -- and it is differentiable with respect to probabilities (smx_synthesis_head_backward, one more
+    launch).  Operands are synthesize_right_view's: probabilities [n, D, h, w] or [D, h, w] float32 on a GPU, left
+    [n, C, H, W], [C, H, W] or [H, W], float32 in 0..1 or uint8.  left gets no gradient: one that requires grad is
+    refused with a ValueError.  Only left is kept for the backward pass, never the volume or anything of its size
+    times scale^2; the backward pass cannot be differentiated again.  Under autocast the head runs in float32."""
+    for name, t in (("probabilities", probabilities), ("left", left)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _int_arg("scale", scale)
+    if left.requires_grad:
+        raise ValueError("left gets no gradient from synthesis_head: detach it")
+    if not probabilities.is_floating_point():
+        raise TypeError(f"probabilities must be float32, got {probabilities.dtype}")
+    if not torch.is_autocast_enabled() or not probabilities.is_cuda:
+        _head_volume_geometry(probabilities, left, scale)                # refuse before autograd records anything
+    return _SynthesisHead.apply(probabilities, left, scale)
+
+
 class StereoSGM:
     """Semi-global matching with a census 9x7 cost (smx_sgm; the rule is in include/stereo_mi355x.h), a second matcher
     beside StereoMatching.  Candidates are min_disparity..max_disparity (at most 256); paths 4 or 8; 0 <= P1 <= P2 <= 191;

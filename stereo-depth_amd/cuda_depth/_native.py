@@ -136,6 +136,12 @@ EXPORTS = {
     # right-view synthesis head: (device_id, n, channels, dtype, D, h, w, scale, prob, left, out, stream)
     "smx_synthesize_right_view": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # its training form and backward: (..., scale, prob, left, view, stream); (..., scale, grad_view, left, grad_prob,
+    # stream)
+    "smx_synthesis_head_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smx_synthesis_head_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # semi-global matching: (n, H, W, num_disparities, paths) -> workspace bytes; (device_id, n, channels, dtype, H, W,
     # left, right, min_disparity, num_disparities, paths, P1, P2, uniqueness, lr_max_diff, subpixel, invalid_disparity,
     # out, gray_left_out, workspace, workspace_bytes, stream)

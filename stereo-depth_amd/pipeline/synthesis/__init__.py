@@ -5,8 +5,10 @@ The reference runs a traced Deep3D: a VGG-based network that ends in a softmax o
 the frame's resolution, followed by an upsampling, a "selection layer" (65 shifted copies of the left frame, weighted
 and summed) and a rescale to 0..255.  Here the network is any callable the caller brings -- its convolutions are
 MIOpen's business -- and everything after its last layer is one HIP kernel (cuda_depth.synthesize_right_view), which
-never stores the upsampled volume or the shifted copies.  No network definition, weights or training code are part of
-this package."""
+never stores the upsampled volume or the shifted copies.  For training, the network, the loss, the optimiser and the
+loop stay the caller's; the differentiable head is here: SelectionLayer (cuda_depth.synthesis_head), the same fused
+kernel without the rescale and a hand-written HIP backward that gives the volume's gradient.  No network definition or
+weights are part of this package."""
 from __future__ import annotations
 
 from typing import Callable, Optional, Tuple
@@ -16,7 +18,32 @@ import torch.nn.functional as F
 
 import cuda_depth
 
-__all__ = ["RightViewSynthesis", "DisparityOracleModel"]
+__all__ = ["RightViewSynthesis", "DisparityOracleModel", "SelectionLayer"]
+
+
+class SelectionLayer(torch.nn.Module):
+    """The selection layer of Deep3D for training: forward(probabilities, left_full) -> the generated right view in
+    0..1, [n, C, H, W] float32, differentiable with respect to probabilities (cuda_depth.synthesis_head).
+
+    It takes the low-resolution volume [n, D, H / scale, W / scale] as the network's softmax leaves it, not the
+    upsampled one: it is the drop-in for F.interpolate(volume, scale_factor=scale, mode="bilinear") followed by the
+    reference's ViewSynthesisNetwork (shifted copies, product, sum), in two launches per step instead of a
+    D x C x H x W stack held for autograd.  left_full is the frame in 0..1 (float32) or uint8; it gets no gradient.
+    The layer has no parameters; the loss (the reference: L1 against the true right view) is the caller's."""
+
+    def __init__(self, scale: int = 4):
+        super().__init__()
+        if isinstance(scale, bool) or not isinstance(scale, int):
+            raise TypeError("scale must be an int")
+        if not 1 <= scale <= 16:
+            raise ValueError(f"scale must be in 1..16, got {scale}")
+        self.scale = scale
+
+    def forward(self, probabilities: torch.Tensor, left_full: torch.Tensor) -> torch.Tensor:
+        return cuda_depth.synthesis_head(probabilities, left_full, self.scale)
+
+    def extra_repr(self) -> str:
+        return f"scale={self.scale}"
 
 
 class DisparityOracleModel:

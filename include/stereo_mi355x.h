@@ -35,6 +35,7 @@
  *                                                         smx_sgm_with_right_map
  *   -- (metric 3D points, coloured, compacted)            smx_reproject_points, smx_reproject_workspace_bytes
  *   -- (voxel-grid downsampling of those points)          smx_voxel_downsample, smx_voxel_workspace_bytes
+ *   -- (those points back into a camera: z-buffered map)  smx_project_points, smx_project_workspace_bytes
  *   -- (TSDF fusion of posed maps into a voxel volume)    smx_tsdf_integrate, smx_tsdf_integrate_workspace_bytes
  *   -- (surface points of that volume, ordered)           smx_tsdf_extract_points, smx_tsdf_extract_workspace_bytes
  *   -- (triangles over those points: marching cubes)      smx_tsdf_extract_triangles,
@@ -56,7 +57,7 @@
  *     torch's allocator) return and the rounding of the layouts inside it, which hold
  *     8-byte values and atomics.  Every entry that takes a workspace (smx_filter_speckles,
  *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
- *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample,
+ *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample, smx_project_points,
  *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles,
  *     smx_tsdf_raycast, smx_track_camera) returns
  *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
@@ -782,6 +783,41 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
                          const int32_t *offsets, float voxel_size, int min_points, float *out_points,
                          uint8_t *out_colors, int32_t *out_counts, int32_t *out_offsets, int32_t *dropped,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_project_points: the inverse of smx_reproject_points -- n point clouds projected into n camera views of H x W
+ * pixels as disparity maps, with a depth test.  points [capacity][3] f32 and offsets [n+1] int32 on the device: cloud f
+ * is rows [offsets[f], offsets[f+1]), the offsets used clamped to a non-decreasing sequence in [0, capacity] as
+ * smx_voxel_downsample uses them; point j of a cloud is its j-th row.  world_to_camera [n][3][4] f32 (device, row-major),
+ * as for smx_tsdf_integrate; P: host 4x4, [u' v' d' w'] = P [X Y Z 1] (the Python layer passes inv(Q), computed in float64
+ * and rounded once).  radius in 0..8: a point covers the square of (2 radius + 1)^2 pixels around its pixel.
+ * Every step is ONE float32 operation (no fused multiply-add, correctly rounded division), in this order, on every
+ * implementation.  For point j = (x, y, z) of cloud f, with M = world_to_camera[f]:
+ *   c_r = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3]            r = 0, 1, 2
+ *   skip unless c_2 is finite, c_2 > 0 and z_min <= c_2 <= z_max
+ *   p_r = ((P[r][0]*c_0 + P[r][1]*c_1) + P[r][2]*c_2) + P[r][3]      r = 0, 1, 2, 3
+ *   skip unless p_3 > 0
+ *   fu = floorf(p_0/p_3 + 0.5f), fv = floorf(p_1/p_3 + 0.5f)
+ *   skip unless -R <= fu <= (W-1)+R and -R <= fv <= (H-1)+R          R = (float)radius; compared as floats, NaN fails
+ *   d = p_2/p_3; skip unless d is finite and d != invalid_disparity
+ *   the point is a candidate for every pixel ((int)fu + dx, (int)fv + dy), |dx|, |dy| <= radius, that lies in the image
+ * The winner of a pixel is its candidate with the smallest c_2 and, among equal c_2, the smallest j: c_2 > 0, so its bit
+ * pattern orders as an unsigned integer, and the winner is the minimum of the 64-bit keys (bits(c_2) << 32) | j.
+ * Outputs: disp [n][H][W] f32, the winner's d, invalid_disparity where no point lands; index [n][H][W] int32 (NULL: none),
+ * the winner's j, -1 where none; depth [n][H][W] f32 (NULL: none), the winner's c_2, NaN where none.  The result depends
+ * on neither the grid, the scheduling nor n: cloud f's view is the same bits alone or in a batch, and from run to run.
+ * Three launches on `stream` (a caller's stream) -- clear the keys, splat, resolve -- with integer atomics only (one
+ * 64-bit unsigned minimum per candidate), no float atomics, no host synchronisation and no allocation: graph-capturable.
+ * workspace: smx_project_workspace_bytes(n, H, W) bytes -- the keys, 8 bytes per output pixel, and the n+1 clamped
+ * offsets, each rounded up to 256 bytes; 0 for sizes the call rejects.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched: a NULL points, offsets, world_to_camera, P, disp or
+ * workspace; n outside 1..65536; capacity outside 1..2^30; H or W outside 1..32768 or n*H*W > 2^30; radius outside 0..8;
+ * a non-finite P entry; a NaN z bound or z_min > z_max; a non-finite invalid_disparity; workspace_bytes below the query;
+ * an output or the workspace overlapping an input or another output; stream == SMX_STREAM_ENGINE. */
+size_t smx_project_workspace_bytes(int n, int H, int W);
+int smx_project_points(int device_id, int n, int capacity, int H, int W, const float *points, const int32_t *offsets,
+                       const float *world_to_camera, const float P[16], int radius, float z_min, float z_max,
+                       float invalid_disparity, float *disp, int32_t *index, float *depth, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /* ---- TSDF fusion ----------------------------------------------------------------------------------------------------
  * A volume of nx * ny * nz voxels with edge s = voxel_size and origin o (host float[3]); voxel (i, j, k) has the linear

@@ -145,6 +145,13 @@ hipError_t launch_voxel_downsample(int n, int capacity, const float *points, con
 // a launch returns at once when gate != NULL and pass * 8 >= *gate (the radix passes of the downsampling)
 void launch_scan(const int *in, int *out, long L, int *block_sums, const int *gate, int pass, hipStream_t s);
 
+// ---- tu_project.hip: point clouds projected into camera views with a depth test (k_project.h) ---------------------------
+// p: the host's 4x4 matrix, copied into the kernel arguments; index / depth may be NULL; workspace:
+// project_layout(n, H, W); arguments checked by smx_project_points
+void launch_project(int n, int capacity, int H, int W, const float *points, const int32_t *offsets,
+                    const float *world_to_camera, const float p[16], int radius, float zmin, float zmax, float invalid,
+                    float *disp, int32_t *index, float *depth, void *workspace, hipStream_t s);
+
 // ---- tu_tsdf.hip: TSDF fusion and surface extraction (k_tsdf.h, k_mesh.h) --------------------------------------------------------
 // q / p / origin: host values, copied into the kernel arguments; world_to_camera [n][3][4] on the device; conf / color /
 // image may be NULL (color needs image); workspace: tsdf_integrate_layout(n, H, W); arguments checked by smx_tsdf_integrate

@@ -605,6 +605,43 @@ int smx_voxel_downsample(int device_id, int n, int capacity, const float *points
     });
 }
 
+// ---- point clouds back into camera views -------------------------------------------------------------------------------
+static bool project_dims_ok(int n, int H, int W) { return n <= 65536 && points_dims_ok(n, H, W); }
+
+size_t smx_project_workspace_bytes(int n, int H, int W) {
+    return project_dims_ok(n, H, W) ? project_layout(n, H, W).total : 0;
+}
+
+int smx_project_points(int device_id, int n, int capacity, int H, int W, const float *points, const int32_t *offsets,
+                       const float *world_to_camera, const float P[16], int radius, float z_min, float z_max,
+                       float invalid_disparity, float *disp, int32_t *index, float *depth, void *workspace,
+                       size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_project_points";
+    if (!points || !offsets || !world_to_camera || !P || !disp || !workspace)
+        return fail(SMX_ERR_INVALID_ARG, "%s: points, offsets, world_to_camera, P, disp and workspace must be non-NULL", fn);
+    if (!voxel_dims_ok(n, capacity))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= n <= 65536 and 1 <= capacity <= 2^30 (got n %d, capacity %d)", fn,
+                    n, capacity);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (int rc = check_int_range(fn, "radius", radius, 0, 8)) return rc;
+    if (int rc = check_finite_array(fn, "P", P, 16)) return rc;
+    if (int rc = check_reprojection_args(fn, z_min, z_max, 0.0f, invalid_disparity, nullptr, 0, 0, nullptr, "")) return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_project_workspace_bytes", workspace_bytes, project_layout(n, H, W).total))
+        return rc;
+    const size_t plane = (size_t)n * H * W * sizeof(float);
+    if (int rc = check_disjoint(fn, {{points, (size_t)capacity * 3 * sizeof(float)}, {offsets, ((size_t)n + 1) * sizeof(int32_t)},
+                                     {world_to_camera, (size_t)n * 12 * sizeof(float)}},
+                                {{disp, plane}, {index, plane}, {depth, plane}, {workspace, workspace_bytes}},
+                                "an output or the workspace overlaps an input", "two outputs (or one and the workspace) overlap"))
+        return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_project(n, capacity, H, W, points, offsets, world_to_camera, P, radius, z_min, z_max,
+                            invalid_disparity, disp, index, depth, workspace, (hipStream_t)stream);
+    });
+}
+
 // ---- TSDF fusion -------------------------------------------------------------------------------------------------------
 static constexpr long SMX_TSDF_VOXELS_MAX = 1L << 30;
 

@@ -112,6 +112,16 @@ inline VoxLayout vox_layout(int n, int cap) {
     return l;
 }
 
+// ---- projection of point clouds: one 64-bit key per output pixel | the clamped offsets int[n + 1] -----------------------
+struct ProjectLayout {
+    WsPart keys, off;
+    size_t total;
+};
+inline ProjectLayout project_layout(int n, int H, int W) {
+    WsCursor c;
+    return ProjectLayout{c.take((size_t)n * H * W * sizeof(unsigned long long)), c.take(((size_t)n + 1) * sizeof(int)), c.at};
+}
+
 // ---- TSDF integrate: measurements float2[P] | colour words u32[P] ---------------------------------------------------
 struct TsdfIntegrateLayout {
     WsPart meas, pcol;

@@ -1571,6 +1571,154 @@ def camera_to_world_poses(camera_to_world) -> np.ndarray:
     return np.ascontiguousarray(m32)
 
 
+# ---- point clouds back into camera views ---------------------------------------------------------------------------------
+
+@dataclasses.dataclass
+class ProjectedView:
+    """A point cloud seen from a camera (project_points): planes [H, W].  disparity: float32, in the convention of every
+    disparity map of this library, invalid_disparity where no point lands; index: int32, the row of the cloud's point
+    that won the pixel's depth test, -1 where none (None with index=False) -- gather any per-point attribute with it;
+    depth: float32 camera depth of that point, NaN where none (None with depth=False); colors: [3, H, W] uint8 RGB
+    gathered from the cloud's colours, 0 where nothing landed (None without them)."""
+    disparity: torch.Tensor
+    index: Optional[torch.Tensor] = None
+    depth: Optional[torch.Tensor] = None
+    colors: Optional[torch.Tensor] = None
+
+
+def _check_p(P) -> np.ndarray:
+    p = np.asarray(P.detach().cpu() if isinstance(P, torch.Tensor) else P)
+    if p.shape != (4, 4) or not np.issubdtype(p.dtype, np.number):
+        raise RuntimeError(f"P must be a numeric 4x4 matrix, got shape {p.shape}")
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    if not np.isfinite(p).all():
+        raise RuntimeError("P must be finite (in float32)")
+    return p
+
+
+def _check_world_to_camera(world_to_camera) -> np.ndarray:
+    m = np.asarray(world_to_camera.detach().cpu() if isinstance(world_to_camera, torch.Tensor) else world_to_camera)
+    if m.ndim != 3 or m.shape[1:] != (3, 4) or m.shape[0] < 1 or not np.issubdtype(m.dtype, np.number):
+        raise RuntimeError(f"world_to_camera must be a numeric [n, 3, 4] array, got shape {m.shape}")
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    if not np.isfinite(m).all():
+        raise RuntimeError("world_to_camera must be finite (in float32)")
+    return m
+
+
+def project_points_batched(points: torch.Tensor, offsets: torch.Tensor, Q, camera_to_world, shape, *, P=None,
+                           radius: int = 0, depth_range=(0.0, math.inf), invalid_disparity: float = -1.0,
+                           index: bool = True, depth: bool = False, world_to_camera=None):
+    """n point clouds into n camera views of shape (H, W) as z-buffered disparity maps, without synchronising
+    (smx_project_points, on the current stream; the rule is in include/stereo_mi355x.h): the inverse of
+    reproject_to_3d_batched.  points: [cap, 3] float32, offsets: [n + 1] int32 on the same device (cloud f is rows
+    offsets[f]..offsets[f+1]), e.g. reproject_to_3d_batched's or voxel_downsample_batched's.  camera_to_world: [n, 4, 4]
+    (numpy or tensor), inverted in float64 as TSDFVolume.integrate does; world_to_camera=[n, 3, 4] float32 gives the
+    matrices applied to the points as they are instead (then camera_to_world must be None; a CUDA tensor is used in place,
+    which is the form to capture into a graph).  Q: the views' reprojection matrix, whose inverse projection_matrix(Q)
+    takes camera points to (column, row, disparity); P=, a 4x4 with [u' v' d' w'] = P [X Y Z 1], replaces it (exactly
+    one of Q and P).  A point counts where its camera depth c_2 is > 0
+    and within depth_range, its rounded pixel lies within `radius` (0..8) of the image and its disparity is finite and
+    != invalid_disparity; it covers the (2 radius + 1)^2 pixels around its pixel.  Every pixel keeps its nearest point
+    (the lowest row among equally near ones).  Returns fresh tensors (disparity [n, H, W] float32 with
+    invalid_disparity where nothing lands, index [n, H, W] int32 row within the cloud or -1 (None with index=False),
+    depth [n, H, W] float32 c_2 or NaN (None with depth=False)); the same bits on every run."""
+    if (Q is None) == (P is None):
+        raise RuntimeError("exactly one of Q and P must be given")
+    p = projection_matrix(Q) if P is None else _check_p(P)
+    z_min, z_max = _check_reproject_params(0.0, depth_range, invalid_disparity)
+    _int_arg("radius", radius)
+    if not 0 <= radius <= 8:
+        raise RuntimeError(f"radius must be in 0..8, got {radius}")
+    for name, v in (("index", index), ("depth", depth)):
+        if not isinstance(v, bool):
+            raise TypeError(f"{name} must be a bool")
+    if (camera_to_world is None) == (world_to_camera is None):
+        raise RuntimeError("exactly one of camera_to_world and world_to_camera must be given")
+    on_device = isinstance(world_to_camera, torch.Tensor) and world_to_camera.is_cuda
+    if on_device:                                                       # used as it is: nothing is copied or read here
+        _check_input("world_to_camera", world_to_camera)
+        if world_to_camera.dtype != torch.float32 or world_to_camera.dim() != 3 or tuple(world_to_camera.shape[1:]) != (3, 4):
+            raise RuntimeError(f"a device world_to_camera must be float32 [n, 3, 4], got {world_to_camera.dtype} "
+                               f"{tuple(world_to_camera.shape)}")
+        w2c = world_to_camera
+    elif world_to_camera is None:
+        w2c = world_to_camera_poses(camera_to_world)
+    else:
+        w2c = _check_world_to_camera(world_to_camera)
+    H, W = _shape2("shape", shape)
+    _check_input("points", points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise RuntimeError(f"points must be float32 [cap >= 1, 3], got {points.dtype} {tuple(points.shape)}")
+    cap, dev = points.shape[0], points.device
+    if cap > 2 ** 30:
+        raise RuntimeError(f"at most 2^30 points, got {cap}")
+    _check_input("offsets", offsets)
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or not 2 <= offsets.shape[0] <= 65537 or offsets.device != dev:
+        raise RuntimeError(f"offsets must be int32 [n + 1] with 1 <= n <= 65536 on {dev}")
+    n = offsets.shape[0] - 1
+    if w2c.shape[0] != n:
+        raise RuntimeError(f"{n} cloud(s) need {n} pose(s), got {w2c.shape[0]}")
+    if n * H * W > 2 ** 30:
+        raise RuntimeError(f"need n * H * W <= 2^30, got {n} views of {(H, W)}")
+    if on_device and w2c.device != dev:
+        raise RuntimeError(f"world_to_camera must be on {dev}, got {w2c.device}")
+    poses = w2c if on_device else torch.from_numpy(w2c).pin_memory().to(dev, non_blocking=True)
+    disp = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    idx = torch.empty((n, H, W), dtype=torch.int32, device=dev) if index else None
+    dep = torch.empty((n, H, W), dtype=torch.float32, device=dev) if depth else None
+    ws_bytes = LIB.smx_project_workspace_bytes(n, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    pc = (C.c_float * 16)(*p.reshape(-1).tolist())
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    check(LIB.smx_project_points(dev.index, n, cap, H, W, points.data_ptr(), offsets.data_ptr(), poses.data_ptr(), pc,
+                                 int(radius), z_min, z_max, float(invalid_disparity), disp.data_ptr(), ptr(idx), ptr(dep),
+                                 ws.data_ptr(), ws_bytes, _stream(dev.index)))
+    return disp, idx, dep
+
+
+def project_points(cloud, Q, camera_to_world=None, shape=None, **kwargs) -> ProjectedView:
+    """One PointCloud, or an [N, 3] float32 tensor of points, seen from camera_to_world [4, 4] (the identity by default)
+    through a camera with the reprojection matrix Q, as maps of shape (H, W): project_points_batched of one cloud, with
+    its keywords (P, radius, depth_range, invalid_disparity, index, depth).  Returns a ProjectedView; colors is the
+    cloud's colours gathered through the index plane (which is then computed even with index=False, and not
+    returned).  An empty cloud gives an empty view."""
+    if shape is None:
+        raise TypeError("project_points needs shape=(H, W)")
+    points, colors = (cloud.points, cloud.colors) if isinstance(cloud, PointCloud) else (cloud, None)
+    if not isinstance(points, torch.Tensor):
+        raise TypeError("project_points takes a PointCloud or an [N, 3] tensor")
+    _check_input("points", points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"points must be float32 [N, 3], got {points.dtype} {tuple(points.shape)}")
+    N, dev = points.shape[0], points.device
+    if colors is not None:
+        _check_like("colors", colors, torch.uint8, (N, 3), dev)
+    if camera_to_world is None and kwargs.get("world_to_camera") is None:
+        camera_to_world = np.eye(4)
+    elif camera_to_world is not None and (camera_to_world.dim() if isinstance(camera_to_world, torch.Tensor)
+                                          else np.ndim(camera_to_world)) != 2:
+        raise RuntimeError("project_points takes one pose [4, 4]")
+    want_index = kwargs.pop("index", True)
+    if not isinstance(want_index, bool):
+        raise TypeError("index must be a bool")
+    offsets = torch.tensor([0, N], dtype=torch.int32).to(dev)
+    if N == 0:                                                         # the device call needs room for one point
+        points = torch.zeros((1, 3), dtype=torch.float32, device=dev)
+    disp, idx, dep = project_points_batched(points, offsets, Q, camera_to_world, shape,
+                                            index=want_index or colors is not None, **kwargs)
+    view_colors = None
+    if colors is not None:
+        if N == 0:
+            view_colors = torch.zeros((3,) + tuple(disp.shape[1:]), dtype=torch.uint8, device=dev)
+        else:
+            hit = idx[0] >= 0
+            gathered = colors[idx[0].clamp(min=0).long()]                  # [H, W, 3]
+            view_colors = (gathered * hit.unsqueeze(-1)).permute(2, 0, 1).contiguous()
+    return ProjectedView(disparity=disp[0], index=idx[0] if want_index else None,
+                         depth=None if dep is None else dep[0], colors=view_colors)
+
+
 def _check_tsdf_volume(dims, voxel_size, origin) -> Tuple[Tuple[int, int, int], float, Tuple[float, float, float]]:
     try:
         nx, ny, nz = dims
@@ -1981,6 +2129,17 @@ class TSDFVolume:
                                      n, H, W, disp.data_ptr(), qc, pc, poses.data_ptr(), ptr(confidence),
                                      float(min_confidence), z_min, z_max, float(invalid_disparity), ptr(image),
                                      channels, dtype, ws.data_ptr(), ws_bytes, _stream(self.device.index)))
+
+    def integrate_points(self, cloud, Q, camera_to_world, shape, *, radius: int = 0, **integrate_kwargs) -> None:
+        """Fuses a point cloud (a PointCloud or an [N, 3] tensor: a LiDAR scan, a spilled box's cloud, a downsampled
+        cloud) as the measurement of a camera at camera_to_world [4, 4] with the reprojection matrix Q and (H, W) pixels.
+        Composition only: integrate(project_points(cloud, Q, camera_to_world, shape, radius=radius, ...).disparity, Q,
+        camera_to_world, image=the view's colours, ...); depth_range and invalid_disparity go to both, the other
+        keywords to integrate.  A colour volume needs a cloud with colours (or image=)."""
+        shared = {k: integrate_kwargs[k] for k in ("depth_range", "invalid_disparity") if k in integrate_kwargs}
+        view = project_points(cloud, Q, camera_to_world, shape, radius=radius, index=False, **shared)
+        integrate_kwargs.setdefault("image", view.colors)
+        self.integrate(view.disparity, Q, camera_to_world, **integrate_kwargs)
 
     def _check_render_args(self, Q, camera_to_world, shape, min_weight, step, depth_range, normals, colors,
                            invalid_disparity):

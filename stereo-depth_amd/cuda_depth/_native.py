@@ -169,6 +169,13 @@ EXPORTS = {
     "smx_voxel_downsample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    # projection of point clouds into views: (n, H, W) -> workspace bytes; (device_id, n, capacity, H, W, points, offsets,
+    # world_to_camera, P (host float32[16]), radius, z_min, z_max, invalid_disparity, disp, index, depth, workspace,
+    # workspace_bytes, stream)
+    "smx_project_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "smx_project_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # TSDF fusion: (n, H, W) -> workspace bytes; (device_id, nx, ny, nz, origin (host float32[3]), voxel_size,
     # truncation, max_weight, tsdf, weight, color, n, H, W, disp, Q, P (host float32[16]), world_to_camera, confidence,
     # min_confidence, z_min, z_max, invalid_disparity, image, image_channels, image_dtype, workspace, workspace_bytes,

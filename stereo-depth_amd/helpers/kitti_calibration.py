@@ -138,6 +138,60 @@ def velodyne_depth_map(calib_dir: str, velo_file_name: str, im_shape: Tuple[int,
     return depth
 
 
+def velodyne_projection(calib_dir: str, cam: int = 2) -> Tuple[np.ndarray, np.ndarray]:
+    """velodyne_to_image_projection in the two factors cuda_depth.project_points_batched takes: (M [3, 4] float32, the top
+    rows of rectify @ rigid, velodyne -> rectified camera 0 frame; P [4, 4] float32 with [u' v' d' w'] = P [X Y Z 1]), both
+    computed in float64 and rounded once.  With Pr = P_rect_0<cam>: rows 0 and 1 of P are Pr[0] - Pr[2] and Pr[1] - Pr[2],
+    so that u'/w' and v'/w' are the projected column and row minus the devkit's 1; row 3 is Pr[2]; row 2 is
+    [0, 0, 0, focal * baseline] of focal_length_and_baseline, a disparity over the projective depth."""
+    cam2cam = read_calibration(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
+    velo2cam = read_calibration(os.path.join(calib_dir, "calib_velo_to_cam.txt"))
+    rigid = np.eye(4)
+    rigid[:3, :3] = np.asarray(velo2cam["R"]).reshape(3, 3)
+    rigid[:3, 3] = np.asarray(velo2cam["T"])
+    rectify = np.eye(4)
+    rectify[:3, :3] = np.asarray(cam2cam["R_rect_00"]).reshape(3, 3)
+    pr = np.asarray(cam2cam["P_rect_0" + str(cam)], dtype=np.float64).reshape(3, 4)
+    focal, baseline = focal_length_and_baseline(calib_dir)
+    P = np.stack([pr[0] - pr[2], pr[1] - pr[2], np.array([0.0, 0.0, 0.0, focal * baseline]), pr[2]])
+    return (rectify @ rigid)[:3].astype(np.float32), P.astype(np.float32)
+
+
+def velodyne_disparity_map_device(calib_dir: str, velo_file_name: str, im_shape: Tuple[int, int], device, cam: int = 2):
+    """The ground-truth disparity of one scan, [H, W] float64 on `device`, 0 where no return lands: what
+    KittiSingleViewCamera derives from velodyne_depth_map(..., vel_depth=True), with the projection and the choice among
+    the returns of a pixel on the GPU (cuda_depth.project_points_batched with velodyne_projection's matrices).  The scan is
+    loaded and its returns behind the sensor (x < 0) dropped on the host, as the reference does; the value of a pixel is
+    baseline * focal / x of the return that won it, in float64 and in the camera's own torch expression.
+
+    It differs from the host path on purpose in two places.  Where several returns land on one pixel, the nearest by
+    camera depth is kept; the host path keeps what the reference's aliasing `sub2ind` grouping produces (the last return
+    in scan order, or the smallest depth of an aliased group written at the group's first pixel).  And the projection is
+    float32: a return that projects exactly onto a half-pixel boundary may round to the other pixel.  On pixels hit by
+    exactly one return away from such boundaries the two paths agree bit for bit.  (A return at or behind the camera's
+    plane, which the host path would still project, is dropped.)"""
+    import cuda_depth
+    import torch
+    H, W = int(im_shape[0]), int(im_shape[1])
+    device = torch.device(device)
+    M, P = velodyne_projection(calib_dir, cam)
+    focal, baseline = focal_length_and_baseline(calib_dir)
+    scan = load_velodyne_scan(velo_file_name)
+    scan = scan[scan[:, 0] >= 0, :]
+    count = scan.shape[0]
+    if count == 0:
+        return torch.zeros((H, W), dtype=torch.float64, device=device)
+    points = torch.from_numpy(np.ascontiguousarray(scan[:, :3])).to(device)
+    offsets = torch.tensor([0, count], dtype=torch.int32).to(device)
+    _, index, _ = cuda_depth.project_points_batched(points, offsets, None, None, (H, W), P=P, world_to_camera=M[None],
+                                                    invalid_disparity=0.0)
+    index = index[0]
+    forward = points[:, 0].to(torch.float64)[index.clamp(min=0).long()]
+    disparity = baseline * focal / forward                              # x = 0 -> inf -> 0, as the host path
+    zero = torch.zeros((), dtype=torch.float64, device=device)
+    return torch.where((index >= 0) & ~torch.isinf(disparity), disparity, zero)
+
+
 def reprojection_matrix(calib_dir: str, cams: Tuple[int, int] = (2, 3)) -> np.ndarray:
     """The float32 4x4 reprojection matrix Q (cuda_depth.reprojection_matrix) of a rectified camera pair from
     calib_cam_to_cam.txt: fx, fy, cx, cy of P_rect_0<left>, cx_right of P_rect_0<right>, and the baseline

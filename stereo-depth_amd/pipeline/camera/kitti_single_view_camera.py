@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from helpers.kitti_calibration import focal_length_and_baseline, velodyne_depth_map
+from helpers.kitti_calibration import focal_length_and_baseline, velodyne_depth_map, velodyne_disparity_map_device
 from pipeline.camera.camera import EvaluationCamera
 
 KITTI_RAW_SHAPE = (375, 1242)            # what the ground-truth projection assumes (.py:60)
@@ -51,12 +51,17 @@ def _read_png_chw_u8(path: str) -> torch.Tensor:
 
 class KittiSingleViewCamera(EvaluationCamera):
 
-    def __init__(self, drive_dir: str, return_right_view: bool = False, only_one: bool = False):
+    def __init__(self, drive_dir: str, return_right_view: bool = False, only_one: bool = False,
+                 gt_on_device: bool = False):
+        """gt_on_device: the ground-truth disparity is projected on the GPU (helpers.kitti_calibration.
+        velodyne_disparity_map_device, which documents where it differs from the host path) and yielded as a CUDA float64
+        tensor with the same padding; by default it is computed on the host, as the reference does."""
         drive_dir = os.path.abspath(drive_dir)
         self._calib_dir = os.path.dirname(drive_dir.rstrip(os.sep))
         self._left_images, self._right_images = list_drive_stereo_pairs(drive_dir)
         self._return_right_view = return_right_view
         self._only_one = only_one
+        self._gt_on_device = gt_on_device
         self._focal_length, self._baseline = focal_length_and_baseline(self._calib_dir)
 
     def focal_length(self) -> float:
@@ -89,6 +94,9 @@ class KittiSingleViewCamera(EvaluationCamera):
         return _pad(_read_png_chw_u8(path))
 
     def _load_velodyne_gt_disparity_map(self, left_image_path: str) -> torch.Tensor:
+        if self._gt_on_device:
+            return _pad(velodyne_disparity_map_device(self._calib_dir, self._velodyne_path(left_image_path),
+                                                      KITTI_RAW_SHAPE, torch.device("cuda", torch.cuda.current_device())))
         depth = torch.from_numpy(velodyne_depth_map(self._calib_dir, self._velodyne_path(left_image_path),
                                                     KITTI_RAW_SHAPE, vel_depth=True))
         disparity = self._baseline * self._focal_length / depth        # .py:68-69; depth 0 -> inf

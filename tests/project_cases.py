@@ -92,3 +92,50 @@ def twin_ground_truth(calib_dir, velo_file):
     forward = torch.from_numpy(scan[:, 0].astype(np.float64)[np.maximum(index, 0)])
     disparity = (baseline * focal / forward).numpy()                           # in torch, as the device path and the camera
     return np.where((index >= 0) & ~np.isinf(disparity), disparity, 0.0)
+
+
+def tiny_clouds(seed, n, most, H, W, Q, margin=1.5):
+    """A batch of n clouds of 0..most points each (points [total + 1, 3] float32 with one spare row, offsets [n + 1] int32,
+    the index of a cloud that follows a run of empty ones): the first two and the last three clouds are empty, and so are
+    40 in a row from n // 3 on, more than one thread's share of the offsets at any n; the cloud after them has `most`
+    points.  The points land in or within `margin` pixels of an H x W view of Q from near the identity, at depths on a
+    0.1 m grid so that equal depths meet."""
+    rng = np.random.default_rng(seed)
+    counts = rng.integers(0, most + 1, n)
+    after = n // 3 + 40
+    counts[:2], counts[-3:], counts[n // 3:after], counts[after] = 0, 0, 0, most
+    total = int(counts.sum())
+    u = rng.uniform(-margin, W - 1 + margin, total)
+    v = rng.uniform(-margin, H - 1 + margin, total)
+    z = np.round(rng.uniform(0.4, 6.0, total), 1)
+    z[rng.random(total) < 0.03] *= -1
+    fx, fy, cx, cy = float(Q[2, 3]), float(Q[2, 3] / Q[1, 1]), -float(Q[0, 3]), -float(Q[1, 3] / Q[1, 1])
+    pts = np.stack([(u - cx) * z / fx, (v - cy) * z / fy, z], 1).astype(np.float32)
+    pts = np.concatenate([pts, np.zeros((1, 3), np.float32)])
+    return pts, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), after
+
+
+def near_identity_views(seed, n):
+    """n world-to-camera matrices [n, 3, 4] float32: the identity moved by a few centimetres."""
+    rng = np.random.default_rng(seed)
+    w2c = np.tile(np.eye(4, dtype=np.float32)[:3], (n, 1, 1))
+    w2c[:, :, 3] = rng.uniform(-0.05, 0.05, (n, 3)).astype(np.float32)
+    return w2c
+
+
+def unruly_offsets(off, cap):
+    """The offsets of a batch with entries that the device has to clamp (points3d_ref.clamp_offsets), for a batch whose
+    n + 1 offsets give a thread of the clamping workgroup `per` = 3 entries (513 <= n + 1 <= 768): negative entries, a
+    large entry at the middle, the end and the start of a thread's share, each of which raises every later entry up to
+    where the true offsets pass it, and an entry above the capacity near the end."""
+    n1 = len(off)
+    per = (n1 + 255) // 256
+    assert per == 3 and n1 > 660, n1
+    raw = np.array(off, dtype=np.int64)
+    raw[0], raw[10], raw[31] = -3, -5, -2 ** 31
+    raw[50 * per + 1] = off[50 * per + 61]               # thread 50's middle entry: clouds up to 60 further on are emptied
+    raw[110 * per + 2] = off[110 * per + 80]             # the last entry of thread 110's share
+    raw[170 * per] = off[170 * per + 47]                 # the first entry of thread 170's
+    raw[650] = cap + 7                                   # everything from here on is clamped to the capacity
+    raw[655] = 2 ** 31 - 1
+    return raw.astype(np.int32)

@@ -187,6 +187,23 @@ def test_voxel_edge_cases(cd):
         voxel_check(cd, pts, None, off, vs, mp)
 
 
+@pytest.mark.parametrize("mp", [1, 2])
+def test_voxel_700_tiny_maps(cd, mp):
+    """700 maps of 0..6 points, many of them empty (tests/project_cases.py: tiny_clouds, folded into one octant): one
+    partial tile and one slice of the histograms per map, and the dropped counts of many maps inside one wave.  At 3 m
+    the voxels are about half as many as the points."""
+    import project_cases
+    Q = cd.reprojection_matrix(60.0, 2.25, 0.5, 0.3, fy=60.6)
+    pts, off, _ = project_cases.tiny_clouds(700, 700, 6, 3, 5, Q)
+    pts = np.abs(pts)
+    cols = np.random.default_rng(700).integers(0, 256, (len(pts), 3)).astype(np.uint8)
+    e = ref.voxel_ref(pts, cols, off, 3.0, mp)
+    assert 0.4 < ref.voxel_ref(pts, None, off, 3.0, 1)[3][-1] / off[-1] < 0.6
+    assert (np.diff(off) == 0).sum() > 100 and (mp == 1 or (e[4] > 0).sum() > 200)
+    voxel_check(cd, pts, cols, off, 3.0, mp)
+    voxel_check(cd, pts, None, off, 3.0, mp)
+
+
 def test_voxel_independent_of_batch_and_runs(cd):
     rng = np.random.default_rng(21)
     n, H, W = 4, 40, 100

@@ -1,7 +1,7 @@
 """Projection of point clouds into camera views on the device (include/stereo_mi355x.h: smx_project_points), bit for bit
 against the NumPy twin (tests/project_ref.py): tiny, odd and batched shapes with every radius and plane selection,
-contention on a handful of pixels, run-to-run and batch independence, row order, unaligned points, clamped offsets, the
-round trip through reproject_to_3d_batched, graph replay, TSDFVolume.integrate_points and the KITTI ground truth."""
+contention on a handful of pixels, run-to-run and batch independence, row order, unaligned points, clamped offsets,
+batches of 700 and of 65536 tiny and empty clouds, the round trip through reproject_to_3d_batched, graph replay, TSDFVolume.integrate_points and the KITTI ground truth."""
 import ctypes as C
 import math
 import os
@@ -215,6 +215,74 @@ def test_device_offsets_are_clamped(cd):
         got = run(cd, pts, raw, Q, c2w, (33, 257), radius=1, depth=True)
         clamped = ref.clamp_offsets(raw, cap)
         assert_planes(got, ref.project_ref(pts, clamped, w2c, P, (33, 257), radius=1), f"offsets {raw}")
+
+
+# ---- many clouds, most of them tiny or empty ----------------------------------------------------------------------------
+# k_project_clear clamps the n + 1 offsets with 256 threads, per = (n + 256) // 256 entries each: the loop inside a thread
+# and the carry from one thread's share into the next exist from n = 256 on.  k_project_splat's search between the
+# workgroup's first and last cloud has more than two clouds to choose from only where clouds are shorter than 256 rows.
+
+def alone_equals_batch(cd, pts, off, Q, w2c, shape, together, clouds, radius):
+    for f in clouds:
+        assert off[f + 1] > off[f], f
+        alone = run(cd, pts[off[f]:off[f + 1]], [0, off[f + 1] - off[f]], Q, None, shape, radius=radius, depth=True,
+                    world_to_camera=w2c[f:f + 1])
+        for x, y in zip(alone, together):
+            assert torch.equal(x[0].view(torch.int32), y[f].view(torch.int32)), f
+
+
+@pytest.fixture(scope="module")
+def tiny700(cd):
+    """700 clouds of 0..6 points into 3 x 5 views: (pts, off, cloud after the empty run, Q, P, w2c)."""
+    n, H, W = 700, 3, 5
+    Q = q_matrix(cd, H, W)
+    pts, off, after = cases.tiny_clouds(700, n, 6, H, W, Q)
+    w2c = cd.world_to_camera_poses(poses(np.random.default_rng(701), n))
+    assert (np.diff(off) == 0).sum() > 100 and np.diff(off).max() == 6 and len(pts) > 256 * 6
+    return pts, off, after, Q, cd.projection_matrix(Q), w2c
+
+
+@pytest.mark.parametrize("radius", [0, 1])
+def test_700_tiny_clouds(cd, tiny700, radius):
+    pts, off, after, Q, P, w2c = tiny700
+    got = run(cd, pts, off, Q, None, (3, 5), radius=radius, depth=True, world_to_camera=w2c)
+    e = ref.project_ref(pts, off, w2c, P, (3, 5), radius=radius)
+    assert (e[1] >= 0).sum() > 300 and len({int(f) for f in np.argwhere(e[1] >= 0)[:, 0]}) > 200
+    assert_planes(got, e, f"700 tiny clouds, radius {radius}")
+    assert off[after] == off[after - 40], "a run of empty clouds before it"
+    full = np.flatnonzero(np.diff(off) > 0)
+    alone_equals_batch(cd, pts, off, Q, w2c, (3, 5), got, (int(full[0]), after, int(full[-1])), radius)
+
+
+@pytest.mark.parametrize("radius", [0, 1])
+def test_700_tiny_clouds_with_offsets_to_clamp(cd, tiny700, radius):
+    pts, off, _, Q, P, w2c = tiny700
+    cap = len(pts)
+    raw = cases.unruly_offsets(off, cap)
+    clamped = ref.clamp_offsets(raw, cap)
+    assert (np.diff(raw.astype(np.int64)) < 0).sum() >= 6 and raw.min() < 0 and raw.max() > cap
+    assert (clamped != off).sum() > 150 and (np.diff(clamped) > 0).sum() > 250 and clamped[-1] == cap
+    got = run(cd, pts, raw, Q, None, (3, 5), radius=radius, depth=True, world_to_camera=w2c)
+    e = ref.project_ref(pts, clamped, w2c, P, (3, 5), radius=radius)
+    assert not all(np.array_equal(a, b) for a, b in zip(e, ref.project_ref(pts, off, w2c, P, (3, 5), radius=radius)))
+    assert_planes(got, e, f"700 tiny clouds, clamped offsets, radius {radius}")
+
+
+def test_as_many_clouds_as_the_entry_takes(cd):
+    """n = 65536, the documented limit: 257 offsets per clamping thread, clouds of 0..2 points into 1 x 2 views."""
+    import time
+    n, H, W = 65536, 1, 2
+    Q = q_matrix(cd, H, W)
+    pts, off, after = cases.tiny_clouds(65536, n, 2, H, W, Q)
+    w2c = cases.near_identity_views(65537, n)
+    got = run(cd, pts, off, Q, None, (H, W), depth=True, world_to_camera=w2c)
+    t = time.perf_counter()
+    e = ref.project_ref(pts, off, w2c, cd.projection_matrix(Q), (H, W))
+    print(f"the twin's time for {n} clouds: {time.perf_counter() - t:.1f} s")
+    assert (e[1] >= 0).sum() > 5000 and (e[1][n // 2:] >= 0).sum() > 2500
+    assert_planes(got, e, f"{n} clouds")
+    full = np.flatnonzero(np.diff(off) > 0)
+    alone_equals_batch(cd, pts, off, Q, w2c, (H, W), got, (int(full[0]), after, int(full[-1])), 0)
 
 
 @pytest.mark.parametrize("name", list(cases.ROUND_TRIPS))

@@ -14,6 +14,7 @@ torch = pytest.importorskip("torch")
 
 import synthesis_grad_ref as gref                    # noqa: E402
 import synthesis_ref as ref                          # noqa: E402
+from synthesis_device_cases import assert_bitwise, bits, case, dev     # noqa: E402
 
 F = np.float32
 IDS = dict(ids=lambda s: "n%d_C%d_D%d_%dx%d_S%d" % s)
@@ -26,38 +27,6 @@ def cd():
         pytest.skip("no GPU")
     import cuda_depth
     return cuda_depth
-
-
-def bits(a) -> np.ndarray:
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
-
-
-def dev(a) -> "torch.Tensor":
-    """A device copy (the cached arrays of case() are read-only)."""
-    return torch.tensor(a, device="cuda")
-
-
-def assert_bitwise(got, expect, what):
-    g, e = bits(got), bits(expect)
-    assert g.shape == e.shape, f"{what}: shape {g.shape} != {e.shape}"
-    bad = np.argwhere(g != e)
-    assert bad.size == 0, f"{what}: {len(bad)} of {g.size} values differ, first at {tuple(bad[0])}"
-
-
-@functools.lru_cache(maxsize=None)
-def case(shape, u8=False):
-    """(prob, left, grad_view, expected view, expected grad_prob) of a shape, computed once and left unchanged."""
-    n, C, D, h, w, S = shape
-    rng = np.random.default_rng(sum(v * 31 ** i for i, v in enumerate(shape)))
-    prob = ref.softmax_noise(rng, n, D, h, w)
-    left = rng.integers(0, 256, (n, C, h * S, w * S)).astype(np.uint8) if u8 else ref.uniform_left(rng, n, C, h * S, w * S)
-    g = gref.gradient_noise(rng, n, C, h * S, w * S)
-    out = prob, left, g, gref.head_forward(prob, left, S), gref.head_backward(g, left, D, S)
-    for a in out:
-        a.setflags(write=False)
-    return out
 
 
 # ----------------------------------------------------------------------------- 1. the kernels against the twin

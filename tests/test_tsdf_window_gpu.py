@@ -17,10 +17,15 @@ import tsdf_window_ref as wref                      # noqa: E402
 
 SENTINEL = 0xDEADBEEF
 GUARDS = (5, 6, 7)                                   # words before each output: three different 16-byte phases
-SOURCE_DIMS = [(13, 7, 5), (1, 6, 4), (67, 9, 6), (130, 3, 3)]
+SOURCE_DIMS = [(13, 7, 5), (1, 6, 4), (67, 9, 6), (130, 3, 3), (517, 3, 2), (4096, 1, 2)]
 OTHER_DIMS = [(5, 3, 2), (16, 7, 9), (131, 4, 3)]
 MIXED_STARTS = [(-2, 1, -1), (3, -2, 2), (-5, -3, 4), (1, 1, 1), (-1, -1, -1), (4, -6, -2), (-64, 2, 1), (7, 0, -3),
                 (200, 0, 0), (0, -100, 0), (-131, -4, -3), (66, 8, 5)]
+# Rows of more than 64 quads: a lane of window_row takes a second trip from 260 voxels on (259 with a head of 3 words is
+# the last width without one), production volumes are 512 wide and the entry takes 4096.  source dims -> the windows'
+# dims; x0 puts lo and hi (the row's voxels that have a source) inside the first 64 quads and past them.
+LONG_ROWS = {(517, 3, 2): [(259, 2, 2), (260, 2, 2), (261, 2, 2), (263, 2, 2), (515, 2, 2)], (4096, 1, 2): [(4096, 1, 2)]}
+LONG_X0 = (-300, -257, -1, 0, 1, 2, 3, 255, 258, 300)
 
 
 @pytest.fixture(scope="module")
@@ -51,7 +56,10 @@ def words(t: "torch.Tensor") -> np.ndarray:
 
 
 def starts_for(dims, out_dims):
-    """One axis at a time, around both volumes' ends (n: the source's and the window's size on that axis), then mixed."""
+    """One axis at a time, around both volumes' ends (n: the source's and the window's size on that axis), then mixed;
+    for the long rows LONG_X0 alone and beside a row and a slice that have no source."""
+    if dims in LONG_ROWS:
+        return [(x0, 0, 0) for x0 in LONG_X0] + [(x0, 1, -1) for x0 in LONG_X0[::3]] + [(dims[0] - 257, 0, 0), (-dims[0] + 1, 0, 0)]
     out = []
     for axis in range(3):
         values = set()
@@ -103,7 +111,7 @@ def test_kernel_matches_the_twin(native, dims, colour):
     names = ("tsdf", "weight", "color")[:3 if colour else 2]
     src = {k: dev_words(state[k]) for k in names}
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for out_dims in [dims] + OTHER_DIMS:
+    for out_dims in LONG_ROWS.get(dims, [dims] + OTHER_DIMS):
         bx, by, bz = out_dims
         count = bx * by * bz
         bufs = {k: torch.empty(g + count + 9, dtype=torch.int32, device="cuda") for k, g in zip(names, GUARDS)}

@@ -42,6 +42,7 @@
  *                                                         smx_tsdf_extract_triangles_workspace_bytes
  *   -- (disparity, normal and colour views of that volume) smx_tsdf_raycast, smx_tsdf_raycast_workspace_bytes
  *   -- (a window of that volume: shift, crop, grow, spill) smx_tsdf_window
+ *   -- (one volume's state merged into another: restore, join) smx_tsdf_merge
  *   -- (the camera pose of a frame against such a view)   smx_track_camera, smx_track_camera_workspace_bytes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
@@ -1004,8 +1005,8 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
  * margin >= 1 a crossing between a leaving voxel and a staying one is in a box.  Surface elements wholly inside a margin
  * layer then exist twice, in the box and in the shifted volume, and so do those in the corner two boxes share;
  * smx_voxel_downsample at voxel_size removes the duplicates from point clouds.  Boxes are ordinary volumes for every
- * entry above.  Not addressed: fusing boxes back when the volume returns to a place it left (it finds that place empty),
- * loop closure and relocalisation.
+ * entry above, and smx_tsdf_merge in FILL mode writes a box back when the volume returns to the place it left (the Python
+ * layer's TSDFSpillStore keeps the boxes and does so).  Not addressed: loop closure and relocalisation.
  * color and color_out are both NULL or both given.  The call is out of place: a destination array may overlap neither a
  * source array nor another destination array.
  * One launch on `stream` (a caller's stream), no atomics, no workspace, no host synchronisation and no allocation:
@@ -1016,6 +1017,44 @@ int smx_tsdf_raycast(int device_id, int nx, int ny, int nz, const float origin[3
 int smx_tsdf_window(int device_id, int nx, int ny, int nz, const float *tsdf, const float *weight, const uint8_t *color,
                     int x0, int y0, int z0, int bx, int by, int bz, float *tsdf_out, float *weight_out,
                     uint8_t *color_out, void *stream);
+
+/* smx_tsdf_merge: one volume's state written into another -- what restores a spilled box when a volume returns to a place
+ * it left, and what joins two volumes fused from different frames.  The destination is smx_tsdf_integrate's state of
+ * nx * ny * nz voxels, tsdf, weight [nz][ny][nx] f32 and color [nz][ny][nx][4] u8, updated IN PLACE.  The source is a state
+ * of sx * sy * sz voxels, src_tsdf, src_weight [sz][sy][sx] and src_color, read only.  Source voxel (0, 0, 0) sits at
+ * destination voxel (x0, y0, z0), of any sign.  Only the REGION of the source that starts at source voxel (rx, ry, rz)
+ * and has cx * cy * cz voxels takes part: source voxel s of the region pairs with destination voxel d = s + (x0, y0, z0),
+ * and pairs whose d lies outside the destination grid are ignored.  A region with no pair launches nothing and returns 0.
+ *   Every step is ONE float32 operation (no fused multiply-add, correctly rounded division).  For a pair, T1, W1, C1 are
+ *   the source's tsdf, weight and colour, T0, W0, C0 the destination's:
+ *     skip unless W1 > 0.0f (a NaN fails the test; the destination's bits stay as they are)
+ *     if not W0 > 0.0f: the destination's three words become the source's, copied bit for bit (NaN payloads and -0.0f
+ *       are kept and the colour word is whole, fourth byte included: no float operation touches a value)
+ *     else with mode == SMX_TSDF_MERGE_FILL: the destination stays as it is
+ *     else with mode == SMX_TSDF_MERGE_AVERAGE, smx_tsdf_integrate's form with the source as the measurement:
+ *       T = ((T0*W0) + (T1*W1)) / (W0 + W1);  W = fminf(W0 + W1, max_weight)
+ *       C = ((C0*W0) + (C1*W1)) / (W0 + W1) per channel, stored as (uint8)floorf(C + 0.5f) (C lies in [0, 255] for
+ *           finite weights; a NaN C stores 0), with a zero fourth byte
+ *   With finite tsdf values and weights that is all; the payloads of NaNs that the AVERAGE arithmetic produces from
+ *   non-finite values are not pinned.
+ * FILL gives back what a shift cut out: the box's voxels go where the volume holds nothing, and what the volume has
+ * measured since wins.  AVERAGE of two volumes fused from disjoint frames equals, up to rounding, one volume fused from
+ * all of them as long as no weight reaches max_weight (a weighted mean is associative; the cap is not).
+ * color and src_color are both NULL or both given.  A destination array may overlap neither a source array nor another
+ * destination array: a volume is not merged into itself.
+ * One launch on `stream` (a caller's stream), no atomics, no workspace, no host synchronisation and no allocation:
+ * graph-capturable.  Every destination voxel has one owner thread, so the update in place is safe.
+ * SMX_ERR_INVALID_ARG, checked before the device is touched, in this order: a NULL tsdf, weight, src_tsdf or src_weight;
+ * color without src_color or src_color without color; nx, ny, nz outside 1..4096 or a product > 2^30; the same for sx,
+ * sy, sz; |x0|, |y0| or |z0| > 8192; a region that is not inside the source (rx, ry, rz < 0, cx, cy, cz < 1,
+ * rx + cx > sx, ry + cy > sy or rz + cz > sz); a mode other than the two; max_weight not finite and > 0 (in both modes);
+ * a destination array overlapping a source array or another destination array; stream == SMX_STREAM_ENGINE. */
+#define SMX_TSDF_MERGE_FILL    0
+#define SMX_TSDF_MERGE_AVERAGE 1
+int smx_tsdf_merge(int device_id, int nx, int ny, int nz, float *tsdf, float *weight, uint8_t *color,
+                   int sx, int sy, int sz, const float *src_tsdf, const float *src_weight, const uint8_t *src_color,
+                   int x0, int y0, int z0, int rx, int ry, int rz, int cx, int cy, int cz,
+                   int mode, float max_weight, void *stream);
 
 /* ---- Camera tracking -------------------------------------------------------------------------------------------------
  * smx_track_camera: the camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against

@@ -184,6 +184,13 @@ void launch_tsdf_window(int nx, int ny, int nz, const float *tsdf, const float *
                         int y0, int z0, int bx, int by, int bz, float *tsdf_out, float *weight_out, uint8_t *color_out,
                         hipStream_t s);
 
+// ---- tu_tsdf_merge.hip: one volume's state merged into another in place (k_tsdf_merge.h) -------------------------------
+// color and src_color both NULL or both given; one launch (none if the region misses the destination), no workspace;
+// arguments checked by smx_tsdf_merge
+void launch_tsdf_merge(int nx, int ny, int nz, float *tsdf, float *weight, uint8_t *color, int sx, int sy, int sz,
+                       const float *src_tsdf, const float *src_weight, const uint8_t *src_color, int x0, int y0, int z0,
+                       int rx, int ry, int rz, int cx, int cy, int cz, int mode, float max_weight, hipStream_t s);
+
 // ---- tu_track.hip: camera tracking against rendered model views (k_track.h) ----------------------------------------------
 // q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every other pointer is device memory; confidence,
 // info, rms and normal_equations may be NULL; workspace: track_layout(n, H, W); arguments checked by smx_track_camera

@@ -849,6 +849,41 @@ int smx_tsdf_window(int device_id, int nx, int ny, int nz, const float *tsdf, co
     });
 }
 
+int smx_tsdf_merge(int device_id, int nx, int ny, int nz, float *tsdf, float *weight, uint8_t *color, int sx, int sy,
+                   int sz, const float *src_tsdf, const float *src_weight, const uint8_t *src_color, int x0, int y0, int z0,
+                   int rx, int ry, int rz, int cx, int cy, int cz, int mode, float max_weight, void *stream) {
+    const char *fn = "smx_tsdf_merge";
+    if (!tsdf || !weight || !src_tsdf || !src_weight)
+        return fail(SMX_ERR_INVALID_ARG, "%s: tsdf, weight, src_tsdf and src_weight must be non-NULL", fn);
+    if ((color == nullptr) != (src_color == nullptr))
+        return fail(SMX_ERR_INVALID_ARG, "%s: color and src_color must both be NULL or both be given", fn);
+    if (int rc = check_tsdf_dims(fn, nx, ny, nz)) return rc;
+    if (!tsdf_dims_ok(sx, sy, sz))
+        return fail(SMX_ERR_INVALID_ARG, "%s: need 1 <= sx, sy, sz <= 4096 and sx * sy * sz <= 2^30 (got %d, %d, %d)", fn, sx,
+                    sy, sz);
+    if (int rc = check_int_range(fn, "x0", x0, -8192, 8192)) return rc;
+    if (int rc = check_int_range(fn, "y0", y0, -8192, 8192)) return rc;
+    if (int rc = check_int_range(fn, "z0", z0, -8192, 8192)) return rc;
+    if (rx < 0 || ry < 0 || rz < 0 || cx < 1 || cy < 1 || cz < 1 || rx > sx - cx || ry > sy - cy || rz > sz - cz)
+        return fail(SMX_ERR_INVALID_ARG,
+                    "%s: the region must lie inside the source: need rx, ry, rz >= 0, cx, cy, cz >= 1 and rx + cx <= sx, "
+                    "ry + cy <= sy, rz + cz <= sz (got start %d, %d, %d and dims %d, %d, %d in %d, %d, %d)", fn, rx, ry, rz,
+                    cx, cy, cz, sx, sy, sz);
+    if (int rc = check_int_range(fn, "mode", mode, SMX_TSDF_MERGE_FILL, SMX_TSDF_MERGE_AVERAGE)) return rc;
+    if (int rc = check_positive(fn, "max_weight", max_weight)) return rc;
+    const size_t vox = (size_t)nx * ny * nz, svox = (size_t)sx * sy * sz;
+    if (int rc = check_disjoint(fn, {{src_tsdf, svox * sizeof(float)}, {src_weight, svox * sizeof(float)}, {src_color, svox * 4}},
+                                {{tsdf, vox * sizeof(float)}, {weight, vox * sizeof(float)}, {color, vox * 4}},
+                                "a destination array overlaps a source array (a volume cannot be merged into itself)",
+                                "two destination arrays overlap"))
+        return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_tsdf_merge(nx, ny, nz, tsdf, weight, color, sx, sy, sz, src_tsdf, src_weight, src_color, x0, y0, z0, rx,
+                               ry, rz, cx, cy, cz, mode, max_weight, (hipStream_t)stream);
+    });
+}
+
 // ---- camera tracking ---------------------------------------------------------------------------------------------------
 static bool track_dims_ok(int n, int H, int W) {
     return points_dims_ok(n, H, W) && track_grid(H, W, 1).tiles <= TRK_MAX_TILES;

@@ -1914,6 +1914,89 @@ def tsdf_follow_shift(position, origin, dims, voxel_size: float, anchor=(0.5, 0.
     return tuple(out)
 
 
+def tsdf_spill_ownership(dims, voxels):
+    """Parallel to tsdf_spill_boxes(dims, voxels, margin): the sub-box (start, dims) of the volume before the shift that
+    each box OWNS, or None for a box that owns nothing.  Only voxels that leave are owned (margin layers stay with the
+    volume), and each by one box: the x box owns its leaving layers over the whole cross-section, the y box its leaving
+    layers over the x range that stays, the z box its leaving layers over the x and y ranges that stay.  So the corner
+    that boxes share has one owner, and the owned boxes together are exactly the voxels that leave."""
+    dims, d = _int_triple("dims", dims), _int_triple("voxels", voxels)
+    leaving, staying = [], []
+    for n, c in zip(dims, d):
+        if c > 0:
+            leaving.append((0, min(n, c)))
+            staying.append((min(n, c), n))
+        elif c < 0:
+            leaving.append((max(0, n + c), n))
+            staying.append((0, max(0, n + c)))
+        else:
+            leaving.append(None)
+            staying.append((0, n))
+    owned = []
+    for a in range(3):
+        if leaving[a] is None:
+            continue
+        ranges = [staying[b] if b < a else leaving[b] if b == a else (0, dims[b]) for b in range(3)]
+        if any(hi <= lo for lo, hi in ranges):
+            owned.append(None)
+        else:
+            owned.append((tuple(lo for lo, _ in ranges), tuple(hi - lo for lo, hi in ranges)))
+    return owned
+
+
+def tsdf_box_intersect(a, b):
+    """The common part of two integer boxes (start, dims), or None."""
+    lo = tuple(max(s, t) for s, t in zip(a[0], b[0]))
+    hi = tuple(min(s + n, t + m) for s, n, t, m in zip(a[0], a[1], b[0], b[1]))
+    if any(h <= l for l, h in zip(lo, hi)):
+        return None
+    return lo, tuple(h - l for l, h in zip(lo, hi))
+
+
+def tsdf_box_subtract(a, b):
+    """What is left of the integer box a = (start, dims) without box b, as at most 6 pairwise disjoint boxes: axis by
+    axis, the slab of a below b and the slab above it are cut off, and what remains is narrowed to b's range."""
+    if tsdf_box_intersect(a, b) is None:
+        return [(tuple(a[0]), tuple(a[1]))]
+    lo, hi = list(a[0]), [s + n for s, n in zip(a[0], a[1])]
+    pieces = []
+    for ax in range(3):
+        b_lo, b_hi = b[0][ax], b[0][ax] + b[1][ax]
+        for cut_lo, cut_hi in ((lo[ax], min(hi[ax], b_lo)), (max(lo[ax], b_hi), hi[ax])):
+            if cut_hi > cut_lo:
+                p_lo, p_hi = list(lo), list(hi)
+                p_lo[ax], p_hi[ax] = cut_lo, cut_hi
+                pieces.append((tuple(p_lo), tuple(h - l for l, h in zip(p_lo, p_hi))))
+        lo[ax], hi[ax] = max(lo[ax], b_lo), min(hi[ax], b_hi)
+    return pieces
+
+
+def tsdf_follow_decision(volume, camera_to_world, threshold: Optional[int] = None, anchor=(0.5, 0.5, 0.5)):
+    """The shift TSDFVolume.follow and TSDFSpillStore.follow make for a pose: tsdf_follow_shift of the camera position of
+    camera_to_world [4, 4] (of the last pose of [n, 4, 4]) once max |d_a| >= threshold (a positive int, default
+    max(1, min(dims) // 8)), else (0, 0, 0).  Needs the volume's .origin, .dims and .voxel_size only."""
+    m = _host_matrices("camera_to_world", camera_to_world, True)
+    if not np.isfinite(m).all():
+        raise RuntimeError("camera_to_world must be finite")
+    if threshold is None:
+        threshold = max(1, min(volume.dims) // 8)
+    _int_arg("threshold", threshold)
+    if threshold < 1:
+        raise RuntimeError(f"threshold must be a positive int, got {threshold}")
+    try:
+        anchor = tuple(anchor)
+    except TypeError:
+        raise TypeError("anchor must be three numbers") from None
+    if len(anchor) != 3:
+        raise TypeError("anchor must be three numbers")
+    for v in anchor:
+        _number_arg("anchor", v)
+        if not math.isfinite(v):
+            raise RuntimeError(f"anchor must be finite, got {anchor}")
+    d = tsdf_follow_shift(m[-1, :3, 3].tolist(), volume.origin, volume.dims, volume.voxel_size, anchor)
+    return d if max(abs(c) for c in d) >= threshold else (0, 0, 0)
+
+
 class TSDFVolume:
     """A dense truncated-signed-distance volume that fuses posed disparity maps (smx_tsdf_integrate; the rules are in
     include/stereo_mi355x.h) and gives back its surface as points (smx_tsdf_extract_points), as a triangle mesh over
@@ -2031,8 +2114,9 @@ class TSDFVolume:
         the crossings between a leaving voxel and a staying one, which neither the shifted volume nor a box without
         margin contains.  Surface elements can then appear twice: those wholly inside a margin layer (in the box and in
         the shifted volume) and those in the corner that two boxes share; voxel_downsample at voxel_size removes the
-        duplicates from point clouds.  Without spill the list is empty and what left is gone.  Boxes are not fused back
-        when the volume returns to a place it has left."""
+        duplicates from point clouds.  Without spill the list is empty and what left is gone.  shift itself does not
+        fuse boxes back when the volume returns to a place it has left: a TSDFSpillStore, which drives shift, keeps the
+        boxes and restores them with merge(mode="fill")."""
         d = _int_triple("voxels", voxels, WINDOW_START_MAX)
         if not isinstance(spill, bool):
             raise TypeError("spill must be a bool")
@@ -2060,28 +2144,61 @@ class TSDFVolume:
         zero (tsdf_follow_shift; host arithmetic in float64), shifts by d once max |d_a| >= threshold and returns
         (d, shift(d, spill=spill, margin=margin)); returns ((0, 0, 0), []) otherwise.  threshold: a positive int,
         default max(1, min(dims) // 8)."""
-        m = _host_matrices("camera_to_world", camera_to_world, True)
-        if not np.isfinite(m).all():
-            raise RuntimeError("camera_to_world must be finite")
-        if threshold is None:
-            threshold = max(1, min(self.dims) // 8)
-        _int_arg("threshold", threshold)
-        if threshold < 1:
-            raise RuntimeError(f"threshold must be a positive int, got {threshold}")
-        try:
-            anchor = tuple(anchor)
-        except TypeError:
-            raise TypeError("anchor must be three numbers") from None
-        if len(anchor) != 3:
-            raise TypeError("anchor must be three numbers")
-        for v in anchor:
-            _number_arg("anchor", v)
-            if not math.isfinite(v):
-                raise RuntimeError(f"anchor must be finite, got {anchor}")
-        d = tsdf_follow_shift(m[-1, :3, 3].tolist(), self.origin, self.dims, self.voxel_size, anchor)
-        if max(abs(c) for c in d) < threshold:
+        d = tsdf_follow_decision(self, camera_to_world, threshold, anchor)
+        if d == (0, 0, 0):
             return (0, 0, 0), []
         return d, self.shift(d, spill=spill, margin=margin)
+
+    def merge(self, other: "TSDFVolume", *, mode: str = "average", region=None) -> None:
+        """Merges another volume's state into this one, in place, on the current stream without synchronising
+        (smx_tsdf_merge; the rule is in include/stereo_mi355x.h).  Where `other` has measured a voxel and this volume
+        has not, the voxel takes other's state bit for bit; where both have, mode="average" (the default) makes it the
+        weighted mean of the two in integrate's form, the weight capped at max_weight -- two volumes fused from disjoint
+        sets of frames become, up to rounding, the volume fused from all of them -- and mode="fill" keeps this volume's
+        state: what restores a spilled box when the volume returns to the place it left (TSDFSpillStore).  `other` is
+        not changed.
+
+        The volumes are placed by integers alone: other.offset - self.offset, plus the distance between the two
+        constructor origins in voxels, which must be a whole number exactly (computed in float64).  Both must have the
+        same voxel_size, truncation, max_weight, colour-ness and device, and other must not be this volume.
+        region=(start, dims), in other's voxels, limits the merge to that box of other (default: all of it); the part of
+        it that lies outside this volume is ignored."""
+        if not isinstance(other, TSDFVolume):
+            raise TypeError("other must be a TSDFVolume")
+        if other is self:
+            raise RuntimeError("a volume cannot be merged into itself")
+        if mode not in _native.TSDF_MERGE_MODES:
+            raise RuntimeError(f"mode must be 'average' or 'fill', got {mode!r}")
+        for name in ("voxel_size", "truncation", "max_weight", "device"):
+            if getattr(self, name) != getattr(other, name):
+                raise RuntimeError(f"merge needs volumes of the same {name}, got {getattr(self, name)} and "
+                                   f"{getattr(other, name)}")
+        if (self.color is None) != (other.color is None):
+            raise RuntimeError("merge needs two colour volumes or two without colour")
+        placement = []
+        for a, b, o0, o1 in zip(self._offset, other._offset, self._origin0, other._origin0):
+            apart = (float(o1) - float(o0)) / float(self.voxel_size)
+            if apart != math.floor(apart):
+                raise RuntimeError(f"the volumes' origins {tuple(self._origin0)} and {tuple(other._origin0)} are not a whole "
+                                   f"number of voxels apart ({apart} on one axis)")
+            placement.append(b - a + int(apart))
+        if region is None:
+            start, dims = (0, 0, 0), other.dims
+        else:
+            try:
+                start, dims = region
+            except (TypeError, ValueError):
+                raise TypeError("region must be (start, dims), three ints each") from None
+            start, dims = _int_triple("region start", start), _int_triple("region dims", dims)
+            if any(s < 0 or n < 1 or s + n > m for s, n, m in zip(start, dims, other.dims)):
+                raise RuntimeError(f"region {start} + {dims} does not lie inside the other volume's {other.dims} voxels")
+        if any(abs(p) > WINDOW_START_MAX for p in placement):
+            raise RuntimeError(f"merge: the volumes are {tuple(placement)} voxels apart, at most {WINDOW_START_MAX} per axis")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(LIB.smx_tsdf_merge(self.device.index, *self.dims, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                 ptr(self.color), *other.dims, other.tsdf.data_ptr(), other.weight.data_ptr(),
+                                 ptr(other.color), *placement, *start, *dims, _native.TSDF_MERGE_MODES[mode],
+                                 self.max_weight, _stream(self.device.index)))
 
     def integrate(self, disp: torch.Tensor, Q, camera_to_world, *, image: Optional[torch.Tensor] = None,
                   confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0, depth_range=(0.0, math.inf),
@@ -2323,3 +2440,127 @@ class TSDFVolume:
             raise RuntimeError(f"the mesh has {total} vertices and {ttotal} triangles: more than 2^30")
         return TriangleMesh(vertices=pts[:total], triangles=tris[:ttotal], normals=None if nrm is None else nrm[:total],
                             colors=None if col is None else col[:total])
+
+
+def _state_bytes(volume) -> int:
+    nx, ny, nz = volume.dims
+    return nx * ny * nz * (8 if volume.color is None else 12)
+
+
+def _measured_flags(views) -> list:
+    """Per array of weights (device tensors, or NumPy arrays of float32 or their uint32 words), whether a weight is > 0;
+    the device's flags come back in ONE copy: the synchronisation of TSDFSpillStore.shift."""
+    if not views:
+        return []
+    if isinstance(views[0], torch.Tensor):
+        return torch.stack([(v > 0).any() for v in views]).tolist()
+    return [bool((np.asarray(v).view(np.float32) > 0).any()) for v in views]
+
+
+class TSDFSpillStore:
+    """Keeps what left a volume that follows the camera and gives it back when the volume returns: the memory of a
+    TSDFVolume beyond its window.  The store drives the volume -- call store.shift(volume, d) or store.follow(volume,
+    pose) in place of the volume's own methods.  Each shift spills the leaving layers into boxes (TSDFVolume.shift with
+    spill=True; the boxes stay on the device), records for each box the region it OWNS, and restores every owned region
+    that lies inside the volume's new window with volume.merge(box, mode="fill", region=...): the voxels go back where
+    the window is empty, bit for bit, and what the volume has measured there since stays.
+
+    Ownership is kept in integer boxes of world voxels (offset space: voxel (0, 0, 0) is the first voxel of the volume
+    as it was built).  Every world voxel that ever left is owned by exactly one holder, the live volume or one entry of
+    the store (tsdf_spill_ownership splits what a shift cuts off among its boxes, margin layers excluded); a restored
+    region passes from the entry back to the volume (tsdf_box_subtract), and an entry that owns nothing any more is
+    dropped with its tensors.  A region in which nothing was measured is not kept either (a new box's, and what is left
+    of a region restored in part): that is read back from the device, one flag per region in one copy, the ONE
+    synchronisation of a shift through the store.
+
+    max_bytes: a bound on the bytes of state the entries hold; beyond it the OLDEST entries are evicted -- that territory
+    is forgotten, and .evicted counts them.  len(store) is the number of entries, .bytes their state's bytes, and
+    volumes() the boxes themselves (ordinary volumes: extract, render or archive them).  One store serves one volume:
+    it refuses a volume whose voxel_size, truncation, max_weight, colour-ness, device or constructor origin differ from
+    the first one it saw.  Not done: offload of entries to the host or to disk, loop closure and relocalisation -- a
+    returning camera finds its old model only as far as its pose estimate is consistent with the old one."""
+
+    def __init__(self, max_bytes: Optional[int] = None):
+        if max_bytes is not None:
+            _int_arg("max_bytes", max_bytes)
+            if max_bytes < 0:
+                raise RuntimeError(f"max_bytes must be >= 0 or None, got {max_bytes}")
+        self.max_bytes, self.evicted = max_bytes, 0
+        self._entries = []                                           # oldest first: [box volume, [owned world boxes]]
+        self._key = None
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    @property
+    def bytes(self) -> int:
+        return sum(_state_bytes(box) for box, _ in self._entries)
+
+    def volumes(self) -> list:
+        """The entries' boxes, oldest first."""
+        return [box for box, _ in self._entries]
+
+    def owned_regions(self) -> list:
+        """Per entry, oldest first, the world-voxel boxes (start, dims) it still owns."""
+        return [list(owned) for _, owned in self._entries]
+
+    def _check_volume(self, volume) -> None:
+        key = (volume.voxel_size, volume.truncation, volume.max_weight, volume.color is not None, volume.device,
+               tuple(volume._origin0))
+        if self._key is None:
+            self._key = key
+        elif key != self._key:
+            raise RuntimeError("a TSDFSpillStore serves one volume: voxel_size, truncation, max_weight, colour-ness, device and "
+                               f"constructor origin were {self._key}, got {key}")
+
+    def shift(self, volume, voxels, *, margin: int = 1):
+        """volume.shift(voxels, spill=True, margin=margin) through the store: returns (boxes, restored) -- the boxes that
+        shift handed back (all of them, whether the store keeps them or not) and the number of merges launched to
+        restore what the store held of the new window.  Everything runs on the current stream; a shift that spills
+        synchronises once (see the class)."""
+        self._check_volume(volume)
+        d = _int_triple("voxels", voxels, WINDOW_START_MAX)
+        before, dims = tuple(volume.offset), tuple(volume.dims)
+        boxes = volume.shift(d, spill=True, margin=margin)
+        if d == (0, 0, 0):
+            return boxes, 0
+        window = (tuple(volume.offset), dims)
+        restored, unsure = 0, []                                     # unsure: (entry, region) that may hold nothing
+        for entry in self._entries:
+            box, owned = entry
+            entry[1] = []
+            for region in owned:
+                part = tsdf_box_intersect(region, window)
+                if part is None:
+                    entry[1].append(region)
+                    continue
+                volume.merge(box, mode="fill", region=(tuple(s - o for s, o in zip(part[0], box.offset)), part[1]))
+                restored += 1
+                unsure.extend((entry, piece) for piece in tsdf_box_subtract(region, part))
+        for box, own in zip(boxes, tsdf_spill_ownership(dims, d)):
+            if own is not None:
+                entry = [box, []]
+                self._entries.append(entry)
+                unsure.append((entry, (tuple(a + b for a, b in zip(before, own[0])), own[1])))
+        views = []                                                   # the weights of each such region in its box
+        for (box, _), (start, size) in unsure:
+            x, y, z = (s - o for s, o in zip(start, box.offset))
+            views.append(box.weight[z:z + size[2], y:y + size[1], x:x + size[0]])
+        for (entry, region), measured in zip(unsure, _measured_flags(views)):
+            if measured:
+                entry[1].append(region)
+        self._entries = [e for e in self._entries if e[1]]
+        while self.max_bytes is not None and self._entries and self.bytes > self.max_bytes:
+            self._entries.pop(0)
+            self.evicted += 1
+        return boxes, restored
+
+    def follow(self, volume, camera_to_world, *, threshold: Optional[int] = None, anchor=(0.5, 0.5, 0.5), margin: int = 1):
+        """TSDFVolume.follow through the store, with the same arithmetic (tsdf_follow_decision): returns
+        (d, boxes, restored), ((0, 0, 0), [], 0) for a pose that does not move the volume."""
+        self._check_volume(volume)
+        d = tsdf_follow_decision(volume, camera_to_world, threshold, anchor)
+        if d == (0, 0, 0):
+            return (0, 0, 0), [], 0
+        boxes, restored = self.shift(volume, d, margin=margin)
+        return d, boxes, restored

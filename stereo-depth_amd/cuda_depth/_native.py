@@ -210,6 +210,12 @@ EXPORTS = {
     "smx_tsdf_window": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    # one volume's state merged into another in place: (device_id, nx, ny, nz, tsdf, weight, color, sx, sy, sz, src_tsdf,
+    # src_weight, src_color, x0, y0, z0, rx, ry, rz, cx, cy, cz, mode, max_weight, stream)
+    "smx_tsdf_merge": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                 C.c_void_p]),
     # camera tracking: (n, H, W) -> workspace bytes; (device_id, n, H, W, disp, confidence, Q (host float32[16]),
     # min_confidence, z_min, z_max, invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm (host float32[16]),
     # model_camera_to_world, model_world_to_camera, pose_in, schedule_pairs, schedule (host int32[pairs][2]),
@@ -225,6 +231,7 @@ EXPORTS = {
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*
 DTYPE_U8, DTYPE_F32 = 0, 1                 # SMX_DTYPE_*
+TSDF_MERGE_MODES = {"fill": 0, "average": 1}   # SMX_TSDF_MERGE_*
 STREAM_ENGINE = C.c_void_p(-1)          # SMX_STREAM_ENGINE: the engine's own streams
 KERNEL_SLOTS = ("prologue", "match_fast", "match_exact", "refine", "fill")
 

@@ -81,6 +81,9 @@ class DepthEstimationResult:
     # (TSDFVolume.shift's boxes, new volumes; empty otherwise).  Keyword-only as well
     volume_shift: Tuple[int, int, int] = dataclasses.field(default=(0, 0, 0), kw_only=True)
     spilled_volumes: list = dataclasses.field(default_factory=list, kw_only=True)
+    # spill_store=: how many stored regions were merged back into the volume when this frame moved it
+    # (TSDFSpillStore.follow); 0 otherwise.  Keyword-only as well
+    restored_boxes: int = dataclasses.field(default=0, kw_only=True)
     # confidence=True: the [H, W] per-pixel confidence in [0, 1] of the map (a persistent buffer, like the map);
     # None otherwise
     confidence_map: Optional[torch.Tensor] = None
@@ -141,7 +144,8 @@ class DepthEstimationPipeline:
                  right_view_synthesis: Optional[RightViewSynthesis] = None, render_model: bool = False,
                  track_camera: bool = False, initial_pose=None, tracking_args: Optional[dict] = None,
                  follow_camera: bool = False, follow_threshold: Optional[int] = None,
-                 follow_anchor: Tuple[float, float, float] = (0.5, 0.5, 0.5), keep_spill: bool = False):
+                 follow_anchor: Tuple[float, float, float] = (0.5, 0.5, 0.5), keep_spill: bool = False,
+                 spill_store: Optional["cuda_depth.TSDFSpillStore"] = None):
         """speckle_max_size / speckle_max_diff / fill_invalid / median_radius / median_sigma_color / median_sigma_space:
         post-processing of the backend's map, after the left-right check if configured
         (CudaStereoMatchingBackend); with the defaults the map is returned as computed.  wls_lambda /
@@ -189,8 +193,11 @@ class DepthEstimationPipeline:
         (TSDFVolume.follow with follow_threshold, default min(dims) // 8, and follow_anchor), so the next frame's model
         view is rendered from the shifted volume; a lost frame does not move it.  The result carries volume_shift and,
         with keep_spill=True, what left the volume as spilled_volumes (TSDFVolume.shift(spill=True): the caller's to
-        extract or drop; they are not fused back).  The volume then holds a spare copy of its state (twice the memory).
-        False (the default) changes nothing."""
+        extract or drop; shift itself does not fuse them back).  The volume then holds a spare copy of its state
+        (twice the memory).  False (the default) changes nothing.  spill_store: a cuda_depth.TSDFSpillStore (needs
+        follow_camera=True); the volume then follows through the store (TSDFSpillStore.follow), which keeps what leaves
+        and merges it back when the camera returns to a place it left; the result carries restored_boxes, and
+        spilled_volumes as before with keep_spill=True.  None (the default) changes nothing."""
         self._config = DepthEstimationPipelineConfig() if config is None else config
         _check_sgm_keywords(sgm_paths, sgm_p1, sgm_p2, sgm_uniqueness)
         self._reprojection_matrix = None
@@ -242,7 +249,12 @@ class DepthEstimationPipeline:
         if follow_threshold is not None and (isinstance(follow_threshold, bool) or not isinstance(follow_threshold, int)
                                              or follow_threshold < 1):
             raise ValueError(f"follow_threshold must be a positive int, got {follow_threshold!r}")
-        self._follow_camera, self._keep_spill = follow_camera, keep_spill
+        if spill_store is not None:
+            if not isinstance(spill_store, cuda_depth.TSDFSpillStore):
+                raise TypeError("spill_store must be a cuda_depth.TSDFSpillStore")
+            if not follow_camera:
+                raise ValueError("spill_store needs follow_camera=True")
+        self._follow_camera, self._keep_spill, self._spill_store = follow_camera, keep_spill, spill_store
         self._follow_threshold, self._follow_anchor = follow_threshold, tuple(follow_anchor)
         if right_view_synthesis is not None and not isinstance(right_view_synthesis, RightViewSynthesis):
             raise TypeError("right_view_synthesis must be a pipeline.synthesis.RightViewSynthesis")
@@ -324,8 +336,14 @@ class DepthEstimationPipeline:
         lost = None
         if self._track_camera:
             camera_pose, lost = self._track(disparity, confidence)
-        shift, spilled = (0, 0, 0), []
-        if self._follow_camera and not lost:
+        shift, spilled, restored = (0, 0, 0), [], 0
+        if self._follow_camera and not lost and self._spill_store is not None:
+            shift, spilled, restored = self._spill_store.follow(self._tsdf_volume, camera_pose,
+                                                                threshold=self._follow_threshold,
+                                                                anchor=self._follow_anchor)
+            if not self._keep_spill:
+                spilled = []
+        elif self._follow_camera and not lost:
             shift, spilled = self._tsdf_volume.follow(camera_pose, threshold=self._follow_threshold,
                                                       anchor=self._follow_anchor, spill=self._keep_spill)
         if self._tsdf_volume is not None and not lost:
@@ -342,7 +360,7 @@ class DepthEstimationPipeline:
         return DepthEstimationResult(left_image=left_on_device, right_image=right_image, disparity_map=disparity,
                                      confidence_map=confidence, point_cloud=cloud, model_disparity_map=model,
                                      camera_pose=camera_pose if self._track_camera else None, tracking_lost=lost,
-                                     volume_shift=shift, spilled_volumes=spilled)
+                                     volume_shift=shift, spilled_volumes=spilled, restored_boxes=restored)
 
     def _track(self, disparity: torch.Tensor, confidence: Optional[torch.Tensor]):
         """(pose [4, 4] float64, lost) of this frame: initial_pose for the first frame, else the frame tracked against

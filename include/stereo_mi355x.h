@@ -44,6 +44,8 @@
  *   -- (a window of that volume: shift, crop, grow, spill) smx_tsdf_window
  *   -- (one volume's state merged into another: restore, join) smx_tsdf_merge
  *   -- (the camera pose of a frame against such a view)   smx_track_camera, smx_track_camera_workspace_bytes
+ *   -- (the same with a photometric term; its planes)     smx_track_camera_photometric,
+ *                                                         smx_track_camera_photometric_workspace_bytes, smx_intensity_planes
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -60,7 +62,7 @@
  *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
  *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample, smx_project_points,
  *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles,
- *     smx_tsdf_raycast, smx_track_camera) returns
+ *     smx_tsdf_raycast, smx_track_camera, smx_track_camera_photometric) returns
  *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
  *   - Calls enqueue work and return without synchronising (like the reference).
  *   - One engine = one device + one set of intermediate buffers: calls on the same
@@ -1135,6 +1137,64 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
                      int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
                      float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
                      double *normal_equations, void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_track_camera_photometric: smx_track_camera with a photometric term summed into the same 6 x 6 system, so that
+ * texture holds the directions that geometry leaves free (a frame that sees one plane).  Arguments, pixel rule, sums,
+ * solve, update, schedule, stop rule and launches are smx_track_camera's; what follows is what is added.  Every step is
+ * ONE float32 operation, as there.
+ *   planes    frame_intensity [n][H][W] f32 (the frame's pixels) and model_intensity [n][Hm][Wm] f32 (the model view's),
+ *             in one unit of the caller's choice (smx_intensity_planes gives 0..255); photometric_weight lambda, in metres
+ *             per intensity unit, scales an intensity residual to the geometric residuals' metres.
+ *   terms     A selected pixel contributes smx_track_camera's thirty terms by that rule, unchanged.  If, and only if, it
+ *             was an inlier there (it reached term 29), with that rule's p, u_0, u_1, u_3, w, Mw and Pm:
+ *               x = u_0/u_3, y = u_1/u_3; x0 = floorf(x), y0 = floorf(y); skip unless 0 <= x0 <= Wm-2 and 0 <= y0 <= Hm-2
+ *               the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1): skip unless model_depth is finite and > 0 at all
+ *                 four and model_intensity is finite at all four: I00, I10, I01, I11
+ *               ax = x - x0, ay = y - y0, bx = 1.0f - ax, by = 1.0f - ay
+ *               Im = by*(bx*I00 + ax*I10) + ay*(bx*I01 + ax*I11)            (the bilinear interpolant ...
+ *               gx = by*(I10 - I00) + ay*(I11 - I01)
+ *               gy = bx*(I01 - I00) + ax*(I11 - I10)                          ... and its exact gradient)
+ *               e = frame_intensity[f][py][px] - Im; skip unless e is finite and |e| <= max_intensity_difference
+ *               h_j = (gx*(Pm[0][j] - x*Pm[3][j]) + gy*(Pm[1][j] - y*Pm[3][j]))/u_3     j = 0, 1, 2 (model camera frame)
+ *               gw_i = (Mw[0][i]*h_0 + Mw[1][i]*h_1) + Mw[2][i]*h_2                    i = 0, 1, 2 (world frame)
+ *               a' = (lambda*(p_1*gw_2 - p_2*gw_1), lambda*(p_2*gw_0 - p_0*gw_2), lambda*(p_0*gw_1 - p_1*gw_0),
+ *                     lambda*gw_0, lambda*gw_1, lambda*gw_2), b' = lambda*e; skip unless all seven are finite
+ *             Its terms, float32 products converted to float64: k = 0..20 (w*a'_i)*a'_j and k = 21..26 (w*a'_i)*b' are
+ *             added into the SAME sums as the geometric terms k; per pixel and per sum the geometric term is added to the
+ *             tile column's sum first and the photometric one second.  Terms 27, 28, 29 and the accepted count stay
+ *             geometric, so rms, inliers, min_inliers and the LOST rule mean what they mean in smx_track_camera.  Three
+ *             new sums, reduced in the same order: k = 30 (w*e)*e, k = 31 w, k = 32 1 (the photometric inlier count).
+ *             With lambda = 0 every photometric product is +-0.0 and changes no bit: pose_out, info, rms and sums 0..29
+ *             are smx_track_camera's.
+ * Outputs as smx_track_camera's, except that normal_equations is [n][33] f64 (sums 0..29 of the joint system, then the
+ * three photometric sums); and, each may be NULL: photometric_info [n][2] int32 = (the photometric inlier count of the
+ * last iteration run, its geometric inliers without a photometric term), photometric_rms [n] f32 =
+ * sqrtf((f32)(sum 30 / sum 31)) of the last iteration run (the division in float64), in intensity units, NaN if none ran
+ * or no pixel was a photometric inlier.  The term's basin is a few model pixels: no pyramid, no robust weights, no
+ * exposure compensation; a caller may blur both planes.
+ * workspace: smx_track_camera_photometric_workspace_bytes(n, H, W) bytes (0 for sizes the call rejects).
+ * SMX_ERR_INVALID_ARG: a NULL frame_intensity or model_intensity; everything smx_track_camera rejects; photometric_weight
+ * not finite and >= 0; max_intensity_difference not finite and > 0; the overlap rule with the planes among the inputs and
+ * photometric_info and photometric_rms among the outputs. */
+size_t smx_track_camera_photometric_workspace_bytes(int n, int H, int W);
+int smx_track_camera_photometric(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                                 const float Q[16], float min_confidence, float z_min, float z_max,
+                                 float invalid_disparity, int Hm, int Wm, const float *model_depth,
+                                 const float *model_normals, const float Qm[16], const float Pm[16],
+                                 const float *model_camera_to_world, const float *model_world_to_camera,
+                                 const float *pose_in, int schedule_pairs, const int32_t *schedule, float max_distance,
+                                 int min_inliers, float min_pivot, float rot_eps, float trans_eps,
+                                 const float *frame_intensity, const float *model_intensity, float photometric_weight,
+                                 float max_intensity_difference, float *pose_out, int32_t *info, float *rms,
+                                 double *normal_equations, int32_t *photometric_info, float *photometric_rms,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* smx_intensity_planes: image uint8 [n][channels][H][W] (device) to out f32 [n][H][W], the planes the entry above reads.
+ * channels == 3 (R, G, B): (float)(77*R + 150*G + 29*B) * 0.00390625f, which is exact; channels == 1: (float)v.  One
+ * launch on `stream` (a caller's stream).  SMX_ERR_INVALID_ARG: a NULL image or out; n < 1, H or W outside 1..32768,
+ * n*H*W > 2^30; channels other than 1 or 3; out overlapping image; stream == SMX_STREAM_ENGINE. */
+int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const uint8_t *image, float *out,
+                         void *stream);
 
 #ifdef __cplusplus
 }

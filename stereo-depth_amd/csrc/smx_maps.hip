@@ -893,14 +893,17 @@ size_t smx_track_camera_workspace_bytes(int n, int H, int W) {
     return track_dims_ok(n, H, W) ? track_layout(n, H, W).total : 0;
 }
 
-int smx_track_camera(int device_id, int n, int H, int W, const float *disp, const float *confidence, const float Q[16],
-                     float min_confidence, float z_min, float z_max, float invalid_disparity, int Hm, int Wm,
-                     const float *model_depth, const float *model_normals, const float Qm[16], const float Pm[16],
-                     const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
-                     int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
-                     float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
-                     double *normal_equations, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "smx_track_camera";
+// The checks smx_track_camera and smx_track_camera_photometric share, in their order: everything before the workspace's
+// size.  intensity: the photometric entry's two planes are part of the NULL check.
+static int check_track_args(const char *fn, bool intensity, const void *frame_intensity, const void *model_intensity,
+                            int n, int H, int W, const float *disp, const float Q[16], float min_confidence, float z_min,
+                            float z_max, float invalid_disparity, int Hm, int Wm, const float *model_depth,
+                            const float *model_normals, const float Qm[16], const float Pm[16],
+                            const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
+                            int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers,
+                            float min_pivot, float rot_eps, float trans_eps, const float *pose_out, const void *workspace) {
+    if (intensity && (!frame_intensity || !model_intensity))
+        return fail(SMX_ERR_INVALID_ARG, "%s: frame_intensity and model_intensity must be non-NULL", fn);
     if (!disp || !Q || !model_depth || !model_normals || !Qm || !Pm || !model_camera_to_world || !model_world_to_camera ||
         !pose_in || !pose_out || !workspace)
         return fail(SMX_ERR_INVALID_ARG,
@@ -938,6 +941,22 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
     if (int rc = check_non_negative(fn, "min_pivot", min_pivot)) return rc;
     if (int rc = check_non_negative(fn, "rot_eps", rot_eps)) return rc;
     if (int rc = check_non_negative(fn, "trans_eps", trans_eps)) return rc;
+    return SMX_OK;
+}
+
+int smx_track_camera(int device_id, int n, int H, int W, const float *disp, const float *confidence, const float Q[16],
+                     float min_confidence, float z_min, float z_max, float invalid_disparity, int Hm, int Wm,
+                     const float *model_depth, const float *model_normals, const float Qm[16], const float Pm[16],
+                     const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
+                     int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
+                     float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
+                     double *normal_equations, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_track_camera";
+    if (int rc = check_track_args(fn, false, nullptr, nullptr, n, H, W, disp, Q, min_confidence, z_min, z_max,
+                                  invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm, model_camera_to_world,
+                                  model_world_to_camera, pose_in, schedule_pairs, schedule, max_distance, min_inliers,
+                                  min_pivot, rot_eps, trans_eps, pose_out, workspace))
+        return rc;
     if (int rc = check_workspace_bytes(fn, "smx_track_camera_workspace_bytes", workspace_bytes,
                                        track_layout(n, H, W).total))
         return rc;
@@ -958,6 +977,74 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
                                  model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
                                  schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps,
                                  pose_out, info, rms, normal_equations, workspace, (hipStream_t)stream);
+    });
+}
+
+size_t smx_track_camera_photometric_workspace_bytes(int n, int H, int W) {
+    return track_dims_ok(n, H, W) ? track_photo_layout(n, H, W).total : 0;
+}
+
+int smx_track_camera_photometric(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                                 const float Q[16], float min_confidence, float z_min, float z_max,
+                                 float invalid_disparity, int Hm, int Wm, const float *model_depth,
+                                 const float *model_normals, const float Qm[16], const float Pm[16],
+                                 const float *model_camera_to_world, const float *model_world_to_camera,
+                                 const float *pose_in, int schedule_pairs, const int32_t *schedule, float max_distance,
+                                 int min_inliers, float min_pivot, float rot_eps, float trans_eps,
+                                 const float *frame_intensity, const float *model_intensity, float photometric_weight,
+                                 float max_intensity_difference, float *pose_out, int32_t *info, float *rms,
+                                 double *normal_equations, int32_t *photometric_info, float *photometric_rms,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "smx_track_camera_photometric";
+    if (int rc = check_track_args(fn, true, frame_intensity, model_intensity, n, H, W, disp, Q, min_confidence, z_min,
+                                  z_max, invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm,
+                                  model_camera_to_world, model_world_to_camera, pose_in, schedule_pairs, schedule,
+                                  max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out, workspace))
+        return rc;
+    if (int rc = check_non_negative(fn, "photometric_weight", photometric_weight)) return rc;
+    if (int rc = check_positive(fn, "max_intensity_difference", max_intensity_difference)) return rc;
+    if (int rc = check_workspace_bytes(fn, "smx_track_camera_photometric_workspace_bytes", workspace_bytes,
+                                       track_photo_layout(n, H, W).total))
+        return rc;
+    const size_t map_bytes = (size_t)n * H * W * sizeof(float), model_bytes = (size_t)n * Hm * Wm * sizeof(float);
+    const size_t pose_bytes = (size_t)n * 12 * sizeof(float);
+    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {model_depth, model_bytes},
+                                     {model_normals, 3 * model_bytes}, {model_camera_to_world, pose_bytes},
+                                     {model_world_to_camera, pose_bytes}, {pose_in != pose_out ? pose_in : nullptr, pose_bytes},
+                                     {frame_intensity, map_bytes}, {model_intensity, model_bytes}},
+                                {{pose_out, pose_bytes}, {info, (size_t)n * 4 * sizeof(int32_t)},
+                                 {rms, (size_t)n * sizeof(float)}, {normal_equations, (size_t)n * TRKP_TERMS * sizeof(double)},
+                                 {photometric_info, (size_t)n * 2 * sizeof(int32_t)},
+                                 {photometric_rms, (size_t)n * sizeof(float)}, {workspace, workspace_bytes}},
+                                "an output or the workspace overlaps an input (pose_out may be pose_in itself)",
+                                "two outputs (the workspace is one) overlap"))
+        return rc;
+    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_track_camera_photometric(n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity,
+                                             Hm, Wm, model_depth, model_normals, Qm, Pm, model_camera_to_world,
+                                             model_world_to_camera, pose_in, schedule_pairs, schedule, max_distance,
+                                             min_inliers, min_pivot, rot_eps, trans_eps, frame_intensity, model_intensity,
+                                             photometric_weight, max_intensity_difference, pose_out, info, rms,
+                                             normal_equations, photometric_info, photometric_rms, workspace,
+                                             (hipStream_t)stream);
+    });
+}
+
+int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const uint8_t *image, float *out,
+                         void *stream) {
+    const char *fn = "smx_intensity_planes";
+    if (!image || !out) return fail(SMX_ERR_INVALID_ARG, "%s: image and out must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (channels != 1 && channels != 3)
+        return fail(SMX_ERR_INVALID_ARG, "%s: channels must be 1 or 3, got %d", fn, channels);
+    const size_t px = (size_t)n * H * W;
+    if (int rc = check_disjoint(fn, {{image, px * channels}}, {{out, px * sizeof(float)}}, "out must not overlap image"))
+        return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_intensity_planes(n, channels, H, W, image, out, (hipStream_t)stream);
     });
 }
 

@@ -204,4 +204,16 @@ inline TrackLayout track_layout(int n, int H, int W) {
                        c.take((size_t)n * groups * TRK_SLOTS * sizeof(double)), c.at};
 }
 
+// ---- camera tracking with the photometric term: the same state record | the sums of every group of four tiles,
+// double[n][groups at stride 1][TRKP_SLOTS].  The grid is track_grid's; the slots are the geometric rule's 0..30 as they
+// are, then the three photometric sums (k_track_photo_rule.h).
+constexpr int TRKP_TERMS = TRK_TERMS + 3;      // the sums of the header: thirty of the joint system, three photometric
+constexpr int TRKP_SLOTS = TRK_TERMS + 4;      // the thirty, the accepted pixels, the three
+inline TrackLayout track_photo_layout(int n, int H, int W) {
+    const int groups = track_grid(H, W, 1).groups;
+    WsCursor c;
+    return TrackLayout{groups, c.take((size_t)n * 32 * sizeof(int)),
+                       c.take((size_t)n * groups * TRKP_SLOTS * sizeof(double)), c.at};
+}
+
 }  // namespace smx

@@ -1276,7 +1276,11 @@ class TrackingResult:
     and the selected accepted pixels of the last one; rms: float32 [] / [n], the weighted point-to-plane residual of
     the last iteration (NaN if none ran); information: float64 [6, 6] / [n, 6, 6], the normal matrix of the last
     iteration over the twist (rotation, translation) in the world frame, which serves as the inverse covariance of the
-    pose up to the residual's variance; normal_equations: float64 [30] / [n, 30], the sums it is made of."""
+    pose up to the residual's variance; normal_equations: float64 [30] / [n, 30], the sums it is made of.  With the
+    photometric term (track_camera(image=...)): normal_equations has the joint system's thirty sums and then the three
+    photometric ones ([33] / [n, 33]), information is the joint matrix, photometric_inliers: int32 [] / [n], the inliers
+    that had a photometric term in the last iteration, and photometric_rms: float32 [] / [n], their weighted intensity
+    residual (NaN without one); both are None without the term."""
     pose: torch.Tensor
     lost: torch.Tensor
     iterations: torch.Tensor
@@ -1285,6 +1289,8 @@ class TrackingResult:
     rms: torch.Tensor
     information: torch.Tensor
     normal_equations: torch.Tensor
+    photometric_inliers: Optional[torch.Tensor] = None
+    photometric_rms: Optional[torch.Tensor] = None
 
 
 def reprojection_matrix(fx: float, cx: float, cy: float, baseline: float, *, fy: Optional[float] = None,
@@ -1767,7 +1773,9 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
                  confidence: Optional[torch.Tensor] = None, schedule=DEFAULT_TRACKING_SCHEDULE,
                  max_distance: float = 0.3, depth_range=(0.0, math.inf), min_inliers: int = 100,
                  min_confidence: float = 0.0, invalid_disparity: float = -1.0, min_pivot: float = 1e-3,
-                 rot_eps: float = 0.0, trans_eps: float = 0.0) -> TrackingResult:
+                 rot_eps: float = 0.0, trans_eps: float = 0.0, image: Optional[torch.Tensor] = None,
+                 photometric_weight: float = 0.0, max_intensity_difference: float = 30.0,
+                 model_intensity: Optional[torch.Tensor] = None) -> TrackingResult:
     """The camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against a rendered
     view of the model (smx_track_camera; the rule, operation by operation, is in include/stereo_mi355x.h).  disp: float32
     [H, W] or [n, H, W] with the reprojection matrix Q; pose: the initial guess [4, 4] / [n, 4, 4] (numpy or tensor;
@@ -1781,7 +1789,22 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     rot_eps / trans_eps (radians, metres) stop a frame early once an update is smaller than both.  Runs on the current
     stream without synchronising and returns a TrackingResult of fresh device tensors.  Rotations are composed in
     float32: over a long sequence they drift from orthogonality, which this function does not repair; nor does it close
-    loops or relocalise a lost camera."""
+    loops or relocalise a lost camera.
+    image with photometric_weight > 0 adds a photometric term to the same system (smx_track_camera_photometric), so that
+    texture holds what geometry leaves free -- a frame that sees one plane is then tracked, not lost.  image: the frame
+    the map was computed on, uint8 [3, H, W] RGB or [H, W] gray ([n, 3, H, W] / [n, H, W] batched), or a float32
+    intensity plane [H, W] / [n, H, W]; the model's intensity comes from model.colors (render with colors=True) or from
+    model_intensity, float32 like model.depth.  photometric_weight: metres per intensity unit (0..255 from uint8), about
+    0.001 to 0.03; a term whose intensities differ by more than max_intensity_difference is left out.  The term's basin
+    is a few model pixels.  Without an image, or with a weight of 0, the geometric entry runs as it always did."""
+    for name, v, positive in (("photometric_weight", photometric_weight, False),
+                              ("max_intensity_difference", max_intensity_difference, True)):
+        _number_arg(name, v)
+        if not (math.isfinite(v) and (v > 0 if positive else v >= 0)):
+            raise RuntimeError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v}")
+    if image is None and photometric_weight > 0:
+        raise RuntimeError("photometric_weight > 0 needs the frame's image")
+    photometric = image is not None and photometric_weight > 0
     q = _check_q(Q)
     qm = q if model_Q is None else _check_q(model_Q)
     if (qm[:3, 2] != 0).any() or qm[3, 0] != 0 or qm[3, 1] != 0 or qm[3, 2] == 0:
@@ -1826,18 +1849,41 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     pose_out = torch.empty((n, 3, 4), dtype=torch.float32, device=dev)
     info = torch.empty((n, 4), dtype=torch.int32, device=dev)
     rms = torch.empty((n,), dtype=torch.float32, device=dev)
-    sums = torch.empty((n, 30), dtype=torch.float64, device=dev)
-    ws_bytes = LIB.smx_track_camera_workspace_bytes(n, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     f16 = lambda m: (C.c_float * 16)(*m.reshape(-1).tolist())  # noqa: E731
     sc = (C.c_int32 * max(sched.size, 1))(*sched.reshape(-1).tolist())
-    check(LIB.smx_track_camera(dev.index, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(),
-                               f16(q), float(min_confidence), z_min, z_max, float(invalid_disparity), Hm, Wm,
-                               model.depth.data_ptr(), model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(),
-                               poses[2].data_ptr(), poses[0].data_ptr(), sched.shape[0], sc, float(max_distance),
-                               min_inliers, float(min_pivot), float(rot_eps), float(trans_eps), pose_out.data_ptr(),
-                               info.data_ptr(), rms.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
-                               _stream(dev.index)))
+    pinfo = prms = None
+    if photometric:
+        frame_int = _intensity_plane("image", image, lead, H, W, dev)
+        if model_intensity is None:
+            if model.colors is None:
+                raise RuntimeError("the photometric term needs model.colors (render with colors=True) or model_intensity")
+            model_intensity = model.colors
+        model_int = _intensity_plane("model_intensity", model_intensity, lead, Hm, Wm, dev)
+        sums = torch.empty((n, 33), dtype=torch.float64, device=dev)
+        pinfo = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        prms = torch.empty((n,), dtype=torch.float32, device=dev)
+        ws_bytes = LIB.smx_track_camera_photometric_workspace_bytes(n, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(LIB.smx_track_camera_photometric(
+            dev.index, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(), f16(q),
+            float(min_confidence), z_min, z_max, float(invalid_disparity), Hm, Wm, model.depth.data_ptr(),
+            model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(), poses[2].data_ptr(), poses[0].data_ptr(),
+            sched.shape[0], sc, float(max_distance), min_inliers, float(min_pivot), float(rot_eps), float(trans_eps),
+            frame_int.data_ptr(), model_int.data_ptr(), float(photometric_weight), float(max_intensity_difference),
+            pose_out.data_ptr(), info.data_ptr(), rms.data_ptr(), sums.data_ptr(), pinfo.data_ptr(), prms.data_ptr(),
+            ws.data_ptr(), ws_bytes, _stream(dev.index)))
+    else:
+        sums = torch.empty((n, 30), dtype=torch.float64, device=dev)
+        ws_bytes = LIB.smx_track_camera_workspace_bytes(n, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(LIB.smx_track_camera(dev.index, n, H, W, disp.data_ptr(),
+                                   None if confidence is None else confidence.data_ptr(), f16(q), float(min_confidence),
+                                   z_min, z_max, float(invalid_disparity), Hm, Wm, model.depth.data_ptr(),
+                                   model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(), poses[2].data_ptr(),
+                                   poses[0].data_ptr(), sched.shape[0], sc, float(max_distance), min_inliers,
+                                   float(min_pivot), float(rot_eps), float(trans_eps), pose_out.data_ptr(),
+                                   info.data_ptr(), rms.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
+                                   _stream(dev.index)))
     index = _INFORMATION_INDEX.get(dev)
     if index is None:
         host = np.zeros((6, 6), np.int64)
@@ -1848,9 +1894,43 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     pose4[:, :3] = pose_out
     pose4[:, 3, 3] = 1.0
     out = (pose4, info[:, 0] != 0, info[:, 1], info[:, 2], info[:, 3], rms, sums[:, index], sums)
+    if photometric:
+        out += (pinfo[:, 0], prms)
     if not batched:
         out = tuple(t[0] for t in out)
     return TrackingResult(*out)
+
+
+def intensity_planes(image: torch.Tensor) -> torch.Tensor:
+    """uint8 frames [n, C, H, W], C = 1 or 3 (RGB), on the GPU to float32 intensity planes [n, H, W]
+    (smx_intensity_planes): (77 R + 150 G + 29 B) / 256, or the gray value itself.  Runs on the current stream."""
+    _check_input("image", image)
+    if image.dtype != torch.uint8 or image.dim() != 4 or image.shape[1] not in (1, 3) or not image.is_cuda:
+        raise RuntimeError(f"image must be uint8 [n, 1 or 3, H, W] on the GPU, got {image.dtype} {tuple(image.shape)} "
+                           f"on {image.device}")
+    n, c, H, W = image.shape
+    if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768 and n * H * W <= 2 ** 30):
+        raise RuntimeError(f"need n >= 1, 1 <= H, W <= 32768 and n * H * W <= 2^30, got {tuple(image.shape)}")
+    out = torch.empty((n, H, W), dtype=torch.float32, device=image.device)
+    check(LIB.smx_intensity_planes(image.device.index, n, c, H, W, image.data_ptr(), out.data_ptr(),
+                                   _stream(image.device.index)))
+    return out
+
+
+def _intensity_plane(name: str, image: torch.Tensor, lead: tuple, H: int, W: int, dev) -> torch.Tensor:
+    """The float32 plane(s) lead + (H, W) of a frame given as uint8 RGB lead + (3, H, W), uint8 gray or float32 intensity
+    lead + (H, W)."""
+    if not isinstance(image, torch.Tensor) or image.device != dev:
+        raise RuntimeError(f"{name} must be a tensor on {dev}")
+    shape = tuple(image.shape)
+    if image.dtype == torch.float32 and shape == lead + (H, W):
+        _check_input(name, image)
+        return image
+    if image.dtype == torch.uint8 and shape in (lead + (3, H, W), lead + (H, W)):
+        c = 3 if shape == lead + (3, H, W) else 1
+        return intensity_planes(image.contiguous().reshape(-1, c, H, W)).reshape(lead + (H, W))
+    raise RuntimeError(f"{name} must be uint8 {lead + (3, H, W)} or {lead + (H, W)}, or float32 {lead + (H, W)}, got "
+                       f"{image.dtype} {shape}")
 
 
 WINDOW_START_MAX = 8192                                            # smx_tsdf_window: |x0|, |y0|, |z0|
@@ -2345,13 +2425,20 @@ class TSDFVolume:
         it from pose_guess [4, 4] / [n, 4, 4] (render, at render_shape -- default the frame's -- with min_weight, step
         and render_depth_range as its depth_range, depth and normals only) and tracks the frame against that view from
         the same pose (track_camera, which takes track_args).  Frame-to-model tracking: fuse the frame at the returned
-        pose if it is not lost, and pass that pose as the next frame's guess."""
+        pose if it is not lost, and pass that pose as the next frame's guess.  With image= and a photometric_weight > 0
+        among track_args the view is rendered with its colours, which then are the model's intensity; the volume must
+        have been created with color=True."""
         if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
             raise RuntimeError("disp must be a float32 tensor [H, W] or [n, H, W]")
         shape = tuple(disp.shape[-2:]) if render_shape is None else render_shape
         invalid = track_args.get("invalid_disparity", -1.0)
+        weight = track_args.get("photometric_weight", 0.0)
+        colors = (track_args.get("image") is not None and track_args.get("model_intensity") is None and
+                  isinstance(weight, (int, float)) and weight > 0)
+        if colors and self.color is None:
+            raise RuntimeError("tracking with the photometric term needs a colour volume (TSDFVolume(..., color=True))")
         view = self.render(Q, pose_guess, shape, min_weight=min_weight, step=step, depth_range=render_depth_range,
-                           normals=True, colors=False, invalid_disparity=invalid)
+                           normals=True, colors=colors, invalid_disparity=invalid)
         return track_camera(disp, Q, pose_guess, view, pose_guess, model_Q=Q, **track_args)
 
     def extract_point_cloud_batched(self, capacity: int, *, min_weight: float = 1.0, normals: bool = True,

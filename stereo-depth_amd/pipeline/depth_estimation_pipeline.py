@@ -184,8 +184,10 @@ class DepthEstimationPipeline:
         pipeline find the poses itself, and process() then takes no camera_pose: the first frame is integrated at
         initial_pose [4, 4] (default the identity); every later frame is tracked against the volume rendered from the
         last pose (TSDFVolume.track with point_cloud_depth_range, the confidence map and point_cloud_min_confidence, and
-        tracking_args on top), its twelve pose values and its lost flag are read back -- one small device-to-host copy,
-        hence one synchronisation, per frame -- and it is integrated at the tracked pose unless it is lost.  The result
+        tracking_args on top; a photometric_weight > 0 among them passes the left frame the map was computed on as the
+        photometric term's image, which needs a colour volume), its twelve pose values and its lost flag are read back
+        -- one small device-to-host copy, hence one synchronisation, per frame -- and it is integrated at the tracked
+        pose unless it is lost.  The result
         carries camera_pose and tracking_lost; reset_tracking() forgets the last pose.  follow_camera /
         follow_threshold / follow_anchor / keep_spill: follow_camera=True (needs tsdf_volume) lets the volume follow the
         camera: before a frame is integrated the volume is shifted in whole voxels so that the frame's pose -- the
@@ -335,7 +337,7 @@ class DepthEstimationPipeline:
             cloud = self._point_cloud(disparity, left_on_device, confidence)
         lost = None
         if self._track_camera:
-            camera_pose, lost = self._track(disparity, confidence)
+            camera_pose, lost = self._track(disparity, confidence, left_on_device)
         shift, spilled, restored = (0, 0, 0), [], 0
         if self._follow_camera and not lost and self._spill_store is not None:
             shift, spilled, restored = self._spill_store.follow(self._tsdf_volume, camera_pose,
@@ -362,15 +364,21 @@ class DepthEstimationPipeline:
                                      camera_pose=camera_pose if self._track_camera else None, tracking_lost=lost,
                                      volume_shift=shift, spilled_volumes=spilled, restored_boxes=restored)
 
-    def _track(self, disparity: torch.Tensor, confidence: Optional[torch.Tensor]):
+    def _track(self, disparity: torch.Tensor, confidence: Optional[torch.Tensor], left: torch.Tensor):
         """(pose [4, 4] float64, lost) of this frame: initial_pose for the first frame, else the frame tracked against
-        the volume seen from the last pose; the last pose moves on unless tracking was lost."""
+        the volume seen from the last pose; the last pose moves on unless tracking was lost.  left: the frame the map was
+        computed on, the image of the photometric term where tracking_args ask for one."""
         if self._last_pose is None:
             self._last_pose = self._initial_pose.copy()
             return self._last_pose.copy(), False
         args = dict(confidence=confidence, min_confidence=self._point_cloud_min_confidence,
                     depth_range=self._point_cloud_depth_range, invalid_disparity=self._config.invalid_disparity)
         args.update(self._tracking_args)
+        if args.get("photometric_weight", 0.0) > 0 and args.get("image") is None:
+            if left.dtype != torch.uint8 and not (left.dtype == torch.float32 and left.dim() == 2):
+                raise ValueError("the photometric term needs uint8 frames or a float32 gray frame, got "
+                                 f"{left.dtype} {tuple(left.shape)}")
+            args["image"] = left.contiguous()
         found = self._tsdf_volume.track(disparity, self._reprojection_matrix, self._last_pose, **args)
         packed = torch.cat([found.pose.reshape(-1), found.lost.reshape(1).to(torch.float32)]).cpu().numpy()
         lost = bool(packed[16] != 0)

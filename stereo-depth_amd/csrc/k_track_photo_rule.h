@@ -13,14 +13,11 @@ constexpr int TRKP_WEE = TRK_SLOTS - 1, TRKP_W = TRK_SLOTS, TRKP_COUNT = TRK_SLO
 static_assert(TRKP_WEE == TRK_TERMS + 1 && TRKP_COUNT == TRKP_SLOTS - 1, "the photometric sums follow the accepted count");
 
 struct TrackPhotoArgs {
-    TrackArgs g;                                                     // sums, partial and partial_stride unused (NULL, 0)
+    TrackArgs g;                                                     // sums: [n][TRKP_TERMS]; the partials hold TRKP_SLOTS
     const float *__restrict__ frame_int, *__restrict__ model_int;    // [n][H][W], [n][Hm][Wm]
     float weight, max_diff;                                          // lambda, max_intensity_difference
     int *pinfo;                                                      // [n][2], may be NULL
     float *prms;                                                     // [n], may be NULL
-    double *sums;                                                    // [n][TRKP_TERMS], may be NULL
-    double *partial;                                                 // workspace [n][groups of stride 1][TRKP_SLOTS]
-    size_t partial_stride;                                           // doubles per triple
 };
 
 // Adds the terms of pixel (px, py) of frame f at the pose T to acc: the geometric ones, and after them, if the pixel was
@@ -95,11 +92,9 @@ TRK_FN void trkp_pixel(const TrackPhotoArgs &pa, const float *T, int f, int px, 
 
 // The outputs of a triple for which no iteration has run, and its state
 TRK_FN void trkp_begin(const TrackPhotoArgs &pa, int f) {
-    trk_begin(pa.g, f);
+    trk_begin(pa.g, f, TRKP_TERMS);
     if (pa.pinfo) pa.pinfo[2 * f] = pa.pinfo[2 * f + 1] = 0;
     if (pa.prms) pa.prms[f] = __builtin_nanf("");
-    if (pa.sums)
-        for (int k = 0; k < TRKP_TERMS; ++k) pa.sums[(size_t)f * TRKP_TERMS + k] = 0.0;
 }
 
 // The end of an iteration of triple f, from its TRKP_SLOTS sums
@@ -110,11 +105,9 @@ TRK_FN void trkp_finish(const TrackPhotoArgs &pa, int f, const double *S) {
         pa.pinfo[2 * f + 1] = (int)S[29] - count;
     }
     if (pa.prms) pa.prms[f] = sqrtf((float)(S[TRKP_WEE] / S[TRKP_W]));
-    if (pa.sums) {
-        for (int k = 0; k < TRK_TERMS; ++k) pa.sums[(size_t)f * TRKP_TERMS + k] = S[k];
-        for (int k = 0; k < 3; ++k) pa.sums[(size_t)f * TRKP_TERMS + TRK_TERMS + k] = S[TRKP_WEE + k];
-    }
-    trk_finish(pa.g, f, S);
+    if (pa.g.sums)
+        for (int k = 0; k < 3; ++k) pa.g.sums[(size_t)f * TRKP_TERMS + TRK_TERMS + k] = S[TRKP_WEE + k];
+    trk_finish(pa.g, f, S, TRKP_TERMS);
 }
 
 }  // namespace smx

@@ -32,9 +32,9 @@ struct TrackArgs {
     const float *pose_in;                                            // [n][3][4]
     float *pose_out, *rms;                                           // rms and the outputs below may be NULL
     int *info;                                                       // [n][4]
-    double *sums;                                                    // [n][30]
+    double *sums;                                                    // [n][the rule's terms]
     TrackState *state;                                               // workspace [n]
-    double *partial;                                                 // workspace [n][groups of stride 1][TRK_SLOTS]
+    double *partial;                                                 // workspace [n][groups of stride 1][the rule's slots]
     size_t partial_stride;                                           // doubles per triple
 };
 
@@ -177,8 +177,8 @@ TRK_FN bool trk_update(float *T, const double x[6], float rot_eps2, float trans_
 }
 
 // The outputs of a triple for which no iteration has run (the first launch of a call writes them, so a schedule of zero
-// iterations is the identity), and its state
-TRK_FN void trk_begin(const TrackArgs &a, int f) {
+// iterations is the identity), and its state.  terms: the sums per triple of the rule that is tracked, this one's or more.
+TRK_FN void trk_begin(const TrackArgs &a, int f, int terms = TRK_TERMS) {
     TrackState &st = a.state[f];
     float in[12];
     for (int i = 0; i < 12; ++i) in[i] = a.pose_in[(size_t)f * 12 + i];   // read whole before pose_out, which may be it
@@ -187,11 +187,12 @@ TRK_FN void trk_begin(const TrackArgs &a, int f) {
     if (a.info) a.info[4 * f] = a.info[4 * f + 1] = a.info[4 * f + 2] = a.info[4 * f + 3] = 0;
     if (a.rms) a.rms[f] = __builtin_nanf("");
     if (a.sums)
-        for (int k = 0; k < TRK_TERMS; ++k) a.sums[(size_t)f * TRK_TERMS + k] = 0.0;
+        for (int k = 0; k < terms; ++k) a.sums[(size_t)f * terms + k] = 0.0;
 }
 
-// The end of an iteration of triple f, from its TRK_SLOTS sums: the outputs, the new pose, the stop flags
-TRK_FN void trk_finish(const TrackArgs &a, int f, const double *S) {
+// The end of an iteration of triple f, from its sums: the outputs (the first TRK_TERMS of the triple's `terms` sums), the
+// new pose, the stop flags
+TRK_FN void trk_finish(const TrackArgs &a, int f, const double *S, int terms = TRK_TERMS) {
     TrackState &st = a.state[f];
     const int inliers = (int)S[29];
     st.iterations += 1;
@@ -202,7 +203,7 @@ TRK_FN void trk_finish(const TrackArgs &a, int f, const double *S) {
     }
     if (a.rms) a.rms[f] = sqrtf((float)(S[27] / S[28]));
     if (a.sums)
-        for (int k = 0; k < TRK_TERMS; ++k) a.sums[(size_t)f * TRK_TERMS + k] = S[k];
+        for (int k = 0; k < TRK_TERMS; ++k) a.sums[(size_t)f * terms + k] = S[k];
     double x[6];
     const bool ok = inliers >= a.min_inliers && trk_solve(S, a.min_pivot, x);
     float *out = a.pose_out + (size_t)f * 12;

@@ -191,32 +191,38 @@ void launch_tsdf_merge(int nx, int ny, int nz, float *tsdf, float *weight, uint8
                        const float *src_tsdf, const float *src_weight, const uint8_t *src_color, int x0, int y0, int z0,
                        int rx, int ry, int rz, int cx, int cy, int cz, int mode, float max_weight, hipStream_t s);
 
-// ---- tu_track.hip: camera tracking against rendered model views (k_track.h) ----------------------------------------------
-// q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every other pointer is device memory; confidence,
-// info, rms and normal_equations may be NULL; workspace: track_layout(n, H, W); arguments checked by smx_track_camera
-void launch_track_camera(int n, int H, int W, const float *disp, const float *confidence, const float q[16],
-                         float min_confidence, float zmin, float zmax, float invalid, int Hm, int Wm,
-                         const float *model_depth, const float *model_normals, const float qm[16], const float pm[16],
-                         const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
-                         int pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
-                         float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
-                         double *normal_equations, void *workspace, hipStream_t s);
-
-// ---- tu_track_photo.hip: tracking with the photometric term, and intensity planes (k_track_photo.h) ----------------------
-// as launch_track_camera, plus the two intensity planes (device) and the term's weight and threshold; normal_equations is
-// [n][33]; photometric_info and photometric_rms may be NULL; workspace: track_photo_layout(n, H, W); arguments checked by
-// smx_track_camera_photometric
-void launch_track_camera_photometric(int n, int H, int W, const float *disp, const float *confidence, const float q[16],
-                                     float min_confidence, float zmin, float zmax, float invalid, int Hm, int Wm,
-                                     const float *model_depth, const float *model_normals, const float qm[16],
-                                     const float pm[16], const float *model_camera_to_world,
-                                     const float *model_world_to_camera, const float *pose_in, int pairs,
-                                     const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
-                                     float rot_eps, float trans_eps, const float *frame_intensity,
-                                     const float *model_intensity, float photometric_weight,
-                                     float max_intensity_difference, float *pose_out, int32_t *info, float *rms,
-                                     double *normal_equations, int32_t *photometric_info, float *photometric_rms,
-                                     void *workspace, hipStream_t s);
+// ---- tu_track.hip, tu_track_photo.hip: camera tracking against rendered model views (k_track.h, k_track_photo.h) ----------
+// A call's operands in the C entries' order.  q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every
+// other pointer is device memory; confidence, info, rms and normal_equations ([n][30], with the photometric term
+// [n][33]) may be NULL; arguments checked by smx_track_camera and smx_track_camera_photometric
+struct TrackCall {
+    int n, H, W;
+    const float *disp, *confidence, *q;
+    float min_confidence, zmin, zmax, invalid;
+    int Hm, Wm;
+    const float *model_depth, *model_normals, *qm, *pm, *model_camera_to_world, *model_world_to_camera, *pose_in;
+    int pairs;
+    const int32_t *schedule;
+    float max_distance;
+    int min_inliers;
+    float min_pivot, rot_eps, trans_eps;
+    float *pose_out;
+    int32_t *info;
+    float *rms;
+    double *normal_equations;
+    void *workspace;
+};
+// the photometric term: the two intensity planes (device), its weight and threshold, and its outputs, which may be NULL
+struct TrackPhotoTerm {
+    const float *frame_intensity, *model_intensity;
+    float weight, max_intensity_difference;
+    int32_t *info;
+    float *rms;
+};
+// workspace: track_layout(n, H, W)
+void launch_track_camera(const TrackCall &c, hipStream_t s);
+// workspace: track_photo_layout(n, H, W)
+void launch_track_camera_photometric(const TrackCall &c, const TrackPhotoTerm &t, hipStream_t s);
 // in: uint8 [n][C][H][W], C 1 or 3; out: f32 [n][H][W]; arguments checked by smx_intensity_planes
 void launch_intensity_planes(int n, int C, int H, int W, const uint8_t *in, float *out, hipStream_t s);
 

@@ -894,18 +894,15 @@ size_t smx_track_camera_workspace_bytes(int n, int H, int W) {
 }
 
 // The checks smx_track_camera and smx_track_camera_photometric share, in their order: everything before the workspace's
-// size.  intensity: the photometric entry's two planes are part of the NULL check.
-static int check_track_args(const char *fn, bool intensity, const void *frame_intensity, const void *model_intensity,
-                            int n, int H, int W, const float *disp, const float Q[16], float min_confidence, float z_min,
-                            float z_max, float invalid_disparity, int Hm, int Wm, const float *model_depth,
-                            const float *model_normals, const float Qm[16], const float Pm[16],
-                            const float *model_camera_to_world, const float *model_world_to_camera, const float *pose_in,
-                            int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers,
-                            float min_pivot, float rot_eps, float trans_eps, const float *pose_out, const void *workspace) {
-    if (intensity && (!frame_intensity || !model_intensity))
+// size.  photo: the photometric entry's term, whose two planes are part of the NULL check.
+static int check_track_args(const char *fn, const smx::TrackCall &c, const smx::TrackPhotoTerm *photo) {
+    const int n = c.n, H = c.H, W = c.W, Hm = c.Hm, Wm = c.Wm, schedule_pairs = c.pairs;
+    const float *Q = c.q, *Qm = c.qm, *Pm = c.pm;
+    const int32_t *schedule = c.schedule;
+    if (photo && (!photo->frame_intensity || !photo->model_intensity))
         return fail(SMX_ERR_INVALID_ARG, "%s: frame_intensity and model_intensity must be non-NULL", fn);
-    if (!disp || !Q || !model_depth || !model_normals || !Qm || !Pm || !model_camera_to_world || !model_world_to_camera ||
-        !pose_in || !pose_out || !workspace)
+    if (!c.disp || !Q || !c.model_depth || !c.model_normals || !Qm || !Pm || !c.model_camera_to_world ||
+        !c.model_world_to_camera || !c.pose_in || !c.pose_out || !c.workspace)
         return fail(SMX_ERR_INVALID_ARG,
                     "%s: disp, Q, model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, "
                     "pose_in, pose_out and workspace must be non-NULL", fn);
@@ -925,7 +922,7 @@ static int check_track_args(const char *fn, bool intensity, const void *frame_in
     if (Qm[2] != 0.0f || Qm[6] != 0.0f || Qm[10] != 0.0f || Qm[12] != 0.0f || Qm[13] != 0.0f || Qm[14] == 0.0f)
         return fail(SMX_ERR_INVALID_ARG,
                     "%s: Qm's ray must not depend on d: need Qm02 = Qm12 = Qm22 = 0, Qm30 = Qm31 = 0 and Qm32 != 0", fn);
-    if (int rc = check_reprojection_args(fn, z_min, z_max, min_confidence, invalid_disparity, nullptr, 0, 0, nullptr, ""))
+    if (int rc = check_reprojection_args(fn, c.zmin, c.zmax, c.min_confidence, c.invalid, nullptr, 0, 0, nullptr, ""))
         return rc;
     if (int rc = check_int_range(fn, "schedule_pairs", schedule_pairs, 0, 8)) return rc;
     if (schedule_pairs > 0 && !schedule) return fail(SMX_ERR_INVALID_ARG, "%s: schedule must be non-NULL", fn);
@@ -936,12 +933,47 @@ static int check_track_args(const char *fn, bool intensity, const void *frame_in
         iterations += schedule[2 * p + 1];
     }
     if (int rc = check_int_range(fn, "the schedule's iterations in total", iterations, 0, 64)) return rc;
-    if (int rc = check_positive(fn, "max_distance", max_distance)) return rc;
-    if (int rc = check_int_range(fn, "min_inliers", min_inliers, 1, 1 << 30)) return rc;
-    if (int rc = check_non_negative(fn, "min_pivot", min_pivot)) return rc;
-    if (int rc = check_non_negative(fn, "rot_eps", rot_eps)) return rc;
-    if (int rc = check_non_negative(fn, "trans_eps", trans_eps)) return rc;
+    if (int rc = check_positive(fn, "max_distance", c.max_distance)) return rc;
+    if (int rc = check_int_range(fn, "min_inliers", c.min_inliers, 1, 1 << 30)) return rc;
+    if (int rc = check_non_negative(fn, "min_pivot", c.min_pivot)) return rc;
+    if (int rc = check_non_negative(fn, "rot_eps", c.rot_eps)) return rc;
+    if (int rc = check_non_negative(fn, "trans_eps", c.trans_eps)) return rc;
     return SMX_OK;
+}
+
+// smx_track_camera and smx_track_camera_photometric: photo NULL is smx_track_camera.
+static int track_entry(const char *fn, int device_id, const smx::TrackCall &c, const smx::TrackPhotoTerm *photo,
+                       size_t workspace_bytes, void *stream) {
+    if (int rc = check_track_args(fn, c, photo)) return rc;
+    if (photo) {
+        if (int rc = check_non_negative(fn, "photometric_weight", photo->weight)) return rc;
+        if (int rc = check_positive(fn, "max_intensity_difference", photo->max_intensity_difference)) return rc;
+    }
+    if (int rc = photo ? check_workspace_bytes(fn, "smx_track_camera_photometric_workspace_bytes", workspace_bytes,
+                                               track_photo_layout(c.n, c.H, c.W).total)
+                       : check_workspace_bytes(fn, "smx_track_camera_workspace_bytes", workspace_bytes,
+                                               track_layout(c.n, c.H, c.W).total))
+        return rc;
+    const size_t n = (size_t)c.n, map_bytes = n * c.H * c.W * sizeof(float), model_bytes = n * c.Hm * c.Wm * sizeof(float);
+    const size_t pose_bytes = n * 12 * sizeof(float);
+    const smx::TrackPhotoTerm none{}, &t = photo ? *photo : none;    // a NULL span overlaps nothing
+    if (int rc = check_disjoint(fn, {{c.disp, map_bytes}, {c.confidence, map_bytes}, {c.model_depth, model_bytes},
+                                     {c.model_normals, 3 * model_bytes}, {c.model_camera_to_world, pose_bytes},
+                                     {c.model_world_to_camera, pose_bytes},
+                                     {c.pose_in != c.pose_out ? c.pose_in : nullptr, pose_bytes},
+                                     {t.frame_intensity, map_bytes}, {t.model_intensity, model_bytes}},
+                                {{c.pose_out, pose_bytes}, {c.info, n * 4 * sizeof(int32_t)}, {c.rms, n * sizeof(float)},
+                                 {c.normal_equations, n * (photo ? TRKP_TERMS : TRK_TERMS) * sizeof(double)},
+                                 {t.info, n * 2 * sizeof(int32_t)}, {t.rms, n * sizeof(float)},
+                                 {c.workspace, workspace_bytes}},
+                                "an output or the workspace overlaps an input (pose_out may be pose_in itself)",
+                                "two outputs (the workspace is one) overlap"))
+        return rc;
+    if (int rc = check_workspace_and_stream(fn, c.workspace, stream)) return rc;
+    return launch_on(device_id, [&] {
+        if (photo) smx::launch_track_camera_photometric(c, *photo, (hipStream_t)stream);
+        else smx::launch_track_camera(c, (hipStream_t)stream);
+    });
 }
 
 int smx_track_camera(int device_id, int n, int H, int W, const float *disp, const float *confidence, const float Q[16],
@@ -951,33 +983,11 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
                      int schedule_pairs, const int32_t *schedule, float max_distance, int min_inliers, float min_pivot,
                      float rot_eps, float trans_eps, float *pose_out, int32_t *info, float *rms,
                      double *normal_equations, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "smx_track_camera";
-    if (int rc = check_track_args(fn, false, nullptr, nullptr, n, H, W, disp, Q, min_confidence, z_min, z_max,
-                                  invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm, model_camera_to_world,
-                                  model_world_to_camera, pose_in, schedule_pairs, schedule, max_distance, min_inliers,
-                                  min_pivot, rot_eps, trans_eps, pose_out, workspace))
-        return rc;
-    if (int rc = check_workspace_bytes(fn, "smx_track_camera_workspace_bytes", workspace_bytes,
-                                       track_layout(n, H, W).total))
-        return rc;
-    const size_t map_bytes = (size_t)n * H * W * sizeof(float), model_bytes = (size_t)n * Hm * Wm * sizeof(float);
-    const size_t pose_bytes = (size_t)n * 12 * sizeof(float);
-    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {model_depth, model_bytes},
-                                     {model_normals, 3 * model_bytes}, {model_camera_to_world, pose_bytes},
-                                     {model_world_to_camera, pose_bytes}, {pose_in != pose_out ? pose_in : nullptr, pose_bytes}},
-                                {{pose_out, pose_bytes}, {info, (size_t)n * 4 * sizeof(int32_t)},
-                                 {rms, (size_t)n * sizeof(float)}, {normal_equations, (size_t)n * TRK_TERMS * sizeof(double)},
-                                 {workspace, workspace_bytes}},
-                                "an output or the workspace overlaps an input (pose_out may be pose_in itself)",
-                                "two outputs (the workspace is one) overlap"))
-        return rc;
-    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
-    return launch_on(device_id, [&] {
-        smx::launch_track_camera(n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity, Hm, Wm,
-                                 model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
-                                 schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps,
-                                 pose_out, info, rms, normal_equations, workspace, (hipStream_t)stream);
-    });
+    const smx::TrackCall c{n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity, Hm, Wm,
+                           model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
+                           schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out,
+                           info, rms, normal_equations, workspace};
+    return track_entry("smx_track_camera", device_id, c, nullptr, workspace_bytes, stream);
 }
 
 size_t smx_track_camera_photometric_workspace_bytes(int n, int H, int W) {
@@ -995,40 +1005,13 @@ int smx_track_camera_photometric(int device_id, int n, int H, int W, const float
                                  float max_intensity_difference, float *pose_out, int32_t *info, float *rms,
                                  double *normal_equations, int32_t *photometric_info, float *photometric_rms,
                                  void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "smx_track_camera_photometric";
-    if (int rc = check_track_args(fn, true, frame_intensity, model_intensity, n, H, W, disp, Q, min_confidence, z_min,
-                                  z_max, invalid_disparity, Hm, Wm, model_depth, model_normals, Qm, Pm,
-                                  model_camera_to_world, model_world_to_camera, pose_in, schedule_pairs, schedule,
-                                  max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out, workspace))
-        return rc;
-    if (int rc = check_non_negative(fn, "photometric_weight", photometric_weight)) return rc;
-    if (int rc = check_positive(fn, "max_intensity_difference", max_intensity_difference)) return rc;
-    if (int rc = check_workspace_bytes(fn, "smx_track_camera_photometric_workspace_bytes", workspace_bytes,
-                                       track_photo_layout(n, H, W).total))
-        return rc;
-    const size_t map_bytes = (size_t)n * H * W * sizeof(float), model_bytes = (size_t)n * Hm * Wm * sizeof(float);
-    const size_t pose_bytes = (size_t)n * 12 * sizeof(float);
-    if (int rc = check_disjoint(fn, {{disp, map_bytes}, {confidence, map_bytes}, {model_depth, model_bytes},
-                                     {model_normals, 3 * model_bytes}, {model_camera_to_world, pose_bytes},
-                                     {model_world_to_camera, pose_bytes}, {pose_in != pose_out ? pose_in : nullptr, pose_bytes},
-                                     {frame_intensity, map_bytes}, {model_intensity, model_bytes}},
-                                {{pose_out, pose_bytes}, {info, (size_t)n * 4 * sizeof(int32_t)},
-                                 {rms, (size_t)n * sizeof(float)}, {normal_equations, (size_t)n * TRKP_TERMS * sizeof(double)},
-                                 {photometric_info, (size_t)n * 2 * sizeof(int32_t)},
-                                 {photometric_rms, (size_t)n * sizeof(float)}, {workspace, workspace_bytes}},
-                                "an output or the workspace overlaps an input (pose_out may be pose_in itself)",
-                                "two outputs (the workspace is one) overlap"))
-        return rc;
-    if (int rc = check_workspace_and_stream(fn, workspace, stream)) return rc;
-    return launch_on(device_id, [&] {
-        smx::launch_track_camera_photometric(n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity,
-                                             Hm, Wm, model_depth, model_normals, Qm, Pm, model_camera_to_world,
-                                             model_world_to_camera, pose_in, schedule_pairs, schedule, max_distance,
-                                             min_inliers, min_pivot, rot_eps, trans_eps, frame_intensity, model_intensity,
-                                             photometric_weight, max_intensity_difference, pose_out, info, rms,
-                                             normal_equations, photometric_info, photometric_rms, workspace,
-                                             (hipStream_t)stream);
-    });
+    const smx::TrackCall c{n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity, Hm, Wm,
+                           model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
+                           schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out,
+                           info, rms, normal_equations, workspace};
+    const smx::TrackPhotoTerm photo{frame_intensity, model_intensity, photometric_weight, max_intensity_difference,
+                                    photometric_info, photometric_rms};
+    return track_entry("smx_track_camera_photometric", device_id, c, &photo, workspace_bytes, stream);
 }
 
 int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const uint8_t *image, float *out,

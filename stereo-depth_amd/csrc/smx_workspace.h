@@ -173,7 +173,7 @@ inline RaycastLayout raycast_layout(int nx, int ny, int nz) {
 }
 
 // ---- camera tracking: one state record of 32 words per triple | the sums of every group of four tiles of the selected
-// grid, double[n][groups at stride 1][TRK_SLOTS].  The constants are shared with k_track.h and fix the order of the sums.
+// grid, double[n][groups at stride 1][TRK_SLOTS].  The constants are shared with k_track_body.h and fix the order of the sums.
 #ifndef SMX_TRK_ROWS                           // tuning experiments only (build.py: SMX_EXTRA_FLAGS): another value sums in
 #define SMX_TRK_ROWS 4                         // another order than the header states
 #endif
@@ -181,7 +181,7 @@ constexpr int TRK_COLS = 64, TRK_ROWS = SMX_TRK_ROWS;   // a tile of the selecte
 constexpr int TRK_WAVES = 4;                   // tiles per workgroup, consecutive in row-major order
 constexpr int TRK_TERMS = 30;                  // the sums of the header ...
 constexpr int TRK_SLOTS = 32;                  // ... then the accepted pixels, and one unused slot
-constexpr int TRK_MAX_TILES = 32768;           // of a frame at stride 1 (the combine kernel's stack: k_track.h)
+constexpr int TRK_MAX_TILES = 32768;           // of a frame at stride 1 (the combine kernel's stack: k_track_body.h)
 struct TrackGrid {
     int ws, hs, tx, ty, tiles, groups;         // selected columns and rows; tiles across, down, in all; groups of 4 tiles
 };
@@ -197,11 +197,11 @@ struct TrackLayout {
     WsPart state, partial;
     size_t total;
 };
-inline TrackLayout track_layout(int n, int H, int W) {
+inline TrackLayout track_layout(int n, int H, int W, int slots = TRK_SLOTS) {
     const int groups = track_grid(H, W, 1).groups;
     WsCursor c;
-    return TrackLayout{groups, c.take((size_t)n * 32 * sizeof(int)),
-                       c.take((size_t)n * groups * TRK_SLOTS * sizeof(double)), c.at};
+    return TrackLayout{groups, c.take((size_t)n * 32 * sizeof(int)), c.take((size_t)n * groups * slots * sizeof(double)),
+                       c.at};
 }
 
 // ---- camera tracking with the photometric term: the same state record | the sums of every group of four tiles,
@@ -209,11 +209,6 @@ inline TrackLayout track_layout(int n, int H, int W) {
 // are, then the three photometric sums (k_track_photo_rule.h).
 constexpr int TRKP_TERMS = TRK_TERMS + 3;      // the sums of the header: thirty of the joint system, three photometric
 constexpr int TRKP_SLOTS = TRK_TERMS + 4;      // the thirty, the accepted pixels, the three
-inline TrackLayout track_photo_layout(int n, int H, int W) {
-    const int groups = track_grid(H, W, 1).groups;
-    WsCursor c;
-    return TrackLayout{groups, c.take((size_t)n * 32 * sizeof(int)),
-                       c.take((size_t)n * groups * TRKP_SLOTS * sizeof(double)), c.at};
-}
+inline TrackLayout track_photo_layout(int n, int H, int W) { return track_layout(n, H, W, TRKP_SLOTS); }
 
 }  // namespace smx

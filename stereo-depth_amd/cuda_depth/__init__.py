@@ -1798,7 +1798,9 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     0.001 to 0.03; a term whose intensities differ by more than max_intensity_difference is left out.  The term's basin
     is a few model pixels.  Without an image, or with a weight of 0, the geometric entry runs as it always did."""
     for name, v, positive in (("photometric_weight", photometric_weight, False),
-                              ("max_intensity_difference", max_intensity_difference, True)):
+                              ("max_intensity_difference", max_intensity_difference, True),
+                              ("max_distance", max_distance, True), ("min_pivot", min_pivot, False),
+                              ("rot_eps", rot_eps, False), ("trans_eps", trans_eps, False)):
         _number_arg(name, v)
         if not (math.isfinite(v) and (v > 0 if positive else v >= 0)):
             raise RuntimeError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v}")
@@ -1812,11 +1814,6 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     pm = projection_matrix(qm)
     z_min, z_max = _check_reproject_params(min_confidence, depth_range, invalid_disparity)
     sched = _check_tracking_schedule(schedule)
-    for name, v, positive in (("max_distance", max_distance, True), ("min_pivot", min_pivot, False),
-                              ("rot_eps", rot_eps, False), ("trans_eps", trans_eps, False)):
-        _number_arg(name, v)
-        if not (math.isfinite(v) and (v > 0 if positive else v >= 0)):
-            raise RuntimeError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v}")
     if not isinstance(min_inliers, int) or isinstance(min_inliers, bool) or not 1 <= min_inliers <= 2 ** 30:
         raise RuntimeError(f"min_inliers must be an int in 1..2^30, got {min_inliers!r}")
     _check_input("disp", disp)
@@ -1851,6 +1848,11 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     rms = torch.empty((n,), dtype=torch.float32, device=dev)
     f16 = lambda m: (C.c_float * 16)(*m.reshape(-1).tolist())  # noqa: E731
     sc = (C.c_int32 * max(sched.size, 1))(*sched.reshape(-1).tolist())
+    # the arguments both entries take first; then the term's operands, if any; then the outputs and the workspace
+    args = (dev.index, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(), f16(q),
+            float(min_confidence), z_min, z_max, float(invalid_disparity), Hm, Wm, model.depth.data_ptr(),
+            model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(), poses[2].data_ptr(), poses[0].data_ptr(),
+            sched.shape[0], sc, float(max_distance), min_inliers, float(min_pivot), float(rot_eps), float(trans_eps))
     pinfo = prms = None
     if photometric:
         frame_int = _intensity_plane("image", image, lead, H, W, dev)
@@ -1859,31 +1861,19 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
                 raise RuntimeError("the photometric term needs model.colors (render with colors=True) or model_intensity")
             model_intensity = model.colors
         model_int = _intensity_plane("model_intensity", model_intensity, lead, Hm, Wm, dev)
-        sums = torch.empty((n, 33), dtype=torch.float64, device=dev)
         pinfo = torch.empty((n, 2), dtype=torch.int32, device=dev)
         prms = torch.empty((n,), dtype=torch.float32, device=dev)
-        ws_bytes = LIB.smx_track_camera_photometric_workspace_bytes(n, H, W)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(LIB.smx_track_camera_photometric(
-            dev.index, n, H, W, disp.data_ptr(), None if confidence is None else confidence.data_ptr(), f16(q),
-            float(min_confidence), z_min, z_max, float(invalid_disparity), Hm, Wm, model.depth.data_ptr(),
-            model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(), poses[2].data_ptr(), poses[0].data_ptr(),
-            sched.shape[0], sc, float(max_distance), min_inliers, float(min_pivot), float(rot_eps), float(trans_eps),
-            frame_int.data_ptr(), model_int.data_ptr(), float(photometric_weight), float(max_intensity_difference),
-            pose_out.data_ptr(), info.data_ptr(), rms.data_ptr(), sums.data_ptr(), pinfo.data_ptr(), prms.data_ptr(),
-            ws.data_ptr(), ws_bytes, _stream(dev.index)))
+        args += (frame_int.data_ptr(), model_int.data_ptr(), float(photometric_weight), float(max_intensity_difference))
+        entry, query = LIB.smx_track_camera_photometric, LIB.smx_track_camera_photometric_workspace_bytes
     else:
-        sums = torch.empty((n, 30), dtype=torch.float64, device=dev)
-        ws_bytes = LIB.smx_track_camera_workspace_bytes(n, H, W)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(LIB.smx_track_camera(dev.index, n, H, W, disp.data_ptr(),
-                                   None if confidence is None else confidence.data_ptr(), f16(q), float(min_confidence),
-                                   z_min, z_max, float(invalid_disparity), Hm, Wm, model.depth.data_ptr(),
-                                   model.normals.data_ptr(), f16(qm), f16(pm), poses[1].data_ptr(), poses[2].data_ptr(),
-                                   poses[0].data_ptr(), sched.shape[0], sc, float(max_distance), min_inliers,
-                                   float(min_pivot), float(rot_eps), float(trans_eps), pose_out.data_ptr(),
-                                   info.data_ptr(), rms.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
-                                   _stream(dev.index)))
+        entry, query = LIB.smx_track_camera, LIB.smx_track_camera_workspace_bytes
+    sums = torch.empty((n, 33 if photometric else 30), dtype=torch.float64, device=dev)
+    ws_bytes = query(n, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    args += (pose_out.data_ptr(), info.data_ptr(), rms.data_ptr(), sums.data_ptr())
+    if photometric:
+        args += (pinfo.data_ptr(), prms.data_ptr())
+    check(entry(*args, ws.data_ptr(), ws_bytes, _stream(dev.index)))
     index = _INFORMATION_INDEX.get(dev)
     if index is None:
         host = np.zeros((6, 6), np.int64)

@@ -227,21 +227,16 @@ EXPORTS = {
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    # the same with a photometric term: smx_track_camera's arguments up to trans_eps, then frame_intensity,
-    # model_intensity, photometric_weight, max_intensity_difference, pose_out, info, rms, normal_equations ([n][33]),
-    # photometric_info, photometric_rms, workspace, workspace_bytes, stream
     "smx_track_camera_photometric_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "smx_track_camera_photometric": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
-                                               C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
-                                               C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                               C.c_void_p]),
     # uint8 frames to float32 intensity planes: (device_id, n, channels, H, W, image, out, stream)
     "smx_intensity_planes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# tracking with a photometric term: smx_track_camera's 27 arguments up to trans_eps, then frame_intensity, model_intensity,
+# photometric_weight, max_intensity_difference; its four outputs (normal_equations: [n][33]), then photometric_info,
+# photometric_rms; its workspace, workspace_bytes, stream
+_TRACK = EXPORTS["smx_track_camera"][1]
+EXPORTS["smx_track_camera_photometric"] = (C.c_int, _TRACK[:27] + [C.c_void_p, C.c_void_p, C.c_float, C.c_float] +
+                                           _TRACK[27:31] + [C.c_void_p, C.c_void_p] + _TRACK[31:])
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*
 DTYPE_U8, DTYPE_F32 = 0, 1                 # SMX_DTYPE_*

@@ -156,7 +156,7 @@ def m():
     c["LR_THREADS"] = one(r"^constexpr int LR_THREADS = (\d+);", "k_lr.h")
     c["LR_PACK_ITEMS"] = one(r"^constexpr int LR_PACK_ITEMS = (\d+);", "k_lr.h")
     c["LR_LDS_W"] = one(r"^constexpr int LR_LDS_W = (\d+);", "k_lr.h")
-    c["TRACK_TRIPLES"] = one(r"const unsigned triples = \(unsigned\)\(n < (\d+) \? n : \1\);", "tu_track.hip")
+    c["TRACK_TRIPLES"] = one(r"const unsigned triples = \(unsigned\)\(n < (\d+) \? n : \1\);", "k_track_body.h")
     # the loops the cases are there to send on a second trip, and what the launchers divide by
     for name, text in (("k_confidence.h", "m += gridDim.y"), ("k_temporal.h", "m += gridDim.y"),
                        ("k_sgm.h", "z += gridDim.y"), ("k_sgm.h", "p += waves"), ("k_median.h", "tile += gridDim.x"),
@@ -168,10 +168,13 @@ def m():
                        ("tu_wls.hip", "grid_of((size_t)n * W, WLS_COL_THREADS)"),
                        ("tu_sgm.hip", "(pixels + SGM_THREADS / 64 - 1) / (SGM_THREADS / 64)"),
                        ("tu_lr.hip", "const bool lds = W <= LR_LDS_W;"),
-                       ("k_track.h", "for (int f = blockIdx.y; f < a.n; f += gridDim.y)"),
-                       ("k_track.h", "for (int f = blockIdx.x; f < a.n; f += gridDim.x)"),
-                       ("tu_track.hip", "k_track_accum, dim3((unsigned)g.groups, triples)"),
-                       ("tu_track.hip", "k_track_solve, dim3(triples)")):
+                       ("k_track_body.h", "for (int f = blockIdx.y; f < a.n; f += gridDim.y)"),
+                       ("k_track_body.h", "for (int f = blockIdx.x; f < a.n; f += gridDim.x)"),
+                       ("k_track_body.h", "hipLaunchKernelGGL(accum, dim3((unsigned)g.groups, triples)"),
+                       ("k_track_body.h", "hipLaunchKernelGGL(solve, dim3(triples)"),
+                       ("k_track.h", "void k_track_accum(const TrackArgs a) { track_accum_body<TrackRule>(a); }"),
+                       ("k_track.h", "void k_track_solve(const TrackArgs a) { track_solve_body<TrackRule>(a); }"),
+                       ("tu_track.hip", "track_launch<TrackRule>(c, a, k_track_begin, k_track_accum, k_track_solve, s)")):
         assert text in source(name), f"{name} no longer holds {text!r}: restate the case's geometry in scale_cases.py"
     return c
 

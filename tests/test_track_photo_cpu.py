@@ -6,6 +6,7 @@ hand; that the deep-tree frames give the combine kernel chunks of more than one 
 argument errors of the Python layer and of the C entries that need no device.  No GPU."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -16,6 +17,7 @@ import track_photo_ref as tp
 import track_ref as tr
 
 f32 = np.float32
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-depth_amd", "csrc")
 
 
 def assert_the_term_is_not_idle(want, what):
@@ -86,12 +88,29 @@ def test_the_edges_of_the_tap_rule(name):
         assert not want["sums"][30:].any() and np.isnan(want["prms"])
 
 
+def test_the_tree_cases_reach_every_form_of_the_combine():
+    """track_photo_cases.py restates the joint rule's combine constants as the source has them, every case has the len it
+    names, and together they take the forms of the chunk tree: a pair, a tree of four, and leaves of eight under the
+    stack."""
+    source = open(os.path.join(CSRC, "k_track_photo.h")).read()
+    assert f"constexpr int TRKP_CHUNKS = {pc.CHUNKS};" in source and f"constexpr int TRKP_STACK = {pc.STACK};" in source
+    assert pc.STACK == 7
+    for shape, want in pc.TREE_CASES:
+        assert pc.tree_len(shape) == want, (shape, pc.tree_len(shape))
+    assert {n for _, n in pc.TREE_CASES} == pc.TREE_LENS == {2, 4, 8, 32}
+    assert [tc.track_grid(s, 1)["groups"] for s in pc.TREE_SHAPES] == [94, 257, 20, 33]
+
+
 @pytest.mark.parametrize("shape", pc.TREE_SHAPES)
 def test_the_deep_tree_frames_reach_past_one_partial_per_chunk(shape):
-    assert pc.tree_len(shape) >= 8                                    # the stack form of the chunk tree
     want = pc.tree_expected(shape)
     assert want["pinfo"][0] > 1000 and np.count_nonzero(want["sums"]) == 33
-    assert tc.track_grid(shape, 1)["groups"] > pc.CHUNKS
+    grid = tc.track_grid(shape, 1)
+    assert grid["groups"] > pc.CHUNKS
+    # every group of four tiles holds inliers: no partial is the +0.0 that any order sums right
+    assert want["tiles"].shape == (tp.SLOTS, grid["tiles"])
+    partials = tc.group_partials(want["tiles"])
+    assert partials.shape[1] == grid["groups"] and (partials[29] != 0).all()
 
 
 def test_the_intensity_rule_is_exact():

@@ -241,7 +241,7 @@ def test_the_edges_of_the_tap_rule(cd, name):
 @pytest.mark.parametrize("shape", pc.TREE_SHAPES)
 def test_one_iteration_past_one_partial_per_chunk(cd, shape):
     want = pc.tree_expected(shape)
-    assert pc.tree_len(shape) >= 8 and want["pinfo"][0] > 1000
+    assert pc.tree_len(shape) == dict(pc.TREE_CASES)[shape] and want["pinfo"][0] > 1000
     disp, Q = tc.scaled_frame(shape)
     d = Direct(disp[None], Q, tc.start_pose(tc.TREE_VIEW)[None], [pc.tree_model()], pc.tree_intensity(shape)[None], pc.WEIGHT,
                200.0, ((1, 1),), conf=tc.wide_confidence(shape)[None], **tc.PARAMS)

@@ -165,6 +165,15 @@ def test_the_edges_of_the_tap_rule(harness, tmp_path, name):
     assert got["info"][2] == 1 and got["pinfo"].tolist() == [count, 1 - count]
 
 
+@pytest.mark.parametrize("shape", pc.TREE_SHAPES)
+def test_one_iteration_on_the_deep_tree_frames(harness, tmp_path, shape):
+    disp, Q = tc.scaled_frame(shape)
+    got = run_arrays(harness, tmp_path, disp[None], Q, tc.start_pose(tc.TREE_VIEW)[None], [pc.tree_model()],
+                     pc.tree_intensity(shape)[None], pc.WEIGHT, 200.0, ((1, 1),), conf=tc.wide_confidence(shape)[None],
+                     **tc.PARAMS)[0]
+    pc.assert_same(got, pc.tree_expected(shape), f"tree {shape}")
+
+
 def test_zero_iterations(harness, tmp_path):
     shape = tc.FRAME_SHAPES[1]
     got = run(harness, tmp_path, [("outside", shape, 0, False, False)], ())[0]

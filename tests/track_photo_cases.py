@@ -103,8 +103,13 @@ def rendered_expected(view, shape, k=0):
 
 
 # ---- the deep tree: one iteration at stride 1 on track_cases.scaled_frame ---------------------------------------------------
-TREE_SHAPES = ((300, 257), (1027, 193))                              # 94 and 209 group partials: 8 and 16 per chunk of 16
-CHUNKS = 16                                                          # k_track_photo.h
+# The combine adds a triple's group partials in 16 chunks of len = padded groups / 16 (k_track_body.h with k_track_photo.h's
+# constants).  (shape, len): 94, 257, 20 and 33 group partials, so one leaf of eight, four leaves of eight under the
+# stack, a pair and a tree of four per chunk
+TREE_CASES = (((300, 257), 8), ((1027, 193), 32), ((80, 193), 2), ((176, 130), 4))
+TREE_SHAPES = tuple(s for s, _ in TREE_CASES)
+TREE_LENS = {2, 4, 8, 32}
+CHUNKS, STACK = 16, 7                                                # k_track_photo.h
 
 
 def tree_len(shape):
@@ -132,7 +137,8 @@ def tree_model():
 def tree_expected(shape):
     d, Q = tc.scaled_frame(shape)
     return tp.track_photo_ref(d, Q, tc.start_pose(tc.TREE_VIEW), tree_model(), tree_intensity(shape), WEIGHT,
-                              confidence=tc.wide_confidence(shape), schedule=((1, 1),), max_difference=200.0, **tc.PARAMS)
+                              confidence=tc.wide_confidence(shape), schedule=((1, 1),), max_difference=200.0, keep_tiles=True,
+                              **tc.PARAMS)
 
 
 # ---- the plane ----------------------------------------------------------------------------------------------------------------

@@ -107,23 +107,24 @@ def tile_sums(G, P):
 def track_photo_ref(disp, Q, pose_in, model, frame_intensity, weight, *, max_difference=DEFAULT_MAX_DIFFERENCE,
                     confidence=None, schedule=tr.DEFAULT_SCHEDULE, max_distance=0.3, depth_range=(0.0, np.inf),
                     min_confidence=0.0, invalid_disparity=-1.0, min_inliers=100, min_pivot=1e-6, rot_eps=0.0,
-                    trans_eps=0.0):
+                    trans_eps=0.0, keep_tiles=False):
     """One triple, as track_ref.track_ref; model: model_view()'s dict with "intensity" [Hm, Wm] added.  Returns a dict of
-    pose, info, rms, sums [33] f64, pinfo [2] int32 (photometric inliers, geometric inliers without the term) and prms."""
+    pose, info, rms, sums [33] f64, pinfo [2] int32 (photometric inliers, geometric inliers without the term) and prms;
+    with keep_tiles also tiles [SLOTS, ty * tx] f64, the tile sums of the last iteration that ran (None if none did)."""
     pts = tr.frame_points(disp, Q, confidence, min_confidence, depth_range, invalid_disparity)
     T0 = np.ascontiguousarray(np.asarray(pose_in, f32)[:3])
     T = T0.copy()
     info, pinfo = np.zeros(4, np.int32), np.zeros(2, np.int32)
     rms = prms = f32(np.nan)
     sums = np.zeros(TERMS, np.float64)
-    done = False
+    done, tiles = False, None
     with np.errstate(all="ignore"):
         for stride, iterations in schedule:
             for _ in range(iterations):
                 if done:
                     break
-                S = tr._pairs_tree(tile_sums(*pixel_terms(pts, T, model, stride, max_distance, frame_intensity, weight,
-                                                          max_difference)))
+                tiles = tile_sums(*pixel_terms(pts, T, model, stride, max_distance, frame_intensity, weight, max_difference))
+                S = tr._pairs_tree(tiles)
                 sums = np.concatenate([S[:30], S[31:34]])
                 info[1] += 1
                 info[2], info[3] = int(S[29]), int(S[30])
@@ -136,4 +137,7 @@ def track_photo_ref(disp, Q, pose_in, model, frame_intensity, weight, *, max_dif
                     break
                 T, ww, tt = tr.update(T, x)
                 done = bool(ww <= f32(rot_eps) * f32(rot_eps) and tt <= f32(trans_eps) * f32(trans_eps))
-    return {"pose": T, "info": info, "rms": f32(rms), "sums": sums, "pinfo": pinfo, "prms": f32(prms)}
+    out = {"pose": T, "info": info, "rms": f32(rms), "sums": sums, "pinfo": pinfo, "prms": f32(prms)}
+    if keep_tiles:
+        out["tiles"] = tiles
+    return out

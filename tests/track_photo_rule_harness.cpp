@@ -79,9 +79,9 @@ int main(int argc, char **argv) {
     std::vector<smx::TrackState> state(n);
     a.disp = disp.data(), a.conf = has_conf ? conf.data() : nullptr, a.depth = depth.data(), a.normals = normals.data();
     a.c2w = c2w.data(), a.w2c = w2c.data(), a.pose_in = pose_in.data();
-    a.pose_out = pose_out.data(), a.rms = rms.data(), a.info = info.data(), a.state = state.data();
+    a.pose_out = pose_out.data(), a.rms = rms.data(), a.info = info.data(), a.sums = sums.data(), a.state = state.data();
     pa.frame_int = fint.data(), pa.model_int = mint.data();
-    pa.pinfo = pinfo.data(), pa.prms = prms.data(), pa.sums = sums.data();
+    pa.pinfo = pinfo.data(), pa.prms = prms.data();
     long ran = 0;
     for (int t = 0; t < a.n; ++t) smx::trkp_begin(pa, t);
     for (int p = 0; p < pairs; ++p) {

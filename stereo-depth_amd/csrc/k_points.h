@@ -6,7 +6,7 @@
 // with a Python double loop on the CPU; here it is an ordered stream compaction on the device:
 // per-row counts -> exclusive scan over rows -> per-row ordered scatter (wave ballots).
 #pragma once
-#include "smx_common.h"
+#include "k_compact.h"
 
 namespace smx {
 
@@ -21,11 +21,8 @@ __global__ __launch_bounds__(256) void k_depth_count(const float *disp, float *d
         if (depth) depth[(size_t)x * W + y] = bf / d;            // hooks.py:91
         cnt += (d != invalid) ? 1 : 0;                            // hooks.py:86
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) row_count[x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int total = block_count(cnt, wsum);
+    if (threadIdx.x == 0) row_count[x] = total;
 }
 
 // single workgroup: exclusive scan of the row counts (H <= 32768), total to *total

@@ -10,7 +10,7 @@
 #pragma once
 #include <climits>
 
-#include "smx_common.h"
+#include "k_camera.h"
 
 namespace smx {
 
@@ -39,32 +39,22 @@ struct ProjPoint {
 
 __device__ __forceinline__ bool project_point(const ProjectArgs &a, const float *pt, const float *M, ProjPoint &r) {
     const float x = pt[0], y = pt[1], z = pt[2];
-    const float c0 = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-    const float c1 = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-    const float c2 = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+    const float c0 = affine_row(M, 0, x, y, z), c1 = affine_row(M, 1, x, y, z), c2 = affine_row(M, 2, x, y, z);
     if (!(isfinite(c2) && c2 > 0.0f && c2 >= a.zmin && c2 <= a.zmax)) return false;
+    // affine_row(p, 0..3, c0, c1, c2), written out: as calls they change the splat kernel's device code
     const float *p = a.p;
     const float p0 = ((p[0] * c0 + p[1] * c1) + p[2] * c2) + p[3];
     const float p1 = ((p[4] * c0 + p[5] * c1) + p[6] * c2) + p[7];
     const float p2 = ((p[8] * c0 + p[9] * c1) + p[10] * c2) + p[11];
     const float p3 = ((p[12] * c0 + p[13] * c1) + p[14] * c2) + p[15];
     if (!(p3 > 0.0f)) return false;
-    const float fu = floorf(p0 / p3 + 0.5f), fv = floorf(p1 / p3 + 0.5f);
+    const float fu = nearest_pixel(p0, p3), fv = nearest_pixel(p1, p3);
     const float R = (float)a.radius;
     if (!(fu >= -R && fu <= (float)(a.W - 1) + R && fv >= -R && fv <= (float)(a.H - 1) + R)) return false;   // NaN fails
     const float d = p2 / p3;
     if (!(isfinite(d) && d != a.invalid)) return false;
     r.c2 = c2, r.d = d, r.u = (int)fu, r.v = (int)fv;
     return true;
-}
-
-// The last m in 0..n with tab[m] <= p, searched in lo..hi (tab is non-decreasing and tab[lo] <= p).
-__device__ __forceinline__ int proj_upper_index(const int *tab, int lo, int hi, int p) {
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // One key per thread; workgroup 0 first clamps the offsets: off[m] = min(cap, max(0, max(offsets[0..m]))), which is the
@@ -102,13 +92,13 @@ __global__ __launch_bounds__(256) void k_project_splat(const ProjectArgs a) {
     if (begin >= end || p0 + 255 < begin || p0 >= end) return;
     __shared__ int span[2];
     if (threadIdx.x == 0) {
-        span[0] = proj_upper_index(a.off, 0, a.n, max(p0, begin));
-        span[1] = proj_upper_index(a.off, span[0], a.n, min(p0 + 255, end - 1));
+        span[0] = upper_index(a.off, 0, a.n, max(p0, begin));
+        span[1] = upper_index(a.off, span[0], a.n, min(p0 + 255, end - 1));
     }
     __syncthreads();
     const int p = p0 + threadIdx.x;
     if (p < begin || p >= end) return;
-    const int f = proj_upper_index(a.off, span[0], span[1], p);   // no iteration where the workgroup has one cloud
+    const int f = upper_index(a.off, span[0], span[1], p);   // no iteration where the workgroup has one cloud
     const int j = p - a.off[f];
     // The pose: three 16-byte loads whose address is the same in every lane of a wave that lies inside one cloud (one
     // request, broadcast).  P is in the kernel arguments.

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void k_raycast_bricks(const RaycastArgs a) {
 #pragma unroll
                 for (int dy = 0; dy < 8; ++dy) {                      // rows past the volume repeat its last row
                     const int y = min(y0 + dy, a.ny - 1), z = min(z0 + dz, a.nz - 1);
-                    const bool ok = a.weight[((size_t)z * a.ny + y) * a.nx + x] >= a.min_weight;
+                    const bool ok = a.weight[voxel_index(z, y, x, a.ny, a.nx)] >= a.min_weight;
                     any |= ok, all &= ok;
                 }
             if (all) {                                                // the tsdf is read only under measured columns
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_raycast_bricks(const RaycastArgs a) {
 #pragma unroll
                     for (int dy = 0; dy < 8; ++dy) {
                         const int y = min(y0 + dy, a.ny - 1), z = min(z0 + dz, a.nz - 1);
-                        all &= a.tsdf[((size_t)z * a.ny + y) * a.nx + x] == 1.0f;
+                        all &= a.tsdf[voxel_index(z, y, x, a.ny, a.nx)] == 1.0f;
                     }
             }
         }

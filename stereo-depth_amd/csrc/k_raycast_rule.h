@@ -2,11 +2,9 @@
 // the exact jumps k_raycast.h explains, then the outputs.  Plain C++ over the kernel's arguments, compiled for the
 // device by k_raycast.h and for the host by tests/raycast_march_harness.cpp, which marches on the CPU.
 #pragma once
-#include "smx_common.h"
+#include "k_camera.h"
 
 namespace smx {
-
-#define RC_FN __host__ __device__ __forceinline__
 
 struct RaycastArgs {
     int nx, ny, nz;
@@ -31,7 +29,7 @@ struct RcRay {
 };
 
 // g_a and f_a of the point at p; true iff it is in bounds
-RC_FN bool rc_cell(const RaycastArgs &a, const float p[3], float g[3], float f[3]) {
+SMX_FN bool rc_cell(const RaycastArgs &a, const float p[3], float g[3], float f[3]) {
     g[0] = (p[0] - a.ox) / a.s - 0.5f;
     g[1] = (p[1] - a.oy) / a.s - 0.5f;
     g[2] = (p[2] - a.oz) / a.s - 0.5f;
@@ -41,28 +39,28 @@ RC_FN bool rc_cell(const RaycastArgs &a, const float p[3], float g[3], float f[3
            f[2] <= (float)(a.nz - 2);                                // NaN fails
 }
 
-RC_FN void rc_point(const RcRay &r, float lam, float p[3]) {
+SMX_FN void rc_point(const RcRay &r, float lam, float p[3]) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) p[c] = r.e[c] + r.dw[c] * lam;
 }
 
-RC_FN float rc_lam(const RaycastArgs &a, int m) { return a.zmin + (float)m * a.step; }
+SMX_FN float rc_lam(const RaycastArgs &a, int m) { return a.zmin + (float)m * a.step; }
 
-RC_FN float rc_lerp(float x, float y, float t) { return x + (y - x) * t; }
+SMX_FN float rc_lerp(float x, float y, float t) { return x + (y - x) * t; }
 
-RC_FN void rc_corners(const float *__restrict__ v, size_t base, size_t sy, size_t sz, float c[8]) {
+SMX_FN void rc_corners(const float *__restrict__ v, size_t base, size_t sy, size_t sz, float c[8]) {
     c[0] = v[base], c[1] = v[base + 1], c[2] = v[base + sy], c[3] = v[base + sy + 1];
     c[4] = v[base + sz], c[5] = v[base + sz + 1], c[6] = v[base + sz + sy], c[7] = v[base + sz + sy + 1];
 }
 
-RC_FN float rc_trilinear(const float c[8], float tx, float ty, float tz) {
+SMX_FN float rc_trilinear(const float c[8], float tx, float ty, float tz) {
     const float c00 = rc_lerp(c[0], c[1], tx), c10 = rc_lerp(c[2], c[3], tx);
     const float c01 = rc_lerp(c[4], c[5], tx), c11 = rc_lerp(c[6], c[7], tx);
     return rc_lerp(rc_lerp(c00, c10, ty), rc_lerp(c01, c11, ty), tz);
 }
 
 // Tri(p) for a point in bounds (g, f: rc_cell's)
-RC_FN float rc_tri(const RaycastArgs &a, const float g[3], const float f[3]) {
+SMX_FN float rc_tri(const RaycastArgs &a, const float g[3], const float f[3]) {
     const size_t sy = (size_t)a.nx, sz = (size_t)a.nx * a.ny;
     const size_t base = (size_t)(int)f[2] * sz + (size_t)(int)f[1] * sy + (size_t)(int)f[0];
     float c[8];
@@ -72,8 +70,8 @@ RC_FN float rc_tri(const RaycastArgs &a, const float g[3], const float f[3]) {
 
 // the estimate of a jump: how many further samples stay where sample m is -- in its brick (inb), or else beyond the
 // faces of the box it lies beyond.  r_a: voxels per sample along a; left: the samples after m.
-RC_FN int rc_jump_estimate(const RaycastArgs &a, const float g[3], const float f[3], const float r[3],
-                                                bool inb, int left) {
+SMX_FN int rc_jump_estimate(const RaycastArgs &a, const float g[3], const float f[3], const float r[3], bool inb,
+                            int left) {
     const float lim[3] = {(float)(a.nx - 2), (float)(a.ny - 2), (float)(a.nz - 2)};
     float k = inb ? (float)left : 0.0f;
 #pragma unroll
@@ -93,13 +91,11 @@ RC_FN int rc_jump_estimate(const RaycastArgs &a, const float g[3], const float f
 }
 
 // one pixel of one view: the march, then the outputs
-RC_FN void rc_pixel(const RaycastArgs &a, int px, int py, int view) {
+SMX_FN void rc_pixel(const RaycastArgs &a, int px, int py, int view) {
     const float *q = a.q;
     const float *__restrict__ M = a.pose + (size_t)view * 12;
     const float u = (float)px, v = (float)py;
-    const float xp = (q[0] * u + q[1] * v) + q[3];
-    const float yp = (q[4] * u + q[5] * v) + q[7];
-    const float zp = (q[8] * u + q[9] * v) + q[11];
+    const float xp = pixel_ray_row(q, 0, u, v), yp = pixel_ray_row(q, 1, u, v), zp = pixel_ray_row(q, 2, u, v);
     const size_t sy = (size_t)a.nx, sz = (size_t)a.nx * a.ny;
     const float lim[3] = {(float)(a.nx - 2), (float)(a.ny - 2), (float)(a.nz - 2)};
     RcRay ray = {};
@@ -110,7 +106,7 @@ RC_FN void rc_pixel(const RaycastArgs &a, int px, int py, int view) {
         float r[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            ray.dw[c] = (M[4 * c] * rx + M[4 * c + 1] * ry) + M[4 * c + 2];
+            ray.dw[c] = rotation_row(M, c, rx, ry);
             ray.e[c] = M[4 * c + 3];
             r[c] = ray.dw[c] / a.s * a.step;                          // estimate only
         }

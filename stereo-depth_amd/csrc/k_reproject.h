@@ -14,7 +14,8 @@
 #pragma once
 #include <climits>
 
-#include "smx_common.h"
+#include "k_camera.h"
+#include "k_compact.h"
 #include "smx_workspace.h"        // SCAN_ITEMS, SCAN_TILE, VOX_TILE, VM_COUNT: shared with the workspace layout
 
 namespace smx {
@@ -42,10 +43,8 @@ __device__ __forceinline__ bool reproj_pixel(const ReprojArgs &a, size_t i, int 
     if (!(isfinite(d) && d != a.invalid)) return false;
     const float u = (float)x, v = (float)y;
     const float *q = a.q;
-    const float xw = ((q[0] * u + q[1] * v) + q[2] * d) + q[3];
-    const float yw = ((q[4] * u + q[5] * v) + q[6] * d) + q[7];
-    const float zw = ((q[8] * u + q[9] * v) + q[10] * d) + q[11];
-    const float ww = ((q[12] * u + q[13] * v) + q[14] * d) + q[15];
+    const float xw = affine_row(q, 0, u, v, d), yw = affine_row(q, 1, u, v, d), zw = affine_row(q, 2, u, v, d);
+    const float ww = affine_row(q, 3, u, v, d);
     if (!(ww > 0.0f)) return false;
     X = xw / ww, Y = yw / ww, Z = zw / ww;
     if (!(isfinite(X) && isfinite(Y) && isfinite(Z))) return false;
@@ -54,13 +53,9 @@ __device__ __forceinline__ bool reproj_pixel(const ReprojArgs &a, size_t i, int 
     return true;
 }
 
-__device__ __forceinline__ uint8_t colour_f32(float v) {
-    return (uint8_t)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);   // fmaxf(NaN, 0) = 0
-}
-
 __device__ __forceinline__ uint8_t colour_at(const ReprojArgs &a, int m, int ch, int y, int x) {
-    const size_t j = (((size_t)m * (a.channels == 3 ? 3 : 1) + (a.channels == 3 ? ch : 0)) * a.H + y) * a.W + x;
-    return a.img_f32 ? colour_f32(((const float *)a.image)[j]) : ((const uint8_t *)a.image)[j];
+    const size_t j = (channel_plane(m, ch, a.channels) * a.H + y) * a.W + x;
+    return a.img_f32 ? colour_byte<uint8_t>(((const float *)a.image)[j]) : ((const uint8_t *)a.image)[j];
 }
 
 // one workgroup (256 threads) per row r = m*H + y: the number of points of the row, and the organised map
@@ -79,11 +74,8 @@ __global__ __launch_bounds__(256) void k_reproj_count(const ReprojArgs a) {
             o[0] = ok ? X : qnan; o[1] = ok ? Y : qnan; o[2] = ok ? Z : qnan;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) a.row_count[r] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int total = block_count(cnt, wsum);
+    if (threadIdx.x == 0) a.row_count[r] = total;
 }
 
 // single workgroup: exclusive scan of the n*H row counts; offsets[m] = the offset of row m*H, offsets[n] = the total
@@ -119,7 +111,7 @@ __global__ __launch_bounds__(256) void k_reproj_scatter(const ReprojArgs a) {
     if (threadIdx.x == 0) base = a.row_offset[r];
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int x0 = 0; x0 < a.W; x0 += 256) {
+    for (int x0 = 0; x0 < a.W; x0 += 256) {                       // the slot as in k_points.h's scatter (k_compact.h)
         const int x = x0 + threadIdx.x;
         float X = 0.0f, Y = 0.0f, Z = 0.0f;
         const bool ok = x < a.W && reproj_pixel(a, (size_t)r * a.W + x, y, x, X, Y, Z);
@@ -245,16 +237,6 @@ struct VoxArgs {
     int *off, *tile_base, *meta;    // [n+1], [n+1], [VM_COUNT]
 };
 
-// largest m in [0, n] with tab[m] <= p (tab non-decreasing, tab[0] <= p)
-__device__ __forceinline__ int upper_index(const int *tab, int n, int p) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ bool vox_index(const float *pt, float vs, int &ix, int &iy, int &iz) {
     const float fx = floorf(pt[0] / vs), fy = floorf(pt[1] / vs), fz = floorf(pt[2] / vs);
     if (!(fx >= -VOX_LIMIT && fx < VOX_LIMIT && fy >= -VOX_LIMIT && fy < VOX_LIMIT && fz >= -VOX_LIMIT && fz < VOX_LIMIT))
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(256) void k_vox_bbox(const VoxArgs a) {
                 ix = min(ix, x), iy = min(iy, y), iz = min(iz, z);
                 jx = max(jx, x), jy = max(jy, y), jz = max(jz, z);
             } else {
-                m = upper_index(a.off, a.n, p), drop = 1;
+                m = upper_index(a.off, 0, a.n, p), drop = 1;
             }
         }
         wave_add_to_map(a.dropped, m, drop);
@@ -375,7 +357,7 @@ __global__ __launch_bounds__(256) void k_vox_keys(const VoxArgs a) {
 struct VoxTile { int m, t, tiles, lo, hi; };
 __device__ __forceinline__ VoxTile vox_tile(const VoxArgs &a, int tile) {
     VoxTile r;
-    r.m = upper_index(a.tile_base, a.n, tile);                      // the last map starting at or before it
+    r.m = upper_index(a.tile_base, 0, a.n, tile);                   // the last map starting at or before it
     r.t = tile - a.tile_base[r.m];
     r.tiles = a.tile_base[r.m + 1] - a.tile_base[r.m];
     r.lo = a.off[r.m] + r.t * VOX_TILE;
@@ -448,7 +430,7 @@ __global__ __launch_bounds__(256) void k_vox_heads(const VoxArgs a) {
     if (p >= a.off[0] && p < a.off[a.n]) {
         const int npass = (a.meta[VM_KEY_BITS] + 7) / 8;
         const unsigned long long *key = a.keys[npass & 1];
-        const int mp = upper_index(a.off, a.n, p);
+        const int mp = upper_index(a.off, 0, a.n, p);
         const unsigned long long k = key[p];
         const bool head = p == a.off[mp] || key[p - 1] != k;
         if (head && !((k >> a.meta[VM_FLAG_SHIFT]) & 1ull)) {

@@ -12,13 +12,13 @@ constexpr int TRK_STACK = 6;                                          // levels 
 struct TrackRule {
     using Args = TrackArgs;
     static constexpr int SLOTS = TRK_SLOTS, BUTTERFLY = TRK_TERMS + 1, CHUNKS = TRK_CHUNKS, STACK = TRK_STACK;
-    static TRK_FN TrackArgs &common(TrackArgs &a) { return a; }
-    static TRK_FN const TrackArgs &common(const TrackArgs &a) { return a; }
-    static TRK_FN void pixel(const TrackArgs &a, const float *T, int f, int px, int py, double *acc) {
+    static SMX_FN TrackArgs &common(TrackArgs &a) { return a; }
+    static SMX_FN const TrackArgs &common(const TrackArgs &a) { return a; }
+    static SMX_FN void pixel(const TrackArgs &a, const float *T, int f, int px, int py, double *acc) {
         trk_pixel(a, T, f, px, py, acc);
     }
-    static TRK_FN void begin(const TrackArgs &a, int f) { trk_begin(a, f); }
-    static TRK_FN void finish(const TrackArgs &a, int f, const double *S) { trk_finish(a, f, S); }
+    static SMX_FN void begin(const TrackArgs &a, int f) { trk_begin(a, f); }
+    static SMX_FN void finish(const TrackArgs &a, int f, const double *S) { trk_finish(a, f, S); }
 };
 
 __global__ __launch_bounds__(256) void k_track_begin(const TrackArgs a) { track_begin_body<TrackRule>(a); }

@@ -17,13 +17,13 @@ constexpr int TRKP_STACK = 7;                                         // levels 
 struct TrackPhotoRule {
     using Args = TrackPhotoArgs;
     static constexpr int SLOTS = TRKP_SLOTS, BUTTERFLY = TRKP_SLOTS, CHUNKS = TRKP_CHUNKS, STACK = TRKP_STACK;
-    static TRK_FN TrackArgs &common(TrackPhotoArgs &a) { return a.g; }
-    static TRK_FN const TrackArgs &common(const TrackPhotoArgs &a) { return a.g; }
-    static TRK_FN void pixel(const TrackPhotoArgs &a, const float *T, int f, int px, int py, double *acc) {
+    static SMX_FN TrackArgs &common(TrackPhotoArgs &a) { return a.g; }
+    static SMX_FN const TrackArgs &common(const TrackPhotoArgs &a) { return a.g; }
+    static SMX_FN void pixel(const TrackPhotoArgs &a, const float *T, int f, int px, int py, double *acc) {
         trkp_pixel(a, T, f, px, py, acc);
     }
-    static TRK_FN void begin(const TrackPhotoArgs &a, int f) { trkp_begin(a, f); }
-    static TRK_FN void finish(const TrackPhotoArgs &a, int f, const double *S) { trkp_finish(a, f, S); }
+    static SMX_FN void begin(const TrackPhotoArgs &a, int f) { trkp_begin(a, f); }
+    static SMX_FN void finish(const TrackPhotoArgs &a, int f, const double *S) { trkp_finish(a, f, S); }
 };
 
 __global__ __launch_bounds__(256) void k_track_photo_begin(const TrackPhotoArgs a) { track_begin_body<TrackPhotoRule>(a); }

@@ -21,9 +21,10 @@ struct TrackPhotoArgs {
 };
 
 // Adds the terms of pixel (px, py) of frame f at the pose T to acc: the geometric ones, and after them, if the pixel was
-// a geometric inlier, the photometric ones.  The values the two parts share (p, u, w) are evaluated again from the same
-// operands by the same operations, hence with the same bits.
-TRK_FN void trkp_pixel(const TrackPhotoArgs &pa, const float *T, int f, int px, int py, double acc[TRKP_SLOTS]) {
+// a geometric inlier, the photometric ones.  The values the two parts share (p, u, w) are evaluated again, by calls of
+// the functions of k_camera.h that trk_pixel calls, on the same operands (keeping them across trk_pixel instead would be
+// this kernel's register decision).
+SMX_FN void trkp_pixel(const TrackPhotoArgs &pa, const float *T, int f, int px, int py, double acc[TRKP_SLOTS]) {
     const TrackArgs &a = pa.g;
     const double inliers = acc[29];
     trk_pixel(a, T, f, px, py, acc);
@@ -32,21 +33,16 @@ TRK_FN void trkp_pixel(const TrackPhotoArgs &pa, const float *T, int f, int px, 
     const float d = a.disp[i];
     const float u = (float)px, v = (float)py;
     const float *q = a.q;
-    const float ww = ((q[12] * u + q[13] * v) + q[14] * d) + q[15];
-    const float Z = (((q[8] * u + q[9] * v) + q[10] * d) + q[11]) / ww;
+    const float ww = affine_row(q, 3, u, v, d), Z = affine_row(q, 2, u, v, d) / ww;
     const float w = a.conf ? a.conf[i] : 1.0f;
-    const float X = (((q[0] * u + q[1] * v) + q[2] * d) + q[3]) / ww;
-    const float Y = (((q[4] * u + q[5] * v) + q[6] * d) + q[7]) / ww;
-    float p[3], c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) p[r] = ((T[4 * r] * X + T[4 * r + 1] * Y) + T[4 * r + 2] * Z) + T[4 * r + 3];
+    const float X = affine_row(q, 0, u, v, d) / ww, Y = affine_row(q, 1, u, v, d) / ww;
+    const float p[3] = {affine_row(T, 0, X, Y, Z), affine_row(T, 1, X, Y, Z), affine_row(T, 2, X, Y, Z)};
     const float *Mw = a.w2c + (size_t)f * 12;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) c[r] = ((Mw[4 * r] * p[0] + Mw[4 * r + 1] * p[1]) + Mw[4 * r + 2] * p[2]) + Mw[4 * r + 3];
+    const float c[3] = {affine_row(Mw, 0, p[0], p[1], p[2]), affine_row(Mw, 1, p[0], p[1], p[2]),
+                        affine_row(Mw, 2, p[0], p[1], p[2])};
     const float *P = a.pm;
-    const float u3 = ((P[12] * c[0] + P[13] * c[1]) + P[14] * c[2]) + P[15];
-    const float u0 = ((P[0] * c[0] + P[1] * c[1]) + P[2] * c[2]) + P[3];
-    const float u1 = ((P[4] * c[0] + P[5] * c[1]) + P[6] * c[2]) + P[7];
+    const float u3 = affine_row(P, 3, c[0], c[1], c[2]);
+    const float u0 = affine_row(P, 0, c[0], c[1], c[2]), u1 = affine_row(P, 1, c[0], c[1], c[2]);
     const float x = u0 / u3, y = u1 / u3;
     const float x0 = floorf(x), y0 = floorf(y);
     if (!(x0 >= 0.0f && x0 <= (float)(a.Wm - 2) && y0 >= 0.0f && y0 <= (float)(a.Hm - 2))) return;    // NaN fails
@@ -91,14 +87,14 @@ TRK_FN void trkp_pixel(const TrackPhotoArgs &pa, const float *T, int f, int px, 
 }
 
 // The outputs of a triple for which no iteration has run, and its state
-TRK_FN void trkp_begin(const TrackPhotoArgs &pa, int f) {
+SMX_FN void trkp_begin(const TrackPhotoArgs &pa, int f) {
     trk_begin(pa.g, f, TRKP_TERMS);
     if (pa.pinfo) pa.pinfo[2 * f] = pa.pinfo[2 * f + 1] = 0;
     if (pa.prms) pa.prms[f] = __builtin_nanf("");
 }
 
 // The end of an iteration of triple f, from its TRKP_SLOTS sums
-TRK_FN void trkp_finish(const TrackPhotoArgs &pa, int f, const double *S) {
+SMX_FN void trkp_finish(const TrackPhotoArgs &pa, int f, const double *S) {
     const int count = (int)S[TRKP_COUNT];
     if (pa.pinfo) {
         pa.pinfo[2 * f] = count;

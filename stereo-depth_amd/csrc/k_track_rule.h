@@ -4,12 +4,10 @@
 #pragma once
 #include <cmath>
 
-#include "smx_common.h"
+#include "k_camera.h"
 #include "smx_workspace.h"
 
 namespace smx {
-
-#define TRK_FN __host__ __device__ __forceinline__
 
 // What a triple carries from launch to launch (workspace, one per triple; 32 words)
 struct TrackState {
@@ -41,38 +39,34 @@ struct TrackArgs {
 // Adds the thirty terms of pixel (px, py) of frame f at the pose T to acc, and 1 to acc[TRK_TERMS] if the pixel is
 // accepted.  A skipped pixel adds nothing: acc starts at +0.0 and a sum of these terms is never -0.0, so leaving the
 // addition of +0.0 out changes no bit.
-TRK_FN void trk_pixel(const TrackArgs &a, const float *T, int f, int px, int py, double acc[TRK_SLOTS]) {
+SMX_FN void trk_pixel(const TrackArgs &a, const float *T, int f, int px, int py, double acc[TRK_SLOTS]) {
     const size_t i = ((size_t)f * a.H + py) * a.W + px;
     const float d = a.disp[i];
     if (!(std::isfinite(d) && d != a.invalid)) return;
     const float u = (float)px, v = (float)py;
     const float *q = a.q;
-    const float ww = ((q[12] * u + q[13] * v) + q[14] * d) + q[15];
+    const float ww = affine_row(q, 3, u, v, d);
     if (!(ww > 0.0f)) return;
-    const float Z = (((q[8] * u + q[9] * v) + q[10] * d) + q[11]) / ww;
+    const float Z = affine_row(q, 2, u, v, d) / ww;
     if (!(std::isfinite(Z) && Z >= a.zmin && Z <= a.zmax)) return;
     float w = 1.0f;
     if (a.conf) {
         w = a.conf[i];
         if (!(w >= a.min_conf && w > 0.0f)) return;                   // a NaN confidence excludes the pixel
     }
-    const float X = (((q[0] * u + q[1] * v) + q[2] * d) + q[3]) / ww;
-    const float Y = (((q[4] * u + q[5] * v) + q[6] * d) + q[7]) / ww;
+    const float X = affine_row(q, 0, u, v, d) / ww, Y = affine_row(q, 1, u, v, d) / ww;
     if (!(std::isfinite(X) && std::isfinite(Y))) return;
     acc[TRK_TERMS] += 1.0;
-    float p[3], c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) p[r] = ((T[4 * r] * X + T[4 * r + 1] * Y) + T[4 * r + 2] * Z) + T[4 * r + 3];
+    const float p[3] = {affine_row(T, 0, X, Y, Z), affine_row(T, 1, X, Y, Z), affine_row(T, 2, X, Y, Z)};
     const float *Mw = a.w2c + (size_t)f * 12, *Mc = a.c2w + (size_t)f * 12;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) c[r] = ((Mw[4 * r] * p[0] + Mw[4 * r + 1] * p[1]) + Mw[4 * r + 2] * p[2]) + Mw[4 * r + 3];
+    const float c[3] = {affine_row(Mw, 0, p[0], p[1], p[2]), affine_row(Mw, 1, p[0], p[1], p[2]),
+                        affine_row(Mw, 2, p[0], p[1], p[2])};
     if (!(c[2] > 0.0f)) return;
     const float *P = a.pm;
-    const float p3 = ((P[12] * c[0] + P[13] * c[1]) + P[14] * c[2]) + P[15];
+    const float p3 = affine_row(P, 3, c[0], c[1], c[2]);
     if (!(p3 > 0.0f)) return;
-    const float p0 = ((P[0] * c[0] + P[1] * c[1]) + P[2] * c[2]) + P[3];
-    const float p1 = ((P[4] * c[0] + P[5] * c[1]) + P[6] * c[2]) + P[7];
-    const float fu = floorf(p0 / p3 + 0.5f), fv = floorf(p1 / p3 + 0.5f);
+    const float fu = nearest_pixel(affine_row(P, 0, c[0], c[1], c[2]), p3);
+    const float fv = nearest_pixel(affine_row(P, 1, c[0], c[1], c[2]), p3);
     if (!(fu >= 0.0f && fu <= (float)(a.Wm - 1) && fv >= 0.0f && fv <= (float)(a.Hm - 1))) return;   // NaN fails
     const size_t plane = (size_t)a.Hm * a.Wm;
     const size_t m = (size_t)(int)fv * a.Wm + (size_t)(int)fu;
@@ -82,14 +76,12 @@ TRK_FN void trk_pixel(const TrackArgs &a, const float *T, int f, int px, int py,
     const float n0 = nr[0], n1 = nr[plane], n2 = nr[2 * plane];
     if (n0 == 0.0f && n1 == 0.0f && n2 == 0.0f) return;
     const float *qm = a.qm;
-    const float xp = (qm[0] * fu + qm[1] * fv) + qm[3];
-    const float yp = (qm[4] * fu + qm[5] * fv) + qm[7];
-    const float zp = (qm[8] * fu + qm[9] * fv) + qm[11];
+    const float xp = pixel_ray_row(qm, 0, fu, fv), yp = pixel_ray_row(qm, 1, fu, fv), zp = pixel_ray_row(qm, 2, fu, fv);
     const float rx = xp / zp, ry = yp / zp;
     float dl[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        const float dw = (Mc[4 * r] * rx + Mc[4 * r + 1] * ry) + Mc[4 * r + 2];
+        const float dw = rotation_row(Mc, r, rx, ry);
         dl[r] = (Mc[4 * r + 3] + dw * lam) - p[r];
     }
     if (!((dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2] <= a.maxd2)) return;                        // NaN fails
@@ -110,7 +102,7 @@ TRK_FN void trk_pixel(const TrackArgs &a, const float *T, int f, int px, int py,
 
 // x of A x = g by LDL^T without pivoting, in the header's order; false when a pivot is not finite or <= min_pivot or a
 // component of x is not finite
-TRK_FN bool trk_solve(const double *S, double min_pivot, double x[6]) {
+SMX_FN bool trk_solve(const double *S, double min_pivot, double x[6]) {
     double A[6][6], L[6][6], d[6], v[6], y[6];
     int k = 0;
 #pragma unroll
@@ -154,7 +146,7 @@ TRK_FN bool trk_solve(const double *S, double min_pivot, double x[6]) {
 }
 
 // T <- (C T, C t + tau) with C the Cayley map of omega; returns true iff the step is within the tolerances
-TRK_FN bool trk_update(float *T, const double x[6], float rot_eps2, float trans_eps2) {
+SMX_FN bool trk_update(float *T, const double x[6], float rot_eps2, float trans_eps2) {
     const float om[3] = {(float)x[0], (float)x[1], (float)x[2]}, tau[3] = {(float)x[3], (float)x[4], (float)x[5]};
     const float a0 = om[0] * 0.5f, a1 = om[1] * 0.5f, a2 = om[2] * 0.5f;
     const float aa = (a0 * a0 + a1 * a1) + a2 * a2;
@@ -178,7 +170,7 @@ TRK_FN bool trk_update(float *T, const double x[6], float rot_eps2, float trans_
 
 // The outputs of a triple for which no iteration has run (the first launch of a call writes them, so a schedule of zero
 // iterations is the identity), and its state.  terms: the sums per triple of the rule that is tracked, this one's or more.
-TRK_FN void trk_begin(const TrackArgs &a, int f, int terms = TRK_TERMS) {
+SMX_FN void trk_begin(const TrackArgs &a, int f, int terms = TRK_TERMS) {
     TrackState &st = a.state[f];
     float in[12];
     for (int i = 0; i < 12; ++i) in[i] = a.pose_in[(size_t)f * 12 + i];   // read whole before pose_out, which may be it
@@ -192,7 +184,7 @@ TRK_FN void trk_begin(const TrackArgs &a, int f, int terms = TRK_TERMS) {
 
 // The end of an iteration of triple f, from its sums: the outputs (the first TRK_TERMS of the triple's `terms` sums), the
 // new pose, the stop flags
-TRK_FN void trk_finish(const TrackArgs &a, int f, const double *S, int terms = TRK_TERMS) {
+SMX_FN void trk_finish(const TrackArgs &a, int f, const double *S, int terms = TRK_TERMS) {
     TrackState &st = a.state[f];
     const int inliers = (int)S[29];
     st.iterations += 1;

@@ -13,7 +13,8 @@
 #pragma once
 #include <climits>
 
-#include "smx_common.h"
+#include "k_camera.h"
+#include "k_compact.h"
 
 namespace smx {
 
@@ -33,14 +34,9 @@ struct TsdfArgs {
     unsigned *pcol;                  // workspace [n*H*W]: the pixel's colour word (with a colour volume)
 };
 
-__device__ __forceinline__ unsigned tsdf_u8(float v) {
-    return (unsigned)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);   // fmaxf(NaN, 0) = 0
-}
-
 __device__ __forceinline__ unsigned tsdf_channel(const TsdfArgs &a, int m, int ch, size_t px) {
-    const size_t plane = (size_t)a.H * a.W;
-    const size_t j = ((size_t)m * (a.channels == 3 ? 3 : 1) + (a.channels == 3 ? ch : 0)) * plane + px;
-    return a.img_f32 ? tsdf_u8(((const float *)a.image)[j]) : (unsigned)((const uint8_t *)a.image)[j];
+    const size_t j = channel_plane(m, ch, a.channels) * ((size_t)a.H * a.W) + px;
+    return a.img_f32 ? colour_byte(((const float *)a.image)[j]) : (unsigned)((const uint8_t *)a.image)[j];
 }
 
 // one thread per pixel of the n maps: the measurement of the acceptance rule of smx_reproject_points (without X, Y),
@@ -58,8 +54,7 @@ __global__ __launch_bounds__(256) void k_tsdf_pixels(const TsdfArgs a) {
     float zm = __builtin_nanf(""), w = 1.0f;
     bool ok = isfinite(d) && d != a.invalid;
     if (ok) {
-        const float zw = ((q[8] * u + q[9] * v) + q[10] * d) + q[11];
-        const float ww = ((q[12] * u + q[13] * v) + q[14] * d) + q[15];
+        const float zw = affine_row(q, 2, u, v, d), ww = affine_row(q, 3, u, v, d);
         ok = ww > 0.0f;
         if (ok) {
             const float z = zw / ww;
@@ -83,13 +78,13 @@ __global__ __launch_bounds__(256) void k_tsdf_pixels(const TsdfArgs a) {
     }
 }
 
-// C = ((C0*W0) + (I*w)) / (W0 + w), stored as (uint8)floorf(C + 0.5f), per channel of the colour words
+// C = ((C0*W0) + (I*w)) / (W0 + w), stored as colour_byte(C), per channel of the colour words
 __device__ __forceinline__ unsigned tsdf_blend_colour(unsigned c0, unsigned in, float W0, float w, float den) {
     unsigned out = 0;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         const float C0 = (float)((c0 >> (8 * ch)) & 255u), I = (float)((in >> (8 * ch)) & 255u);
-        out |= tsdf_u8(((C0 * W0) + (I * w)) / den) << (8 * ch);
+        out |= colour_byte(((C0 * W0) + (I * w)) / den) << (8 * ch);
     }
     return out;
 }
@@ -100,10 +95,8 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(const TsdfArgs a) {
     const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int k = blockIdx.z;
     if (i >= a.nx || j >= a.ny) return;
-    const float gx = a.ox + ((float)i + 0.5f) * a.s;
-    const float gy = a.oy + ((float)j + 0.5f) * a.s;
-    const float gz = a.oz + ((float)k + 0.5f) * a.s;
-    const size_t vox = ((size_t)k * a.ny + j) * a.nx + i;
+    const float gx = voxel_centre(a.ox, i, a.s), gy = voxel_centre(a.oy, j, a.s), gz = voxel_centre(a.oz, k, a.s);
+    const size_t vox = voxel_index(k, j, i, a.ny, a.nx);
     const float wmax = (float)(a.W - 1), hmax = (float)(a.H - 1);
     const float *P = a.p;
     float T = 0.0f, Wt = 0.0f;
@@ -111,15 +104,13 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(const TsdfArgs a) {
     bool have = false;
     for (int f = 0; f < a.n; ++f) {
         const float *M = a.pose + (size_t)f * 12;
-        const float c2 = ((M[8] * gx + M[9] * gy) + M[10] * gz) + M[11];
+        const float c2 = affine_row(M, 2, gx, gy, gz);
         if (!(c2 > 0.0f)) continue;
-        const float c0 = ((M[0] * gx + M[1] * gy) + M[2] * gz) + M[3];
-        const float c1 = ((M[4] * gx + M[5] * gy) + M[6] * gz) + M[7];
-        const float p3 = ((P[12] * c0 + P[13] * c1) + P[14] * c2) + P[15];
+        const float c0 = affine_row(M, 0, gx, gy, gz), c1 = affine_row(M, 1, gx, gy, gz);
+        const float p3 = affine_row(P, 3, c0, c1, c2);
         if (!(p3 > 0.0f)) continue;
-        const float p0 = ((P[0] * c0 + P[1] * c1) + P[2] * c2) + P[3];
-        const float p1 = ((P[4] * c0 + P[5] * c1) + P[6] * c2) + P[7];
-        const float fu = floorf(p0 / p3 + 0.5f), fv = floorf(p1 / p3 + 0.5f);
+        const float fu = nearest_pixel(affine_row(P, 0, c0, c1, c2), p3);
+        const float fv = nearest_pixel(affine_row(P, 1, c0, c1, c2), p3);
         if (!(fu >= 0.0f && fu <= wmax && fv >= 0.0f && fv <= hmax)) continue;   // NaN fails
         const size_t px = ((size_t)f * a.H + (int)fv) * a.W + (int)fu;
         const float2 mw = a.meas[px];
@@ -185,11 +176,8 @@ __global__ __launch_bounds__(256) void k_tsdf_count(const TsdfExtractArgs a) {
     int cnt = 0;
     for (int i = threadIdx.x; i < a.nx; i += 256)
         cnt += __popc(tsdf_crossings(a, i, j, k, (size_t)r * a.nx + i));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) a.row_count[r] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int total = block_count(cnt, wsum);
+    if (threadIdx.x == 0) a.row_count[r] = total;
 }
 
 __device__ __forceinline__ size_t tsdf_clamped(int c, int d, int lim, size_t v, size_t step) {
@@ -201,7 +189,7 @@ __device__ void tsdf_emit(const TsdfExtractArgs &a, int i, int j, int k, size_t 
     const size_t step[3] = {1, (size_t)a.nx, (size_t)a.nx * a.ny};
     const float T0 = a.tsdf[v], T1 = a.tsdf[v + step[ax]];
     const float t = T0 / (T0 - T1);
-    float g[3] = {a.ox + ((float)i + 0.5f) * a.s, a.oy + ((float)j + 0.5f) * a.s, a.oz + ((float)k + 0.5f) * a.s};
+    float g[3] = {voxel_centre(a.ox, i, a.s), voxel_centre(a.oy, j, a.s), voxel_centre(a.oz, k, a.s)};
     g[ax] = g[ax] + t * a.s;
     float *pt = a.points + (size_t)o * 3;
     pt[0] = g[0]; pt[1] = g[1]; pt[2] = g[2];

@@ -20,7 +20,7 @@
 #pragma once
 #include <cstddef>
 
-#include "smx_common.h"
+#include "k_camera.h"
 
 namespace smx {
 
@@ -42,10 +42,6 @@ struct TsdfMergeArgs {
 typedef unsigned mrg_quad __attribute__((ext_vector_type(4)));
 typedef unsigned mrg_quad_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-__device__ __forceinline__ unsigned merge_u8(float v) {
-    return (unsigned)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);   // fmaxf(NaN, 0) = 0
-}
-
 // The rule for one pair in AVERAGE mode with W0 > 0 and W1 > 0: every step one float32 operation, integrate's form.
 __device__ __forceinline__ void merge_average(unsigned &t0, unsigned &w0, unsigned &c0, unsigned t1, unsigned w1,
                                               unsigned c1, float max_weight, bool colour) {
@@ -58,7 +54,7 @@ __device__ __forceinline__ void merge_average(unsigned &t0, unsigned &w0, unsign
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const float C0 = (float)((c0 >> (8 * ch)) & 255u), C1 = (float)((c1 >> (8 * ch)) & 255u);
-            out |= merge_u8(((C0 * W0) + (C1 * W1)) / den) << (8 * ch);
+            out |= colour_byte(((C0 * W0) + (C1 * W1)) / den) << (8 * ch);
         }
         c0 = out;
     }
@@ -165,7 +161,8 @@ __global__ __launch_bounds__(64 * MRG_WAVES) void k_tsdf_merge(const TsdfMergeAr
     if (r >= rows) return;
     const unsigned k = r / (unsigned)a.oy, j = r - k * (unsigned)a.oy;
     const int y = a.dy + (int)j, z = a.dz + (int)k;                  // the destination row
-    const size_t drow = ((size_t)z * a.ny + y) * (size_t)a.nx + a.dx;
+    const size_t drow = voxel_index(z, y, a.dx, a.ny, a.nx);
+    // voxel_index of the source row, written out: as a call its three differences move in the device code
     const size_t srow = ((size_t)(z - a.z0) * a.sy + (y - a.y0)) * (size_t)a.sx + (a.dx - a.x0);
     unsigned *d[3] = {a.dst[0] + drow, a.dst[1] + drow, a.dst[2] ? a.dst[2] + drow : nullptr};
     const unsigned *s[3] = {a.src[0] + srow, a.src[1] + srow, a.src[2] ? a.src[2] + srow : nullptr};

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #define SMX_FLT_MIN 1.17549435e-38f   // std::numeric_limits<float>::min(), wta_disparity_selection.cu:22
+#define SMX_FN __host__ __device__ __forceinline__   // k_camera.h, *_rule.h: the kernels' code, also built for the host by tests
 
 namespace smx {
 

@@ -46,6 +46,8 @@
  *   -- (the camera pose of a frame against such a view)   smx_track_camera, smx_track_camera_workspace_bytes
  *   -- (the same with a photometric term; its planes)     smx_track_camera_photometric,
  *                                                         smx_track_camera_photometric_workspace_bytes, smx_intensity_planes
+ *   -- (the term read coarse to fine from pyramids)      smx_intensity_pyramid, smx_intensity_pyramid_bytes,
+ *                                                         smx_track_camera_pyramid
  *   TORCH_CHECK -> c10::Error -> RuntimeError             int status + smx_last_error()
  *     depth/stereo_matching.cc:13-15
  *
@@ -62,7 +64,7 @@
  *     smx_fill_invalid, smx_weighted_median, smx_wls_filter, smx_sgm,
  *     smx_sgm_with_right_map, smx_reproject_points, smx_voxel_downsample, smx_project_points,
  *     smx_tsdf_integrate, smx_tsdf_extract_points, smx_tsdf_extract_triangles,
- *     smx_tsdf_raycast, smx_track_camera, smx_track_camera_photometric) returns
+ *     smx_tsdf_raycast, smx_track_camera, smx_track_camera_photometric, smx_track_camera_pyramid) returns
  *     SMX_ERR_INVALID_ARG for a non-NULL workspace that is not, before any device call.
  *   - Calls enqueue work and return without synchronising (like the reference).
  *   - One engine = one device + one set of intermediate buffers: calls on the same
@@ -1170,8 +1172,9 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
  * three photometric sums); and, each may be NULL: photometric_info [n][2] int32 = (the photometric inlier count of the
  * last iteration run, its geometric inliers without a photometric term), photometric_rms [n] f32 =
  * sqrtf((f32)(sum 30 / sum 31)) of the last iteration run (the division in float64), in intensity units, NaN if none ran
- * or no pixel was a photometric inlier.  The term's basin is a few model pixels: no pyramid, no robust weights, no
- * exposure compensation; a caller may blur both planes.
+ * or no pixel was a photometric inlier.  The term's basin is a few model pixels; smx_track_camera_pyramid below reads
+ * the term coarse to fine from pyramids and weighs it by Huber's rule.  Neither entry compensates exposure or gain, and
+ * the geometric term has no pyramid: it reads the full-resolution depth and normals at every stride.
  * workspace: smx_track_camera_photometric_workspace_bytes(n, H, W) bytes (0 for sizes the call rejects).
  * SMX_ERR_INVALID_ARG: a NULL frame_intensity or model_intensity; everything smx_track_camera rejects; photometric_weight
  * not finite and >= 0; max_intensity_difference not finite and > 0; the overlap rule with the planes among the inputs and
@@ -1195,6 +1198,62 @@ int smx_track_camera_photometric(int device_id, int n, int H, int W, const float
  * n*H*W > 2^30; channels other than 1 or 3; out overlapping image; stream == SMX_STREAM_ENGINE. */
 int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const uint8_t *image, float *out,
                          void *stream);
+
+/* smx_intensity_pyramid: the Gaussian pyramid of n float32 planes [n][H][W] (device), the operand of
+ * smx_track_camera_pyramid.  pyramid (device, smx_intensity_pyramid_bytes(n, H, W, levels) bytes; 0 for arguments the
+ * call rejects) holds level 0, then level 1, and so on; level l is [n][H_l][W_l] f32 with H_0 = H, H_(l+1) = (H_l + 1)/2
+ * in integers, and W alike: ceil(H / 2^l), the selected grid of stride 2^l.
+ *   level 0   plane; where mask_depth ([n][H][W] f32, may be NULL) is given and is not finite and > 0 at a pixel, a NaN.
+ *   level l+1 Burt and Adelson's reduce of level l = a [H_l][W_l]: pixel (x, y) sits on a's pixel (2x, 2y).  Every step is
+ *             ONE float32 operation; column indices are clamped to 0..W_l-1 and row indices to 0..H_l-1:
+ *               h(r, x) = (((a[r][2x-2] + a[r][2x+2]) + 4.0f*(a[r][2x-1] + a[r][2x+1])) + 6.0f*a[r][2x]) * 0.0625f
+ *               out(x, y) = (((h(2y-2, x) + h(2y+2, x)) + 4.0f*(h(2y-1, x) + h(2y+1, x))) + 6.0f*h(2y, x)) * 0.0625f
+ *             NaNs and infinities propagate by that arithmetic: a level pixel with a NaN in its 5 x 5 footprint is a NaN,
+ *             which is how model pixels without a surface stay out of the photometric term at every level.
+ * One launch per level on `stream` (a caller's stream); no workspace, no atomics.
+ * SMX_ERR_INVALID_ARG: a NULL plane or pyramid; n < 1, H or W outside 1..32768, n*H*W > 2^30; levels outside 1..8; pyramid
+ * overlapping plane or mask_depth; stream == SMX_STREAM_ENGINE. */
+size_t smx_intensity_pyramid_bytes(int n, int H, int W, int levels);
+int smx_intensity_pyramid(int device_id, int n, int H, int W, int levels, const float *plane, const float *mask_depth,
+                          float *pyramid, void *stream);
+
+/* smx_track_camera_pyramid: smx_track_camera_photometric with the photometric term read from a level of two intensity
+ * pyramids per schedule pair, coarse to fine, and weighed by Huber's rule, so that the term pulls from starts many
+ * pixels off.  Arguments, geometric terms (from the full-resolution depth and normals at every stride), sums, solve,
+ * update, LOST rule, stop rule, outputs, workspace (smx_track_camera_photometric_workspace_bytes) and launches are that
+ * entry's; what follows is what differs.
+ *   pyramids  frame_pyramid of (n, H, W) and model_pyramid of (n, Hm, Wm), both of `levels` levels in
+ *             smx_intensity_pyramid's layout, in place of the two planes.  The model's is built with mask_depth =
+ *             model_depth, so the term has no depth test of its own.  schedule_levels (host) [schedule_pairs] int32: the
+ *             level l of every pair, with 2^l dividing the pair's stride s, so that a selected pixel (px, py) is the
+ *             level's pixel (px >> l, py >> l) exactly.  huber_delta, in intensity units; +inf: no robust weights.
+ *   terms     Of a geometric inlier in a pair of level l, with inv = 2^-l, Wl, Hl the model pyramid's dimensions at level
+ *             l and x, y, u_3 of smx_track_camera_photometric:
+ *               xl = x*inv, yl = y*inv; x0 = floorf(xl), y0 = floorf(yl); skip unless 0 <= x0 <= Wl-2 and 0 <= y0 <= Hl-2
+ *               the four taps from the model's level l: skip unless all four are finite
+ *               ax = xl - x0, ay = yl - y0; bx, by, Im as there, and the level's gradient gxl, gyl as gx, gy there
+ *               gx = gxl*inv, gy = gyl*inv                                          (per level-0 pixel; exact)
+ *               e = frame_pyramid[l][f][py >> l][px >> l] - Im; skip unless e is finite and |e| <= max_intensity_difference
+ *               h, gw, a', b' and the finiteness test as there, with the level-0 x, y and u_3
+ *               wh = |e| <= huber_delta ? 1.0f : huber_delta/|e|; wp = w*wh
+ *             wp takes w's place in the photometric products: k = 0..20 (wp*a'_i)*a'_j, k = 21..26 (wp*a'_i)*b',
+ *             k = 30 (wp*e)*e, k = 31 wp, k = 32 1.  With every level 0 and huber_delta = +inf every added operation is a
+ *             multiplication by 1.0f: on pyramids whose level 0 is the frame's plane and the model's plane masked by
+ *             model_depth, the entry returns smx_track_camera_photometric's bits.
+ * SMX_ERR_INVALID_ARG: everything smx_track_camera_photometric rejects (a NULL frame_pyramid or model_pyramid; the overlap
+ * rule over the whole pyramids); levels outside 1..8; a NULL schedule_levels with schedule_pairs > 0; a level outside
+ * 0..levels-1; a stride not divisible by 2^level; huber_delta NaN or <= 0.  Not here: exposure or gain compensation,
+ * robust weights or a pyramid for the geometric term. */
+int smx_track_camera_pyramid(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                             const float Q[16], float min_confidence, float z_min, float z_max, float invalid_disparity,
+                             int Hm, int Wm, const float *model_depth, const float *model_normals, const float Qm[16],
+                             const float Pm[16], const float *model_camera_to_world, const float *model_world_to_camera,
+                             const float *pose_in, int schedule_pairs, const int32_t *schedule, float max_distance,
+                             int min_inliers, float min_pivot, float rot_eps, float trans_eps, const float *frame_pyramid,
+                             const float *model_pyramid, int levels, const int32_t *schedule_levels,
+                             float photometric_weight, float max_intensity_difference, float huber_delta, float *pose_out,
+                             int32_t *info, float *rms, double *normal_equations, int32_t *photometric_info,
+                             float *photometric_rms, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

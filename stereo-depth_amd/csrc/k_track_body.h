@@ -1,6 +1,7 @@
 // k_track_body.h -- the launches of camera tracking, written once over the rule that is tracked: the three kernel bodies
 // and the launcher that fills the common record and runs the schedule.  k_track.h instantiates them for the geometric
-// rule (smx_track_camera) and k_track_photo.h for the joint one (smx_track_camera_photometric).
+// rule (smx_track_camera), k_track_photo.h for the joint one (smx_track_camera_photometric) and k_track_pyramid.h for
+// the joint one read from pyramids (smx_track_camera_pyramid).
 //
 // A rule R holds
 //   Args                 its kernel argument record, and common(a): the TrackArgs in it
@@ -133,11 +134,18 @@ template <class R> static __device__ __forceinline__ void track_solve_body(const
 
 static_assert(sizeof(TrackState) == 32 * sizeof(int), "track_layout reserves 32 words per triple");
 
+// A rule whose record has no field that depends on the schedule pair
+struct TrackSamePerPair {
+    template <class A> void operator()(A &, int) const {}
+};
+
 // Fills the common record of `ra` (the rule's own fields are the caller's) and enqueues the call: one launch that takes
-// the poses in, then two launches per iteration of the schedule.
-template <class R>
+// the poses in, then two launches per iteration of the schedule.  per_pair(ra, p) sets the rule's fields that belong to
+// pair p of the schedule, before that pair's launches take the record by value.
+template <class R, class PerPair = TrackSamePerPair>
 void track_launch(const TrackCall &c, typename R::Args &ra, void (*begin)(typename R::Args),
-                  void (*accum)(typename R::Args), void (*solve)(typename R::Args), hipStream_t s) {
+                  void (*accum)(typename R::Args), void (*solve)(typename R::Args), hipStream_t s,
+                  PerPair per_pair = PerPair()) {
     const int n = c.n;
     const TrackLayout l = track_layout(n, c.H, c.W, R::SLOTS);
     TrackArgs &a = R::common(ra);
@@ -160,6 +168,7 @@ void track_launch(const TrackCall &c, typename R::Args &ra, void (*begin)(typena
     for (int p = 0; p < c.pairs; ++p) {
         const TrackGrid g = track_grid(c.H, c.W, c.schedule[2 * p]);
         a.stride = c.schedule[2 * p], a.ws = g.ws, a.hs = g.hs, a.tx = g.tx, a.tiles = g.tiles, a.groups = g.groups;
+        per_pair(ra, p);
         for (int it = 0; it < c.schedule[2 * p + 1]; ++it) {
             hipLaunchKernelGGL(accum, dim3((unsigned)g.groups, triples), dim3(256), 0, s, ra);
             hipLaunchKernelGGL(solve, dim3(triples), dim3(1024), 0, s, ra);

@@ -14,17 +14,7 @@ namespace smx {
 constexpr int TRKP_CHUNKS = 16;                                       // chunks of consecutive partials per triple: one wave each
 constexpr int TRKP_STACK = 7;                                         // levels above a leaf of 8: chunks of up to 512 partials
 
-struct TrackPhotoRule {
-    using Args = TrackPhotoArgs;
-    static constexpr int SLOTS = TRKP_SLOTS, BUTTERFLY = TRKP_SLOTS, CHUNKS = TRKP_CHUNKS, STACK = TRKP_STACK;
-    static SMX_FN TrackArgs &common(TrackPhotoArgs &a) { return a.g; }
-    static SMX_FN const TrackArgs &common(const TrackPhotoArgs &a) { return a.g; }
-    static SMX_FN void pixel(const TrackPhotoArgs &a, const float *T, int f, int px, int py, double *acc) {
-        trkp_pixel(a, T, f, px, py, acc);
-    }
-    static SMX_FN void begin(const TrackPhotoArgs &a, int f) { trkp_begin(a, f); }
-    static SMX_FN void finish(const TrackPhotoArgs &a, int f, const double *S) { trkp_finish(a, f, S); }
-};
+using TrackPhotoRule = TrackJointRule<TrackPhotoArgs, TRKP_CHUNKS, TRKP_STACK>;
 
 __global__ __launch_bounds__(256) void k_track_photo_begin(const TrackPhotoArgs a) { track_begin_body<TrackPhotoRule>(a); }
 __global__ __launch_bounds__(256) void k_track_photo_accum(const TrackPhotoArgs a) { track_accum_body<TrackPhotoRule>(a); }

@@ -194,7 +194,7 @@ void launch_tsdf_merge(int nx, int ny, int nz, float *tsdf, float *weight, uint8
 // ---- tu_track.hip, tu_track_photo.hip: camera tracking against rendered model views (k_track.h, k_track_photo.h) ----------
 // A call's operands in the C entries' order.  q / qm / pm / schedule ([pairs][2]: stride, iterations): host values; every
 // other pointer is device memory; confidence, info, rms and normal_equations ([n][30], with the photometric term
-// [n][33]) may be NULL; arguments checked by smx_track_camera and smx_track_camera_photometric
+// [n][33]) may be NULL; arguments checked by smx_track_camera, smx_track_camera_photometric and smx_track_camera_pyramid
 struct TrackCall {
     int n, H, W;
     const float *disp, *confidence, *q;
@@ -225,5 +225,21 @@ void launch_track_camera(const TrackCall &c, hipStream_t s);
 void launch_track_camera_photometric(const TrackCall &c, const TrackPhotoTerm &t, hipStream_t s);
 // in: uint8 [n][C][H][W], C 1 or 3; out: f32 [n][H][W]; arguments checked by smx_intensity_planes
 void launch_intensity_planes(int n, int C, int H, int W, const uint8_t *in, float *out, hipStream_t s);
+
+// ---- tu_pyramid.hip, tu_track_pyramid.hip: intensity pyramids, and tracking that reads them (k_pyramid.h, k_track_pyramid.h) ----
+// plane, mask_depth (may be NULL): [n][H][W]; pyramid: the levels one after another, level l [n][H_l][W_l] with
+// H_l = ceil(H / 2^l) (smx_workspace.h: pyramid_level); one launch per level, no workspace; arguments checked by
+// smx_intensity_pyramid
+void launch_intensity_pyramid(int n, int H, int W, int levels, const float *plane, const float *mask_depth, float *pyramid,
+                              hipStream_t s);
+// what the photometric term takes on when it is read from pyramids: TrackPhotoTerm's two planes are then pyramids
+// (device) of `levels` levels; the level of every schedule pair (host), and Huber's bound
+struct TrackPyramidTerm {
+    int levels;
+    const int32_t *schedule_levels;
+    float huber_delta;
+};
+// workspace: track_photo_layout(n, H, W)
+void launch_track_camera_pyramid(const TrackCall &c, const TrackPhotoTerm &t, const TrackPyramidTerm &py, hipStream_t s);
 
 }  // namespace smx

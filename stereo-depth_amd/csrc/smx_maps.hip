@@ -893,14 +893,15 @@ size_t smx_track_camera_workspace_bytes(int n, int H, int W) {
     return track_dims_ok(n, H, W) ? track_layout(n, H, W).total : 0;
 }
 
-// The checks smx_track_camera and smx_track_camera_photometric share, in their order: everything before the workspace's
-// size.  photo: the photometric entry's term, whose two planes are part of the NULL check.
-static int check_track_args(const char *fn, const smx::TrackCall &c, const smx::TrackPhotoTerm *photo) {
+// The checks smx_track_camera, smx_track_camera_photometric and smx_track_camera_pyramid share, in their order: everything
+// before the workspace's size.  photo: the photometric entries' term, whose two planes (named `planes`: the pyramid entry's
+// are its pyramids) are part of the NULL check.
+static int check_track_args(const char *fn, const smx::TrackCall &c, const smx::TrackPhotoTerm *photo, const char *planes) {
     const int n = c.n, H = c.H, W = c.W, Hm = c.Hm, Wm = c.Wm, schedule_pairs = c.pairs;
     const float *Q = c.q, *Qm = c.qm, *Pm = c.pm;
     const int32_t *schedule = c.schedule;
     if (photo && (!photo->frame_intensity || !photo->model_intensity))
-        return fail(SMX_ERR_INVALID_ARG, "%s: frame_intensity and model_intensity must be non-NULL", fn);
+        return fail(SMX_ERR_INVALID_ARG, "%s: frame_%s and model_%s must be non-NULL", fn, planes, planes);
     if (!c.disp || !Q || !c.model_depth || !c.model_normals || !Qm || !Pm || !c.model_camera_to_world ||
         !c.model_world_to_camera || !c.pose_in || !c.pose_out || !c.workspace)
         return fail(SMX_ERR_INVALID_ARG,
@@ -941,14 +942,33 @@ static int check_track_args(const char *fn, const smx::TrackCall &c, const smx::
     return SMX_OK;
 }
 
-// smx_track_camera and smx_track_camera_photometric: photo NULL is smx_track_camera.
+// The rules of smx_track_camera_pyramid's own arguments, after check_track_args has passed the schedule.
+static int check_track_pyramid_args(const char *fn, const smx::TrackCall &c, const smx::TrackPyramidTerm &t) {
+    if (int rc = check_int_range(fn, "levels", t.levels, 1, PYR_MAX_LEVELS)) return rc;
+    if (c.pairs > 0 && !t.schedule_levels) return fail(SMX_ERR_INVALID_ARG, "%s: schedule_levels must be non-NULL", fn);
+    for (int p = 0; p < c.pairs; ++p) {
+        const int level = t.schedule_levels[p], stride = c.schedule[2 * p];
+        if (int rc = check_int_range(fn, "a schedule level", level, 0, t.levels - 1)) return rc;
+        if (stride % (1 << level) != 0)
+            return fail(SMX_ERR_INVALID_ARG, "%s: a stride must be divisible by 2^level (got stride %d at level %d)", fn, stride,
+                        level);
+    }
+    if (!(t.huber_delta > 0.0f))                                    // +inf passes: no robust weights
+        return fail(SMX_ERR_INVALID_ARG, "%s: huber_delta must be > 0, got %g", fn, (double)t.huber_delta);
+    return SMX_OK;
+}
+
+// smx_track_camera, smx_track_camera_photometric and smx_track_camera_pyramid: photo NULL is smx_track_camera; with pyr,
+// photo holds the term's arguments that the two photometric entries share and the pyramids in place of the planes.
 static int track_entry(const char *fn, int device_id, const smx::TrackCall &c, const smx::TrackPhotoTerm *photo,
-                       size_t workspace_bytes, void *stream) {
-    if (int rc = check_track_args(fn, c, photo)) return rc;
+                       const smx::TrackPyramidTerm *pyr, size_t workspace_bytes, void *stream) {
+    if (int rc = check_track_args(fn, c, photo, pyr ? "pyramid" : "intensity")) return rc;
     if (photo) {
         if (int rc = check_non_negative(fn, "photometric_weight", photo->weight)) return rc;
         if (int rc = check_positive(fn, "max_intensity_difference", photo->max_intensity_difference)) return rc;
     }
+    if (pyr)
+        if (int rc = check_track_pyramid_args(fn, c, *pyr)) return rc;
     if (int rc = photo ? check_workspace_bytes(fn, "smx_track_camera_photometric_workspace_bytes", workspace_bytes,
                                                track_photo_layout(c.n, c.H, c.W).total)
                        : check_workspace_bytes(fn, "smx_track_camera_workspace_bytes", workspace_bytes,
@@ -956,12 +976,14 @@ static int track_entry(const char *fn, int device_id, const smx::TrackCall &c, c
         return rc;
     const size_t n = (size_t)c.n, map_bytes = n * c.H * c.W * sizeof(float), model_bytes = n * c.Hm * c.Wm * sizeof(float);
     const size_t pose_bytes = n * 12 * sizeof(float);
+    const size_t frame_bytes = pyr ? pyramid_level(c.n, c.H, c.W, pyr->levels).offset * sizeof(float) : map_bytes;
+    const size_t view_bytes = pyr ? pyramid_level(c.n, c.Hm, c.Wm, pyr->levels).offset * sizeof(float) : model_bytes;
     const smx::TrackPhotoTerm none{}, &t = photo ? *photo : none;    // a NULL span overlaps nothing
     if (int rc = check_disjoint(fn, {{c.disp, map_bytes}, {c.confidence, map_bytes}, {c.model_depth, model_bytes},
                                      {c.model_normals, 3 * model_bytes}, {c.model_camera_to_world, pose_bytes},
                                      {c.model_world_to_camera, pose_bytes},
                                      {c.pose_in != c.pose_out ? c.pose_in : nullptr, pose_bytes},
-                                     {t.frame_intensity, map_bytes}, {t.model_intensity, model_bytes}},
+                                     {t.frame_intensity, frame_bytes}, {t.model_intensity, view_bytes}},
                                 {{c.pose_out, pose_bytes}, {c.info, n * 4 * sizeof(int32_t)}, {c.rms, n * sizeof(float)},
                                  {c.normal_equations, n * (photo ? TRKP_TERMS : TRK_TERMS) * sizeof(double)},
                                  {t.info, n * 2 * sizeof(int32_t)}, {t.rms, n * sizeof(float)},
@@ -971,7 +993,8 @@ static int track_entry(const char *fn, int device_id, const smx::TrackCall &c, c
         return rc;
     if (int rc = check_workspace_and_stream(fn, c.workspace, stream)) return rc;
     return launch_on(device_id, [&] {
-        if (photo) smx::launch_track_camera_photometric(c, *photo, (hipStream_t)stream);
+        if (pyr) smx::launch_track_camera_pyramid(c, *photo, *pyr, (hipStream_t)stream);
+        else if (photo) smx::launch_track_camera_photometric(c, *photo, (hipStream_t)stream);
         else smx::launch_track_camera(c, (hipStream_t)stream);
     });
 }
@@ -987,7 +1010,7 @@ int smx_track_camera(int device_id, int n, int H, int W, const float *disp, cons
                            model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
                            schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out,
                            info, rms, normal_equations, workspace};
-    return track_entry("smx_track_camera", device_id, c, nullptr, workspace_bytes, stream);
+    return track_entry("smx_track_camera", device_id, c, nullptr, nullptr, workspace_bytes, stream);
 }
 
 size_t smx_track_camera_photometric_workspace_bytes(int n, int H, int W) {
@@ -1011,7 +1034,27 @@ int smx_track_camera_photometric(int device_id, int n, int H, int W, const float
                            info, rms, normal_equations, workspace};
     const smx::TrackPhotoTerm photo{frame_intensity, model_intensity, photometric_weight, max_intensity_difference,
                                     photometric_info, photometric_rms};
-    return track_entry("smx_track_camera_photometric", device_id, c, &photo, workspace_bytes, stream);
+    return track_entry("smx_track_camera_photometric", device_id, c, &photo, nullptr, workspace_bytes, stream);
+}
+
+int smx_track_camera_pyramid(int device_id, int n, int H, int W, const float *disp, const float *confidence,
+                             const float Q[16], float min_confidence, float z_min, float z_max, float invalid_disparity,
+                             int Hm, int Wm, const float *model_depth, const float *model_normals, const float Qm[16],
+                             const float Pm[16], const float *model_camera_to_world, const float *model_world_to_camera,
+                             const float *pose_in, int schedule_pairs, const int32_t *schedule, float max_distance,
+                             int min_inliers, float min_pivot, float rot_eps, float trans_eps, const float *frame_pyramid,
+                             const float *model_pyramid, int levels, const int32_t *schedule_levels,
+                             float photometric_weight, float max_intensity_difference, float huber_delta, float *pose_out,
+                             int32_t *info, float *rms, double *normal_equations, int32_t *photometric_info,
+                             float *photometric_rms, void *workspace, size_t workspace_bytes, void *stream) {
+    const smx::TrackCall c{n, H, W, disp, confidence, Q, min_confidence, z_min, z_max, invalid_disparity, Hm, Wm,
+                           model_depth, model_normals, Qm, Pm, model_camera_to_world, model_world_to_camera, pose_in,
+                           schedule_pairs, schedule, max_distance, min_inliers, min_pivot, rot_eps, trans_eps, pose_out,
+                           info, rms, normal_equations, workspace};
+    const smx::TrackPhotoTerm photo{frame_pyramid, model_pyramid, photometric_weight, max_intensity_difference,
+                                    photometric_info, photometric_rms};
+    const smx::TrackPyramidTerm pyr{levels, schedule_levels, huber_delta};
+    return track_entry("smx_track_camera_pyramid", device_id, c, &photo, &pyr, workspace_bytes, stream);
 }
 
 int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const uint8_t *image, float *out,
@@ -1028,6 +1071,29 @@ int smx_intensity_planes(int device_id, int n, int channels, int H, int W, const
     if (int rc = check_caller_stream(fn, stream)) return rc;
     return launch_on(device_id, [&] {
         smx::launch_intensity_planes(n, channels, H, W, image, out, (hipStream_t)stream);
+    });
+}
+
+size_t smx_intensity_pyramid_bytes(int n, int H, int W, int levels) {
+    if (!points_dims_ok(n, H, W) || levels < 1 || levels > PYR_MAX_LEVELS) return 0;
+    return pyramid_level(n, H, W, levels).offset * sizeof(float);
+}
+
+int smx_intensity_pyramid(int device_id, int n, int H, int W, int levels, const float *plane, const float *mask_depth,
+                          float *pyramid, void *stream) {
+    const char *fn = "smx_intensity_pyramid";
+    if (!plane || !pyramid) return fail(SMX_ERR_INVALID_ARG, "%s: plane and pyramid must be non-NULL", fn);
+    if (int rc = check_map_dims(fn, n, H, W)) return rc;
+    if (int rc = check_pixel_count(fn, n, H, W)) return rc;
+    if (int rc = check_int_range(fn, "levels", levels, 1, PYR_MAX_LEVELS)) return rc;
+    const size_t px = (size_t)n * H * W;
+    if (int rc = check_disjoint(fn, {{plane, px * sizeof(float)}, {mask_depth, px * sizeof(float)}},
+                                {{pyramid, smx_intensity_pyramid_bytes(n, H, W, levels)}},
+                                "pyramid must not overlap plane or mask_depth"))
+        return rc;
+    if (int rc = check_caller_stream(fn, stream)) return rc;
+    return launch_on(device_id, [&] {
+        smx::launch_intensity_pyramid(n, H, W, levels, plane, mask_depth, pyramid, (hipStream_t)stream);
     });
 }
 

@@ -211,4 +211,21 @@ constexpr int TRKP_TERMS = TRK_TERMS + 3;      // the sums of the header: thirty
 constexpr int TRKP_SLOTS = TRK_TERMS + 4;      // the thirty, the accepted pixels, the three
 inline TrackLayout track_photo_layout(int n, int H, int W) { return track_layout(n, H, W, TRKP_SLOTS); }
 
+// ---- intensity pyramids (not a workspace: the caller's buffer): level 0 [n][H][W] | level 1 [n][H_1][W_1] | ..., float32,
+// a level's dimension ceil(d / 2) of the one before it, which is the selected grid of stride 2^level.
+constexpr int PYR_MAX_LEVELS = 8;
+struct PyramidLevel {
+    size_t offset;                             // in floats
+    int H, W;
+};
+// level == levels gives the pyramid's size
+inline PyramidLevel pyramid_level(int n, int H, int W, int level) {
+    PyramidLevel l{0, H, W};
+    for (int k = 0; k < level; ++k) {
+        l.offset += (size_t)n * l.H * l.W;
+        l.H = (l.H + 1) / 2, l.W = (l.W + 1) / 2;
+    }
+    return l;
+}
+
 }  // namespace smx

@@ -1775,7 +1775,8 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
                  min_confidence: float = 0.0, invalid_disparity: float = -1.0, min_pivot: float = 1e-3,
                  rot_eps: float = 0.0, trans_eps: float = 0.0, image: Optional[torch.Tensor] = None,
                  photometric_weight: float = 0.0, max_intensity_difference: float = 30.0,
-                 model_intensity: Optional[torch.Tensor] = None) -> TrackingResult:
+                 model_intensity: Optional[torch.Tensor] = None, pyramid_levels: Optional[int] = None,
+                 huber_delta: float = math.inf, schedule_levels=None) -> TrackingResult:
     """The camera-to-world pose of a frame from its disparity map, by projective point-to-plane ICP against a rendered
     view of the model (smx_track_camera; the rule, operation by operation, is in include/stereo_mi355x.h).  disp: float32
     [H, W] or [n, H, W] with the reprojection matrix Q; pose: the initial guess [4, 4] / [n, 4, 4] (numpy or tensor;
@@ -1796,7 +1797,13 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     intensity plane [H, W] / [n, H, W]; the model's intensity comes from model.colors (render with colors=True) or from
     model_intensity, float32 like model.depth.  photometric_weight: metres per intensity unit (0..255 from uint8), about
     0.001 to 0.03; a term whose intensities differ by more than max_intensity_difference is left out.  The term's basin
-    is a few model pixels.  Without an image, or with a weight of 0, the geometric entry runs as it always did."""
+    is a few model pixels.  Without an image, or with a weight of 0, the geometric entry runs as it always did.
+    pyramid_levels = L (1..8) widens that basin (smx_track_camera_pyramid): the term is read from Gaussian pyramids of
+    the two planes (intensity_pyramid; the model's masked by model.depth), a schedule pair of stride s from level
+    min(L - 1, number of trailing zero bits of s) or from schedule_levels' entry for the pair (2^level must divide s),
+    so the coarse strides see coarse texture; huber_delta (intensity units, default inf: off) caps the pull of a large
+    residual at that of one of huber_delta.  The geometric term still reads the full-resolution view at every stride,
+    and neither exposure nor gain is compensated.  With pyramid_levels=None the call is what it was."""
     for name, v, positive in (("photometric_weight", photometric_weight, False),
                               ("max_intensity_difference", max_intensity_difference, True),
                               ("max_distance", max_distance, True), ("min_pivot", min_pivot, False),
@@ -1807,6 +1814,16 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     if image is None and photometric_weight > 0:
         raise RuntimeError("photometric_weight > 0 needs the frame's image")
     photometric = image is not None and photometric_weight > 0
+    if pyramid_levels is None:
+        if schedule_levels is not None or huber_delta != math.inf:
+            raise RuntimeError("schedule_levels and huber_delta need pyramid_levels")
+    else:
+        if not isinstance(pyramid_levels, int) or isinstance(pyramid_levels, bool) or not 1 <= pyramid_levels <= 8:
+            raise RuntimeError(f"pyramid_levels must be an int in 1..8, got {pyramid_levels!r}")
+        _number_arg("huber_delta", huber_delta)
+        if not huber_delta > 0:
+            raise RuntimeError(f"huber_delta must be > 0 (inf: no robust weights), got {huber_delta}")
+    pyramid = photometric and pyramid_levels is not None
     q = _check_q(Q)
     qm = q if model_Q is None else _check_q(model_Q)
     if (qm[:3, 2] != 0).any() or qm[3, 0] != 0 or qm[3, 1] != 0 or qm[3, 2] == 0:
@@ -1814,6 +1831,8 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
     pm = projection_matrix(qm)
     z_min, z_max = _check_reproject_params(min_confidence, depth_range, invalid_disparity)
     sched = _check_tracking_schedule(schedule)
+    if pyramid_levels is not None:
+        levels = _check_schedule_levels(sched, pyramid_levels, schedule_levels)
     if not isinstance(min_inliers, int) or isinstance(min_inliers, bool) or not 1 <= min_inliers <= 2 ** 30:
         raise RuntimeError(f"min_inliers must be an int in 1..2^30, got {min_inliers!r}")
     _check_input("disp", disp)
@@ -1863,8 +1882,18 @@ def track_camera(disp: torch.Tensor, Q, pose, model: RenderedView, model_pose, *
         model_int = _intensity_plane("model_intensity", model_intensity, lead, Hm, Wm, dev)
         pinfo = torch.empty((n, 2), dtype=torch.int32, device=dev)
         prms = torch.empty((n,), dtype=torch.float32, device=dev)
-        args += (frame_int.data_ptr(), model_int.data_ptr(), float(photometric_weight), float(max_intensity_difference))
-        entry, query = LIB.smx_track_camera_photometric, LIB.smx_track_camera_photometric_workspace_bytes
+        query = LIB.smx_track_camera_photometric_workspace_bytes
+        if pyramid:
+            frame_pyr = _pyramid_buffer(frame_int.reshape(n, H, W), pyramid_levels, None)
+            model_pyr = _pyramid_buffer(model_int.reshape(n, Hm, Wm), pyramid_levels, model.depth)
+            lv = (C.c_int32 * max(levels.size, 1))(*levels.tolist())
+            args += (frame_pyr.data_ptr(), model_pyr.data_ptr(), pyramid_levels, lv, float(photometric_weight),
+                     float(max_intensity_difference), float(huber_delta))
+            entry = LIB.smx_track_camera_pyramid
+        else:
+            args += (frame_int.data_ptr(), model_int.data_ptr(), float(photometric_weight),
+                     float(max_intensity_difference))
+            entry = LIB.smx_track_camera_photometric
     else:
         entry, query = LIB.smx_track_camera, LIB.smx_track_camera_workspace_bytes
     sums = torch.empty((n, 33 if photometric else 30), dtype=torch.float64, device=dev)
@@ -1904,6 +1933,72 @@ def intensity_planes(image: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n, H, W), dtype=torch.float32, device=image.device)
     check(LIB.smx_intensity_planes(image.device.index, n, c, H, W, image.data_ptr(), out.data_ptr(),
                                    _stream(image.device.index)))
+    return out
+
+
+def _check_schedule_levels(sched: np.ndarray, pyramid_levels: int, schedule_levels) -> np.ndarray:
+    """int32 [pairs]: the pyramid level of every pair of the checked schedule; by default the coarsest level whose grid
+    holds the pair's stride."""
+    strides = [int(s) for s in sched[:, 0]]
+    if schedule_levels is None:
+        lv = [min(pyramid_levels - 1, (s & -s).bit_length() - 1) for s in strides]
+    else:
+        try:
+            lv = [int(v) for v in schedule_levels]
+            if any(v != v0 for v, v0 in zip(lv, schedule_levels)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise TypeError("schedule_levels must be a sequence of integers, one per schedule pair") from None
+        if len(lv) != len(strides):
+            raise RuntimeError(f"schedule_levels needs one level per schedule pair ({len(strides)}), got {len(lv)}")
+    for s, v in zip(strides, lv):
+        if not 0 <= v < pyramid_levels or s % (1 << v):
+            raise RuntimeError(f"a schedule level must be in 0..{pyramid_levels - 1} and 2^level must divide the stride, "
+                               f"got level {v} at stride {s}")
+    return np.array(lv, np.int32)
+
+
+def _pyramid_dims(H: int, W: int, levels: int):
+    dims = [(H, W)]
+    for _ in range(levels - 1):
+        dims.append(((dims[-1][0] + 1) // 2, (dims[-1][1] + 1) // 2))
+    return dims
+
+
+def _pyramid_buffer(planes: torch.Tensor, levels: int, mask_depth: Optional[torch.Tensor]) -> torch.Tensor:
+    """The pyramid of checked float32 planes [n, H, W] as one flat buffer (smx_intensity_pyramid's layout)."""
+    n, H, W = planes.shape
+    out = torch.empty((sum(n * h * w for h, w in _pyramid_dims(H, W, levels)),), dtype=torch.float32, device=planes.device)
+    check(LIB.smx_intensity_pyramid(planes.device.index, n, H, W, levels, planes.data_ptr(),
+                                    None if mask_depth is None else mask_depth.data_ptr(), out.data_ptr(),
+                                    _stream(planes.device.index)))
+    return out
+
+
+def intensity_pyramid(planes: torch.Tensor, levels: int, mask_depth: Optional[torch.Tensor] = None):
+    """The Gaussian pyramid of float32 intensity planes [n, H, W] (or one plane [H, W]) on the GPU
+    (smx_intensity_pyramid): a list of `levels` tensors [n, H_l, W_l] ([H_l, W_l]), H_l = ceil(H / 2^l), views of one
+    buffer in the layout smx_track_camera_pyramid reads.  Level 0 is the plane, NaN where mask_depth (float32, the
+    planes' shape) is not finite and > 0; a level halves the one before it with the taps (1 4 6 4 1) / 16, and a pixel
+    with a NaN in its footprint is a NaN.  Runs on the current stream."""
+    _check_input("planes", planes)
+    if planes.dtype != torch.float32 or planes.dim() not in (2, 3) or not planes.is_cuda:
+        raise RuntimeError(f"planes must be float32 [H, W] or [n, H, W] on the GPU, got {planes.dtype} "
+                           f"{tuple(planes.shape)} on {planes.device}")
+    if not isinstance(levels, int) or isinstance(levels, bool) or not 1 <= levels <= 8:
+        raise RuntimeError(f"levels must be an int in 1..8, got {levels!r}")
+    batched = planes.dim() == 3
+    n, H, W = planes.shape if batched else (1,) + tuple(planes.shape)
+    if not (n >= 1 and 1 <= H <= 32768 and 1 <= W <= 32768 and n * H * W <= 2 ** 30):
+        raise RuntimeError(f"need n >= 1, 1 <= H, W <= 32768 and n * H * W <= 2^30, got {tuple(planes.shape)}")
+    if mask_depth is not None:
+        _check_like("mask_depth", mask_depth, torch.float32, planes.shape, planes.device)
+    buf = _pyramid_buffer(planes.reshape(n, H, W), levels, mask_depth)
+    out, at = [], 0
+    for h, w in _pyramid_dims(H, W, levels):
+        level = buf[at:at + n * h * w].view(n, h, w)
+        out.append(level if batched else level[0])
+        at += n * h * w
     return out
 
 

@@ -237,6 +237,15 @@ EXPORTS = {
 _TRACK = EXPORTS["smx_track_camera"][1]
 EXPORTS["smx_track_camera_photometric"] = (C.c_int, _TRACK[:27] + [C.c_void_p, C.c_void_p, C.c_float, C.c_float] +
                                            _TRACK[27:31] + [C.c_void_p, C.c_void_p] + _TRACK[31:])
+# intensity pyramids: (n, H, W, levels) -> bytes; (device_id, n, H, W, levels, plane, mask_depth or NULL, pyramid, stream)
+EXPORTS["smx_intensity_pyramid_bytes"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int])
+EXPORTS["smx_intensity_pyramid"] = (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p])
+# tracking with the term read from pyramids: the photometric entry's arguments with frame_pyramid, model_pyramid, levels,
+# schedule_levels (host int32[pairs]) in place of the two planes, and huber_delta after max_intensity_difference
+EXPORTS["smx_track_camera_pyramid"] = (C.c_int, _TRACK[:27] + [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                                                               C.c_float, C.c_float, C.c_float] +
+                                       _TRACK[27:31] + [C.c_void_p, C.c_void_p] + _TRACK[31:])
 
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1   # SMX_BORDER_*
 DTYPE_U8, DTYPE_F32 = 0, 1                 # SMX_DTYPE_*

@@ -185,7 +185,8 @@ class DepthEstimationPipeline:
         initial_pose [4, 4] (default the identity); every later frame is tracked against the volume rendered from the
         last pose (TSDFVolume.track with point_cloud_depth_range, the confidence map and point_cloud_min_confidence, and
         tracking_args on top; a photometric_weight > 0 among them passes the left frame the map was computed on as the
-        photometric term's image, which needs a colour volume), its twelve pose values and its lost flag are read back
+        photometric term's image, which needs a colour volume; pyramid_levels and huber_delta among them read that term
+        coarse to fine from intensity pyramids), its twelve pose values and its lost flag are read back
         -- one small device-to-host copy, hence one synchronisation, per frame -- and it is integrated at the tracked
         pose unless it is lost.  The result
         carries camera_pose and tracking_lost; reset_tracking() forgets the last pose.  follow_camera /

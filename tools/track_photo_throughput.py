@@ -62,7 +62,9 @@ class PhotoTracker(base.Tracker):
         return out
 
 
-def cost(args):
+def cost_operands():
+    """(Q, frame, view, model_pose, true_pose, plane [1, H, W]): the C2 frame, the spheres volume's model view and the
+    smooth intensity plane that the cost runs read."""
     H, W = tt.H, tt.W
     Q = cuda_depth.reprojection_matrix(tt.FOCAL, W / 2.0, H / 2.0, tt.BASELINE)
     vol = cuda_depth.TSDFVolume(tt.DIMS, tt.VS, tt.ORIGIN, truncation=0.3, color=False)
@@ -85,6 +87,11 @@ def cost(args):
     view()
     v, u = torch.meshgrid(torch.arange(H, device="cuda").float(), torch.arange(W, device="cuda").float(), indexing="ij")
     plane = (128.0 + 40.0 * torch.sin(0.021 * u) + 30.0 * torch.cos(0.017 * v))[None].contiguous()
+    return Q, frame, view, model_pose, true_pose, plane
+
+
+def cost(args):
+    Q, frame, view, model_pose, true_pose, plane = cost_operands()
     res = {}
     for name, schedule in (("default_schedule", track_ref.DEFAULT_SCHEDULE), ("one_at_stride_1", ((1, 1),))):
         geo = base.Tracker(frame, Q, view, model_pose, schedule)
@@ -125,19 +132,21 @@ def painted(scene, pose, rng, noise_px, outliers):
     return d, gray
 
 
-def sequence(scene, poses, dims, vs, origin, **track_args):
+def sequence(scene, poses, dims, vs, origin, variants=None, **track_args):
     """Tracks every frame after the first against the colour volume so far from the previous true pose, with and without
-    the term, then fuses it at its true pose."""
+    the term (or once per entry of variants: name -> track arguments on top of the term's), then fuses it at its true
+    pose."""
     Q = cuda_depth.reprojection_matrix(tt.FOCAL, tt.W / 2.0, tt.H / 2.0, tt.BASELINE)
     rng = np.random.default_rng(7)
     vol = cuda_depth.TSDFVolume(dims, vs, origin)
-    rows = {"geometric": [], "joint": []}
+    variants = {"joint": {}} if variants is None else variants
+    rows = {name: [] for name in ("geometric",) + tuple(variants)}
     for i, pose in enumerate(poses):
         d, gray = painted(scene, pose, rng, 0.5, 0.05)
         td, tg = torch.from_numpy(d).cuda(), torch.from_numpy(gray).cuda()
         if i > 0:
-            for name, extra in (("geometric", {}), ("joint", dict(image=tg, photometric_weight=WEIGHT,
-                                                                  max_intensity_difference=MAX_DIFFERENCE))):
+            term = dict(image=tg, photometric_weight=WEIGHT, max_intensity_difference=MAX_DIFFERENCE)
+            for name, extra in [("geometric", {})] + [(k, dict(term, **v)) for k, v in variants.items()]:
                 found = vol.track(td, Q, poses[i - 1], **track_args, **extra)
                 m, deg = track_ref.pose_error(found.pose.cpu().numpy(), pose)
                 rows[name].append({"lost": int(found.lost), "error_m": round(m, 4), "error_deg": round(deg, 3)})
@@ -157,22 +166,29 @@ def sequence(scene, poses, dims, vs, origin, **track_args):
     return res
 
 
-def quality(n_poses=12):
+def analytic_sequence(n_poses=12):
+    """sequence()'s arguments for the ground plane and three boxes seen from n_poses poses."""
     rng = np.random.default_rng(7)
     scene = tsdf_ref.Scene(ground_y=1.65, boxes=[((-3.0, -0.2, 8.0), (-1.0, 1.65, 10.0)),
                                                  ((1.0, -0.5, 12.0), (3.5, 1.65, 14.0)),
                                                  ((-2.0, 0.2, 16.0), (1.0, 1.65, 18.0))])
     poses = np.stack([tsdf_ref.look_at((rng.uniform(-0.3, 0.3), rng.uniform(-0.1, 0.1), 0.25 * i),
                                        (rng.uniform(-0.5, 0.5), 0.5, 0.25 * i + 20.0)) for i in range(n_poses)])
-    res = {"analytic_sequence": sequence(scene, poses, (128, 48, 192), 0.1, (-6.4, -3.0, 3.0), max_distance=1.0,
-                                         depth_range=(0.0, 40.0))}
-    # a wall 8 m ahead that fills the view; the camera drifts sideways, 5 cm and a fifth of a degree a frame
+    return scene, poses, (128, 48, 192), 0.1, (-6.4, -3.0, 3.0)
+
+
+def textured_wall():
+    """sequence()'s arguments for a wall 8 m ahead that fills the view; the camera drifts sideways, 5 cm and a fifth of a
+    degree a frame."""
     wall = tsdf_ref.Scene(ground_y=1000.0, boxes=[((-40.0, -40.0, 8.0), (40.0, 40.0, 9.0))])
     steps = np.stack([tsdf_ref.look_at((0.05 * i, -0.02 * i, 0.01 * i), (0.05 * i + 0.03 * i, -0.02 * i, 8.0))
                       for i in range(6)])
-    res["textured_wall"] = sequence(wall, steps, (192, 64, 32), 0.1, (-9.6, -3.2, 6.5), max_distance=1.0,
-                                    depth_range=(0.0, 40.0))
-    return res
+    return wall, steps, (192, 64, 32), 0.1, (-9.6, -3.2, 6.5)
+
+
+def quality(n_poses=12, variants=None):
+    return {"analytic_sequence": sequence(*analytic_sequence(n_poses), variants=variants, max_distance=1.0, depth_range=(0.0, 40.0)),
+            "textured_wall": sequence(*textured_wall(), variants=variants, max_distance=1.0, depth_range=(0.0, 40.0))}
 
 
 def main():
